@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: activations/sec (+ recon-MSE) of BinarySAE 512->32768 n_bits=4 forward.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One step = one full ``BinarySAE.forward`` (reference signature: dense sparse latent [B, H],
@@ -10,6 +10,10 @@ already resident in HBM, plus the on-device squared-error accumulation of the re
 Rows shard across ranks with no data-path collective (weak scaling: 65536 rows per GPU); the only
 exchange is the final 2-element fp64 all-reduce of the MSE pair and the max-over-ranks timing.
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline.  --full adds everything
+else: the live roofline of the dominant kernel, the blocking SAEWrapper call, the sustained run,
+the exact-fp32-only path, the secondary configurations and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -36,6 +40,7 @@ PEAK_FP32_MFMA_TFLOPS = 157.3                           # MI355X_MICROARCH.md, c
 PEAK_HBM_GBPS = 8000.0                                  # HBM3E, MI355X_MICROARCH.md
 PEAK_FP16_MFMA_TFLOPS = 2500.0                          # dense (the ~5 PF headline figure includes 2:1 sparsity)
 WEIGHT_BYTES_PER_BATCH = 4 * H * D + 4 * H + (H * D * N_BITS) // 8 + 4 * D      # 75 630 592 B
+DUMP_LATENT_ROWS, DUMP_RECON_ROWS = 256, 8192           # --dump-outputs: 32 MiB + 16 MiB of fp32 at the headline shape
 
 
 TRAFFIC_FILES = ("r03_traffic.json", "r02_traffic.json", "r01_traffic.json")      # newest first
@@ -76,6 +81,25 @@ def build_model(device, seed=1):
         model.decoder.weight.copy_((bits.float() * 2 - 1) * 30.0)
         model.decoder.bias.zero_()
     return model
+
+
+def dump_outputs(out_dir, latent, recon, pol):
+    """Write what the timed path returned in its last step as fp32 .npy files under out_dir: latent.npy and
+    reconstruction.npy hold the rows of the dense latent and of the reconstruction at a fixed sample of row indices
+    (the first DUMP_LATENT_ROWS / DUMP_RECON_ROWS entries of numpy's default_rng(0).permutation(B), in ascending
+    order; the latent rows are a subset of the reconstruction rows), polarize_loss.npy the 0-d loss.  (The recon-MSE
+    of the result line is left out: it sums all timed steps, in fp64 atomics whose order varies in the last bits.)"""
+    import numpy as np
+    perm = np.random.default_rng(0).permutation(recon.shape[0])
+    arrays = {}
+    for name, t, n in (("latent", latent, DUMP_LATENT_ROWS), ("reconstruction", recon, DUMP_RECON_ROWS)):
+        rows = torch.from_numpy(np.sort(perm[:n])).to(t.device)
+        arrays[name] = t.index_select(0, rows).to(torch.float32).cpu().numpy()
+    arrays["polarize_loss"] = pol.detach().to(torch.float32).cpu().numpy()
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
 
 
 def cpu_baseline(model, x_sample, max_threads):
@@ -246,7 +270,15 @@ def main():
     ap.add_argument("--batches", type=int, default=4, help="distinct input batches the timed loop rotates over")
     ap.add_argument("--sustained-seconds", type=float, default=2.5,
                     help="extra run of at least this many seconds of steps, reported under `sustained` (0 = skip; N=1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too: roofline, blocking call, sustained run, "
+                         "fp32-only path, secondary configurations, CPU baseline (the --no-* / --sustained-seconds "
+                         "options apply here)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the outputs of the last one as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -284,24 +316,24 @@ def main():
 
     def step(acc, i=0):
         xi = xs[i % len(xs)]
-        latent, recon, _pol = model(xi)
+        latent, recon, pol = model(xi)
         ops.sq_err_sum(recon, xi, acc)
-        return latent, recon
+        return latent, recon, pol
 
     def run_steps(n_steps, acc, pipeline=None, marks=None):
-        """n_steps full forwards + MSE accumulation.  pipeline 2: step i+1's kernels are queued before step i's
-        flagged-row count is read (every step still completes inside the caller's timed region); pipeline 1: the
-        blocking forward().  marks: optional list of n_steps + 1 timing events, one recorded per step on the launch
-        stream."""
+        """n_steps full forwards + MSE accumulation; returns the last step's (latent, reconstruction, polarize loss).
+        pipeline 2: step i+1's kernels are queued before step i's flagged-row count is read (every step still
+        completes inside the caller's timed region); pipeline 1: the blocking forward().  marks: optional list of
+        n_steps + 1 timing events, one recorded per step on the launch stream."""
         pipeline = args.pipeline if pipeline is None else pipeline
         if marks:
             marks[0].record()
         if pipeline <= 1:
             for i in range(n_steps):
-                step(acc, i)
+                outs = step(acc, i)
                 if marks:
                     marks[i + 1].record()
-            return
+            return outs
         pending, xprev = None, None
         for i in range(n_steps):
             xi = xs[i % len(xs)]
@@ -312,65 +344,77 @@ def main():
                 if marks:
                     marks[i].record()
             pending, xprev = h, xi
-        _lat, rec, _pol = pending.result()
-        ops.sq_err_sum(rec, xprev, acc)
+        outs = pending.result()
+        ops.sq_err_sum(outs[1], xprev, acc)
         if marks:
             marks[n_steps].record()
+        return outs
 
-    def timed_region(n_steps, acc, pipeline=None):
-        """barrier + sync, n_steps forwards, sync + barrier; returns elapsed seconds (max over ranks) and
-        the live HIP-event timing of the dominant sweep kernel."""
+    def timed_region(n_steps, acc, pipeline=None, kernel_timing=True):
+        """barrier + sync, n_steps forwards, sync + barrier; returns elapsed seconds (max over ranks), the live
+        HIP-event timing of the dominant sweep kernel (with kernel_timing, else None) and the last step's outputs."""
         ops.kernel_timer.reset()
-        ops.kernel_timer.enabled = True
-        ops.sweep_timing(True)
+        ops.kernel_timer.enabled = kernel_timing
+        ops.sweep_timing(kernel_timing)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         t0 = time.perf_counter()
-        run_steps(n_steps, acc, pipeline)
+        outs = run_steps(n_steps, acc, pipeline)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         dt = time.perf_counter() - t0
         ops.kernel_timer.enabled = False
         ops.sweep_timing(False)
-        sweep = ops.sweep_timing_collect(H)
-        return sharding.max_over_ranks(dt, device=device), sweep
+        sweep = ops.sweep_timing_collect(H) if kernel_timing else None
+        return sharding.max_over_ranks(dt, device=device), sweep, outs
 
     if args.warmup > 0:
         run_steps(args.warmup, torch.zeros((), dtype=torch.float64, device=device))
-    elapsed, (sweep_ms, sweep_n, sweep_frac) = timed_region(args.steps, sq)
+    # a plain run times the steps alone; --full also brackets the dominant kernel with HIP events for the roofline
+    elapsed, sweep, last = timed_region(args.steps, sq, kernel_timing=args.full)
     mse = sharding.reduce_mse(sq, args.steps * B * D)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last)
+    del last
     path_used = model.resolved_latent_path(B)
 
-    # what drops in: the blocking call a user of the reference makes -- SAEWrapper.__call__(batch) -> outputs dict
-    # (inference/framework.py:316-319) -- same steps, same batches, same MSE accumulation; reported beside `value`
-    from quantizedsae_amd.inference.framework import SAE_REGISTRY, SAEWrapper
-    wrapper = SAEWrapper(SAE_REGISTRY["b_sae"], model, device)
+    forward_blocking = None
+    if args.full:
+        # what drops in: the blocking call a user of the reference makes -- SAEWrapper.__call__(batch) -> outputs dict
+        # (inference/framework.py:316-319) -- same steps, same batches, same MSE accumulation; reported beside `value`
+        from quantizedsae_amd.inference.framework import SAE_REGISTRY, SAEWrapper
+        wrapper = SAEWrapper(SAE_REGISTRY["b_sae"], model, device)
 
-    def run_blocking(n_steps, acc):
-        for i in range(n_steps):
-            xi = xs[i % len(xs)]
-            outs = wrapper(xi)
-            ops.sq_err_sum(outs["reconstruction"], xi, acc)
+        def run_blocking(n_steps, acc):
+            for i in range(n_steps):
+                xi = xs[i % len(xs)]
+                outs = wrapper(xi)
+                ops.sq_err_sum(outs["reconstruction"], xi, acc)
 
-    run_blocking(1, torch.zeros((), dtype=torch.float64, device=device))
-    sq_b = torch.zeros((), dtype=torch.float64, device=device)
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    t0 = time.perf_counter()
-    run_blocking(args.steps, sq_b)
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    el_block = sharding.max_over_ranks(time.perf_counter() - t0, device=device)
-    mse_block = sharding.reduce_mse(sq_b, args.steps * B * D)
-    flagged_last = int(model.last_flagged_rows)
+        run_blocking(1, torch.zeros((), dtype=torch.float64, device=device))
+        sq_b = torch.zeros((), dtype=torch.float64, device=device)
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        t0 = time.perf_counter()
+        run_blocking(args.steps, sq_b)
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        el_block = sharding.max_over_ranks(time.perf_counter() - t0, device=device)
+        mse_block = sharding.reduce_mse(sq_b, args.steps * B * D)
+        forward_blocking = {"value": world * B * args.steps / el_block, "unit": "activations/s",
+                            "ms_per_step": el_block / args.steps * 1e3, "steps": args.steps, "recon_mse": mse_block,
+                            "what": "the same steps through the call a user of the reference makes: SAEWrapper.__call__(batch) "
+                                    "-> outputs dict (inference/framework.py:316-319), i.e. BinarySAE.forward() with its one "
+                                    "host round trip per batch (the flagged-row count); one batch in flight",
+                            "flagged_rows_last_batch": int(model.last_flagged_rows)}
 
     # sustained: >= args.sustained_seconds of steps in one region, one event per step
     sustained = None
-    if world == 1 and args.sustained_seconds > 0:
+    if args.full and world == 1 and args.sustained_seconds > 0:
         n_sus = max(args.steps, int(args.sustained_seconds / (elapsed / args.steps)) + 1)
         marks = [torch.cuda.Event(enable_timing=True) for _ in range(n_sus + 1)]
         sq_s = torch.zeros((), dtype=torch.float64, device=device)
@@ -403,12 +447,12 @@ def main():
 
     # the exact-fp32-only path, same model and batch, measured separately (not part of `value`)
     fp32_ref = None
-    if path_used == "prefilter" and not args.no_fp32_reference:
+    if args.full and path_used == "prefilter" and not args.no_fp32_reference:
         model.latent_path = "fused"
         n_ref = max(3, min(args.steps, 5))
         step(torch.zeros((), dtype=torch.float64, device=device))
         sq_ref = torch.zeros((), dtype=torch.float64, device=device)
-        el_ref, (ms_ref, n_sw, fr_ref) = timed_region(n_ref, sq_ref, pipeline=1)
+        el_ref, (ms_ref, n_sw, fr_ref), _ = timed_region(n_ref, sq_ref, pipeline=1)
         mse_ref = sharding.reduce_mse(sq_ref, n_ref * B * D)
         model.latent_path = args.latent_path
         ach = fr_ref * FLOPS_PER_ROW_ENCODER * B / (ms_ref * 1e-3) / 1e12 if n_sw else None
@@ -424,26 +468,6 @@ def main():
     if rank == 0:
         total_rows = world * B * args.steps
         value = total_rows / elapsed
-        if path_used == "prefilter" and sweep_n:
-            enc_ms, peak = sweep_ms, PEAK_FP16_MFMA_TFLOPS
-            achieved = sweep_frac * FLOPS_PER_ROW_ENCODER * B / (enc_ms * 1e-3) / 1e12
-            kname = (f"sweep_xstat_f16_kernel<32> (fp16 MFMA candidate sweep {B}x512 @ 512x{int(round(H * sweep_frac))}: "
-                     "activation panel stationary in registers, weights streamed once per workgroup, in-kernel pilot pass and "
-                     "threshold, threshold filter in the MFMA shadows) together with fill_zero_co_kernel, which writes the zeros of "
-                     "the dense [B,32768] latent from the 16 VGPRs per SIMD the sweep leaves free (second stream, joined before "
-                     "the refinement); avg_kernel_ms is the HIP-event time of the pair")
-            tkey = "sweep_xstat_f16+fill_zero_co"
-        elif sweep_n:
-            enc_ms, peak = sweep_ms, PEAK_FP32_MFMA_TFLOPS
-            achieved = sweep_frac * FLOPS_PER_ROW_ENCODER * B / (enc_ms * 1e-3) / 1e12
-            kname = (f"gemm_nt_f32_dma_kernel<EpiFilter<256,128,4,2>> (fp32 MFMA encoder sweep {B}x512 @ "
-                     f"512x{int(round(H * sweep_frac))} with threshold-filter epilogue)")
-            tkey = "sweep_dma_fp32"
-        else:
-            enc_ms, peak = ops.kernel_timer.mean_ms("encode_dense"), PEAK_FP32_MFMA_TFLOPS
-            achieved = FLOPS_PER_ROW_ENCODER * B / (enc_ms * 1e-3) / 1e12 if enc_ms else None
-            kname = f"gemm_nt_f32_kernel<..., EpiDense> (encoder {B}x512 @ 512x{H}, fp32 MFMA)"
-            tkey = None
         out = {
             "metric": "activations/sec, BinarySAE 512->32768 n_bits=4 forward (dense latent + reconstruction + MSE)",
             "value": value,
@@ -471,14 +495,33 @@ def main():
                                           "with a 4-MiB slice of the encoder weights resident in each XCD's L2 / rank + row "
                                           "decode, DESIGN.md 7.6)")},
             "recon_mse": mse,
-            "forward_blocking": {"value": world * B * args.steps / el_block, "unit": "activations/s",
-                                 "ms_per_step": el_block / args.steps * 1e3, "steps": args.steps, "recon_mse": mse_block,
-                                 "what": "the same steps through the call a user of the reference makes: SAEWrapper.__call__(batch) "
-                                         "-> outputs dict (inference/framework.py:316-319), i.e. BinarySAE.forward() with its one "
-                                         "host round trip per batch (the flagged-row count); one batch in flight",
-                                 "flagged_rows_last_batch": flagged_last},
-            "sustained": sustained,
             "input_batches": len(xs),
+        }
+    if rank == 0 and args.full:
+        sweep_ms, sweep_n, sweep_frac = sweep
+        if path_used == "prefilter" and sweep_n:
+            enc_ms, peak = sweep_ms, PEAK_FP16_MFMA_TFLOPS
+            achieved = sweep_frac * FLOPS_PER_ROW_ENCODER * B / (enc_ms * 1e-3) / 1e12
+            kname = (f"sweep_xstat_f16_kernel<32> (fp16 MFMA candidate sweep {B}x512 @ 512x{int(round(H * sweep_frac))}: "
+                     "activation panel stationary in registers, weights streamed once per workgroup, in-kernel pilot pass and "
+                     "threshold, threshold filter in the MFMA shadows) together with fill_zero_co_kernel, which writes the zeros of "
+                     "the dense [B,32768] latent from the 16 VGPRs per SIMD the sweep leaves free (second stream, joined before "
+                     "the refinement); avg_kernel_ms is the HIP-event time of the pair")
+            tkey = "sweep_xstat_f16+fill_zero_co"
+        elif sweep_n:
+            enc_ms, peak = sweep_ms, PEAK_FP32_MFMA_TFLOPS
+            achieved = sweep_frac * FLOPS_PER_ROW_ENCODER * B / (enc_ms * 1e-3) / 1e12
+            kname = (f"gemm_nt_f32_dma_kernel<EpiFilter<256,128,4,2>> (fp32 MFMA encoder sweep {B}x512 @ "
+                     f"512x{int(round(H * sweep_frac))} with threshold-filter epilogue)")
+            tkey = "sweep_dma_fp32"
+        else:
+            enc_ms, peak = ops.kernel_timer.mean_ms("encode_dense"), PEAK_FP32_MFMA_TFLOPS
+            achieved = FLOPS_PER_ROW_ENCODER * B / (enc_ms * 1e-3) / 1e12 if enc_ms else None
+            kname = f"gemm_nt_f32_kernel<..., EpiDense> (encoder {B}x512 @ 512x{H}, fp32 MFMA)"
+            tkey = None
+        out.update({
+            "forward_blocking": forward_blocking,
+            "sustained": sustained,
             "whole_path_tflops_per_gpu": value / world * FLOPS_PER_ROW / 1e12,
             "whole_path_vs_fp32_mfma_roofline": value / world * FLOPS_PER_ROW / 1e12 / PEAK_FP32_MFMA_TFLOPS,
             "whole_path_dense_gbps_per_gpu": value / world * BYTES_PER_ROW_DENSE / 1e9,
@@ -488,7 +531,7 @@ def main():
                          "avg_kernel_ms": enc_ms,
                          "traffic": pmc_traffic(tkey) if (tkey and B == ROWS_PER_GPU) else None},
             "fp32_only_path": fp32_ref,
-        }
+        })
         # the whole step against the HBM roofline: SURVEY 8(d) bytes per row (x in, dense latent + reconstruction out) plus
         # the weights once per batch, over the step time the driver also sees
         step_bytes = BYTES_PER_ROW_DENSE * B + WEIGHT_BYTES_PER_BATCH
@@ -526,6 +569,7 @@ def main():
             out["cpu_baseline"] = cpu_baseline(model, x[: args.cpu_sample_rows], threads)
         else:
             out["cpu_baseline"] = None
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -190,3 +190,49 @@ def test_four_times_the_benchmarked_batch():
     i1, v1, r1 = model.forward_compact(x[:half].contiguous())
     i2, v2, r2 = model.forward_compact(x[half:].contiguous())
     assert torch.equal(torch.cat([i1, i2]), idx) and bits_equal(torch.cat([v1, v2]), val) and bits_equal(torch.cat([r1, r2]), recon_c)
+
+
+def test_bench_plain_run_dumps_its_last_step(tmp_path):
+    """`bench.py --steps 3 --warmup 1 --dump-outputs DIR` in a fresh process: one JSON line with the headline alone,
+    timed over exactly 3 steps; the dumped outputs of the last step equal those of the same model's forward() on the
+    same batch in this process (bench.dump_outputs over them, bit for bit), the recon-MSE that of the three batches."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parents[1]
+    sys.path.insert(0, str(root))
+    import bench
+    from quantizedsae_amd import sharding
+    steps = 3
+    cmd = [sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+           "--dump-outputs", str(tmp_path / "bench")]
+    # a child of this process (which has initialised the GPU): started, never exec'ed into; the earlier tests' cached
+    # blocks are handed back first, the child holds two 8 GiB dense latents
+    torch.cuda.empty_cache()
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=str(root))
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    doc = json.loads(lines[0])
+    assert doc["steps"] == steps and doc["config"]["rows_per_gpu"] == B and doc["higher_is_better"] is True
+    assert doc["value"] == pytest.approx(B * steps / (doc["ms_per_step"] * steps * 1e-3), rel=1e-9)
+    full_only = {"roofline", "forward_blocking", "sustained", "fp32_only_path", "secondary_configs", "cpu_baseline"}
+    assert not full_only & set(doc)
+    # the same weights and batches here: torch.Generator(seed 1000), step i takes batch i mod 4 (bench.py)
+    model = bench.build_model(torch.device(DEV))
+    g = torch.Generator(device=DEV)
+    g.manual_seed(1000)
+    xs = [torch.randn((B, D), device=DEV, generator=g) for _ in range(4)]
+    sq = torch.zeros((), dtype=torch.float64, device=DEV)
+    for i in range(steps):
+        latent, recon, pol = model(xs[i % 4])
+        ops.sq_err_sum(recon, xs[i % 4], sq)
+    bench.dump_outputs(tmp_path / "here", latent, recon, pol)
+    names = sorted(p.name for p in (tmp_path / "bench").iterdir())
+    assert names == ["latent.npy", "polarize_loss.npy", "reconstruction.npy"]
+    for name in ("latent", "reconstruction", "polarize_loss"):
+        got, want = np.load(tmp_path / "bench" / f"{name}.npy"), np.load(tmp_path / "here" / f"{name}.npy")
+        assert got.dtype == np.float32 and got.shape == want.shape, name
+        assert np.array_equal(got.view(np.int32), want.view(np.int32)), name
+    assert doc["recon_mse"] == pytest.approx(sharding.reduce_mse(sq, steps * B * D), rel=1e-9)

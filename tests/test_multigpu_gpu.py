@@ -31,7 +31,7 @@ def test_bench_two_ranks_on_one_card_reduce_the_right_mse():
     env = dict(os.environ, QSAE_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), str(ROOT / "bench.py"), "--gpus", "2", "--rows", str(rows), "--steps", str(steps),
-           "--warmup", "1", "--no-cpu-baseline", "--no-fp32-reference", "--no-secondary"]
+           "--warmup", "1", "--full", "--no-cpu-baseline", "--no-fp32-reference", "--no-secondary"]
     # children of this process (which has initialised the GPU): started, never exec'ed into
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=str(ROOT))
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]

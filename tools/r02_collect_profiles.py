@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Fold the output of tools/r02_profile.sh (gpurun_out/r2prof) into profiles/: headline bench line, kernel stats CSV, and
-the per-launch FETCH_SIZE / WRITE_SIZE means of the sweep / fill / refinement kernels (printed; the judged numbers live in
-profiles/r02_traffic.json, whose refinement and sweep entries are updated in place)."""
+"""python3 tools/r02_collect_profiles.py OUT: fold the output of tools/r02_profile.sh OUT into profiles/: headline
+bench line, kernel stats CSV, and the per-launch FETCH_SIZE / WRITE_SIZE means of the sweep / fill / refinement kernels
+(printed; the judged numbers live in profiles/r02_traffic.json, whose refinement and sweep entries are updated in
+place)."""
 import csv
 import glob
 import json
@@ -11,7 +12,7 @@ from collections import defaultdict
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
-src = ROOT / "gpurun_out" / "r2prof"
+src = Path(sys.argv[1]).resolve()
 newest = lambda pat: max(glob.glob(str(src / pat), recursive=True), key=lambda f: Path(f).stat().st_mtime)
 shutil.copy(newest("stats/**/*kernel_stats.csv"), ROOT / "profiles" / "r02_bench_headline_kernel_stats.csv")
 line = (src / "bench_headline.json").read_text().strip().splitlines()[-1]

@@ -1,17 +1,18 @@
 #!/usr/bin/env python3
-"""Fold the output of tools/r03_profile.sh (gpurun_out/r3prof) into profiles/: headline bench line + kernel stats CSV, the
-full bench line (secondary configurations) + its kernel stats, and profiles/r03_traffic.json (per-launch FETCH_SIZE /
-WRITE_SIZE means of the sweep / fill / refinement / split-decoder kernels; FETCH_SIZE doubled per the gfx950 correction of
-MI355X_MICROARCH.md)."""
+"""python3 tools/r03_collect_profiles.py OUT: fold the output of tools/r03_profile.sh OUT into profiles/: headline
+bench line + kernel stats CSV, the full bench line (secondary configurations) + its kernel stats, and
+profiles/r03_traffic.json (per-launch FETCH_SIZE / WRITE_SIZE means of the sweep / fill / refinement / split-decoder
+kernels; FETCH_SIZE doubled per the gfx950 correction of MI355X_MICROARCH.md)."""
 import csv
 import glob
 import json
 import shutil
+import sys
 from collections import defaultdict
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
-src = ROOT / "gpurun_out" / "r3prof"
+src = Path(sys.argv[1]).resolve()
 newest = lambda pat: max(glob.glob(str(src / pat), recursive=True), key=lambda f: Path(f).stat().st_mtime)
 shutil.copy(newest("stats/**/*kernel_stats.csv"), ROOT / "profiles" / "r03_bench_headline_kernel_stats.csv")
 shutil.copy(newest("stats_all/**/*kernel_stats.csv"), ROOT / "profiles" / "r03_bench_all_kernel_stats.csv")
