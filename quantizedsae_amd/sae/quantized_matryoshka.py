@@ -116,34 +116,30 @@ class QuantizedMatryoshkaDecoder(nn.Module):
     #: the sparse walk beats the dense contraction below ~12 % active units (measured: 15 ms at 16 %, 23 ms dense)
     SPARSE_MAX_ACTIVE_FRACTION = 0.12
 
-    def active_fraction_hint(self):
-        """Fraction of active units in the most recent decode call whose counts have reached the host (None before the
-        first one).  The counts travel to a page-locked buffer behind the decode (asynchronous copy + event) and are
-        taken from there once the event has completed -- nothing here waits for the GPU, so a forward queued behind
-        another one is not held up by the hint; at worst the hint is one batch older."""
-        pending = getattr(self, "_pending_counts", None)
-        if pending is not None:
-            host, event, rows, units = pending
-            if event.query():
-                self._active_fraction = float(host.sum()) / max(rows * units, 1)
-                self._pending_counts = None
-        return getattr(self, "_active_fraction", None)
+    #: rows of a batch whose active units decide between the decoders: evenly spaced, so the choice is a function of the
+    #: batch alone, and few, so the count costs one small kernel (the count over every row of a 65536-row batch takes 0.6 ms
+    #: at 0.6 % density and 2 ms at 50 %: per-unit atomics)
+    DENSITY_SAMPLE_ROWS = 64
+
+    def active_fraction(self, zbits: torch.Tensor) -> float:
+        """Fraction of active units over DENSITY_SAMPLE_ROWS evenly spaced rows of this batch of z bits (rows
+        floor(i B / n), i < n; every row of a batch of at most n rows): one popcount kernel and one host read."""
+        B, n = zbits.shape[0], self.DENSITY_SAMPLE_ROWS
+        if B == 0:
+            return 0.0
+        rows = zbits if B <= n else zbits.index_select(0, torch.arange(n, device=zbits.device) * B // n)
+        return float(ops.activation_counts_bits(rows).sum().item()) / (rows.shape[0] * 32 * zbits.shape[1])
 
     def decode_bits(self, zbits: torch.Tensor, sparse=None) -> Tuple[list, list]:
         """zbits: int32-packed [B, H_padded/32] in the packed (padded) hidden order.  ``sparse``: walk the active
-        units only (same outputs); None = decide from the previous call's activation density."""
+        units only (same outputs as the exact-fp32 chain); None = decide from this batch's own activation density.  The sparse
+        walk and the bf16 split decoder round their sums in different orders, so the choice is a function of the z bits and
+        the attributes alone -- never of earlier batches or of how far the GPU has got."""
         st = self.packed()
         B = zbits.shape[0]
-        hint = self.active_fraction_hint()
-        if hint is None and sparse is None and B > 0:
-            # first decode of this model: measure this batch's density now (one host read, once per model) instead of
-            # guessing -- the two decoders round their sums in different orders, and a model that switched after its
-            # first call would return different low-order bits for the same batch
-            hint = self._active_fraction = float(ops.activation_counts_bits(zbits).sum().item()) / max(B * st["H"], 1)
         if sparse is None:
-            sparse = hint is not None and hint < self.SPARSE_MAX_ACTIVE_FRACTION
-        elif sparse and hint is not None and hint >= self.SPARSE_MAX_ACTIVE_FRACTION:
-            sparse = False
+            sparse = ("codes_rows" in st and B > 0 and self.SPARSE_MAX_ACTIVE_FRACTION > 0
+                      and self.active_fraction(zbits) < self.SPARSE_MAX_ACTIVE_FRACTION)
         if sparse and "codes_rows" in st:
             levels, counts = ops.decode_matryoshka_sparse(zbits, st["H"], self.out_features, self.n_bits,
                                                           st["codes_rows"], st["scale"], self.bias.detach(),
@@ -156,11 +152,6 @@ class QuantizedMatryoshkaDecoder(nn.Module):
         else:
             levels, counts = ops.decode_matryoshka(zbits, st["H"], self.out_features, self.n_bits, st["codes"],
                                                    st["scale"], self.bias.detach(), self.allow_bias, st["sizes"])
-        host = torch.empty((self.n_bits,), dtype=torch.int64).pin_memory()
-        host.copy_(counts, non_blocking=True)
-        event = torch.cuda.Event()
-        event.record()
-        self._pending_counts = (host, event, B, st["H"])
         groups = (counts.to(torch.float64) / max(B, 1)).to(torch.float32)
         return [groups[i] for i in range(self.n_bits)], [levels[i] for i in range(self.n_bits)]
 
@@ -294,18 +285,15 @@ class QuantizedMatryoshkaSAE(ops.GraphForwardMixin, SparseAutoencoder):
     def _forward_eager(self, x):
         with torch.no_grad():
             x = require_device_input(x, "x")
-            self.decoder.active_fraction_hint()            # reads the previous call's counts before anything is queued
             path = self.resolved_bits_path(x.shape[0])
-            z = self.activation_bits(x, path)
-            # few flagged rows = few active units: walk them; otherwise the decoder decides from the last batch's density
-            sparse = True if (path == "prefilter" and self.last_flagged_rows * 8 <= x.shape[0]) else None
-            return self.decoder.decode_bits(z, sparse=sparse)
+            return self.decoder.decode_bits(self.activation_bits(x, path))
 
     def forward_submit(self, x, slot: int = 0):
         """Queue one forward without waiting for the GPU (see BinarySAE.forward_submit): the z bits of the fp16 candidate
         sweep are queued here (qsae_encode_bits_prefilter_submit); ``result()`` takes the count of rows that need the
-        exact dense kernel, queues those and the decoder, and returns ``(latent_groups, reconstruction_levels)``.
-        Batches in flight together need different ``slot`` numbers; models on the dense path compute eagerly."""
+        exact dense kernel, queues those, reads the batch's active-unit count, queues the decoder and returns
+        ``(latent_groups, reconstruction_levels)``.  Batches in flight together need different ``slot`` numbers; models on the
+        dense path compute eagerly."""
         with torch.no_grad():
             xd = require_device_input(x, "x")
             path = self.resolved_bits_path(xd.shape[0])
@@ -330,7 +318,5 @@ class _SubmittedMatryoshka:
                 self._pending = None
                 if self._path == "prefilter" and flagged * 2 > self._rows:
                     m._dense_regime = True
-                m.decoder.active_fraction_hint()
-                sparse = True if (self._path == "prefilter" and flagged * 8 <= self._rows) else None
-                self._outs = m.decoder.decode_bits(z, sparse=sparse)
+                self._outs = m.decoder.decode_bits(z)
             return self._outs
