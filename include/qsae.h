@@ -408,6 +408,29 @@ int qsae_coactivation_sparse(const int32_t* idx, const float* val, int B, int k,
 int qsae_quantize_bits(const float* x, int64_t ld, int B, int D, int n_bits, float scale_factor, int is_signed,
                        float* bits, qsae_stream_t stream);
 
+/* -- decoder dictionary comparison (scripts/analysis/analyze_sae.py:24-91, data/load_baseline.py:102-122) ---- */
+/* inv_norm[h] = 1 / max(||atoms[h]||_2, 1e-12), squares summed in fp64 (F.normalize semantics: a zero atom has
+ * cosine 0 with everything).  atoms [H][ld] fp32. */
+int qsae_atom_inv_norms(const float* atoms, int64_t ld, int H, int D, float* inv_norm, qsae_stream_t stream);
+/* Device workspace of qsae_cosine_compare (0 for an invalid shape); in self mode Hb is ignored. */
+size_t qsae_cosine_compare_workspace_bytes(int Ha, int Hb, int self_mode);
+/* Cosine similarities c(i, j) = (a_i . b_j)_fp32-chain * (inv_a[i] * inv_b[j]) of atoms A [Ha][lda] and B [Hb][ldb]
+ * (fp32, 16-byte aligned, D, lda, ldb multiples of 4), reduced without forming the matrix.  Every output is
+ * overwritten.  Keys are (order-preserving bits of c) << 32 | ~index, 0 = none (ties go to the lower index):
+ *   row_best[i] (u64 [Ha]) best (c, j) of row i;  col_best[j] (u64 [Hb]) best (c, i) of column j;
+ *   moments = {sum c, sum c^2} in fp64, summed in a fixed order;  extrema = {key(max), ~key(min)} (32-bit keys);
+ *   counts[t] = #pairs with c > thresholds[t] (n_thresholds <= 8, thresholds in host memory);
+ *   hist[b] (bins <= 4096, NULL when 0): #pairs with clamp(floor((c + 1) * (bins / 2)), 0, bins - 1) == b (fp32);
+ *   out (nullable): c stored into [Ha][out_ld].
+ * self_mode != 0: B is A (B, ldb, Hb, col_best ignored); only pairs i < j count, a pair updates row_best[i] with
+ * (c, j) and row_best[j] with (c, i); `out` then receives the tiles on and above the diagonal only (c(j, i) == c(i, j)
+ * bit for bit, the caller mirrors). */
+int qsae_cosine_compare(const float* A, int64_t lda, int Ha, const float* B, int64_t ldb, int Hb, int D, int self_mode,
+                        const float* thresholds, int n_thresholds, int bins, unsigned long long* row_best,
+                        unsigned long long* col_best, double* moments, unsigned long long* extrema,
+                        unsigned long long* counts, unsigned long long* hist, float* out, int64_t out_ld,
+                        void* workspace, size_t workspace_bytes, qsae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

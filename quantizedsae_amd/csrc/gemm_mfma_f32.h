@@ -323,6 +323,9 @@ struct TileCtx {
     int tid;
     int part;          // which of the map's msplit slices of the R range this workgroup sweeps (0 when it sweeps all of it)
     float* lds_epi;    // epilogue scratch (kLdsFloats floats), after the staging buffers
+    // during finish(): the staging buffer the tile's last K step read (BM + BN rows of BK + 4 floats).  Nothing writes
+    // it before the middle of the next step, so finish() may use it as scratch if it ends with a workgroup barrier.
+    float* lds_free;
 };
 
 // Output row inside a 32x32 MFMA tile held by accumulator register `reg` of this lane.
@@ -334,10 +337,12 @@ __device__ __forceinline__ int mfma_row(int reg, int lane_half) {
 // the second launch-bounds argument (waves per SIMD) makes the register allocator honour that.
 // ABLATE (diagnosis builds only, wrong results): 1 = no global loads / LDS writes inside the K loop,
 // 2 = additionally no LDS fragment reads (operands stay in registers): isolates the MFMA stream.
-template <class LA, class LB, class Epi, int BM, int BN, int BK, int ABLATE = 0>
+// Map: the workgroup -> (Cm panel, R tile range) mapping; SweepMap unless a caller brings its own with the same
+// members (sweep, stagger, locate) -- e.g. the upper-triangular map of the dictionary self-comparison.
+template <class LA, class LB, class Epi, int BM, int BN, int BK, int ABLATE = 0, class Map = SweepMap>
 __global__ void __launch_bounds__(kGemmThreads, (BM * BN <= 128 * 128) ? 2 : 1)
 gemm_nt_f32_kernel(typename LA::Args la, typename LB::Args lb, typename Epi::Args ea, int M, int N,
-                   int K, SweepMap map) {
+                   int K, Map map) {
     using G = TileGeom<BK>;
     constexpr int WTM = BM / 2, WTN = BN / 2;      // per-wave tile
     constexpr int MT = WTM / 32, NT = WTN / 32;    // MFMA tiles per wave
@@ -476,6 +481,7 @@ gemm_nt_f32_kernel(typename LA::Args la, typename LB::Args lb, typename Epi::Arg
         if (Epi::kCheckpoints) epi.checkpoint(ea, acc, ctx, (kt + 1) * BK);
         __syncthreads();
         if (++kt == nk) {
+            ctx.lds_free = smem + P * (TILE_A + TILE_B);
             epi.finish(ea, acc, ctx);
             kt = 0;
             ++tile;

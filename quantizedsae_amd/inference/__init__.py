@@ -7,3 +7,4 @@ from .framework import (  # noqa: F401
     compute_reconstruction_error,
     load_sae,
 )
+from .dictionary import compare_decoders, decoder_atoms, decoder_cosine_similarity  # noqa: F401,E402

@@ -942,3 +942,80 @@ def quantize_bits(x: torch.Tensor, n_bits: int, scale_factor: float, signed: boo
     check(_lib.load().qsae_quantize_bits(_p(x), D, B, D, int(n_bits), float(scale_factor), 1 if signed else 0, _p(out),
                                          _stream()))
     return out
+
+
+# ---- decoder dictionary comparison -----------------------------------------------------------
+def _atoms(t: torch.Tensor, name: str) -> torch.Tensor:
+    """fp32 [H, D] rows, contiguous and 16-byte aligned, D padded with zero columns to a multiple of 4 (a zero column
+    changes no dot product and no norm)."""
+    t = _f32c(t, name)
+    if t.dim() != 2:
+        raise ValueError(f"{name}: expected [H, D] atoms, got shape {tuple(t.shape)}")
+    if t.shape[1] % 4:
+        t = torch.nn.functional.pad(t, (0, 4 - t.shape[1] % 4))
+    if t.data_ptr() % 16:
+        t = t.clone()
+    return t
+
+
+@_on_tensor_device
+def atom_inv_norms(atoms: torch.Tensor) -> torch.Tensor:
+    """1 / max(||atoms[h]||_2, 1e-12) per row, squares summed in fp64.  fp32 [H]."""
+    atoms = _f32c(atoms, "atoms")
+    H, D = atoms.shape
+    inv = torch.empty((H,), dtype=torch.float32, device=atoms.device)
+    check(_lib.load().qsae_atom_inv_norms(_p(atoms), D, H, D, _p(inv), _stream()))
+    return inv
+
+
+COSINE_MAX_THRESHOLDS, COSINE_MAX_BINS = 8, 4096
+
+
+@_on_tensor_device
+def cosine_compare(A: torch.Tensor, B: Optional[torch.Tensor], thresholds=(), bins: int = 0,
+                   want_matrix: bool = False):
+    """One pass of qsae_cosine_compare over atoms A [Ha, D] and B [Hb, D] (B None: self mode, pairs i < j).
+    Returns (row_best int64 [Ha], col_best int64 [Hb] ([0] in self mode), moments fp64 [2], extrema int64 [2],
+    counts int64 [len(thresholds)], hist int64 [bins], matrix fp32 [Ha, Hb] or [0, 0]); keys as in include/qsae.h.
+    In self mode the matrix is returned whole (the upper triangle mirrored)."""
+    self_mode = B is None
+    if not self_mode:
+        if B.device != A.device:
+            raise ValueError(f"A and B are on different devices ({A.device}, {B.device})")
+        if B.dim() != 2 or A.dim() != 2 or B.shape[1] != A.shape[1]:
+            raise ValueError(f"A and B must be [H, D] atoms of the same D ({tuple(A.shape)}, {tuple(B.shape)})")
+    A = _atoms(A, "A")
+    Bt = A if self_mode else _atoms(B, "B")
+    thresholds = [float(t) for t in thresholds]
+    if len(thresholds) > COSINE_MAX_THRESHOLDS:
+        raise ValueError(f"at most {COSINE_MAX_THRESHOLDS} thresholds")
+    if not 0 <= int(bins) <= COSINE_MAX_BINS:
+        raise ValueError(f"bins must lie in [0, {COSINE_MAX_BINS}]")
+    bins = int(bins)
+    Ha, D = A.shape
+    Hb = Bt.shape[0]
+    if Ha == 0 or Hb == 0:
+        raise ValueError("empty dictionary")
+    dev = A.device
+    i64 = dict(dtype=torch.int64, device=dev)
+    row_best = torch.empty((Ha,), **i64)
+    col_best = torch.empty((0 if self_mode else Hb,), **i64)
+    moments = torch.empty((2,), dtype=torch.float64, device=dev)
+    extrema = torch.empty((2,), **i64)
+    counts = torch.empty((len(thresholds),), **i64)
+    hist = torch.empty((bins,), **i64)
+    matrix = torch.empty((Ha, Hb) if want_matrix else (0, 0), dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    nbytes = lib.qsae_cosine_compare_workspace_bytes(Ha, Hb, 1 if self_mode else 0)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    thr = (C.c_float * max(1, len(thresholds)))(*thresholds)
+    check(lib.qsae_cosine_compare(_p(A), D, Ha, None if self_mode else _p(Bt), D, Hb, D, 1 if self_mode else 0,
+                                  C.cast(thr, C.c_void_p), len(thresholds), bins, _p(row_best),
+                                  None if self_mode else _p(col_best), _p(moments), _p(extrema),
+                                  _p(counts) if thresholds else None, _p(hist) if bins else None,
+                                  _p(matrix) if want_matrix else None, Hb, _p(ws), nbytes, _stream()))
+    if want_matrix and self_mode:
+        # the kernel wrote the tiles on and above the diagonal; c(j, i) == c(i, j) bit for bit
+        upper = torch.triu(matrix)
+        matrix = upper + torch.triu(matrix, 1).t()
+    return row_best, col_best, moments, extrema, counts, hist, matrix

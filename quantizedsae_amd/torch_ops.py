@@ -442,6 +442,26 @@ def _(x, n_bits, scale_factor, signed):
     return _f32((x.shape[0], x.shape[1] * n_bits), x)
 
 
+# ---- decoder dictionary comparison ------------------------------------------------------------------------------------
+@_op("cosine_compare")
+def _cosine_compare(A: Tensor, B: Optional[Tensor], thresholds: List[float], bins: int,
+                    want_matrix: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """-> (row_best [Ha], col_best [Hb] ([0] in self mode, B None), moments fp64 [2], extrema [2], counts [len(thresholds)],
+    hist [bins], matrix [Ha, Hb] or [0, 0]); keys int64 as in qsae_cosine_compare"""
+    return _ops.cosine_compare(A, B, thresholds, bins, want_matrix)
+
+
+@_cosine_compare.register_fake
+def _(A, B, thresholds, bins, want_matrix):
+    Ha = A.shape[0]
+    Hb = Ha if B is None else B.shape[0]
+    i64 = dict(dtype=torch.int64, device=A.device)
+    return (torch.empty((Ha,), **i64), torch.empty((0 if B is None else Hb,), **i64),
+            torch.empty((2,), dtype=torch.float64, device=A.device), torch.empty((2,), **i64),
+            torch.empty((len(thresholds),), **i64), torch.empty((bins,), **i64),
+            _f32((Ha, Hb) if want_matrix else (0, 0), A))
+
+
 Q = torch.ops.qsae
 
 
@@ -637,6 +657,10 @@ def coactivation_sparse(idx, val, H, coact=None):
 
 def quantize_bits(x, n_bits, scale_factor, signed=True):
     return Q.quantize_bits(x, int(n_bits), float(scale_factor), bool(signed))
+
+
+def cosine_compare(A, B=None, thresholds=(), bins=0, want_matrix=False):
+    return Q.cosine_compare(A, B, [float(t) for t in thresholds], int(bins), bool(want_matrix))
 
 
 # what has no tensor result (shape queries, handles of batches in flight) stays plain Python
