@@ -431,6 +431,43 @@ int qsae_cosine_compare(const float* A, int64_t lda, int Ha, const float* B, int
                         unsigned long long* counts, unsigned long long* hist, float* out, int64_t out_ld,
                         void* workspace, size_t workspace_bytes, qsae_stream_t stream);
 
+/* -- BinarySAE training: the gradient of the soft-decoder forward (sae/binary.py:24-47, 91-103) ----------------- */
+/* Device workspace of qsae_binary_soft_table_polarize (0 for an invalid shape). */
+size_t qsae_binary_soft_table_polarize_workspace_bytes(int H, int D);
+/* table[h][d] as qsae_binary_soft_table computes it, and *polarize (fp32, device) = mean over [H][D][n_bits] of
+ * p (1 - p) 2^b, p = sigmoid(logit): summed in fp64 in a fixed order, divided by H D n_bits in fp64, rounded once --
+ * the value BinarySAE.forward reports, without reading anything back to the host. */
+int qsae_binary_soft_table_polarize(const float* logits, int H, int D, int n_bits, float* table, float* polarize,
+                                    void* workspace, size_t workspace_bytes, qsae_stream_t stream);
+/* Device workspace of qsae_train_csr (0 for an invalid shape). */
+size_t qsae_train_csr_workspace_bytes(int B, int k, int H);
+/* The top-k lists idx [B][k] grouped by unit: offsets[H + 1] (int32), entries[B k] = flat index r k + j of every entry
+ * of unit h at entries[offsets[h] .. offsets[h + 1]), ordered by row.  O(B k + H B / 32), deterministic. */
+int qsae_train_csr(const int32_t* idx, int B, int k, int H, int32_t* offsets, int32_t* entries, void* workspace,
+                   size_t workspace_bytes, qsae_stream_t stream);
+/* Per selected entry: gv[r][j] = g_latent[r][h] + step * <g_recon[r], table[h]>, h = idx[r][j] (g_recon or g_latent
+ * NULL: that term is 0; g_latent is [B][g_latent_ld], ld 0 broadcasts one row); dx (nullable) [B][D] =
+ * sum_j gv[r][j] W_enc[h].  D a multiple of 4 up to 4096, k <= 256. */
+int qsae_train_row_grad(const int32_t* idx, int B, int k, const float* table, int H, int D, float step,
+                        const float* g_recon, const float* g_latent, int64_t g_latent_ld, const float* W_enc, float* gv,
+                        float* dx, qsae_stream_t stream);
+/* Device workspace of qsae_train_unit_grad (0 for an unsupported shape). */
+size_t qsae_train_unit_grad_workspace_bytes(int B, int k, int H, int D);
+/* Over each unit's list (qsae_train_csr): dW_enc[h] = sum gv x[r], db_enc[h] = sum gv,
+ * dInt[h][d] = step sum val g_recon[r][d], and the logit gradient
+ *   dlogits[h][d n + b] = (dInt[h][d] bw[b] + g_polarize 2^b (1 - 2p) / (H D n)) p (1 - p)
+ * (g_recon / g_polarize NULL: 0).  Every row of every non-NULL output is written once; lists longer than 256 entries
+ * are split into chunks whose partials are added in chunk order.  No float atomics: bitwise reproducible. */
+int qsae_train_unit_grad(const int32_t* offsets, const int32_t* entries, const float* val, const float* gv, int B, int k,
+                         const float* x, const float* g_recon, const float* logits, int H, int D, int n_bits, float step,
+                         const float* g_polarize, float* dW_enc, float* db_enc, float* dlogits, void* workspace,
+                         size_t workspace_bytes, qsae_stream_t stream);
+/* Device workspace of qsae_train_col_sum. */
+size_t qsae_train_col_sum_workspace_bytes(int B, int D);
+/* out[d] = sum_r g[r][d] in a fixed order (the decoder-bias gradient). */
+int qsae_train_col_sum(const float* g, int B, int D, float* out, void* workspace, size_t workspace_bytes,
+                       qsae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

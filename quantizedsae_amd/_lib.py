@@ -106,6 +106,16 @@ SIGNATURES = {
     "qsae_cosine_compare_workspace_bytes": (_sz, [_i, _i, _i]),
     "qsae_cosine_compare": (_i, [_vp, _i64, _i, _vp, _i64, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
                                  _vp, _sz, _vp]),
+    "qsae_binary_soft_table_polarize_workspace_bytes": (_sz, [_i, _i]),
+    "qsae_binary_soft_table_polarize": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "qsae_train_csr_workspace_bytes": (_sz, [_i, _i, _i]),
+    "qsae_train_csr": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "qsae_train_row_grad": (_i, [_vp, _i, _i, _vp, _i, _i, _f, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "qsae_train_unit_grad_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "qsae_train_unit_grad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _sz,
+                                  _vp]),
+    "qsae_train_col_sum_workspace_bytes": (_sz, [_i, _i]),
+    "qsae_train_col_sum": (_i, [_vp, _i, _i, _vp, _vp, _sz, _vp]),
 }
 
 

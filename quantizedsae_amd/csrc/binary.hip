@@ -39,7 +39,7 @@ pack_binary_kernel(const float* __restrict__ logits, int H, int D, int n, int fw
                 const float w = lrow[d * n + b];
                 code |= (sig_gt_half(w) ? 1u : 0u) << b;
                 if (stats) {
-                    const float p = 1.0f / (1.0f + expf(-w));
+                    const float p = soft_bit_prob(w);
                     psum += static_cast<double>(p * (1.0f - p) * static_cast<float>(1u << b));
                     soft = soft + p * ((b == n - 1) ? -static_cast<float>(1u << b) : static_cast<float>(1u << b));
                 }
@@ -85,7 +85,7 @@ soft_table_kernel(const float* __restrict__ logits, int H, int D, int n, float* 
     const float* l = logits + gid * n;
     float acc = 0.0f;
     for (int b = 0; b < n; ++b) {
-        const float p = 1.0f / (1.0f + expf(-l[b]));
+        const float p = soft_bit_prob(l[b]);
         const float bw = (b == n - 1) ? -static_cast<float>(1u << b) : static_cast<float>(1u << b);
         acc = acc + p * bw;
     }

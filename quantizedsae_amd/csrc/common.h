@@ -104,6 +104,8 @@ SweepProfile take_sweep_profile();                // misc.hip: the calling threa
 #define QSAE_SIG_GE_BITS 0xB43FFFFEu
 
 __device__ __forceinline__ bool sig_gt_half(float w) { return w >= __uint_as_float(QSAE_SIG_GT_BITS); }
+// sigmoid of a decoder-bit logit as the soft table, the polarize sum and the training backward all round it
+__device__ __forceinline__ float soft_bit_prob(float w) { return 1.0f / (1.0f + expf(-w)); }
 __device__ __forceinline__ bool sig_ge_half(float w) { return w >= __uint_as_float(QSAE_SIG_GE_BITS); }
 
 // Monotone map float -> uint32 (larger float -> larger key); NaN above +inf; -0 == +0.

@@ -1,0 +1,579 @@
+// train.hip -- the gradient of the BinarySAE forward (reference: sae/binary.py:24-47, 91-103; the b_sae branch of
+// training/trainer.py:144-153), computed from the k selected latents of each row instead of dense [B, H] tensors.
+//
+// Notation: S = selected entries (r, j) -> h = idx[r][j], v = val[r][j]; T = soft table [H][D]; step = gamma / 2^(n-1);
+// p = sigmoid(logit); bw = [1, 2, .., -2^(n-1)]; gR, gL, gP = incoming gradients of recon [B][D], sparse latent [B][H],
+// polarize [].
+//   gv[r][j]       = gL[r][h] + step * <gR[r], T[h]>
+//   dW_enc[h]      = sum over S with idx = h of gv * x[r];   db_enc[h] = sum of gv
+//   dx[r]          = sum_j gv[r][j] * W_enc[h]
+//   dInt[h][d]     = step * sum over S with idx = h of v * gR[r][d]
+//   dlogit[h][d n + b] = (dInt[h][d] bw[b] + gP 2^b (1 - 2p) / (H D n)) p (1 - p)
+//   db_dec[d]      = sum_r gR[r][d]
+//
+// Every sum runs in a fixed order (no float atomics): gradients are bitwise reproducible.  The only atomics are the
+// integer ORs that mark (unit, row) pairs in the CSR build, whose result does not depend on their order.
+#include "common.h"
+
+namespace qsae {
+
+constexpr int kTrainChunk = 256;        // entries of a unit list one workgroup sums; longer lists are split
+constexpr int kTrainMaxD = 4096;
+constexpr int kTrainMaxK = 256;
+constexpr int kColRows = 256;           // rows per partial of the column sum
+constexpr size_t kTrainAlign = 256;
+
+typedef float tr_f32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ int clamp_unit(int h, int H) { return h < 0 ? 0 : (h >= H ? H - 1 : h); }
+__device__ __forceinline__ tr_f32x4 ld4(const float* p) { return *reinterpret_cast<const tr_f32x4*>(p); }
+__device__ __forceinline__ void st4(float* p, tr_f32x4 v) { *reinterpret_cast<tr_f32x4*>(p) = v; }
+__device__ __forceinline__ tr_f32x4 fma4(float a, tr_f32x4 w, tr_f32x4 acc) {
+    tr_f32x4 r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) r[e] = fmaf(a, w[e], acc[e]);
+    return r;
+}
+
+__host__ __device__ inline int list_chunks(int len) { return len <= kTrainChunk ? 1 : (len + kTrainChunk - 1) / kTrainChunk; }
+
+// ---- soft table + polarize ------------------------------------------------------------------------------------------
+// table as soft_table_kernel (binary.hip) computes it, plus one fp64 partial of sum p (1 - p) 2^b per workgroup, with the
+// same per-term rounding as pack_binary_kernel; pol_final_kernel adds the partials in index order.
+__global__ void __launch_bounds__(256)
+soft_table_pol_kernel(const float* __restrict__ logits, int H, int D, int n, float* __restrict__ table,
+                      double* __restrict__ partial) {
+    __shared__ double s_w[4];
+    const long long gid = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+    double ps = 0.0;
+    if (gid < static_cast<long long>(H) * D) {
+        const float* l = logits + gid * n;
+        float acc = 0.0f;
+        for (int b = 0; b < n; ++b) {
+            const float p = soft_bit_prob(l[b]);
+            const float bw = (b == n - 1) ? -static_cast<float>(1u << b) : static_cast<float>(1u << b);
+            acc = acc + p * bw;
+            ps += static_cast<double>(p * (1.0f - p) * static_cast<float>(1u << b));
+        }
+        table[gid] = acc;
+    }
+    for (int off = 32; off > 0; off >>= 1) ps += __shfl_down(ps, off, 64);
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = ps;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+}
+
+__global__ void __launch_bounds__(1024)
+pol_final_kernel(const double* __restrict__ partial, int nb, double count, float* __restrict__ out) {
+    __shared__ double s_w[16];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nb; i += 1024) s += partial[i];
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int w = 0; w < 16; ++w) t += s_w[w];
+        out[0] = static_cast<float>(t / count);      // (sum / numel) in fp64, then fp32: what BinarySAE.forward returns
+    }
+}
+
+// ---- top-k lists by unit (CSR) ----------------------------------------------------------------------------------------
+// bitmap[h][w] bit (r & 31) of word w = r >> 5: row r selected unit h.  prefix[h][w] = set bits of row h before word w.
+// The position of entry (r, j) in unit h's list is offsets[h] + (rows before r that selected h): lists come out ordered by
+// row, whatever order the threads ran in.
+__global__ void __launch_bounds__(256)
+csr_mark_kernel(const int32_t* __restrict__ idx, long long Bk, int k, int H, int W, uint32_t* __restrict__ bitmap) {
+    const long long e = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (e >= Bk) return;
+    const int h = clamp_unit(idx[e], H);
+    const int r = static_cast<int>(e / k);
+    atomicOr(bitmap + static_cast<long long>(h) * W + (r >> 5), 1u << (r & 31));
+}
+
+// one wave per unit: inclusive wave scan of the word popcounts, carried across rounds of 64 words
+__global__ void __launch_bounds__(256)
+csr_count_kernel(const uint32_t* __restrict__ bitmap, int H, int W, int* __restrict__ prefix, int* __restrict__ counts) {
+    const int lane = threadIdx.x & 63;
+    const int h = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (h >= H) return;                                    // wave-uniform
+    const uint32_t* row = bitmap + static_cast<long long>(h) * W;
+    int* pre = prefix + static_cast<long long>(h) * W;
+    int carry = 0;
+    for (int w0 = 0; w0 < W; w0 += 64) {                   // every lane runs every round
+        const int w = w0 + lane;
+        const int c = w < W ? __popc(row[w]) : 0;
+        int incl = c;
+        for (int off = 1; off < 64; off <<= 1) {
+            const int t = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += t;
+        }
+        if (w < W) pre[w] = carry + incl - c;
+        carry += __shfl(incl, 63, 64);
+    }
+    if (lane == 0) counts[h] = carry;
+}
+
+// Exclusive scan of n values into out[0..n] (out[n] = total), one workgroup.  MODE 0: the values are in[i]; MODE 1: the
+// number of chunks of list i, from the list offsets in[0..n].
+template <int MODE>
+__global__ void __launch_bounds__(1024)
+scan_kernel(const int* __restrict__ in, int n, int* __restrict__ out) {
+    __shared__ int s_w[16];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int per = (n + 1023) / 1024;
+    const int beg = min(n, t * per), end = min(n, beg + per);
+    auto value = [&](int i) { return MODE == 0 ? in[i] : list_chunks(in[i + 1] - in[i]); };
+    int s = 0;
+    for (int i = beg; i < end; ++i) s += value(i);
+    int incl = s;
+    for (int off = 1; off < 64; off <<= 1) {
+        const int u = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += u;
+    }
+    if (lane == 63) s_w[wave] = incl;
+    __syncthreads();
+    int base = 0;
+    for (int w = 0; w < wave; ++w) base += s_w[w];
+    int run = base + incl - s;
+    for (int i = beg; i < end; ++i) {
+        out[i] = run;
+        run += value(i);
+    }
+    if (t == 1023) out[n] = run;
+}
+
+__global__ void __launch_bounds__(256)
+csr_fill_kernel(const int32_t* __restrict__ idx, long long Bk, int k, int H, int W, const uint32_t* __restrict__ bitmap,
+                const int* __restrict__ prefix, const int* __restrict__ offsets, int* __restrict__ entries) {
+    const long long e = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (e >= Bk) return;
+    const int h = clamp_unit(idx[e], H);
+    const int r = static_cast<int>(e / k);
+    const long long wi = static_cast<long long>(h) * W + (r >> 5);
+    // bit r of row h is set, so pos < offsets[h] + count[h] <= Bk
+    const int pos = offsets[h] + prefix[wi] + __popc(bitmap[wi] & ((1u << (r & 31)) - 1u));
+    entries[pos] = static_cast<int>(e);
+}
+
+// ---- row kernel: gv and dx --------------------------------------------------------------------------------------------
+// One wave per row, four rows per workgroup.  Lane l owns columns 4 (l + 64 i) .. + 3; each dot product is the lane's
+// chain over its columns, then a butterfly (every lane of the wave takes part in every shuffle, whatever D is).
+constexpr int kRowWaves = 4;
+
+__global__ void __launch_bounds__(64 * kRowWaves)
+train_row_kernel(const int32_t* __restrict__ idx, int B, int k, int H, int D, const float* __restrict__ table, float step,
+                 const float* __restrict__ gR, const float* __restrict__ gL, long long gl_ld,
+                 const float* __restrict__ Wenc, float* __restrict__ gv, float* __restrict__ dx) {
+    __shared__ int s_h[kRowWaves][kTrainMaxK];
+    __shared__ float s_g[kRowWaves][kTrainMaxK];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r = blockIdx.x * kRowWaves + wave;
+    const bool active = r < B;
+    const int D4 = D / 4;
+    if (active)
+        for (int j = lane; j < k; j += 64) s_h[wave][j] = clamp_unit(idx[static_cast<long long>(r) * k + j], H);
+    __syncthreads();
+    if (active) {
+        const float* g = gR ? gR + static_cast<long long>(r) * D : nullptr;
+        for (int j0 = 0; j0 < k; j0 += 4) {
+            float part[4] = {0.f, 0.f, 0.f, 0.f};
+            if (g) {
+                int hh[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) hh[u] = s_h[wave][min(j0 + u, k - 1)];
+                for (int c = lane; c < D4; c += 64) {
+                    const tr_f32x4 a = ld4(g + 4 * c);
+                    tr_f32x4 t[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) t[u] = ld4(table + static_cast<long long>(hh[u]) * D + 4 * c);
+#pragma unroll
+                    for (int u = 0; u < 4; ++u)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) part[u] = fmaf(a[e], t[u][e], part[u]);
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+                    for (int off = 32; off > 0; off >>= 1) part[u] += __shfl_xor(part[u], off, 64);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int j = j0 + u;
+                if (j < k) {
+                    float val = g ? step * part[u] : 0.0f;
+                    if (gL) val = gL[static_cast<long long>(r) * gl_ld + s_h[wave][j]] + val;
+                    if (lane == 0) {
+                        gv[static_cast<long long>(r) * k + j] = val;
+                        s_g[wave][j] = val;
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (active && dx) {
+        for (int c = lane; c < D4; c += 64) {
+            tr_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            for (int j = 0; j < k; ++j)
+                acc = fma4(s_g[wave][j], ld4(Wenc + static_cast<long long>(s_h[wave][j]) * D + 4 * c), acc);
+            st4(dx + static_cast<long long>(r) * D + 4 * c, acc);
+        }
+    }
+}
+
+// ---- unit kernels: dW_enc, db_enc, dInt and the logit-gradient row ---------------------------------------------------
+struct UnitArgs {
+    const int* offsets;     // [H + 1] list offsets (qsae_train_csr)
+    const int* entries;     // [B k] flat entry indices r k + j, grouped by unit, ordered by row
+    const int* chunk_off;   // [H + 1] chunk offsets (list_chunks of every list, scanned)
+    const float* val;       // [B k]
+    const float* gv;        // [B k]
+    long long Bk;
+    int k, H, D, n;
+    const float* x;         // [B][D]
+    const float* gR;        // [B][D] or nullptr
+    const float* logits;    // [H][D n]
+    float step;
+    const float* gP;        // device scalar or nullptr
+    double pol_count;       // H D n
+    float* dW;              // [H][D] or nullptr
+    float* db;              // [H] or nullptr
+    float* dlogit;          // [H][D n] or nullptr
+    float* slab;            // [slab_rows][slab_ld]: partials of the chunks of split lists
+    int slab_rows, slab_ld;
+};
+
+// dlogit row h from s_dint[D] (dInt, step applied); the whole workgroup calls it
+__device__ __forceinline__ void unit_logit_row(const UnitArgs& a, int h, const float* s_dint) {
+    const int n = a.n, Dn4 = a.D * n / 4;
+    const float pcoef = a.gP ? static_cast<float>(static_cast<double>(a.gP[0]) / a.pol_count) : 0.0f;
+    const float* L = a.logits + static_cast<long long>(h) * a.D * n;
+    float* G = a.dlogit + static_cast<long long>(h) * a.D * n;
+    for (int i4 = threadIdx.x; i4 < Dn4; i4 += blockDim.x) {
+        const tr_f32x4 l = ld4(L + 4 * i4);
+        tr_f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int i = 4 * i4 + e;
+            const int d = i / n, b = i - d * n;
+            const float p = soft_bit_prob(l[e]);
+            const float pw = static_cast<float>(1u << b);
+            const float bw = (b == n - 1) ? -pw : pw;
+            const float t = s_dint[d] * bw + pcoef * (pw * (1.0f - 2.0f * p));
+            o[e] = t * (p * (1.0f - p));
+        }
+        st4(G + 4 * i4, o);
+    }
+}
+
+// One workgroup per chunk of a unit list (every unit has at least one chunk, empty lists included).  A unit with one
+// chunk is finished here; the chunks of a split list store their partials in the slab for unit_final_kernel.
+__global__ void __launch_bounds__(256)
+unit_chunk_kernel(UnitArgs a) {
+    extern __shared__ float s_dint[];                      // [D]
+    __shared__ int s_r[kTrainChunk];
+    __shared__ float s_v[kTrainChunk], s_gv[kTrainChunk];
+    const int g = blockIdx.x;
+    if (g >= a.chunk_off[a.H]) return;                     // workgroup-uniform: the grid is an upper bound
+    int lo = 0, hi = a.H - 1;                              // the unit: largest h with chunk_off[h] <= g
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (a.chunk_off[mid] <= g) lo = mid;
+        else hi = mid - 1;
+    }
+    const int h = lo;
+    const int c = g - a.chunk_off[h], nch = a.chunk_off[h + 1] - a.chunk_off[h];
+    const int beg = a.offsets[h] + c * kTrainChunk;
+    const int len = max(0, min(beg + kTrainChunk, a.offsets[h + 1]) - beg);
+    for (int i = threadIdx.x; i < len; i += blockDim.x) {
+        long long e = a.entries[beg + i];
+        e = e < 0 ? 0 : (e >= a.Bk ? a.Bk - 1 : e);
+        s_r[i] = static_cast<int>(e / a.k);
+        s_v[i] = a.val[e];
+        s_gv[i] = a.gv[e];
+    }
+    __syncthreads();
+    const int D = a.D, D4 = D / 4;
+    const int row = 2 * (a.chunk_off[h] - h) + c;          // slab row of a split list's chunk (< slab_rows, see host)
+    const bool split = nch > 1;
+    float* srow = (split && row < a.slab_rows) ? a.slab + static_cast<long long>(row) * a.slab_ld : nullptr;
+    for (int c4 = threadIdx.x; c4 < D4; c4 += blockDim.x) {
+        tr_f32x4 w = {0.f, 0.f, 0.f, 0.f}, s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+        for (int i = 0; i < len; ++i) {
+            const long long ro = static_cast<long long>(s_r[i]) * D + 4 * c4;
+            w = fma4(s_gv[i], ld4(a.x + ro), w);
+            if (a.gR) s = fma4(s_v[i], ld4(a.gR + ro), s);
+        }
+        if (!split) {
+            if (a.dW) st4(a.dW + static_cast<long long>(h) * D + 4 * c4, w);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) s_dint[4 * c4 + e] = a.step * s[e];
+        } else if (srow) {
+            st4(srow + 4 * c4, w);
+            st4(srow + D + 4 * c4, s);
+        }
+    }
+    if (threadIdx.x == 0) {
+        float db = 0.0f;
+        for (int i = 0; i < len; ++i) db += s_gv[i];
+        if (!split) {
+            if (a.db) a.db[h] = db;
+        } else if (srow) {
+            srow[2 * D] = db;
+        }
+    }
+    if (!split && a.dlogit) {
+        __syncthreads();
+        unit_logit_row(a, h, s_dint);
+    }
+}
+
+// Units whose list was split: add the chunk partials in chunk order, then finish as above.
+__global__ void __launch_bounds__(256)
+unit_final_kernel(UnitArgs a) {
+    extern __shared__ float s_dint[];
+    const int h = blockIdx.x;
+    const int nch = a.chunk_off[h + 1] - a.chunk_off[h];
+    if (nch <= 1) return;                                  // workgroup-uniform
+    const int row0 = 2 * (a.chunk_off[h] - h);
+    const int rows = min(nch, a.slab_rows - row0);
+    const int D = a.D, D4 = D / 4;
+    for (int c4 = threadIdx.x; c4 < D4; c4 += blockDim.x) {
+        tr_f32x4 w = {0.f, 0.f, 0.f, 0.f}, s = {0.f, 0.f, 0.f, 0.f};
+        for (int c = 0; c < rows; ++c) {
+            const float* srow = a.slab + static_cast<long long>(row0 + c) * a.slab_ld;
+            w += ld4(srow + 4 * c4);
+            s += ld4(srow + D + 4 * c4);
+        }
+        if (a.dW) st4(a.dW + static_cast<long long>(h) * D + 4 * c4, w);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s_dint[4 * c4 + e] = a.step * s[e];
+    }
+    if (threadIdx.x == 0 && a.db) {
+        float db = 0.0f;
+        for (int c = 0; c < rows; ++c) db += a.slab[static_cast<long long>(row0 + c) * a.slab_ld + 2 * D];
+        a.db[h] = db;
+    }
+    if (a.dlogit) {
+        __syncthreads();
+        unit_logit_row(a, h, s_dint);
+    }
+}
+
+// ---- column sum (db_dec) ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+col_sum_partial_kernel(const float* __restrict__ g, int B, int D, float* __restrict__ partial) {
+    const int d = blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= D) return;
+    const int r0 = blockIdx.y * kColRows, r1 = min(B, r0 + kColRows);
+    float s = 0.0f;
+    for (int r = r0; r < r1; ++r) s += g[static_cast<long long>(r) * D + d];
+    partial[static_cast<long long>(blockIdx.y) * D + d] = s;
+}
+
+__global__ void __launch_bounds__(256)
+col_sum_final_kernel(const float* __restrict__ partial, int nparts, int D, float* __restrict__ out) {
+    const int d = blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= D) return;
+    float s = 0.0f;
+    for (int p = 0; p < nparts; ++p) s += partial[static_cast<long long>(p) * D + d];
+    out[d] = s;
+}
+
+// ---- workspace layouts -----------------------------------------------------------------------------------------------
+inline size_t align_up(size_t v) { return (v + kTrainAlign - 1) / kTrainAlign * kTrainAlign; }
+
+struct CsrLayout {
+    size_t bitmap, prefix, counts, total;
+    int W;
+};
+inline CsrLayout csr_layout(int B, int H) {
+    CsrLayout L;
+    L.W = (B + 31) / 32;
+    const size_t words = static_cast<size_t>(H) * static_cast<size_t>(L.W < 1 ? 1 : L.W);
+    L.bitmap = 0;
+    L.prefix = align_up(words * 4);
+    L.counts = L.prefix + align_up(words * 4);
+    L.total = L.counts + align_up(static_cast<size_t>(H) * 4);
+    return L;
+}
+
+struct UnitLayout {
+    size_t chunk_off, slab, total;
+    int slab_rows, slab_ld;
+};
+inline UnitLayout unit_layout(long long Bk, int H, int D) {
+    UnitLayout L;
+    // rows of split lists: 2 (chunk_off[h] - h) + c < 2 sum (list_chunks - 1) <= 2 Bk / kTrainChunk
+    L.slab_rows = static_cast<int>(2 * ((Bk + kTrainChunk - 1) / kTrainChunk) + 1);
+    L.slab_ld = 2 * D + 4;                                 // [dW partial | sum v gR | db], rows 16-byte aligned
+    L.chunk_off = 0;
+    L.slab = align_up(static_cast<size_t>(H + 1) * 4);
+    L.total = L.slab + align_up(static_cast<size_t>(L.slab_rows) * L.slab_ld * 4);
+    return L;
+}
+
+inline bool train_shape_ok(int D) { return D > 0 && D % 4 == 0 && D <= kTrainMaxD; }
+
+}  // namespace qsae
+
+using namespace qsae;
+
+extern "C" size_t qsae_binary_soft_table_polarize_workspace_bytes(int H, int D) {
+    if (H <= 0 || D <= 0) return 0;
+    const long long blocks = (static_cast<long long>(H) * D + 255) / 256;
+    return static_cast<size_t>(blocks) * sizeof(double);
+}
+
+extern "C" int qsae_binary_soft_table_polarize(const float* logits, int H, int D, int n_bits, float* table,
+                                               float* polarize, void* workspace, size_t workspace_bytes,
+                                               qsae_stream_t stream) {
+    QSAE_CHECK_ARG(H > 0 && D > 0, "H > 0 and D > 0 required");
+    QSAE_CHECK_ARG(n_bits >= 1 && n_bits <= 8, "1 <= n_bits <= 8 required");
+    QSAE_CHECK_ARG(logits && table && polarize && workspace, "null pointer");
+    const size_t need = qsae_binary_soft_table_polarize_workspace_bytes(H, D);
+    if (workspace_bytes < need) return fail(QSAE_ERR_WORKSPACE, "%s: workspace too small", __func__);
+    const long long blocks = (static_cast<long long>(H) * D + 255) / 256;
+    QSAE_CHECK_SUPPORTED(blocks < (1LL << 31), "H * D < 2^39");
+    hipStream_t s = as_stream(stream);
+    double* partial = static_cast<double*>(workspace);
+    hipLaunchKernelGGL(soft_table_pol_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, logits, H, D, n_bits,
+                       table, partial);
+    QSAE_LAUNCH_CHECK();
+    hipLaunchKernelGGL(pol_final_kernel, dim3(1), dim3(1024), 0, s, partial, static_cast<int>(blocks),
+                       static_cast<double>(H) * D * n_bits, polarize);
+    QSAE_LAUNCH_CHECK();
+    return QSAE_OK;
+}
+
+extern "C" size_t qsae_train_csr_workspace_bytes(int B, int k, int H) {
+    if (B < 0 || k < 0 || H <= 0) return 0;
+    return csr_layout(B, H).total;
+}
+
+extern "C" int qsae_train_csr(const int32_t* idx, int B, int k, int H, int32_t* offsets, int32_t* entries,
+                              void* workspace, size_t workspace_bytes, qsae_stream_t stream) {
+    QSAE_CHECK_ARG(B >= 0 && k >= 0 && H > 0, "B >= 0, k >= 0, H > 0 required");
+    QSAE_CHECK_ARG(offsets && workspace, "null pointer");
+    const long long Bk = static_cast<long long>(B) * k;
+    QSAE_CHECK_SUPPORTED(Bk < (1LL << 31), "B * k < 2^31");
+    QSAE_CHECK_ARG(Bk == 0 || (idx && entries), "null pointer");
+    const CsrLayout L = csr_layout(B, H);
+    if (workspace_bytes < L.total) return fail(QSAE_ERR_WORKSPACE, "%s: workspace too small", __func__);
+    hipStream_t s = as_stream(stream);
+    char* ws = static_cast<char*>(workspace);
+    uint32_t* bitmap = reinterpret_cast<uint32_t*>(ws + L.bitmap);
+    int* prefix = reinterpret_cast<int*>(ws + L.prefix);
+    int* counts = reinterpret_cast<int*>(ws + L.counts);
+    if (Bk == 0) {
+        QSAE_HIP(hipMemsetAsync(counts, 0, static_cast<size_t>(H) * 4, s));
+    } else {
+        QSAE_HIP(hipMemsetAsync(bitmap, 0, static_cast<size_t>(H) * L.W * 4, s));
+        const unsigned eb = static_cast<unsigned>((Bk + 255) / 256);
+        hipLaunchKernelGGL(csr_mark_kernel, dim3(eb), dim3(256), 0, s, idx, Bk, k, H, L.W, bitmap);
+        QSAE_LAUNCH_CHECK();
+        hipLaunchKernelGGL(csr_count_kernel, dim3((H + 3) / 4), dim3(256), 0, s, bitmap, H, L.W, prefix, counts);
+        QSAE_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(scan_kernel<0>, dim3(1), dim3(1024), 0, s, counts, H, offsets);
+    QSAE_LAUNCH_CHECK();
+    if (Bk > 0) {
+        const unsigned eb = static_cast<unsigned>((Bk + 255) / 256);
+        hipLaunchKernelGGL(csr_fill_kernel, dim3(eb), dim3(256), 0, s, idx, Bk, k, H, L.W, bitmap, prefix, offsets, entries);
+        QSAE_LAUNCH_CHECK();
+    }
+    return QSAE_OK;
+}
+
+extern "C" int qsae_train_row_grad(const int32_t* idx, int B, int k, const float* table, int H, int D, float step,
+                                   const float* g_recon, const float* g_latent, int64_t g_latent_ld, const float* W_enc,
+                                   float* gv, float* dx, qsae_stream_t stream) {
+    QSAE_CHECK_ARG(B >= 0 && k >= 0 && H > 0 && D > 0, "B >= 0, k >= 0, H > 0, D > 0 required");
+    QSAE_CHECK_SUPPORTED(train_shape_ok(D), "D a multiple of 4, at most 4096");
+    QSAE_CHECK_SUPPORTED(k <= kTrainMaxK, "k <= 256");
+    if (B == 0) return QSAE_OK;
+    if (k == 0) {                                          // nothing selected: dx = 0
+        if (dx) QSAE_HIP(hipMemsetAsync(dx, 0, static_cast<size_t>(B) * D * 4, as_stream(stream)));
+        return QSAE_OK;
+    }
+    QSAE_CHECK_ARG(idx && table && gv, "null pointer");
+    QSAE_CHECK_ARG(!dx || W_enc, "dx needs W_enc");
+    QSAE_CHECK_ARG(aligned16(table) && (!g_recon || aligned16(g_recon)) && (!dx || (aligned16(dx) && aligned16(W_enc))),
+                   "table, g_recon, W_enc and dx must be 16-byte aligned");
+    QSAE_CHECK_ARG(!g_latent || g_latent_ld >= 0, "g_latent_ld >= 0 required");
+    hipLaunchKernelGGL(train_row_kernel, dim3((B + kRowWaves - 1) / kRowWaves), dim3(64 * kRowWaves), 0,
+                       as_stream(stream), idx, B, k, H, D, table, step, g_recon, g_latent,
+                       static_cast<long long>(g_latent_ld), W_enc, gv, dx);
+    QSAE_LAUNCH_CHECK();
+    return QSAE_OK;
+}
+
+extern "C" size_t qsae_train_unit_grad_workspace_bytes(int B, int k, int H, int D) {
+    if (B < 0 || k < 0 || H <= 0 || !train_shape_ok(D)) return 0;
+    return unit_layout(static_cast<long long>(B) * k, H, D).total;
+}
+
+extern "C" int qsae_train_unit_grad(const int32_t* offsets, const int32_t* entries, const float* val, const float* gv,
+                                    int B, int k, const float* x, const float* g_recon, const float* logits, int H, int D,
+                                    int n_bits, float step, const float* g_polarize, float* dW_enc, float* db_enc,
+                                    float* dlogits, void* workspace, size_t workspace_bytes, qsae_stream_t stream) {
+    QSAE_CHECK_ARG(B >= 0 && k >= 0 && H > 0 && D > 0, "B >= 0, k >= 0, H > 0, D > 0 required");
+    QSAE_CHECK_ARG(n_bits >= 1 && n_bits <= 8, "1 <= n_bits <= 8 required");
+    QSAE_CHECK_SUPPORTED(train_shape_ok(D), "D a multiple of 4, at most 4096");
+    const long long Bk = static_cast<long long>(B) * k;
+    QSAE_CHECK_SUPPORTED(Bk < (1LL << 31), "B * k < 2^31");
+    QSAE_CHECK_ARG(offsets && workspace, "null pointer");
+    QSAE_CHECK_ARG(Bk == 0 || (entries && val && gv && x), "null pointer");
+    QSAE_CHECK_ARG(!dlogits || logits, "dlogits needs logits");
+    QSAE_CHECK_ARG((!x || aligned16(x)) && (!g_recon || aligned16(g_recon)) && (!dW_enc || aligned16(dW_enc)) &&
+                   (!dlogits || (aligned16(dlogits) && aligned16(logits))),
+                   "x, g_recon, logits, dW_enc and dlogits must be 16-byte aligned");
+    const UnitLayout L = unit_layout(Bk, H, D);
+    if (workspace_bytes < L.total) return fail(QSAE_ERR_WORKSPACE, "%s: workspace too small", __func__);
+    hipStream_t s = as_stream(stream);
+    char* ws = static_cast<char*>(workspace);
+    int* chunk_off = reinterpret_cast<int*>(ws + L.chunk_off);
+    hipLaunchKernelGGL(scan_kernel<1>, dim3(1), dim3(1024), 0, s, offsets, H, chunk_off);
+    QSAE_LAUNCH_CHECK();
+    UnitArgs a{offsets, entries, chunk_off, val, gv, Bk, k > 0 ? k : 1, H, D, n_bits, x, Bk > 0 ? g_recon : nullptr,
+               logits, step, g_polarize, static_cast<double>(H) * D * n_bits, dW_enc, db_enc, dlogits,
+               reinterpret_cast<float*>(ws + L.slab), L.slab_rows, L.slab_ld};
+    const int D4 = D / 4;
+    const int threads = D4 >= 256 ? 256 : ((D4 + 63) / 64) * 64;
+    const size_t lds = static_cast<size_t>(D) * 4;
+    const long long grid = static_cast<long long>(H) + (Bk + kTrainChunk - 1) / kTrainChunk;   // >= number of chunks
+    hipLaunchKernelGGL(unit_chunk_kernel, dim3(static_cast<unsigned>(grid)), dim3(threads), lds, s, a);
+    QSAE_LAUNCH_CHECK();
+    if (Bk > kTrainChunk) {                                // otherwise no list can be split
+        hipLaunchKernelGGL(unit_final_kernel, dim3(H), dim3(threads), lds, s, a);
+        QSAE_LAUNCH_CHECK();
+    }
+    return QSAE_OK;
+}
+
+extern "C" size_t qsae_train_col_sum_workspace_bytes(int B, int D) {
+    if (B < 0 || D <= 0) return 0;
+    const size_t parts = static_cast<size_t>((B + kColRows - 1) / kColRows);
+    return (parts < 1 ? 1 : parts) * static_cast<size_t>(D) * 4;
+}
+
+extern "C" int qsae_train_col_sum(const float* g, int B, int D, float* out, void* workspace, size_t workspace_bytes,
+                                  qsae_stream_t stream) {
+    QSAE_CHECK_ARG(B >= 0 && D > 0, "B >= 0, D > 0 required");
+    QSAE_CHECK_ARG(out && workspace && (B == 0 || g), "null pointer");
+    if (workspace_bytes < qsae_train_col_sum_workspace_bytes(B, D))
+        return fail(QSAE_ERR_WORKSPACE, "%s: workspace too small", __func__);
+    hipStream_t s = as_stream(stream);
+    if (B == 0) {
+        QSAE_HIP(hipMemsetAsync(out, 0, static_cast<size_t>(D) * 4, s));
+        return QSAE_OK;
+    }
+    const int parts = (B + kColRows - 1) / kColRows;
+    float* partial = static_cast<float*>(workspace);
+    hipLaunchKernelGGL(col_sum_partial_kernel, dim3((D + 255) / 256, parts), dim3(256), 0, s, g, B, D, partial);
+    QSAE_LAUNCH_CHECK();
+    hipLaunchKernelGGL(col_sum_final_kernel, dim3((D + 255) / 256), dim3(256), 0, s, partial, parts, D, out);
+    QSAE_LAUNCH_CHECK();
+    return QSAE_OK;
+}

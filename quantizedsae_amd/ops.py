@@ -1019,3 +1019,135 @@ def cosine_compare(A: torch.Tensor, B: Optional[torch.Tensor], thresholds=(), bi
         upper = torch.triu(matrix)
         matrix = upper + torch.triu(matrix, 1).t()
     return row_best, col_best, moments, extrema, counts, hist, matrix
+
+
+# ---- BinarySAE training (the gradient of the soft-decoder forward) ---------------------------------------------------
+# Workspaces come from the caching allocator per call (not the shared _workspaces cache: a backward may run on another
+# thread than the forward).
+TRAIN_MAX_D, TRAIN_MAX_K = 4096, 256
+
+
+def train_supported(D: int, k: int) -> bool:
+    return 0 < D <= TRAIN_MAX_D and D % 4 == 0 and 0 <= k <= TRAIN_MAX_K
+
+
+def _train_ws(nbytes: int, device) -> torch.Tensor:
+    return torch.empty((max(1, int(nbytes)),), dtype=torch.uint8, device=device)
+
+
+@_on_tensor_device
+def binary_soft_table_polarize(logits: torch.Tensor, D: int, n_bits: int):
+    """-> (soft table fp32 [H, D], polarize fp32 0-d): the table of binary_soft_table and the mean p (1 - p) 2^b that
+    BinarySAE.forward reports, both on the device (no host read)."""
+    logits = _f32c(logits, "logits")
+    H = logits.shape[0]
+    if logits.dim() != 2 or logits.shape[1] != D * n_bits:
+        raise ValueError(f"logits is {tuple(logits.shape)}, expected [H, {D * n_bits}]")
+    table = torch.empty((H, D), dtype=torch.float32, device=logits.device)
+    pol = torch.empty((), dtype=torch.float32, device=logits.device)
+    lib = _lib.load()
+    ws = _train_ws(lib.qsae_binary_soft_table_polarize_workspace_bytes(H, D), logits.device)
+    check(lib.qsae_binary_soft_table_polarize(_p(logits), H, D, n_bits, _p(table), _p(pol), _p(ws), ws.numel(), _stream()))
+    return table, pol
+
+
+@_on_tensor_device
+def train_csr(idx: torch.Tensor, H: int):
+    """Top-k lists [B, k] grouped by unit -> (offsets int32 [H + 1], entries int32 [B k]); see qsae_train_csr."""
+    _dev(idx, "idx", torch.int32)
+    idx = idx.contiguous()
+    B, k = idx.shape
+    offsets = torch.empty((H + 1,), dtype=torch.int32, device=idx.device)
+    entries = torch.empty((B * k,), dtype=torch.int32, device=idx.device)
+    lib = _lib.load()
+    ws = _train_ws(lib.qsae_train_csr_workspace_bytes(B, k, H), idx.device)
+    check(lib.qsae_train_csr(_p(idx), B, k, H, _p(offsets), _p(entries), _p(ws), ws.numel(), _stream()))
+    return offsets, entries
+
+
+def _check_train_shape(D: int, k: int) -> None:
+    if not train_supported(D, k):
+        raise ValueError(f"BinarySAE training kernels take D a multiple of 4 up to {TRAIN_MAX_D} and k <= {TRAIN_MAX_K} "
+                         f"(got D = {D}, k = {k})")
+
+
+def _latent_grad(g_latent: Optional[torch.Tensor], B: int, H: int):
+    """(tensor, row stride) of an incoming [B, H] latent gradient with unit column stride (autograd may hand in an
+    expanded tensor: a stride-0 row broadcast is read as is, anything else is made contiguous)."""
+    if g_latent is None:
+        return None, 0
+    _dev(g_latent, "g_latent")
+    if g_latent.dtype != torch.float32:
+        g_latent = g_latent.float()
+    if tuple(g_latent.shape) != (B, H):
+        raise ValueError(f"g_latent is {tuple(g_latent.shape)}, expected [{B}, {H}]")
+    if g_latent.stride(1) != 1 or (g_latent.stride(0) != 0 and g_latent.stride(0) < H):
+        g_latent = g_latent.contiguous()
+    return g_latent, g_latent.stride(0) if B > 1 else H
+
+
+@_on_tensor_device
+def train_row_grad(idx: torch.Tensor, table: torch.Tensor, step: float, g_recon: Optional[torch.Tensor],
+                   g_latent: Optional[torch.Tensor], W_enc: Optional[torch.Tensor], want_dx: bool = False):
+    """-> (gv fp32 [B, k], dx fp32 [B, D] or None); see qsae_train_row_grad."""
+    _dev(idx, "idx", torch.int32)
+    idx = idx.contiguous()
+    table = _f32c(table, "table")
+    B, k = idx.shape
+    H, D = table.shape
+    _check_train_shape(D, k)
+    gR = _f32c(g_recon, "g_recon") if g_recon is not None else None
+    if gR is not None and tuple(gR.shape) != (B, D):
+        raise ValueError(f"g_recon is {tuple(gR.shape)}, expected [{B}, {D}]")
+    gL, gl_ld = _latent_grad(g_latent, B, H)
+    W = _f32c(W_enc, "W_enc") if want_dx else None
+    if W is not None and tuple(W.shape) != (H, D):
+        raise ValueError(f"W_enc is {tuple(W.shape)}, expected [{H}, {D}]")
+    gv = torch.empty((B, k), dtype=torch.float32, device=idx.device)
+    dx = torch.empty((B, D), dtype=torch.float32, device=idx.device) if want_dx else None
+    check(_lib.load().qsae_train_row_grad(_p(idx), B, k, _p(table), H, D, float(step), _p(gR), _p(gL), int(gl_ld),
+                                          _p(W), _p(gv), _p(dx), _stream()))
+    return gv, dx
+
+
+@_on_tensor_device
+def train_unit_grad(offsets: torch.Tensor, entries: torch.Tensor, val: torch.Tensor, gv: torch.Tensor, x: torch.Tensor,
+                    g_recon: Optional[torch.Tensor], logits: torch.Tensor, n_bits: int, step: float,
+                    g_polarize: Optional[torch.Tensor], want_encoder: bool = True, want_logits: bool = True):
+    """-> (dW_enc [H, D], db_enc [H], dlogits [H, D n_bits]), each None when not wanted; see qsae_train_unit_grad."""
+    _dev(offsets, "offsets", torch.int32)
+    _dev(entries, "entries", torch.int32)
+    val, gv, x, logits = _f32c(val, "val"), _f32c(gv, "gv"), _f32c(x, "x"), _f32c(logits, "logits")
+    B, k = val.shape
+    D = x.shape[1]
+    H = offsets.shape[0] - 1
+    _check_train_shape(D, k)
+    if tuple(logits.shape) != (H, D * n_bits) or tuple(x.shape) != (B, D) or tuple(gv.shape) != (B, k) \
+            or entries.numel() != B * k:
+        raise ValueError("train_unit_grad: inconsistent shapes")
+    gR = _f32c(g_recon, "g_recon") if g_recon is not None else None
+    if gR is not None and tuple(gR.shape) != (B, D):
+        raise ValueError(f"g_recon is {tuple(gR.shape)}, expected [{B}, {D}]")
+    gP = _f32c(g_polarize.reshape(()), "g_polarize") if g_polarize is not None else None
+    dev = x.device
+    dW = torch.empty((H, D), dtype=torch.float32, device=dev) if want_encoder else None
+    db = torch.empty((H,), dtype=torch.float32, device=dev) if want_encoder else None
+    dl = torch.empty((H, D * n_bits), dtype=torch.float32, device=dev) if want_logits else None
+    lib = _lib.load()
+    ws = _train_ws(lib.qsae_train_unit_grad_workspace_bytes(B, k, H, D), dev)
+    check(lib.qsae_train_unit_grad(_p(offsets.contiguous()), _p(entries.contiguous()), _p(val), _p(gv), B, k, _p(x), _p(gR),
+                                   _p(logits), H, D, n_bits, float(step), _p(gP), _p(dW), _p(db), _p(dl), _p(ws),
+                                   ws.numel(), _stream()))
+    return dW, db, dl
+
+
+@_on_tensor_device
+def train_col_sum(g: torch.Tensor) -> torch.Tensor:
+    """sum over rows of g [B, D] in a fixed order (the decoder-bias gradient)."""
+    g = _f32c(g, "g")
+    B, D = g.shape
+    out = torch.empty((D,), dtype=torch.float32, device=g.device)
+    lib = _lib.load()
+    ws = _train_ws(lib.qsae_train_col_sum_workspace_bytes(B, D), g.device)
+    check(lib.qsae_train_col_sum(_p(g), B, D, _p(out), _p(ws), ws.numel(), _stream()))
+    return out

@@ -212,16 +212,17 @@ class BinarySAE(ops.GraphForwardMixin, SparseAutoencoder):
         val = torch.empty((B, 0), dtype=torch.float32, device=x.device)
         return idx, val, latent, recon
 
-    def _run(self, x, want_dense: bool):
-        """-> (idx, val, dense latent or None, reconstruction): the one implementation behind forward() and
-        forward_compact()."""
+    def _run(self, x, want_dense: bool, soft_table=None):
+        """-> (idx, val, dense latent or None, reconstruction): the one implementation behind forward(),
+        forward_compact() and forward_train().  soft_table: decode with this fp32 [H, D] table of soft integers (the
+        reference's arithmetic) instead of what decoder.decode_mode resolves to."""
         x = require_device_input(x, "x")
         if self.top_k == 0:
             return self._zero_k(x, want_dense)
         lin = self.encoder.linear
         path = self.resolved_latent_path(x.shape[0])
         self._check_limits(path)
-        hard = self.decoder.resolved_decode_mode() == "hard"
+        hard = soft_table is None and self.decoder.resolved_decode_mode() == "hard"
         latent = None
         if path == "prefilter":
             pw = self._prefilter_weights()
@@ -238,8 +239,9 @@ class BinarySAE(ops.GraphForwardMixin, SparseAutoencoder):
                         dec.n_bits, dec.quantization_step, dec.bias.detach(), want_dense=want_dense, spec_rows=spec, info=info)
                 else:
                     idx, val, latent, recon = ops.table_forward_prefilter(
-                        xf, lin.weight.detach(), lin.bias.detach(), pw["Wq"], pw["meta"], self.top_k, dec.soft_table(),
-                        dec.quantization_step, dec.bias.detach(), want_dense=want_dense, spec_rows=spec, info=info)
+                        xf, lin.weight.detach(), lin.bias.detach(), pw["Wq"], pw["meta"], self.top_k,
+                        dec.soft_table() if soft_table is None else soft_table, dec.quantization_step, dec.bias.detach(),
+                        want_dense=want_dense, spec_rows=spec, info=info)
                 self.last_flagged_rows = info["flagged_rows"]
                 return idx, val, latent, recon
             idx, val, latent = ops.encode_topk_prefilter(xf, lin.weight.detach(), lin.bias.detach(), pw["Wq"], pw["meta"],
@@ -254,6 +256,9 @@ class BinarySAE(ops.GraphForwardMixin, SparseAutoencoder):
         else:   # inplace
             latent = self.encoder(x)
             idx, val = ops.topk_rows(latent, self.top_k, zero_rest=True)     # latent * mask, in place
+        if soft_table is not None:
+            dec = self.decoder
+            return idx, val, latent, ops.decode_table_sparse(idx, val, soft_table, dec.quantization_step, dec.bias.detach())
         return idx, val, latent, self.decoder.decode_sparse(idx, val)
 
     def _graph_params(self):
@@ -277,6 +282,28 @@ class BinarySAE(ops.GraphForwardMixin, SparseAutoencoder):
                 return latent, recon, pol
             _, _, latent, recon = self._run(x, want_dense=True)
             return latent, recon, self.decoder.packed()["polarize"]
+
+    # -- training -------------------------------------------------------------------------------------------------
+    def forward_train(self, x, *, dense_latent: bool = True):
+        """``(sparse_latent [B,H] or None, reconstruction [B,D], polarize_loss [])`` with a ``grad_fn``: the forward the
+        reference trains through (sae/binary.py:91-103 with the soft sigmoid-bit decoder, whatever ``decoder.decode_mode``
+        says), whose backward runs the HIP gradient kernels (csrc/train.hip).  ``loss.backward()`` fills the ``.grad`` of
+        encoder.0.weight / .bias, decoder.weight / .bias (and of ``x`` if it requires grad).
+
+        Same selection path and bits as ``forward()``: latent and reconstruction equal ``forward()`` with
+        ``decode_mode = "soft"`` bit for bit, the polarize loss to within one fp32 ulp (a device-side fixed-order sum;
+        nothing is read back to the host except the prefilter path's 4-byte flagged-row count).  ``dense_latent=False``:
+        the first output is None and the dense [B, H] latent is never written.  Derived weights (prefilter copies, packed
+        dictionary) are keyed on the parameters' version counters, so an optimizer step is picked up by the next call."""
+        x = require_device_input(x, "x")
+        lin, dec = self.encoder.linear, self.decoder
+        if not ops.train_supported(self.input_dim, self.top_k):
+            raise ValueError(f"BinarySAE.forward_train: the gradient kernels take input_dim a multiple of 4 up to 4096 and "
+                             f"top-k <= 256 (got input_dim = {self.input_dim}, top-k = {self.top_k})")
+        if x.shape[1] != self.input_dim:
+            raise ValueError(f"x is {tuple(x.shape)}, expected [batch, {self.input_dim}]")
+        latent, recon, pol = _BinaryTrainStep.apply(self, bool(dense_latent), x, lin.weight, lin.bias, dec.weight, dec.bias)
+        return (latent if dense_latent else None), recon, pol
 
     # -- two batches in flight --------------------------------------------------------------------------------
     def forward_submit(self, x, slot: int = 0, want_dense: bool = True):
@@ -319,3 +346,47 @@ class _SubmittedForward:
             if self._want_dense:
                 return latent, recon, self._model.decoder.packed()["polarize"]
             return idx, val, recon
+
+
+class _BinaryTrainStep(torch.autograd.Function):
+    """The BinarySAE soft-decoder forward and its gradient (the table in DESIGN.md section 4.10):
+    gv = g_latent[r, h] + step <g_recon[r], T[h]> on the k selected entries of each row, then per unit the sums over
+    the rows that selected it (dW_enc, db_enc, dInt -> the logit gradient with the polarize term), and db_dec."""
+
+    @staticmethod
+    def forward(ctx, model, dense_latent, x, W_enc, b_enc, logits, b_dec):
+        dec = model.decoder
+        table, pol = ops.binary_soft_table_polarize(logits.detach(), dec.out_features, dec.n_bits)
+        xf = x.detach()
+        xf = xf if (xf.dtype == torch.float32 and xf.is_contiguous()) else xf.float().contiguous()
+        idx, val, latent, recon = model._run(xf, dense_latent, soft_table=table)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(xf, idx, val, table)
+        ctx.model = model
+        ctx.x_dtype = x.dtype
+        if latent is None:
+            return None, recon, pol
+        return latent, recon, pol
+
+    @staticmethod
+    def backward(ctx, g_latent, g_recon, g_pol):
+        xf, idx, val, table = ctx.saved_tensors
+        model = ctx.model
+        lin, dec = model.encoder.linear, model.decoder
+        need_x, need_W, need_b, need_l, need_bd = ctx.needs_input_grad[2:7]
+        H = model.hidden_dim
+        want_enc = need_W or need_b
+        dx = dW = db = dl = dbd = None
+        if need_x or want_enc or need_l:
+            gv, dx = ops.train_row_grad(idx, table, dec.quantization_step, g_recon, g_latent, lin.weight.detach(),
+                                        want_dx=need_x)
+            if want_enc or need_l:
+                offsets, entries = ops.train_csr(idx, H)
+                dW, db, dl = ops.train_unit_grad(offsets, entries, val, gv, xf, g_recon, dec.weight.detach(), dec.n_bits,
+                                                 dec.quantization_step, g_pol, want_encoder=want_enc, want_logits=need_l)
+        if need_bd:
+            dbd = ops.train_col_sum(g_recon) if g_recon is not None else torch.zeros_like(dec.bias)
+        if dx is not None and dx.dtype != ctx.x_dtype:
+            dx = dx.to(ctx.x_dtype)
+        return (None, None, dx if need_x else None, dW if need_W else None, db if need_b else None,
+                dl if need_l else None, dbd)

@@ -462,6 +462,71 @@ def _(A, B, thresholds, bins, want_matrix):
             _f32((Ha, Hb) if want_matrix else (0, 0), A))
 
 
+# ---- BinarySAE training ----------------------------------------------------------------------------------------------
+@_op("binary_soft_table_polarize")
+def _binary_soft_table_polarize(logits: Tensor, D: int, n_bits: int) -> Tuple[Tensor, Tensor]:
+    """-> (soft table [H, D], polarize fp32 0-d), both on the device"""
+    return _ops.binary_soft_table_polarize(logits, D, n_bits)
+
+
+@_binary_soft_table_polarize.register_fake
+def _(logits, D, n_bits):
+    return _f32((logits.shape[0], D), logits), _f32((), logits)
+
+
+@_op("train_csr")
+def _train_csr(idx: Tensor, H: int) -> Tuple[Tensor, Tensor]:
+    """-> (offsets int32 [H + 1], entries int32 [B k]): the top-k lists grouped by unit, ordered by row"""
+    return _ops.train_csr(idx, H)
+
+
+@_train_csr.register_fake
+def _(idx, H):
+    return _i32((H + 1,), idx), _i32((idx.shape[0] * idx.shape[1],), idx)
+
+
+@_op("train_row_grad")
+def _train_row_grad(idx: Tensor, table: Tensor, step: float, g_recon: Optional[Tensor], g_latent: Optional[Tensor],
+                    W_enc: Optional[Tensor], want_dx: bool) -> Tuple[Tensor, Tensor]:
+    """-> (gv [B, k], dx [B, D] ([0, D] when not wanted))"""
+    gv, dx = _ops.train_row_grad(idx, table, step, g_recon, g_latent, W_enc, want_dx)
+    return gv, (dx if dx is not None else _f32((0, table.shape[1]), idx))
+
+
+@_train_row_grad.register_fake
+def _(idx, table, step, g_recon, g_latent, W_enc, want_dx):
+    return _f32(tuple(idx.shape), idx), _f32((idx.shape[0] if want_dx else 0, table.shape[1]), idx)
+
+
+@_op("train_unit_grad")
+def _train_unit_grad(offsets: Tensor, entries: Tensor, val: Tensor, gv: Tensor, x: Tensor, g_recon: Optional[Tensor],
+                     logits: Tensor, n_bits: int, step: float, g_polarize: Optional[Tensor], want_encoder: bool,
+                     want_logits: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    """-> (dW_enc [H, D], db_enc [H], dlogits [H, D n_bits]); an output not wanted has 0 rows"""
+    dW, db, dl = _ops.train_unit_grad(offsets, entries, val, gv, x, g_recon, logits, n_bits, step, g_polarize,
+                                      want_encoder, want_logits)
+    D = x.shape[1]
+    return (dW if dW is not None else _f32((0, D), x), db if db is not None else _f32((0,), x),
+            dl if dl is not None else _f32((0, logits.shape[1]), x))
+
+
+@_train_unit_grad.register_fake
+def _(offsets, entries, val, gv, x, g_recon, logits, n_bits, step, g_polarize, want_encoder, want_logits):
+    H, D = offsets.shape[0] - 1, x.shape[1]
+    return (_f32((H if want_encoder else 0, D), x), _f32((H if want_encoder else 0,), x),
+            _f32((H if want_logits else 0, logits.shape[1]), x))
+
+
+@_op("train_col_sum")
+def _train_col_sum(g: Tensor) -> Tensor:
+    return _ops.train_col_sum(g)
+
+
+@_train_col_sum.register_fake
+def _(g):
+    return _f32((g.shape[1],), g)
+
+
 Q = torch.ops.qsae
 
 
@@ -663,7 +728,32 @@ def cosine_compare(A, B=None, thresholds=(), bins=0, want_matrix=False):
     return Q.cosine_compare(A, B, [float(t) for t in thresholds], int(bins), bool(want_matrix))
 
 
+def binary_soft_table_polarize(logits, D, n_bits):
+    return Q.binary_soft_table_polarize(logits, int(D), int(n_bits))
+
+
+def train_csr(idx, H):
+    return Q.train_csr(idx, int(H))
+
+
+def train_row_grad(idx, table, step, g_recon, g_latent, W_enc=None, want_dx=False):
+    gv, dx = Q.train_row_grad(idx, table, float(step), g_recon, g_latent, W_enc if want_dx else None, bool(want_dx))
+    return gv, (dx if want_dx else None)
+
+
+def train_unit_grad(offsets, entries, val, gv, x, g_recon, logits, n_bits, step, g_polarize, want_encoder=True,
+                    want_logits=True):
+    dW, db, dl = Q.train_unit_grad(offsets, entries, val, gv, x, g_recon, logits, int(n_bits), float(step), g_polarize,
+                                   bool(want_encoder), bool(want_logits))
+    return (dW if want_encoder else None), (db if want_encoder else None), (dl if want_logits else None)
+
+
+def train_col_sum(g):
+    return Q.train_col_sum(g)
+
+
 # what has no tensor result (shape queries, handles of batches in flight) stays plain Python
+train_supported = _ops.train_supported
 prefilter_supported = _ops.prefilter_supported
 encode_bits_prefilter_supported = _ops.encode_bits_prefilter_supported
 encode_bits_band_supported = _ops.encode_bits_band_supported
