@@ -125,7 +125,8 @@ int qsae_topk_rows(float* latent, int64_t ld, int B, int H, int k, int32_t* idx,
 
 /* Fused encoder + top-k without materialising the dense latent: same results as
  * qsae_encode_dense(act=NONE) followed by qsae_topk_rows.  Workspace from
- * qsae_encode_topk_workspace_bytes(). */
+ * qsae_encode_topk_workspace_bytes(), which is 0 exactly for the shapes refused with QSAE_ERR_UNSUPPORTED before any
+ * launch: D % 4 == 0, H % 4 == 0, k <= 256 and H <= 32768 -- or H <= 65536 for B >= 2048, H >= 8192 (fused form). */
 size_t qsae_encode_topk_workspace_bytes(int B, int D, int H, int k);
 int qsae_encode_topk(const float* x, const float* W, const float* bias, int B, int D, int H, int k,
                      int32_t* idx, float* val, void* workspace, size_t workspace_bytes,

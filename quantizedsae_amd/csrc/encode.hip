@@ -212,7 +212,7 @@ static int encode_dense_impl(const float* x, const float* W, const float* bias, 
     QSAE_CHECK_ARG(out_ld >= H, "out_ld < H");
     QSAE_CHECK_ARG(act >= QSAE_ACT_NONE && act <= QSAE_ACT_SIGMOID, "unknown activation");
     QSAE_CHECK_SUPPORTED(D % 4 == 0, "D must be a multiple of 4");
-    if (kperm) QSAE_CHECK_SUPPORTED(D % 32 == 0, "K-interleaved operands need D % 32 == 0");
+    if (kperm) QSAE_CHECK_SUPPORTED(D % 32 == 0, "K-interleaved operands need D %% 32 == 0");
     QSAE_CHECK_ARG(aligned16(x) && aligned16(W), "x and W must be 16-byte aligned");
     hipStream_t s = as_stream(stream);
     switch (act) {

@@ -37,6 +37,7 @@ int decode_binary_sparse_rows(const int* rows, int nrows, const int32_t* idx, co
 int densify_rows(const int32_t* idx, const float* val, int B, int k, int H, float* dense, int64_t ld, hipStream_t s);
 
 constexpr int kChunkRows = 1024;   // chunked form: 1024 x 32768 x 4 B = 128 MiB of latent per chunk
+constexpr int kTopkMaxH = 32768;   // widest row qsae_topk_rows ranks (topk.hip: the row lives in registers)
 constexpr int kCandCap = 1024;     // candidate slots per row
 constexpr int kFusedMinRows = 2048;
 constexpr int kFusedMinHidden = 8192;
@@ -98,7 +99,7 @@ static int pilot_width(int H) {
 constexpr int kFusedSplit = 4;     // exact fp32 sweep: workgroups per activation panel (hidden range in quarters, see run_fused)
 
 struct FusedLayout {
-    size_t pilot, tau, cnt, cnt_split, cand, flags, fx, flat, fidx, fval, total;
+    size_t pilot, tau, cnt, cnt_split, cand, flags, fx, flat, fidx, fval, fpart, total;
 };
 
 static FusedLayout fused_layout(int B, int D, int H, int k) {
@@ -115,6 +116,8 @@ static FusedLayout fused_layout(int B, int D, int H, int k) {
     L.flat = off;  off = align_up(off + static_cast<size_t>(kChunkRows) * H * 4, 256);
     L.fidx = off;  off = align_up(off + static_cast<size_t>(kChunkRows) * k * 4, 256);
     L.fval = off;  off = align_up(off + static_cast<size_t>(kChunkRows) * k * 4, 256);
+    L.fpart = off;                                                                 // rows wider than kTopkMaxH: the two
+    if (H > kTopkMaxH) off = align_up(off + static_cast<size_t>(kChunkRows) * k * 16, 256);   // halves' idx and val lists
     L.total = off;
     return L;
 }
@@ -400,6 +403,35 @@ scatter_topk_dev_kernel(const int32_t* __restrict__ sidx, const float* __restric
     if (dense && sidx[gid] >= 0 && sidx[gid] < H) dense[static_cast<long long>(rows[r]) * dense_ld + sidx[gid]] = sval[gid];
 }
 
+// Top-k of rows wider than kTopkMaxH from the top-k lists of their two column halves ([2][n][k], each list in (value desc,
+// index asc) order, every column of half 0 left of every column of half 1, half-1 indices relative to off1).  An entry's
+// rank is its rank in its own list plus the entries of the other list ahead of it: the larger values of half 1, the
+// larger or equal values of half 0 (lower columns).  The ranks below k are the row's top-k in the same order.
+__global__ void __launch_bounds__(256)
+merge_topk_halves_kernel(const int32_t* __restrict__ pidx, const float* __restrict__ pval, int n, int k, int off1,
+                         int32_t* __restrict__ idx, float* __restrict__ val) {
+    const long long nk = static_cast<long long>(n) * k;
+    const long long gid = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (gid >= 2 * nk) return;
+    const int half = gid >= nk ? 1 : 0;
+    const long long e = gid - half * nk;
+    const int r = static_cast<int>(e / k), j = static_cast<int>(e % k);
+    const float v = pval[gid];
+    const uint32_t key = mono_key(v);
+    const float* other = pval + (half ? 0 : nk) + static_cast<long long>(r) * k;
+    int lo = 0, hi = k;                                  // entries of the other list ahead of this one: a prefix of it
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const uint32_t km = mono_key(other[mid]);
+        if (half ? km >= key : km > key) lo = mid + 1; else hi = mid;
+    }
+    const int rank = j + lo;
+    if (rank < k) {
+        idx[static_cast<long long>(r) * k + rank] = pidx[gid] + (half ? off1 : 0);
+        val[static_cast<long long>(r) * k + rank] = v;
+    }
+}
+
 static int dense_latent(const float* x, const float* W, const float* bias, int B, int D, int H, float* out, int64_t ld,
                  qsae_stream_t stream, bool kperm) {
     return kperm ? qsae_encode_dense_kperm(x, W, bias, B, D, H, QSAE_ACT_NONE, out, ld, stream)
@@ -436,6 +468,25 @@ struct FlaggedArgs {
     float* dense; int64_t dense_ld;      // optional already zero-filled dense latent: the rows' entries are written into it
 };
 
+// Exact top-k of n rows of the dense latent flat [n][H] into fidx / fval [n][k].  Rows up to kTopkMaxH wide take
+// qsae_topk_rows in one piece; wider ones (the fused forms accept H <= 65536) two halves split at a multiple of 4, whose
+// lists merge_topk_halves_kernel joins.
+static int fallback_topk(const FlaggedArgs& a, float* flat, int n, int32_t* fidx, float* fval) {
+    if (a.H <= kTopkMaxH) return qsae_topk_rows(flat, a.H, n, a.H, a.k, fidx, fval, 0, a.stream);
+    const int h0 = (a.H / 2 + 3) / 4 * 4;               // both halves hold more than 16380 >= k columns
+    const long long nk = static_cast<long long>(n) * a.k;
+    int32_t* pidx = reinterpret_cast<int32_t*>(a.ws + a.L.fpart);
+    float* pval = reinterpret_cast<float*>(pidx + 2 * nk);
+    int rc = qsae_topk_rows(flat, a.H, n, h0, a.k, pidx, pval, 0, a.stream);
+    if (rc != QSAE_OK) return rc;
+    rc = qsae_topk_rows(flat + h0, a.H, n, a.H - h0, a.k, pidx + nk, pval + nk, 0, a.stream);
+    if (rc != QSAE_OK) return rc;
+    hipLaunchKernelGGL(merge_topk_halves_kernel, dim3(static_cast<unsigned>((2 * nk + 255) / 256)), dim3(256), 0,
+                       as_stream(a.stream), pidx, pval, n, a.k, h0, fidx, fval);
+    QSAE_LAUNCH_CHECK();
+    return QSAE_OK;
+}
+
 static int flagged_spec(const FlaggedArgs& a, int spec) {
     if (spec <= 0) return QSAE_OK;
     hipStream_t s = as_stream(a.stream);
@@ -450,7 +501,7 @@ static int flagged_spec(const FlaggedArgs& a, int spec) {
     QSAE_LAUNCH_CHECK();
     int rc = dense_latent(fx, a.W, a.bias, spec, a.D, a.H, flat, a.H, a.stream, a.kperm);
     if (rc != QSAE_OK) return rc;
-    rc = qsae_topk_rows(flat, a.H, spec, a.H, a.k, fidx, fval, 0, a.stream);
+    rc = fallback_topk(a, flat, spec, fidx, fval);
     if (rc != QSAE_OK) return rc;
     const long long tk = static_cast<long long>(spec) * a.k;
     hipLaunchKernelGGL(scatter_topk_dev_kernel, dim3(static_cast<unsigned>((tk + 255) / 256)), dim3(256), 0, s, fidx,
@@ -475,7 +526,7 @@ static int flagged_range(const FlaggedArgs& a, int first, int nflag) {
         QSAE_LAUNCH_CHECK();
         int rc = dense_latent(fx, a.W, a.bias, n, a.D, a.H, flat, a.H, a.stream, a.kperm);
         if (rc != QSAE_OK) return rc;
-        rc = qsae_topk_rows(flat, a.H, n, a.H, a.k, fidx, fval, 0, a.stream);
+        rc = fallback_topk(a, flat, n, fidx, fval);
         if (rc != QSAE_OK) return rc;
         const long long tk = static_cast<long long>(n) * a.k;
         hipLaunchKernelGGL(scatter_topk_kernel, dim3(static_cast<unsigned>((tk + 255) / 256)), dim3(256), 0, s, fidx, fval,
@@ -2816,8 +2867,15 @@ extern "C" double qsae_profile_sweep_flop_fraction(int H) {
     return static_cast<double>(H - pilot_width(H)) / static_cast<double>(H);
 }
 
+// Shapes some form of qsae_encode_topk runs: the fused form, else the chunked one (qsae_encode_dense + qsae_topk_rows,
+// whose limits apply).  Checked before anything is launched.
+static bool encode_topk_shape_ok(int B, int D, int H, int k) {
+    if (B <= 0 || H <= 0 || D <= 0 || D % 4 != 0 || k <= 0 || k > H) return false;
+    return use_fused(B, D, H, k) || (H % 4 == 0 && H <= kTopkMaxH && k <= 256);
+}
+
 extern "C" size_t qsae_encode_topk_workspace_bytes(int B, int D, int H, int k) {
-    if (B <= 0 || H <= 0 || D <= 0 || k <= 0) return 0;
+    if (!encode_topk_shape_ok(B, D, H, k)) return 0;
     if (use_fused(B, D, H, k)) return fused_layout(B, D, H, k).total;
     const size_t rows = static_cast<size_t>(B < kChunkRows ? B : kChunkRows);
     return rows * static_cast<size_t>(H) * sizeof(float);
@@ -2828,8 +2886,11 @@ static int encode_topk_impl(const float* x, const float* W, const float* bias, i
                             qsae_stream_t stream, bool kperm, float* dense = nullptr, int64_t dense_ld = 0) {
     QSAE_CHECK_ARG(B >= 0 && D > 0 && H > 0, "B >= 0, D > 0, H > 0 required");
     if (B == 0) return QSAE_OK;
-    QSAE_CHECK_ARG(x && W && idx && val && workspace, "null pointer");
     QSAE_CHECK_ARG(k >= 1 && k <= H, "1 <= k <= H required");
+    QSAE_CHECK_SUPPORTED(encode_topk_shape_ok(B, D, H, k),
+                         "shape outside both forms (D %% 4 == 0, H %% 4 == 0, k <= 256; fused: B >= 2048, H in [8192, 65536]; "
+                         "chunked: H <= 32768)");
+    QSAE_CHECK_ARG(x && W && idx && val && workspace, "null pointer");
     if (workspace_bytes < qsae_encode_topk_workspace_bytes(B, D, H, k))
         return fail(QSAE_ERR_WORKSPACE, "%s: workspace too small", __func__);
     QSAE_CHECK_ARG(aligned16(workspace), "workspace must be 16-byte aligned");
@@ -2837,7 +2898,7 @@ static int encode_topk_impl(const float* x, const float* W, const float* bias, i
         QSAE_CHECK_SUPPORTED(D % 4 == 0, "D must be a multiple of 4");
         QSAE_CHECK_ARG(aligned16(x) && aligned16(W), "x and W must be 16-byte aligned");
         if (dense) {
-            QSAE_CHECK_ARG(dense_ld >= H && dense_ld % 4 == 0 && aligned16(dense), "dense latent must be 16-byte aligned with ld >= H, ld % 4 == 0");
+            QSAE_CHECK_ARG(dense_ld >= H && dense_ld % 4 == 0 && aligned16(dense), "dense latent must be 16-byte aligned with ld >= H, ld %% 4 == 0");
         }
         return run_fused(x, W, bias, B, D, H, k, idx, val, static_cast<char*>(workspace), stream, kperm, dense, dense_ld);
     }
@@ -3067,7 +3128,7 @@ extern "C" int qsae_encode_bits_prefilter(const float* x, const float* W, const 
     if (B == 0) return QSAE_OK;
     QSAE_CHECK_ARG(x && W && Wq && meta && zbits, "null pointer");
     QSAE_CHECK_ARG(words_ld >= (H + 31) / 32, "words_ld < ceil(H/32)");
-    QSAE_CHECK_SUPPORTED(bits_prefilter_shape_ok(B, D, H), "shape not covered by the fp16 candidate sweep (D in {128,256,512}, H % 64 == 0)");
+    QSAE_CHECK_SUPPORTED(bits_prefilter_shape_ok(B, D, H), "shape not covered by the fp16 candidate sweep (D in {128,256,512}, H %% 64 == 0)");
     QSAE_CHECK_ARG(aligned16(x) && aligned16(W) && aligned16(Wq), "x, W and Wq must be 16-byte aligned");
     QSAE_CHECK_ARG(workspace && workspace_bytes >= bits_layout(B, D, H).total, "workspace too small");
     QSAE_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, "workspace must be 256-byte aligned");
@@ -3131,7 +3192,7 @@ extern "C" int qsae_encode_bits_band(const float* x, const float* W, const float
     if (B == 0) return QSAE_OK;
     QSAE_CHECK_ARG(x && W && Wq && meta && zbits, "null pointer");
     QSAE_CHECK_ARG(words_ld >= (H + 31) / 32, "words_ld < ceil(H/32)");
-    QSAE_CHECK_SUPPORTED(bits_band_shape_ok(B, D, H), "shape not covered (D % 64 == 0, H % 32 == 0; use qsae_encode_bits)");
+    QSAE_CHECK_SUPPORTED(bits_band_shape_ok(B, D, H), "shape not covered (D %% 64 == 0, H %% 32 == 0; use qsae_encode_bits)");
     QSAE_CHECK_ARG(aligned16(x) && aligned16(W) && aligned16(Wq), "x, W and Wq must be 16-byte aligned");
     QSAE_CHECK_ARG(workspace && workspace_bytes >= bits_layout(B, D, H, kBandCap).total, "workspace too small");
     QSAE_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, "workspace must be 256-byte aligned");

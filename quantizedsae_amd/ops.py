@@ -351,6 +351,19 @@ def release_workspaces() -> None:
     _workspaces.clear()
 
 
+def encode_topk_supported(B: int, D: int, H: int, k: int) -> bool:
+    """Whether encode_topk / encode_topk_latent run this shape (fused form for large batches, chunked form otherwise)."""
+    return int(_lib.load().qsae_encode_topk_workspace_bytes(B, D, H, k)) > 0
+
+
+def _encode_topk_workspace(lib, B: int, D: int, H: int, k: int) -> int:
+    need = int(lib.qsae_encode_topk_workspace_bytes(B, D, H, k))
+    if need == 0 and B > 0:
+        raise ValueError(f"encode_topk: shape B={B}, D={D}, H={H}, k={k} is outside what the kernels run (fused form: "
+                         "B >= 2048, 8192 <= H <= 65536; otherwise H <= 32768; H % 4 == 0, D % 4 == 0, k <= 256)")
+    return need
+
+
 @_on_tensor_device
 def encode_topk(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], k: int, kperm: bool = False):
     """kperm=True: x and W are already K-interleaved (kperm_rows)."""
@@ -359,7 +372,7 @@ def encode_topk(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], 
     H = W.shape[0]
     b = _f32c(bias, "bias") if bias is not None else None
     lib = _lib.load()
-    need = int(lib.qsae_encode_topk_workspace_bytes(B, D, H, k))
+    need = _encode_topk_workspace(lib, B, D, H, k)
     ws = _workspace(x.device, need)
     idx = torch.empty((B, k), dtype=torch.int32, device=x.device)
     val = torch.empty((B, k), dtype=torch.float32, device=x.device)
@@ -377,7 +390,7 @@ def encode_topk_latent(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Te
     H = W.shape[0]
     b = _f32c(bias, "bias") if bias is not None else None
     lib = _lib.load()
-    need = int(lib.qsae_encode_topk_workspace_bytes(B, D, H, k))
+    need = _encode_topk_workspace(lib, B, D, H, k)
     ws = _workspace(x.device, need)
     idx = torch.empty((B, k), dtype=torch.int32, device=x.device)
     val = torch.empty((B, k), dtype=torch.float32, device=x.device)

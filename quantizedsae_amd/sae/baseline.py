@@ -36,10 +36,18 @@ class BaselineSparseAutoencoder(ops.GraphForwardMixin, nn.Module):
         return self._pref_cache.get((lin.weight, lin.bias), lambda: dict(zip(
             ("Wq", "meta"), ops.prefilter_pack_w(lin.weight.detach(), lin.bias.detach()))))
 
+    def _check_limits(self, rows: int) -> None:
+        H, D = self.encoder.linear.weight.shape
+        if (H > 32768 and self.latent_path == "inplace") or not ops.encode_topk_supported(max(rows, 1), D, H, self.topk):
+            raise ValueError(f"BaselineSparseAutoencoder: no top-k path takes input_dim = {D}, hidden_dim = {H} at a batch of "
+                             f"{rows} rows (input_dim and hidden_dim multiples of 4; hidden_dim <= 32768, or up to 65536 for "
+                             "batches of >= 2048 rows off the in-place path)")
+
     def _run(self, x, want_dense: bool):
         """-> (idx, val, dense latent or None, reconstruction): the one implementation behind forward() and
         forward_compact()."""
         x = require_device_input(x, "x")
+        self._check_limits(x.shape[0])
         lin = self.encoder.linear
         H = lin.weight.shape[0]
         big = x.shape[0] >= 2048 and H >= 8192
@@ -89,6 +97,7 @@ class BaselineSparseAutoencoder(ops.GraphForwardMixin, nn.Module):
         returned handle gives ``(h_sparse, reconstruction)`` (``(idx, val, reconstruction)`` with want_dense=False)."""
         with torch.no_grad():
             xd = require_device_input(x, "x")
+            self._check_limits(xd.shape[0])
             if self._prefilter_ok(xd.shape[0]):
                 lin = self.encoder.linear
                 pw = self._prefilter_weights()

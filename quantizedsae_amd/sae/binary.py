@@ -132,8 +132,8 @@ class BinarySAE(ops.GraphForwardMixin, SparseAutoencoder):
     """``forward(x) -> (sparse_latent [B,H], reconstruction [B,D], polarize_loss [])``
     (sae/binary.py:71-103).  k = int(hidden_dim * self.k) with self.k = 0.002.
 
-    Shape limits of the kernels (checked at the first forward with a clear message): hidden_dim <= 32768 for the
-    in-place path and the exact fallback, k <= 256.  k == 0 (hidden_dim < 500) is served like the reference: an
+    Shape limits of the kernels (checked before every forward's first launch, ValueError): k <= 256, input_dim and
+    hidden_dim multiples of 4, hidden_dim <= 32768 for batches under 2048 rows and the in-place path, <= 65536 otherwise.  k == 0 (hidden_dim < 500) is served like the reference: an
     all-zero latent and a bias-only reconstruction."""
 
     def __init__(self, input_dim, hidden_dim, gamma=4.0, n_bits=8):
@@ -195,13 +195,17 @@ class BinarySAE(ops.GraphForwardMixin, SparseAutoencoder):
         if hasattr(self.encoder, "_kperm_cache"):
             self.encoder._kperm_cache.clear()
 
-    def _check_limits(self, path: str) -> None:
+    def _check_limits(self, path: str, rows: int) -> None:
         k = self.top_k
         if k > 256:
             raise ValueError(f"BinarySAE: top-k = int({self.hidden_dim} * {self.k}) = {k} exceeds the kernels' limit of 256")
         if self.hidden_dim > 32768 and path == "inplace":
             raise ValueError(f"BinarySAE: hidden_dim = {self.hidden_dim} exceeds the in-place top-k kernel's limit of 32768 "
                              "(batches of >= 2048 rows take the fused path up to 65536)")
+        if not ops.encode_topk_supported(max(rows, 1), self.input_dim, self.hidden_dim, k):
+            raise ValueError(f"BinarySAE: no top-k path takes input_dim = {self.input_dim}, hidden_dim = {self.hidden_dim} at "
+                             f"a batch of {rows} rows (input_dim and hidden_dim multiples of 4; hidden_dim <= 32768, or up "
+                             "to 65536 for batches of >= 2048 rows)")
 
     def _zero_k(self, x, want_dense: bool):
         """k == 0: the reference's topk(0) keeps nothing -- zero latent, reconstruction = decoder bias (sae/binary.py:94-99)."""
@@ -221,7 +225,7 @@ class BinarySAE(ops.GraphForwardMixin, SparseAutoencoder):
             return self._zero_k(x, want_dense)
         lin = self.encoder.linear
         path = self.resolved_latent_path(x.shape[0])
-        self._check_limits(path)
+        self._check_limits(path, x.shape[0])
         hard = soft_table is None and self.decoder.resolved_decode_mode() == "hard"
         latent = None
         if path == "prefilter":
@@ -316,7 +320,7 @@ class BinarySAE(ops.GraphForwardMixin, SparseAutoencoder):
         with torch.no_grad():
             xd = require_device_input(x, "x")
             if self.top_k > 0 and self.resolved_latent_path(xd.shape[0]) == "prefilter" and self.fuse_decode:
-                self._check_limits("prefilter")
+                self._check_limits("prefilter", xd.shape[0])
                 lin, dec = self.encoder.linear, self.decoder
                 pw = self._prefilter_weights()
                 xf = xd if (xd.dtype == torch.float32 and xd.is_contiguous()) else xd.float().contiguous()

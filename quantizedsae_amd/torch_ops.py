@@ -754,6 +754,7 @@ def train_col_sum(g):
 
 # what has no tensor result (shape queries, handles of batches in flight) stays plain Python
 train_supported = _ops.train_supported
+encode_topk_supported = _ops.encode_topk_supported
 prefilter_supported = _ops.prefilter_supported
 encode_bits_prefilter_supported = _ops.encode_bits_prefilter_supported
 encode_bits_band_supported = _ops.encode_bits_band_supported

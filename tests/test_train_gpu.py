@@ -238,6 +238,79 @@ def test_unsupported_shape_raises_value_error():
         model.forward_train(torch.randn(8, 50, device=DEV))
 
 
+# ---- the kernels' limits (train.hip: kTrainMaxD, kTrainMaxK, kTrainChunk, kColRows) ----------------------------------------
+def set_k(model, k):
+    model.k = (k + 0.5) / model.hidden_dim
+    assert model.top_k == k
+    return model
+
+
+def check_step(model, x, what, mu=1e-3):
+    x = x.requires_grad_(True)
+    got = train_step_grads(model, x, mu=mu)
+    got["x"] = x.grad
+    want = restated(model, x.detach(), mu=mu, want_dx=True)
+    assert_close(got, want, list(U.GRAD_KEYS) + ["x"], what=what)
+
+
+def test_widest_rows_with_the_largest_k():
+    """D = 4096 and k = 256 (both limits), over H = 1000 units (not a multiple of 64)."""
+    B, D, H, n = 32, 4096, 1000, 4
+    sd = S.binary_sae_params(91, D, H, n, logit_std=1.0, enc_bias_std=0.05, dec_bias_std=0.1)
+    model = set_k(make_model(sd, D, H, n, 2.0), 256)
+    check_step(model, torch.from_numpy(S.activations(92, B, D)).to(DEV), "D=4096 k=256")
+
+
+@pytest.mark.parametrize("N", [255, 256, 257, 512, 513])
+def test_unit_lists_at_the_chunk_splits(N):
+    """Unit 7 is selected by exactly N rows (encoder row 100 e0, zero bias, x[:, 0] = 1 on N rows and 0 elsewhere): its list
+    is summed in chunks of kTrainChunk = 256 entries, split at 256 and 512."""
+    B, D, H, n, u = 600, 64, 1024, 4, 7
+    sd = S.binary_sae_params(100 + N, D, H, n, logit_std=1.0, dec_bias_std=0.1)
+    sd["encoder.0.weight"][u] = 0.0
+    sd["encoder.0.weight"][u, 0] = 100.0
+    model = set_k(make_model(sd, D, H, n, 2.0), 4)
+    x = S.activations(200 + N, B, D)
+    x[:, 0] = 0.0
+    x[np.random.default_rng(N).permutation(B)[:N], 0] = 1.0
+    x = torch.from_numpy(x).to(DEV)
+    with torch.no_grad():
+        idx, _, _ = model.forward_compact(x)
+    assert int((idx == u).sum()) == N
+    check_step(model, x, f"list of {N}")
+
+
+@pytest.mark.parametrize("B", [256, 257])
+def test_one_unit_in_every_row_at_the_split_switch(B):
+    """k = 1 and unit 7 on top of every row: B k = 256 keeps its list in one chunk (no final launch), 257 splits it."""
+    D, H, n = 64, 1024, 4
+    sd = S.binary_sae_params(300 + B, D, H, n, logit_std=1.0, dec_bias_std=0.1)
+    sd["encoder.0.bias"][7] = 100.0
+    model = set_k(make_model(sd, D, H, n, 2.0), 1)
+    x = torch.from_numpy(S.activations(301, B, D)).to(DEV)
+    with torch.no_grad():
+        idx, _, _ = model.forward_compact(x)
+    assert bool((idx[:, 0] == 7).all())
+    check_step(model, x, f"B k = {B}")
+
+
+@pytest.mark.parametrize("B", [1, 255, 256, 257])
+def test_batches_around_the_column_sum_partials(B):
+    D, H, n = 64, 1024, 4
+    sd = S.binary_sae_params(400 + B, D, H, n, logit_std=1.0, enc_bias_std=0.05, dec_bias_std=0.1)
+    model = set_k(make_model(sd, D, H, n, 2.0), 8)
+    check_step(model, torch.from_numpy(S.activations(401, B, D)).to(DEV), f"B={B}")
+
+
+def test_past_the_limits_raises_value_error():
+    model = BinarySAE(4100, 1024, gamma=4.0, n_bits=4).to(DEV)
+    with pytest.raises(ValueError, match="4096"):
+        model.forward_train(torch.randn(8, 4100, device=DEV))
+    model = set_k(BinarySAE(64, 1024, gamma=4.0, n_bits=4).to(DEV), 257)
+    with pytest.raises(ValueError, match="top-k <= 256"):
+        model.forward_train(torch.randn(8, 64, device=DEV))
+
+
 # ---- a training loop ----------------------------------------------------------------------------------------------------
 def test_sgd_step_cache_invalidation_and_adam_loop():
     B, D, H, n, lr = 512, 128, 4096, 4, 1e-2
