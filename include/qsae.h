@@ -469,6 +469,28 @@ size_t qsae_train_col_sum_workspace_bytes(int B, int D);
 int qsae_train_col_sum(const float* g, int B, int D, float* out, void* workspace, size_t workspace_bytes,
                        qsae_stream_t stream);
 
+/* -- BaselineSparseAutoencoder training (sae/baseline.py:17-51; the baseline_sae branch of training/trainer.py:166-173) --- */
+/* The baseline SAE's gradient is the one above without the sigmoid chain: qsae_train_row_grad with table =
+ * decoder.weight transposed and step = 1, qsae_train_csr, then this call, then qsae_train_col_sum. */
+/* Device workspace of qsae_train_table_unit_grad (0 for an unsupported shape: D not a multiple of 4 or over 4096,
+ * k > 256, B k >= 2^31). */
+size_t qsae_train_table_unit_grad_workspace_bytes(int B, int k, int H, int D);
+/* Over each unit's list (qsae_train_csr): dW_enc[h][:] = sum gv x[r], db_enc[h] = sum gv, and column h of the
+ * decoder.weight gradient, dW_dec[d][h] = sum val g_recon[r][d], stored in the nn.Linear layout [D][dW_dec_ld]
+ * (the sums go to a [H][D] block of the workspace and through a tiled LDS transpose).  Every element of every non-NULL
+ * output is written exactly once, units nobody selected included (zeros); g_recon NULL: dW_dec is all zeros.  Lists
+ * longer than 256 entries are split into chunks whose partials are added in chunk order, as in qsae_train_unit_grad.
+ * No float atomics: bitwise reproducible. */
+int qsae_train_table_unit_grad(const int32_t* offsets, const int32_t* entries, const float* val, const float* gv, int B,
+                               int k, const float* x, const float* g_recon, int H, int D, float* dW_enc, float* db_enc,
+                               float* dW_dec, int64_t dW_dec_ld, void* workspace, size_t workspace_bytes,
+                               qsae_stream_t stream);
+/* normalize_decoder_weights() in one pass over W [D][H] (decoder.weight, contiguous, 16-byte aligned):
+ * norm[h] = sqrt(sum_d W[d][h]^2), squares added for d = 0, 1, .. in fp32 (one fixed chain per column), then in place
+ * W[d][h] /= max(norm[h], 1e-8) (a zero column stays zero, a NaN column stays NaN).  table (nullable) [H][D] receives
+ * the normalised transpose, the rows the sparse decoder and qsae_train_row_grad gather.  H a multiple of 4, any D. */
+int qsae_normalize_columns_table(float* W, int D, int H, float* table, qsae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

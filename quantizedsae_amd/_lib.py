@@ -116,6 +116,9 @@ SIGNATURES = {
                                   _vp]),
     "qsae_train_col_sum_workspace_bytes": (_sz, [_i, _i]),
     "qsae_train_col_sum": (_i, [_vp, _i, _i, _vp, _vp, _sz, _vp]),
+    "qsae_train_table_unit_grad_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "qsae_train_table_unit_grad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _i64, _vp, _sz, _vp]),
+    "qsae_normalize_columns_table": (_i, [_vp, _i, _i, _vp, _vp]),
 }
 
 

@@ -11,6 +11,11 @@
 //   dlogit[h][d n + b] = (dInt[h][d] bw[b] + gP 2^b (1 - 2p) / (H D n)) p (1 - p)
 //   db_dec[d]      = sum_r gR[r][d]
 //
+// The baseline SAE (Linear -> top-k -> Linear, sae/baseline.py:17-40) is the same gradient without the sigmoid chain: T is
+// decoder.weight transposed, step = 1, and the per-unit sum  sum v gR[r][:]  is column h of the decoder.weight gradient
+// [D][H] (TABLE instantiation of the unit kernels + transpose_rows_kernel).  normalize_columns_kernel is its trainer's
+// normalize_decoder_weights() (sae/baseline.py:42-51) in one pass, which also leaves the normalised transpose.
+//
 // Every sum runs in a fixed order (no float atomics): gradients are bitwise reproducible.  The only atomics are the
 // integer ORs that mark (unit, row) pairs in the CSR build, whose result does not depend on their order.
 #include "common.h"
@@ -241,6 +246,7 @@ struct UnitArgs {
     float* dlogit;          // [H][D n] or nullptr
     float* slab;            // [slab_rows][slab_ld]: partials of the chunks of split lists
     int slab_rows, slab_ld;
+    float* dT;              // TABLE instantiation: [H][D] = sum v gR (the decoder.weight gradient, transposed) or nullptr
 };
 
 // dlogit row h from s_dint[D] (dInt, step applied); the whole workgroup calls it
@@ -268,6 +274,8 @@ __device__ __forceinline__ void unit_logit_row(const UnitArgs& a, int h, const f
 
 // One workgroup per chunk of a unit list (every unit has at least one chunk, empty lists included).  A unit with one
 // chunk is finished here; the chunks of a split list store their partials in the slab for unit_final_kernel.
+// TABLE = false: the BinarySAE epilogue (dInt -> LDS -> logit-gradient row); TABLE = true: the row of sums goes to dT as is.
+template <bool TABLE>
 __global__ void __launch_bounds__(256)
 unit_chunk_kernel(UnitArgs a) {
     extern __shared__ float s_dint[];                      // [D]
@@ -307,8 +315,12 @@ unit_chunk_kernel(UnitArgs a) {
         }
         if (!split) {
             if (a.dW) st4(a.dW + static_cast<long long>(h) * D + 4 * c4, w);
+            if constexpr (TABLE) {
+                if (a.dT) st4(a.dT + static_cast<long long>(h) * D + 4 * c4, s);
+            } else {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) s_dint[4 * c4 + e] = a.step * s[e];
+                for (int e = 0; e < 4; ++e) s_dint[4 * c4 + e] = a.step * s[e];
+            }
         } else if (srow) {
             st4(srow + 4 * c4, w);
             st4(srow + D + 4 * c4, s);
@@ -323,13 +335,16 @@ unit_chunk_kernel(UnitArgs a) {
             srow[2 * D] = db;
         }
     }
-    if (!split && a.dlogit) {
-        __syncthreads();
-        unit_logit_row(a, h, s_dint);
+    if constexpr (!TABLE) {
+        if (!split && a.dlogit) {
+            __syncthreads();
+            unit_logit_row(a, h, s_dint);
+        }
     }
 }
 
 // Units whose list was split: add the chunk partials in chunk order, then finish as above.
+template <bool TABLE>
 __global__ void __launch_bounds__(256)
 unit_final_kernel(UnitArgs a) {
     extern __shared__ float s_dint[];
@@ -347,17 +362,151 @@ unit_final_kernel(UnitArgs a) {
             s += ld4(srow + D + 4 * c4);
         }
         if (a.dW) st4(a.dW + static_cast<long long>(h) * D + 4 * c4, w);
+        if constexpr (TABLE) {
+            if (a.dT) st4(a.dT + static_cast<long long>(h) * D + 4 * c4, s);
+        } else {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) s_dint[4 * c4 + e] = a.step * s[e];
+            for (int e = 0; e < 4; ++e) s_dint[4 * c4 + e] = a.step * s[e];
+        }
     }
     if (threadIdx.x == 0 && a.db) {
         float db = 0.0f;
         for (int c = 0; c < rows; ++c) db += a.slab[static_cast<long long>(row0 + c) * a.slab_ld + 2 * D];
         a.db[h] = db;
     }
-    if (a.dlogit) {
-        __syncthreads();
-        unit_logit_row(a, h, s_dint);
+    if constexpr (!TABLE) {
+        if (a.dlogit) {
+            __syncthreads();
+            unit_logit_row(a, h, s_dint);
+        }
+    }
+}
+
+// ---- dT [H][D] -> decoder.weight gradient [D][ld] ---------------------------------------------------------------------
+// One workgroup moves 32 units x 64 columns through two 32 x 32 LDS tiles of pitch 33 floats.  Both global sides move 16
+// bytes per lane, 8 lanes per 128-byte line.  LDS (bank = dword address mod 32 for 4-byte accesses, conflicts within a
+// 32-lane half): the fill writes dword r 33 + 4 c4 + e = r + 4 c4 + e (mod 32) for 4 consecutive r and c4 = 0..7, the
+// drain reads (4 h4 + e) 33 + dr = 4 h4 + e + dr for h4 = 0..7 and 4 consecutive dr: 32 different banks on either side.
+// src == nullptr: zeros (no incoming reconstruction gradient).
+constexpr int kTrTile = 32;
+constexpr int kTrTilesD = 2;
+
+__global__ void __launch_bounds__(256)
+transpose_rows_kernel(const float* __restrict__ src, int H, int D, float* __restrict__ dst, long long ld, int vec) {
+    __shared__ float s_t[kTrTilesD][kTrTile][kTrTile + 1];
+    const int t = threadIdx.x, lo = t & 7, hi = t >> 3;     // hi = 0..31
+    const int h0 = blockIdx.x * kTrTile, d0 = blockIdx.y * (kTrTile * kTrTilesD);
+    tr_f32x4 v[kTrTilesD];
+#pragma unroll
+    for (int j = 0; j < kTrTilesD; ++j) {
+        const int h = h0 + hi, d = d0 + kTrTile * j + 4 * lo;
+        v[j] = tr_f32x4{0.f, 0.f, 0.f, 0.f};
+        if (src && h < H && d < D) v[j] = ld4(src + static_cast<long long>(h) * D + d);   // D % 4 == 0: d + 3 < D
+    }
+#pragma unroll
+    for (int j = 0; j < kTrTilesD; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s_t[j][hi][4 * lo + e] = v[j][e];
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < kTrTilesD; ++j) {
+        const int d = d0 + kTrTile * j + hi, h = h0 + 4 * lo;
+        if (d >= D || h >= H) continue;
+        tr_f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = s_t[j][4 * lo + e][hi];
+        float* out = dst + static_cast<long long>(d) * ld + h;
+        if (vec && h + 3 < H) {
+            st4(out, o);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (h + e < H) out[e] = o[e];
+        }
+    }
+}
+
+// ---- unit-norm columns of W [D][H] in place, and the normalised transpose ---------------------------------------------
+// One workgroup owns 32 columns (one 128-byte line of every row) and reads each element from HBM once: the raw tile sits
+// in LDS (D <= kNormRows; wider matrices re-read global memory, which is correct and slower).  Thread h < 32 adds the
+// squares of column h for d = 0, 1, .. in fp32 -- one fixed chain per column, so the norms are reproducible -- then the
+// tile is divided and written twice: along rows into W, and transposed into table [H][D].
+// LDS layout: element (d, h) at dword d 32 + (h ^ 4 ((d >> 2) & 7)).  Row accesses are 16-byte (8 lanes = one bank row of
+// 32 dwords, the swizzle permutes 16-byte slots); the transposed 4-byte reads of 4 consecutive h at rows 4 d4 + e,
+// d4 = 0..7, hit banks (h ^ 4 d4) = 4 (q ^ d4) + r: 32 different banks per 32-lane half.
+constexpr int kNormCols = 32;
+constexpr int kNormRows = 512;
+
+__device__ __forceinline__ int norm_slot(int d, int h) { return d * kNormCols + (h ^ (4 * ((d >> 2) & 7))); }
+
+__global__ void __launch_bounds__(256)
+normalize_columns_kernel(float* __restrict__ W, int D, int H, float* __restrict__ table) {
+    extern __shared__ float s_norm[];                      // [kNormCols] clamped norms, then the tile [min(D, kNormRows)][32]
+    float* s_tile = s_norm + kNormCols;
+    const int t = threadIdx.x, lo = t & 7, hi = t >> 3;
+    const int h0 = blockIdx.x * kNormCols;
+    const long long ld = H;
+    const bool cached = D <= kNormRows;
+    const int hrow = h0 + 4 * lo;                          // this thread's 4 columns of the row passes (H % 4 == 0)
+    if (cached && hrow < H)
+#pragma unroll 4
+        for (int d = hi; d < D; d += 32) st4(s_tile + norm_slot(d, 4 * lo), ld4(W + static_cast<long long>(d) * ld + hrow));
+    __syncthreads();
+    if (t < kNormCols && h0 + t < H) {
+        float ss = 0.0f;
+        if (cached) {
+#pragma unroll 8
+            for (int d = 0; d < D; ++d) {
+                const float v = s_tile[norm_slot(d, t)];
+                ss = ss + v * v;
+            }
+        } else {
+            for (int d = 0; d < D; ++d) {
+                const float v = W[static_cast<long long>(d) * ld + h0 + t];
+                ss = ss + v * v;
+            }
+        }
+        const float nrm = sqrtf(ss);
+        s_norm[t] = nrm < 1e-8f ? 1e-8f : nrm;              // clamp(min = 1e-8); a NaN norm stays NaN
+    }
+    __syncthreads();
+    if (table) {                                           // transposed pass: 4 units x 8 float4 of d per 32 lanes
+        const int h = 4 * (t >> 5) + ((t >> 3) & 3);
+        if (h0 + h < H) {
+            const float nrm = s_norm[h];
+            float* trow = table + static_cast<long long>(h0 + h) * D;
+            const bool vec = (D & 3) == 0;
+            for (int d4 = lo; 4 * d4 < D; d4 += 8) {
+                tr_f32x4 o = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int d = 4 * d4 + e;
+                    if (d < D) o[e] = (cached ? s_tile[norm_slot(d, h)] : W[static_cast<long long>(d) * ld + h0 + h]) / nrm;
+                }
+                if (vec) {
+                    st4(trow + 4 * d4, o);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (4 * d4 + e < D) trow[4 * d4 + e] = o[e];
+                }
+            }
+        }
+    }
+    __syncthreads();                                       // every raw read of W is done before W is overwritten
+    if (hrow < H) {
+        tr_f32x4 nrm;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) nrm[e] = s_norm[4 * lo + e];
+#pragma unroll 4
+        for (int d = hi; d < D; d += 32) {
+            float* p = W + static_cast<long long>(d) * ld + hrow;
+            const tr_f32x4 v = cached ? ld4(s_tile + norm_slot(d, 4 * lo)) : ld4(p);
+            tr_f32x4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = v[e] / nrm[e];
+            st4(p, o);
+        }
     }
 }
 
@@ -538,15 +687,15 @@ extern "C" int qsae_train_unit_grad(const int32_t* offsets, const int32_t* entri
     QSAE_LAUNCH_CHECK();
     UnitArgs a{offsets, entries, chunk_off, val, gv, Bk, k > 0 ? k : 1, H, D, n_bits, x, Bk > 0 ? g_recon : nullptr,
                logits, step, g_polarize, static_cast<double>(H) * D * n_bits, dW_enc, db_enc, dlogits,
-               reinterpret_cast<float*>(ws + L.slab), L.slab_rows, L.slab_ld};
+               reinterpret_cast<float*>(ws + L.slab), L.slab_rows, L.slab_ld, nullptr};
     const int D4 = D / 4;
     const int threads = D4 >= 256 ? 256 : ((D4 + 63) / 64) * 64;
     const size_t lds = static_cast<size_t>(D) * 4;
     const long long grid = static_cast<long long>(H) + (Bk + kTrainChunk - 1) / kTrainChunk;   // >= number of chunks
-    hipLaunchKernelGGL(unit_chunk_kernel, dim3(static_cast<unsigned>(grid)), dim3(threads), lds, s, a);
+    hipLaunchKernelGGL(unit_chunk_kernel<false>, dim3(static_cast<unsigned>(grid)), dim3(threads), lds, s, a);
     QSAE_LAUNCH_CHECK();
     if (Bk > kTrainChunk) {                                // otherwise no list can be split
-        hipLaunchKernelGGL(unit_final_kernel, dim3(H), dim3(threads), lds, s, a);
+        hipLaunchKernelGGL(unit_final_kernel<false>, dim3(H), dim3(threads), lds, s, a);
         QSAE_LAUNCH_CHECK();
     }
     return QSAE_OK;
@@ -574,6 +723,77 @@ extern "C" int qsae_train_col_sum(const float* g, int B, int D, float* out, void
     hipLaunchKernelGGL(col_sum_partial_kernel, dim3((D + 255) / 256, parts), dim3(256), 0, s, g, B, D, partial);
     QSAE_LAUNCH_CHECK();
     hipLaunchKernelGGL(col_sum_final_kernel, dim3((D + 255) / 256), dim3(256), 0, s, partial, parts, D, out);
+    QSAE_LAUNCH_CHECK();
+    return QSAE_OK;
+}
+
+inline size_t table_unit_dT_offset(long long Bk, int H, int D) { return unit_layout(Bk, H, D).total; }
+
+extern "C" size_t qsae_train_table_unit_grad_workspace_bytes(int B, int k, int H, int D) {
+    if (B < 0 || k < 0 || k > kTrainMaxK || H <= 0 || !train_shape_ok(D)) return 0;
+    const long long Bk = static_cast<long long>(B) * k;
+    if (Bk >= (1LL << 31)) return 0;
+    return table_unit_dT_offset(Bk, H, D) + align_up(static_cast<size_t>(H) * D * 4);
+}
+
+extern "C" int qsae_train_table_unit_grad(const int32_t* offsets, const int32_t* entries, const float* val,
+                                          const float* gv, int B, int k, const float* x, const float* g_recon, int H,
+                                          int D, float* dW_enc, float* db_enc, float* dW_dec, int64_t dW_dec_ld,
+                                          void* workspace, size_t workspace_bytes, qsae_stream_t stream) {
+    QSAE_CHECK_ARG(B >= 0 && k >= 0 && H > 0 && D > 0, "B >= 0, k >= 0, H > 0, D > 0 required");
+    QSAE_CHECK_SUPPORTED(train_shape_ok(D), "D a multiple of 4, at most 4096");
+    QSAE_CHECK_SUPPORTED(k <= kTrainMaxK, "k <= 256");
+    const long long Bk = static_cast<long long>(B) * k;
+    QSAE_CHECK_SUPPORTED(Bk < (1LL << 31), "B * k < 2^31");
+    QSAE_CHECK_SUPPORTED((static_cast<long long>(H) + kTrTile - 1) / kTrTile < (1LL << 31), "H < 2^36");
+    QSAE_CHECK_ARG(offsets && workspace, "null pointer");
+    QSAE_CHECK_ARG(Bk == 0 || (entries && val && gv && x), "null pointer");
+    QSAE_CHECK_ARG(!dW_dec || dW_dec_ld >= H, "dW_dec_ld >= H required");
+    QSAE_CHECK_ARG((!x || aligned16(x)) && (!g_recon || aligned16(g_recon)) && (!dW_enc || aligned16(dW_enc)),
+                   "x, g_recon and dW_enc must be 16-byte aligned");
+    const UnitLayout L = unit_layout(Bk, H, D);
+    if (workspace_bytes < qsae_train_table_unit_grad_workspace_bytes(B, k, H, D))
+        return fail(QSAE_ERR_WORKSPACE, "%s: workspace too small", __func__);
+    hipStream_t s = as_stream(stream);
+    char* ws = static_cast<char*>(workspace);
+    const float* gR = Bk > 0 ? g_recon : nullptr;
+    float* dT = (dW_dec && gR) ? reinterpret_cast<float*>(ws + L.total) : nullptr;
+    if (dW_enc || db_enc || dT) {
+        int* chunk_off = reinterpret_cast<int*>(ws + L.chunk_off);
+        hipLaunchKernelGGL(scan_kernel<1>, dim3(1), dim3(1024), 0, s, offsets, H, chunk_off);
+        QSAE_LAUNCH_CHECK();
+        UnitArgs a{offsets, entries, chunk_off, val, gv, Bk, k > 0 ? k : 1, H, D, 1, x, gR, nullptr, 1.0f, nullptr, 1.0,
+                   dW_enc, db_enc, nullptr, reinterpret_cast<float*>(ws + L.slab), L.slab_rows, L.slab_ld, dT};
+        const int D4 = D / 4;
+        const int threads = D4 >= 256 ? 256 : ((D4 + 63) / 64) * 64;
+        const long long grid = static_cast<long long>(H) + (Bk + kTrainChunk - 1) / kTrainChunk;   // >= number of chunks
+        hipLaunchKernelGGL(unit_chunk_kernel<true>, dim3(static_cast<unsigned>(grid)), dim3(threads), 0, s, a);
+        QSAE_LAUNCH_CHECK();
+        if (Bk > kTrainChunk) {                            // otherwise no list can be split
+            hipLaunchKernelGGL(unit_final_kernel<true>, dim3(H), dim3(threads), 0, s, a);
+            QSAE_LAUNCH_CHECK();
+        }
+    }
+    if (dW_dec) {
+        const int vec = (dW_dec_ld % 4 == 0 && aligned16(dW_dec)) ? 1 : 0;
+        const dim3 grid((H + kTrTile - 1) / kTrTile, (D + kTrTile * kTrTilesD - 1) / (kTrTile * kTrTilesD));
+        hipLaunchKernelGGL(transpose_rows_kernel, grid, dim3(256), 0, s, dT, H, D, dW_dec,
+                           static_cast<long long>(dW_dec_ld), vec);
+        QSAE_LAUNCH_CHECK();
+    }
+    return QSAE_OK;
+}
+
+extern "C" int qsae_normalize_columns_table(float* W, int D, int H, float* table, qsae_stream_t stream) {
+    QSAE_CHECK_ARG(D >= 1 && H >= 1, "D >= 1 and H >= 1 required");
+    QSAE_CHECK_SUPPORTED(H % 4 == 0, "H a multiple of 4");
+    QSAE_CHECK_ARG(W != nullptr, "null pointer");
+    QSAE_CHECK_ARG(aligned16(W), "W must be 16-byte aligned");
+    QSAE_CHECK_ARG(!table || D % 4 != 0 || aligned16(table), "table must be 16-byte aligned");
+    const size_t lds = (static_cast<size_t>(D <= kNormRows ? D : 0) * kNormCols + kNormCols) * 4;
+    QSAE_SET_MAX_LDS_ONCE(normalize_columns_kernel, (static_cast<size_t>(kNormRows) * kNormCols + kNormCols) * 4);
+    hipLaunchKernelGGL(normalize_columns_kernel, dim3((H + kNormCols - 1) / kNormCols), dim3(256), lds, as_stream(stream), W,
+                       D, H, table);
     QSAE_LAUNCH_CHECK();
     return QSAE_OK;
 }

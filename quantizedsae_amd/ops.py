@@ -1164,3 +1164,55 @@ def train_col_sum(g: torch.Tensor) -> torch.Tensor:
     ws = _train_ws(lib.qsae_train_col_sum_workspace_bytes(B, D), g.device)
     check(lib.qsae_train_col_sum(_p(g), B, D, _p(out), _p(ws), ws.numel(), _stream()))
     return out
+
+
+# ---- BaselineSparseAutoencoder training ---------------------------------------------------------------------------------
+@_on_tensor_device
+def train_table_unit_grad(offsets: torch.Tensor, entries: torch.Tensor, val: torch.Tensor, gv: torch.Tensor, x: torch.Tensor,
+                          g_recon: Optional[torch.Tensor], want_encoder: bool = True, want_decoder: bool = True):
+    """-> (dW_enc [H, D], db_enc [H], dW_dec [D, H] in the layout of nn.Linear(H, D).weight), each None when not wanted;
+    see qsae_train_table_unit_grad."""
+    _dev(offsets, "offsets", torch.int32)
+    _dev(entries, "entries", torch.int32)
+    val, gv, x = _f32c(val, "val"), _f32c(gv, "gv"), _f32c(x, "x")
+    if val.dim() != 2 or x.dim() != 2 or offsets.dim() != 1:
+        raise ValueError("train_table_unit_grad: val and x must be 2-D, offsets 1-D")
+    B, k = val.shape
+    D = x.shape[1]
+    H = offsets.shape[0] - 1
+    _check_train_shape(D, k)
+    if H < 1 or tuple(x.shape) != (B, D) or tuple(gv.shape) != (B, k) or entries.numel() != B * k:
+        raise ValueError("train_table_unit_grad: inconsistent shapes")
+    if B * k >= 2 ** 31:
+        raise ValueError(f"train_table_unit_grad: B * k = {B * k} is not below 2^31")
+    gR = _f32c(g_recon, "g_recon") if g_recon is not None else None
+    if gR is not None and tuple(gR.shape) != (B, D):
+        raise ValueError(f"g_recon is {tuple(gR.shape)}, expected [{B}, {D}]")
+    dev = x.device
+    dW = torch.empty((H, D), dtype=torch.float32, device=dev) if want_encoder else None
+    db = torch.empty((H,), dtype=torch.float32, device=dev) if want_encoder else None
+    dWd = torch.empty((D, H), dtype=torch.float32, device=dev) if want_decoder else None
+    lib = _lib.load()
+    ws = _train_ws(lib.qsae_train_table_unit_grad_workspace_bytes(B, k, H, D), dev)
+    check(lib.qsae_train_table_unit_grad(_p(offsets.contiguous()), _p(entries.contiguous()), _p(val), _p(gv), B, k, _p(x),
+                                         _p(gR), H, D, _p(dW), _p(db), _p(dWd), H, _p(ws), ws.numel(), _stream()))
+    return dW, db, dWd
+
+
+def normalize_columns_supported(H: int) -> bool:
+    return H > 0 and H % 4 == 0
+
+
+@_on_tensor_device
+def normalize_columns_table(W: torch.Tensor, want_table: bool = True) -> Optional[torch.Tensor]:
+    """Unit-norm columns of W [D, H] IN PLACE (W / clamp(norm(W, dim=0), min=1e-8)); -> the normalised transpose [H, D]
+    (None unless want_table); see qsae_normalize_columns_table."""
+    _dev(W, "W", torch.float32)
+    if W.dim() != 2 or W.shape[0] < 1 or not normalize_columns_supported(W.shape[1]):
+        raise ValueError(f"normalize_columns_table: W is {tuple(W.shape)}, expected [D >= 1, H a multiple of 4]")
+    if not W.is_contiguous() or W.data_ptr() % 16 != 0:
+        raise ValueError("normalize_columns_table: W must be contiguous and 16-byte aligned (it is updated in place)")
+    D, H = W.shape
+    table = torch.empty((H, D), dtype=torch.float32, device=W.device) if want_table else None
+    check(_lib.load().qsae_normalize_columns_table(_p(W), D, H, _p(table), _stream()))
+    return table

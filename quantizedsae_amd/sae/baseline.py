@@ -86,6 +86,31 @@ class BaselineSparseAutoencoder(ops.GraphForwardMixin, nn.Module):
             _, _, h, recon = self._run(x, want_dense=True)
             return h, recon
 
+    # -- training -------------------------------------------------------------------------------------------------
+    def forward_train(self, x, *, dense_latent: bool = True):
+        """``(h_sparse [B,H] or None, reconstruction [B,D])`` with a ``grad_fn``: the forward the reference trains through
+        (sae/baseline.py:17-40; the baseline_sae branch of training/trainer.py:166-173), whose backward runs the HIP gradient
+        kernels (csrc/train.hip).  ``loss.backward()`` fills the ``.grad`` of encoder.0.weight / .bias and decoder.weight /
+        .bias (and of ``x`` if it requires grad); a gradient arriving at ``h_sparse`` counts at the selected entries only, as
+        through the reference's ``scatter_``.
+
+        Same path selection and bits as ``forward()``.  ``dense_latent=False``: the first output is None and the dense
+        [B, H] latent is never written.  ``self.topk`` is read per call.  Derived weights are keyed on the parameters'
+        version counters, so an optimizer step is picked up by the next call."""
+        x = require_device_input(x, "x")
+        lin, dec = self.encoder.linear, self.decoder
+        H, D = lin.weight.shape
+        if not ops.train_supported(D, self.topk) or self.topk < 1:
+            raise ValueError(f"BaselineSparseAutoencoder.forward_train: the gradient kernels take input_dim a multiple of 4 up "
+                             f"to 4096 and 1 <= topk <= 256 (got input_dim = {D}, topk = {self.topk})")
+        if x.shape[1] != D:
+            raise ValueError(f"x is {tuple(x.shape)}, expected [batch, {D}]")
+        if x.shape[0] * self.topk >= 2 ** 31:
+            raise ValueError(f"BaselineSparseAutoencoder.forward_train: batch * topk = {x.shape[0] * self.topk} is not below 2^31")
+        self._check_limits(x.shape[0])
+        latent, recon = _BaselineTrainStep.apply(self, bool(dense_latent), x, lin.weight, lin.bias, dec.weight, dec.bias)
+        return (latent if dense_latent else None), recon
+
     def forward_compact(self, x):
         """(idx, val, reconstruction) without the dense latent; same path selection as forward()."""
         with torch.no_grad():
@@ -124,8 +149,20 @@ class BaselineSparseAutoencoder(ops.GraphForwardMixin, nn.Module):
             return out
 
     def normalize_decoder_weights(self):
-        """Unit-norm decoder columns (sae/baseline.py:42-51; training utility, plain torch ops)."""
+        """Unit-norm decoder columns (sae/baseline.py:42-51): one HIP pass that divides ``decoder.weight`` in place -- same
+        storage, same Parameter, optimizer state untouched -- and leaves the normalised transpose, which becomes the cached
+        decoder table of the next forward.  Shapes the kernel does not take (hidden_dim not a multiple of 4, a CPU or
+        non-fp32 model) go through the reference's three torch ops."""
         with torch.no_grad():
+            w = self.decoder.weight
+            if w.is_cuda and w.dtype == torch.float32 and w.is_contiguous() and w.data_ptr() % 16 == 0 \
+                    and ops.normalize_columns_supported(w.shape[1]):
+                table = ops.normalize_columns_table(w.detach(), want_table=True)
+                self.invalidate_packed()
+                # the kernel wrote through the raw pointer: neither data_ptr nor (necessarily) the version counter moved,
+                # so the cache could not notice by itself -- the table of the new weights replaces the old one explicitly
+                self._cache.put((self.decoder.weight,), {"t": table})
+                return
             w = self.decoder.weight.data
             self.decoder.weight.data = w / torch.clamp(torch.norm(w, dim=0, keepdim=True), min=1e-8)
             self.invalidate_packed()
@@ -143,3 +180,45 @@ class _SubmittedBaseline:
                 self._pending = None
             idx, val, h, recon = self._outs
             return (h, recon) if self._want_dense else (idx, val, recon)
+
+
+class _BaselineTrainStep(torch.autograd.Function):
+    """The baseline forward and its gradient (the table in DESIGN.md section 4.11): the BinarySAE gradient without the
+    sigmoid chain.  gv = g_latent[r, h] + <g_recon[r], W_dec[:, h]> on the k selected entries of each row, then per unit
+    the sums over the rows that selected it (dW_enc, db_enc, and column h of dW_dec), and db_dec.  Selected values may be
+    negative (no ReLU in this model): nothing here looks at their sign."""
+
+    @staticmethod
+    def forward(ctx, model, dense_latent, x, W_enc, b_enc, W_dec, b_dec):
+        xf = x.detach()
+        xf = xf if (xf.dtype == torch.float32 and xf.is_contiguous()) else xf.float().contiguous()
+        idx, val, latent, recon = model._run(xf, dense_latent)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(xf, idx, val, model._table())
+        ctx.model = model
+        ctx.x_dtype = x.dtype
+        if latent is None:
+            return None, recon
+        return latent, recon
+
+    @staticmethod
+    def backward(ctx, g_latent, g_recon):
+        xf, idx, val, table = ctx.saved_tensors
+        model = ctx.model
+        lin, dec = model.encoder.linear, model.decoder
+        need_x, need_W, need_b, need_Wd, need_bd = ctx.needs_input_grad[2:7]
+        H = table.shape[0]
+        want_enc = need_W or need_b
+        dx = dW = db = dWd = dbd = None
+        if need_x or want_enc or need_Wd:
+            gv, dx = ops.train_row_grad(idx, table, 1.0, g_recon, g_latent, lin.weight.detach(), want_dx=need_x)
+            if want_enc or need_Wd:
+                offsets, entries = ops.train_csr(idx, H)
+                dW, db, dWd = ops.train_table_unit_grad(offsets, entries, val, gv, xf, g_recon, want_encoder=want_enc,
+                                                        want_decoder=need_Wd)
+        if need_bd:
+            dbd = ops.train_col_sum(g_recon) if g_recon is not None else torch.zeros_like(dec.bias)
+        if dx is not None and dx.dtype != ctx.x_dtype:
+            dx = dx.to(ctx.x_dtype)
+        return (None, None, dx if need_x else None, dW if need_W else None, db if need_b else None,
+                dWd if need_Wd else None, dbd)

@@ -527,6 +527,36 @@ def _(g):
     return _f32((g.shape[1],), g)
 
 
+# ---- BaselineSparseAutoencoder training ---------------------------------------------------------------------------------
+@_op("train_table_unit_grad")
+def _train_table_unit_grad(offsets: Tensor, entries: Tensor, val: Tensor, gv: Tensor, x: Tensor, g_recon: Optional[Tensor],
+                           want_encoder: bool, want_decoder: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    """-> (dW_enc [H, D], db_enc [H], dW_dec [D, H]); an output not wanted is empty ([0, D], [0], [D, 0])"""
+    dW, db, dWd = _ops.train_table_unit_grad(offsets, entries, val, gv, x, g_recon, want_encoder, want_decoder)
+    D = x.shape[1]
+    return (dW if dW is not None else _f32((0, D), x), db if db is not None else _f32((0,), x),
+            dWd if dWd is not None else _f32((D, 0), x))
+
+
+@_train_table_unit_grad.register_fake
+def _(offsets, entries, val, gv, x, g_recon, want_encoder, want_decoder):
+    H, D = offsets.shape[0] - 1, x.shape[1]
+    return (_f32((H if want_encoder else 0, D), x), _f32((H if want_encoder else 0,), x),
+            _f32((D, H if want_decoder else 0), x))
+
+
+@_op("normalize_columns_table", mutates=("W",))
+def _normalize_columns_table(W: Tensor, want_table: bool) -> Tensor:
+    """W [D, H] -> unit-norm columns in place; -> the normalised transpose [H, D] ([0, D] when not wanted)"""
+    table = _ops.normalize_columns_table(W, want_table)
+    return table if table is not None else _f32((0, W.shape[0]), W)
+
+
+@_normalize_columns_table.register_fake
+def _(W, want_table):
+    return _f32((W.shape[1] if want_table else 0, W.shape[0]), W)
+
+
 Q = torch.ops.qsae
 
 
@@ -752,8 +782,19 @@ def train_col_sum(g):
     return Q.train_col_sum(g)
 
 
+def train_table_unit_grad(offsets, entries, val, gv, x, g_recon, want_encoder=True, want_decoder=True):
+    dW, db, dWd = Q.train_table_unit_grad(offsets, entries, val, gv, x, g_recon, bool(want_encoder), bool(want_decoder))
+    return (dW if want_encoder else None), (db if want_encoder else None), (dWd if want_decoder else None)
+
+
+def normalize_columns_table(W, want_table=True):
+    table = Q.normalize_columns_table(W, bool(want_table))
+    return table if want_table else None
+
+
 # what has no tensor result (shape queries, handles of batches in flight) stays plain Python
 train_supported = _ops.train_supported
+normalize_columns_supported = _ops.normalize_columns_supported
 encode_topk_supported = _ops.encode_topk_supported
 prefilter_supported = _ops.prefilter_supported
 encode_bits_prefilter_supported = _ops.encode_bits_prefilter_supported
