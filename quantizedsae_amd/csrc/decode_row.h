@@ -1,6 +1,6 @@
 // decode_row.h -- one activation row of the BinarySAE sparse decode (reference sae/binary.py:38 evaluated on the k
 // kept entries): shared by the stand-alone decode kernel (binary.hip) and the refinement kernel of the prefilter
-// pipeline (encode_topk.hip), which decodes a row as soon as it has ranked it.
+// pipeline (refine_row.h, refine_sliced.h), which decodes a row as soon as it has ranked it.
 #pragma once
 
 #include "common.h"

@@ -20,7 +20,7 @@
 // HALF = true instantiates the same pipeline over fp16 operands ([rows][K] _Float16, natural k order)
 // with v_mfma_f32_32x32x16_f16: a K step is still 128 bytes per row (64 k), the image and the swizzle
 // are unchanged, one 16-byte fragment read feeds one MFMA instead of four.  It is used only as the
-// order-preserving *prefilter* of the encoder+top-k path (encode_topk.hip), never for returned values.
+// order-preserving *prefilter* of the encoder+top-k path (prefilter_topk.hip), never for returned values.
 #pragma once
 
 #include "gemm_mfma_f32.h"

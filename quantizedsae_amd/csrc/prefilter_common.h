@@ -1,5 +1,5 @@
 // prefilter_common.h -- per-row scaling and error budget of the fp16 candidate pass (shared by the stand-alone
-// preparation kernel in encode_topk.hip and the fused prologue of sweep_xstat_f16.h).
+// preparation kernel in prefilter_topk.hip and the fused prologue of sweep_xstat_f16.h).
 #pragma once
 
 #include "common.h"

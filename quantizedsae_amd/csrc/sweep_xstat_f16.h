@@ -1,6 +1,6 @@
 // sweep_xstat_f16.h -- the fp16 candidate sweep with the activation panel stationary in registers.
 //
-// Role: the candidate pass of the prefilter pipeline (encode_topk.hip).  For every activation row b and every
+// Role: the candidate pass of the prefilter pipeline (prefilter_topk.hip; encode_bits.hip).  For every activation row b and every
 // hidden unit h it forms the approximate latent  v = bias[h] + inv[b] sum_k xq[b,k] wq[h,k]  with
 // v_mfma_f32_32x32x16_f16 (the chain of a row tile starts from bias / inv, so the accumulators are v / inv and are
 // compared with (tau[b] - margin[b]) / inv directly) and appends (v, h) to the row's candidate list when
@@ -669,38 +669,9 @@ inline int xstat_parts(int B, int Hs, int cap) {
     return parts;
 }
 
-template <int KB, int ABL = 0>
-inline int launch_xstat_one(const XsArgs& a, hipStream_t stream) {
-    constexpr size_t lds = static_cast<size_t>(kXsStages) * kXsHT * 16 * KB * 2 +
-                           3 * kXsHT * 4 + static_cast<size_t>(kXsWaves) * kXsRingSlots * 256;
-    auto kern = sweep_xstat_f16_kernel<KB, ABL>;
-    QSAE_SET_MAX_LDS_ONCE(kern, lds);     // per instantiation and device
-    hipLaunchKernelGGL(kern, dim3((a.B + kXsRows - 1) / kXsRows, a.parts), dim3(64 * kXsWaves), lds, stream, a);
-    QSAE_LAUNCH_CHECK();
-    return QSAE_OK;
-}
-
 // ablate: 0 = the complete kernel; 9 = the build without any zero-fill code (the product path when the zeros come from
 // the co-resident fill kernel); 1-8 = timing ablations whose results are wrong, instantiated in the debug library only.
-inline int launch_xstat(int D, const XsArgs& a, hipStream_t stream, int ablate = 0) {
-#ifdef QSAE_DEBUG_BUILD
-    if (D == 512 && ablate == 1) return launch_xstat_one<32, 1>(a, stream);
-    if (D == 512 && ablate == 2) return launch_xstat_one<32, 2>(a, stream);
-    if (D == 512 && ablate == 3) return launch_xstat_one<32, 3>(a, stream);
-    if (D == 512 && ablate == 4) return launch_xstat_one<32, 4>(a, stream);
-    if (D == 512 && ablate == 5) return launch_xstat_one<32, 5>(a, stream);
-    if (D == 512 && ablate == 6) return launch_xstat_one<32, 6>(a, stream);
-    if (D == 512 && ablate == 7) return launch_xstat_one<32, 7>(a, stream);
-    if (D == 512 && ablate == 8) return launch_xstat_one<32, 8>(a, stream);
-    if (D == 512 && ablate == 10) return launch_xstat_one<32, 10>(a, stream);
-#endif
-    if (D == 512 && ablate == 9) return launch_xstat_one<32, 9>(a, stream);
-    switch (D) {
-        case 512: return launch_xstat_one<32>(a, stream);
-        case 256: return launch_xstat_one<16>(a, stream);
-        case 128: return launch_xstat_one<8>(a, stream);
-        default: return fail(QSAE_ERR_UNSUPPORTED, "%s: D must be 128, 256 or 512", __func__);
-    }
-}
+// Defined in prefilter_topk.hip, the one unit that emits the kernels.
+int launch_xstat(int D, const XsArgs& a, hipStream_t stream, int ablate = 0);
 
 }  // namespace qsae

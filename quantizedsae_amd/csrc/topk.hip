@@ -244,7 +244,7 @@ static int launch_topk(float* latent, int64_t ld, int B, int H, int k, int32_t* 
     return QSAE_OK;
 }
 
-// shared by qsae_topk_rows and the pilot stage of qsae_encode_topk (encode_topk.hip)
+// shared by qsae_topk_rows and the pilot stages of qsae_encode_topk (encode_topk.hip) and of the fp16 prefilter (prefilter_topk.hip)
 int topk_rows_dispatch(float* latent, int64_t ld, int B, int H, int k, int32_t* idx, float* val, int zero_rest,
                        float* tau, uint2* cand, int* cnt, int cap, float* dense, int64_t dense_ld, hipStream_t s,
                        const float* margin, int stride) {

@@ -925,3 +925,52 @@ def test_sliced_refinement_ranks_equal_latents_like_the_oracle(sliced_refinement
         assert np.array_equal(host(idx), want_idx), form
         assert np.array_equal(host(val).view(np.uint32), want_val.view(np.uint32)), form
     lib.qsae_debug_set_refine_sliced(2)
+
+
+def test_refine_sliced_switch_reaches_the_unit_that_launches_the_refinement(fused_path):
+    """Both refinements return the same bits, so the tests above cannot tell a qsae_debug_set_refine_sliced that works from
+    one that reaches no reader (the switch and the code that reads it may live in different translation units).  What
+    tells them apart: with bit 2 (value 4) of the phase mask the three-launch form returns before its rank launch, so only
+    the rows that the exact kernels took are written; the one-launch form ignores that bit."""
+    ops = _ops()
+    lib = fused_path
+    lib.qsae_debug_set_refine_sliced.argtypes = [C.c_int]
+    lib.qsae_debug_set_phases.argtypes = [C.c_int, C.c_int]
+    B, D, H, k = 1000, 512, 8192, 65
+    x = S.activations(197, B, D)
+    W = S.xavier_uniform(197, H, D, stream=1)
+    bias = S.normal(197, (H,), stream=3, std=0.05)
+    want_idx, _ = oracle.topk(oracle.encode(x, W, bias), k)
+    xd, Wd, bd = dev(x), dev(W), dev(bias)
+    Wq, meta = ops.prefilter_pack_w(Wd, bd)
+    need = int(lib.qsae_encode_topk_prefilter_workspace_bytes(B, D, H, k))
+    assert need > 0
+    ws = torch.empty((need,), dtype=torch.uint8, device=DEV)
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def call(sliced):
+        idx = torch.full((B, k), -1, dtype=torch.int32, device=DEV)
+        val = torch.zeros((B, k), dtype=torch.float32, device=DEV)
+        flagged = C.c_int(-1)
+        lib.qsae_debug_set_refine_sliced(sliced)
+        lib.qsae_debug_set_phases(7, 0)
+        rc = lib.qsae_encode_topk_prefilter(xd.data_ptr(), Wd.data_ptr(), bd.data_ptr(), Wq.data_ptr(), meta.data_ptr(), B, D, H,
+                                            k, idx.data_ptr(), val.data_ptr(), None, 0, ws.data_ptr(), need, 0,
+                                            C.byref(flagged), stream)
+        torch.cuda.synchronize()
+        assert rc == 0
+        return host(idx), flagged.value
+
+    try:
+        idx2, flagged2 = call(2)
+        idx0, _ = call(0)
+    finally:
+        lib.qsae_debug_set_refine_sliced(1)
+        lib.qsae_debug_set_phases(3, 0)
+    print(f"three-launch form without its rank launch: {int((idx2 == -1).all(axis=1).sum())} of {B} rows unwritten, "
+          f"{flagged2} flagged")
+    unwritten = (idx2 == -1).all(axis=1)
+    assert 0 <= flagged2 <= B // 20
+    assert unwritten.sum() == B - flagged2                   # rows that were not flagged still hold -1 ...
+    assert np.array_equal(idx2[~unwritten], want_idx[~unwritten])     # ... flagged ones come from the exact kernels
+    assert np.array_equal(idx0, want_idx)                    # the one-launch form ignores the bit

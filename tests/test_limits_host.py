@@ -15,7 +15,7 @@ FAKE = C.c_void_p(1 << 20)          # non-null, 256-byte aligned, never derefere
 
 # ---- the regions -----------------------------------------------------------------------------------------------------------
 def fused_region(B, D, H, k):
-    """qsae_encode_topk's fused form (encode_topk.hip use_fused) and qsae_encode_topk_latent on large batches."""
+    """qsae_encode_topk's fused form (encode_topk.hip use_fused; the fp16 prefilter, prefilter_topk.hip, takes the same region) and qsae_encode_topk_latent on large batches."""
     return B >= 2048 and 8192 <= H <= 65536 and H % 4 == 0 and 1 <= k <= 256 and D > 0 and D % 4 == 0
 
 

@@ -1,5 +1,6 @@
 """Register / scratch use of the kernels of one source file, from the compiler's own resource remarks
-(-Rpass-analysis=kernel-resource-usage; nothing is written).  usage: python tools/kernel_regs.py encode_topk.hip [substring ...]"""
+(-Rpass-analysis=kernel-resource-usage; nothing is written).  usage: python tools/kernel_regs.py prefilter_topk.hip [substring ...]
+(tools/kernel_table.py: every unit's kernels with size and code hash, for comparing two trees)"""
 import re
 import subprocess
 import sys
