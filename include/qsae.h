@@ -491,6 +491,63 @@ int qsae_train_table_unit_grad(const int32_t* offsets, const int32_t* entries, c
  * the normalised transpose, the rows the sparse decoder and qsae_train_row_grad gather.  H a multiple of 4, any D. */
 int qsae_normalize_columns_table(float* W, int D, int H, float* table, qsae_stream_t stream);
 
+/* -- QuantizedMatryoshkaSAE training: the gradient of the nested-dictionary forward under the straight-through estimators
+ *    (sae/quantized_matryoshka.py:47-190; the q_sae / rq_sae branches of training/trainer.py:88-142).  Hidden units are in
+ *    the packed order of qsae_pack_matryoshka (every level padded to a multiple of 32); index[slot] (nullable = identity)
+ *    is the parameter row of a slot, -1 for an inert pad slot.  No float atomics anywhere: bitwise reproducible. -------- */
+/* dst [D][H] = transpose of src [H][D] (fp32, D a multiple of 4, src 16-byte aligned). */
+int qsae_transpose_rows(const float* src, int H, int D, float* dst, qsae_stream_t stream);
+/* zbits[r][h / 32] bit h % 32 = (sigmoid(pre[r][h]) > 0.5) by the fp32 cutoff every bits path uses (pre >= 0x33C00001):
+ * the z bits of a saved pre-activation [B][ld], equal to qsae_encode_bits' on the same operands.  H a multiple of 32, ld a
+ * multiple of 4, pre 16-byte aligned. */
+int qsae_train_pre_bits(const float* pre, int64_t ld, int B, int H, uint32_t* zbits, int64_t words_ld, qsae_stream_t stream);
+/* sign_rows[slot][d] = S = sgn(sigmoid(w) >= .5) + sgn(sigmoid(wm) >= .5) in {-2, 0, 2} as fp32, 0 on pad slots: the
+ * K-contiguous dictionary operand of qsae_train_matryoshka_dpre.  H = slots, D a multiple of 4. */
+int qsae_train_matryoshka_sign_rows(const float* w, const float* wm, const int32_t* index, int H, int D, float* sign_rows,
+                                    qsae_stream_t stream);
+/* pre [B][pre_ld] holds the encoder pre-activation on entry and dpre on return:
+ *   dpre[r][h] = (scale[h] <g_levels[i][r], sign_rows[h]> + g_groups[i] / B) p (1 - p),  p = sigmoid(pre[r][h]), h in level i
+ * on the fp32 matrix pipe (k ascending).  g_levels [n_bits][B][D] / g_groups [n_bits] (device) may be NULL (that term is
+ * 0).  level_sizes[n_bits] sum to H, each a multiple of 32; D a multiple of 4 up to 4096; B >= 1. */
+int qsae_train_matryoshka_dpre(const float* g_levels, const float* g_groups, const float* sign_rows, const float* scale,
+                               int B, int D, int H, int n_bits, const int32_t* level_sizes, float* pre, int64_t pre_ld,
+                               qsae_stream_t stream);
+/* C[m][n] = sum_k A[k][m] X[k][n], k ascending (one fp32 fmaf chain per element, on the matrix pipe): both operands with
+ * the contraction index as the slow axis (A [K][lda], X [K][ldx], C [M][ldc]).  dW_enc = dpre^T x.  M, N, lda, ldx
+ * multiples of 4, A and X 16-byte aligned, K >= 1 (any value: the last K slice is zero-filled). */
+int qsae_train_gemm_tn(const float* A, int64_t lda, const float* X, int64_t ldx, int K, int M, int N, float* C, int64_t ldc,
+                       qsae_stream_t stream);
+/* dsum[h][d] = sum over rows r with z bit h set of g_levels[i][r][d] (h in level i), r ascending, as the same TN
+ * contraction with A expanded from zbits [B][words_ld]: for dense activations.  Shapes as qsae_train_matryoshka_dpre. */
+int qsae_train_matryoshka_dsum_dense(const uint32_t* zbits, int64_t words_ld, const float* g_levels, int B, int D, int H,
+                                     int n_bits, const int32_t* level_sizes, float* dsum, qsae_stream_t stream);
+/* Device workspace of qsae_train_bits_csr (0 for a refused shape: H not a multiple of 32, B < 1, B * H >= 2^31). */
+size_t qsae_train_bits_csr_workspace_bytes(int B, int H);
+/* The active rows of every unit from zbits [B][words_ld]: offsets[H + 1] (int32) and, for n_entries > 0,
+ * entries[offsets[h] .. offsets[h + 1]) = the rows r whose bit h is set, ascending -- the lists qsae_train_csr builds, from
+ * a bit transpose instead of top-k indices.  n_entries = capacity of entries (the batch's active-unit count; positions at or
+ * beyond it are not written). */
+int qsae_train_bits_csr(const uint32_t* zbits, int64_t words_ld, int B, int H, int32_t* offsets, int32_t* entries,
+                        int64_t n_entries, void* workspace, size_t workspace_bytes, qsae_stream_t stream);
+/* Device workspace of qsae_train_matryoshka_dsum_lists (0 for a refused shape: D not a multiple of 4 or over 4096,
+ * n_entries >= 2^31, B < 1). */
+size_t qsae_train_matryoshka_dsum_lists_workspace_bytes(int B, int64_t n_entries, int H, int D);
+/* dsum as qsae_train_matryoshka_dsum_dense, summed over each unit's list (qsae_train_bits_csr) in list order: for sparse
+ * activations.  Units nobody activates get exact zeros.  Lists longer than 256 rows are split into chunks whose partials
+ * are added in chunk order. */
+int qsae_train_matryoshka_dsum_lists(const int32_t* offsets, const int32_t* entries, int64_t n_entries, const float* g_levels,
+                                     int B, int D, int H, int n_bits, const int32_t* level_sizes, float* dsum,
+                                     void* workspace, size_t workspace_bytes, qsae_stream_t stream);
+/* dweight[u][d] = scale[slot] dsum[slot][d] sw (1 - sw), sw = sigmoid(w[u][d]), u = index[slot]; dweight_mirror likewise
+ * from wm: one pass over the two logit tensors.  dsum NULL: zeros.  H = slots. */
+int qsae_train_matryoshka_finish(const float* dsum, const float* scale, const int32_t* index, const float* w, const float* wm,
+                                 int H, int D, float* dweight, float* dweight_mirror, qsae_stream_t stream);
+/* apply_secant_grad(): grad_weight[u][d] -= c counts[slot] scale[slot]^2 Bs sw (1 - sw) in place, Bs = sgn(sigmoid(w) >= .5);
+ * the mirror likewise with wm.  counts int64 [H] = active rows per slot (qsae_activation_counts_bits), c = 1 / (B D). */
+int qsae_train_matryoshka_secant(const int64_t* counts, float c, const float* scale, const int32_t* index, const float* w,
+                                 const float* wm, int H, int D, float* grad_weight, float* grad_weight_mirror,
+                                 qsae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,6 +118,18 @@ SIGNATURES = {
     "qsae_train_col_sum": (_i, [_vp, _i, _i, _vp, _vp, _sz, _vp]),
     "qsae_train_table_unit_grad_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "qsae_train_table_unit_grad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _i64, _vp, _sz, _vp]),
+    "qsae_transpose_rows": (_i, [_vp, _i, _i, _vp, _vp]),
+    "qsae_train_pre_bits": (_i, [_vp, _i64, _i, _i, _vp, _i64, _vp]),
+    "qsae_train_matryoshka_sign_rows": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "qsae_train_matryoshka_dpre": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i64, _vp]),
+    "qsae_train_gemm_tn": (_i, [_vp, _i64, _vp, _i64, _i, _i, _i, _vp, _i64, _vp]),
+    "qsae_train_matryoshka_dsum_dense": (_i, [_vp, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "qsae_train_bits_csr_workspace_bytes": (_sz, [_i, _i]),
+    "qsae_train_bits_csr": (_i, [_vp, _i64, _i, _i, _vp, _vp, _i64, _vp, _sz, _vp]),
+    "qsae_train_matryoshka_dsum_lists_workspace_bytes": (_sz, [_i, _i64, _i, _i]),
+    "qsae_train_matryoshka_dsum_lists": (_i, [_vp, _vp, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "qsae_train_matryoshka_finish": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "qsae_train_matryoshka_secant": (_i, [_vp, _f, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "qsae_normalize_columns_table": (_i, [_vp, _i, _i, _vp, _vp]),
 }
 

@@ -235,7 +235,7 @@ struct UnitArgs {
     const float* gv;        // [B k]
     long long Bk;
     int k, H, D, n;
-    const float* x;         // [B][D]
+    const float* x;         // [B][D]; nullptr: no dW / db sums (the list sums of the matryoshka decoder gradient)
     const float* gR;        // [B][D] or nullptr
     const float* logits;    // [H][D n]
     float step;
@@ -310,7 +310,7 @@ unit_chunk_kernel(UnitArgs a) {
 #pragma unroll 4
         for (int i = 0; i < len; ++i) {
             const long long ro = static_cast<long long>(s_r[i]) * D + 4 * c4;
-            w = fma4(s_gv[i], ld4(a.x + ro), w);
+            if (a.x) w = fma4(s_gv[i], ld4(a.x + ro), w);
             if (a.gR) s = fma4(s_v[i], ld4(a.gR + ro), s);
         }
         if (!split) {
@@ -528,6 +528,146 @@ col_sum_final_kernel(const float* __restrict__ partial, int nparts, int D, float
     float s = 0.0f;
     for (int p = 0; p < nparts; ++p) s += partial[static_cast<long long>(p) * D + d];
     out[d] = s;
+}
+
+// ---- QuantizedMatryoshkaSAE: unit lists from the z bits, decoder-logit gradients --------------------------------------
+// (reference: sae/quantized_matryoshka.py:47-190; the table in DESIGN.md section 4.12)
+//
+// bitmap[h][w] bit (r & 31) of word w = r >> 5  <-  bit (h & 31) of zbits[r][h >> 5]: the layout csr_count_kernel scans.
+// One wave transposes 32 rows x 2 words: lane l holds word 2 wp + (l >> 5) of row 32 rb + (l & 31); ballot j collects bit j
+// of all 64 lanes, its low half is word rb of unit 64 wp + j, its high half that of unit 64 wp + 32 + j.
+__global__ void __launch_bounds__(256)
+bits_transpose_kernel(const uint32_t* __restrict__ zbits, long long words_ld, int B, int words, int W,
+                      uint32_t* __restrict__ bitmap) {
+    const int lane = threadIdx.x & 63;
+    const int wi = 2 * (blockIdx.x * 4 + (threadIdx.x >> 6)) + (lane >> 5);
+    const int rb = blockIdx.y;
+    const int row = rb * 32 + (lane & 31);
+    const uint32_t v = (row < B && wi < words) ? zbits[static_cast<long long>(row) * words_ld + wi] : 0u;
+    uint32_t mine = 0;
+#pragma unroll
+    for (int j = 0; j < 32; ++j) {                         // every lane takes part in every ballot
+        const unsigned long long m = __ballot((v >> j) & 1u);
+        const uint32_t part = (lane >> 5) ? static_cast<uint32_t>(m >> 32) : static_cast<uint32_t>(m);
+        if ((lane & 31) == j) mine = part;
+    }
+    if (wi < words) bitmap[(static_cast<long long>(wi) * 32 + (lane & 31)) * W + rb] = mine;
+}
+
+// zbits[r][h >> 5] bit (h & 31) = sig_gt_half(pre[r][h]) -- the cutoff of every bits path (common.h) applied to a saved
+// pre-activation.  One thread per 4 units (one 16-byte load), 8 lanes OR their nibbles into one word; H % 32 == 0, so the 8
+// lanes of a word share a row and whole waves stay in the loop together.
+__global__ void __launch_bounds__(256)
+pre_bits_kernel(const float* __restrict__ pre, long long ld, long long total4, int H4, uint32_t* __restrict__ zbits,
+                long long words_ld) {
+    const int lane = threadIdx.x & 63;
+    const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
+    for (long long base = static_cast<long long>(blockIdx.x) * blockDim.x + (threadIdx.x - lane); base < total4; base += stride) {
+        const long long i = base + lane;
+        const bool ok = i < total4;
+        const long long r = ok ? i / H4 : 0;
+        const int c4 = ok ? static_cast<int>(i % H4) : 0;
+        uint32_t word = 0;
+        if (ok) {
+            const tr_f32x4 v = ld4(pre + r * ld + 4 * c4);
+            const uint32_t nib = (sig_gt_half(v[0]) ? 1u : 0u) | (sig_gt_half(v[1]) ? 2u : 0u) | (sig_gt_half(v[2]) ? 4u : 0u) |
+                                 (sig_gt_half(v[3]) ? 8u : 0u);
+            word = nib << (4 * (lane & 7));
+        }
+        word |= __shfl_xor(word, 1, 64);                   // every lane of the wave takes part
+        word |= __shfl_xor(word, 2, 64);
+        word |= __shfl_xor(word, 4, 64);
+        if (ok && (lane & 7) == 0) zbits[r * words_ld + (c4 >> 3)] = word;
+    }
+}
+
+// one wave per unit: entries[offsets[h] + rank] = r for every row r whose bit is set, in row order
+__global__ void __launch_bounds__(256)
+bits_fill_kernel(const uint32_t* __restrict__ bitmap, const int* __restrict__ prefix, const int* __restrict__ offsets, int H,
+                 int W, long long cap, int* __restrict__ entries) {
+    const int lane = threadIdx.x & 63;
+    const int h = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (h >= H) return;                                    // wave-uniform
+    for (int w = lane; w < W; w += 64) {
+        const long long wi = static_cast<long long>(h) * W + w;
+        uint32_t word = bitmap[wi];
+        long long pos = static_cast<long long>(offsets[h]) + prefix[wi];
+        while (word) {
+            const int b = __ffs(word) - 1;
+            if (pos < cap) entries[pos] = 32 * w + b;      // cap = the caller's entry count: stays in bounds whatever it is
+            ++pos;
+            word &= word - 1u;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256)
+fill_f32_kernel(float* __restrict__ p, int n, float v) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+
+// S[slot][:] = sgn(sigmoid(w) >= .5) + sgn(sigmoid(wm) >= .5) of the slot's source unit (index, or the slot itself); 0 on
+// the inert pad slots (index < 0).  The fp32 image of the dictionary in the packed hidden order.
+__global__ void __launch_bounds__(256)
+matryoshka_sign_rows_kernel(const float* __restrict__ w, const float* __restrict__ wm, const int* __restrict__ index,
+                            long long total4, int D4, float* __restrict__ S) {
+    const long long gid = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (gid >= total4) return;
+    const long long slot = gid / D4;
+    const int c4 = static_cast<int>(gid % D4);
+    const long long src = index ? index[slot] : slot;
+    tr_f32x4 o = {0.f, 0.f, 0.f, 0.f};
+    if (src >= 0) {
+        const tr_f32x4 a = ld4(w + (src * D4 + c4) * 4), b = ld4(wm + (src * D4 + c4) * 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = (sig_ge_half(a[e]) ? 1.0f : -1.0f) + (sig_ge_half(b[e]) ? 1.0f : -1.0f);
+    }
+    st4(S + gid * 4, o);
+}
+
+// SECANT = false: dweight[src][d] = scale_slot dSum[slot][d] sw (1 - sw), sw = sigmoid(weight[src][d]); the mirror likewise
+//                 (dsum == nullptr: zeros).  One pass over the two logit tensors.
+// SECANT = true:  gw[src][d] -= c cnt_slot scale_slot^2 Bs sw (1 - sw) in place, Bs = sgn(sigmoid(weight) >= .5); the mirror
+//                 likewise (apply_secant_grad, sae/quantized_matryoshka.py:145-190).
+template <bool SECANT>
+__global__ void __launch_bounds__(256)
+matryoshka_logit_grad_kernel(const float* __restrict__ dsum, const long long* __restrict__ cnt, float c,
+                             const float* __restrict__ scale, const int* __restrict__ index,
+                             const float* __restrict__ w, const float* __restrict__ wm, long long total4, int D4,
+                             float* __restrict__ gw, float* __restrict__ gwm) {
+    const long long gid = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (gid >= total4) return;
+    const long long slot = gid / D4;
+    const int c4 = static_cast<int>(gid % D4);
+    const long long src = index ? index[slot] : slot;
+    if (src < 0) return;
+    const long long o = (src * D4 + c4) * 4;
+    const float sc = scale[slot];
+    const tr_f32x4 a = ld4(w + o), b = ld4(wm + o);
+    tr_f32x4 ga, gb;
+    if constexpr (SECANT) {
+        const float coef = (c * static_cast<float>(cnt[slot])) * (sc * sc);
+        ga = ld4(gw + o);
+        gb = ld4(gwm + o);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float pa = soft_bit_prob(a[e]), pb = soft_bit_prob(b[e]);
+            ga[e] = ga[e] - (coef * (sig_ge_half(a[e]) ? 1.0f : -1.0f)) * (pa * (1.0f - pa));
+            gb[e] = gb[e] - (coef * (sig_ge_half(b[e]) ? 1.0f : -1.0f)) * (pb * (1.0f - pb));
+        }
+    } else {
+        tr_f32x4 ds = {0.f, 0.f, 0.f, 0.f};
+        if (dsum) ds = ld4(dsum + gid * 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float pa = soft_bit_prob(a[e]), pb = soft_bit_prob(b[e]);
+            ga[e] = (sc * ds[e]) * (pa * (1.0f - pa));
+            gb[e] = (sc * ds[e]) * (pb * (1.0f - pb));
+        }
+    }
+    st4(gw + o, ga);
+    st4(gwm + o, gb);
 }
 
 // ---- workspace layouts -----------------------------------------------------------------------------------------------
@@ -794,6 +934,193 @@ extern "C" int qsae_normalize_columns_table(float* W, int D, int H, float* table
     QSAE_SET_MAX_LDS_ONCE(normalize_columns_kernel, (static_cast<size_t>(kNormRows) * kNormCols + kNormCols) * 4);
     hipLaunchKernelGGL(normalize_columns_kernel, dim3((H + kNormCols - 1) / kNormCols), dim3(256), lds, as_stream(stream), W,
                        D, H, table);
+    QSAE_LAUNCH_CHECK();
+    return QSAE_OK;
+}
+
+// ---- QuantizedMatryoshkaSAE training (the dense contractions are in train_gemm.hip) ------------------------------------
+extern "C" int qsae_transpose_rows(const float* src, int H, int D, float* dst, qsae_stream_t stream) {
+    QSAE_CHECK_ARG(H > 0 && D > 0 && src && dst, "H > 0, D > 0, non-null pointers");
+    QSAE_CHECK_SUPPORTED(D % 4 == 0, "D a multiple of 4");
+    QSAE_CHECK_ARG(aligned16(src), "src must be 16-byte aligned");
+    const int vec = (H % 4 == 0 && aligned16(dst)) ? 1 : 0;
+    const dim3 grid((H + kTrTile - 1) / kTrTile, (D + kTrTile * kTrTilesD - 1) / (kTrTile * kTrTilesD));
+    hipLaunchKernelGGL(transpose_rows_kernel, grid, dim3(256), 0, as_stream(stream), src, H, D, dst, static_cast<long long>(H),
+                       vec);
+    QSAE_LAUNCH_CHECK();
+    return QSAE_OK;
+}
+
+extern "C" int qsae_train_pre_bits(const float* pre, int64_t ld, int B, int H, uint32_t* zbits, int64_t words_ld,
+                                   qsae_stream_t stream) {
+    QSAE_CHECK_ARG(B >= 0 && H > 0, "B >= 0, H > 0 required");
+    QSAE_CHECK_SUPPORTED(H % 32 == 0 && ld % 4 == 0, "H a multiple of 32, ld a multiple of 4");
+    if (B == 0) return QSAE_OK;
+    QSAE_CHECK_ARG(pre && zbits && ld >= H && words_ld >= H / 32, "null pointer, ld < H or words_ld < H / 32");
+    QSAE_CHECK_ARG(aligned16(pre), "pre must be 16-byte aligned");
+    const long long total4 = static_cast<long long>(B) * (H / 4);
+    long long blocks = (total4 + 255) / 256;
+    if (blocks > 16384) blocks = 16384;
+    hipLaunchKernelGGL(pre_bits_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, as_stream(stream), pre,
+                       static_cast<long long>(ld), total4, H / 4, zbits, static_cast<long long>(words_ld));
+    QSAE_LAUNCH_CHECK();
+    return QSAE_OK;
+}
+
+inline bool bits_csr_shape_ok(int B, int H) {
+    return B >= 1 && H > 0 && H % 32 == 0 && static_cast<long long>(B) * H < (1LL << 31) && (B + 31) / 32 <= 65535;
+}
+
+extern "C" size_t qsae_train_bits_csr_workspace_bytes(int B, int H) {
+    if (!bits_csr_shape_ok(B, H)) return 0;
+    return csr_layout(B, H).total;
+}
+
+extern "C" int qsae_train_bits_csr(const uint32_t* zbits, int64_t words_ld, int B, int H, int32_t* offsets, int32_t* entries,
+                                   int64_t n_entries, void* workspace, size_t workspace_bytes, qsae_stream_t stream) {
+    QSAE_CHECK_ARG(B >= 1 && H > 0, "B >= 1, H > 0 required");
+    QSAE_CHECK_SUPPORTED(bits_csr_shape_ok(B, H), "H a multiple of 32, B * H < 2^31, B <= 2097120");
+    QSAE_CHECK_ARG(zbits && offsets && workspace && words_ld >= H / 32, "null pointer or words_ld < H / 32");
+    QSAE_CHECK_ARG(n_entries >= 0 && (n_entries == 0 || entries), "n_entries >= 0, entries required");
+    const CsrLayout L = csr_layout(B, H);
+    if (workspace_bytes < L.total) return fail(QSAE_ERR_WORKSPACE, "%s: workspace too small", __func__);
+    hipStream_t s = as_stream(stream);
+    char* ws = static_cast<char*>(workspace);
+    uint32_t* bitmap = reinterpret_cast<uint32_t*>(ws + L.bitmap);
+    int* prefix = reinterpret_cast<int*>(ws + L.prefix);
+    int* counts = reinterpret_cast<int*>(ws + L.counts);
+    const int words = H / 32;
+    // every word of the bitmap is written: words / 2 word pairs (4 per workgroup) x W row blocks
+    const dim3 grid(((words + 1) / 2 + 3) / 4, L.W);
+    hipLaunchKernelGGL(bits_transpose_kernel, grid, dim3(256), 0, s, zbits, static_cast<long long>(words_ld), B, words, L.W,
+                       bitmap);
+    QSAE_LAUNCH_CHECK();
+    hipLaunchKernelGGL(csr_count_kernel, dim3((H + 3) / 4), dim3(256), 0, s, bitmap, H, L.W, prefix, counts);
+    QSAE_LAUNCH_CHECK();
+    hipLaunchKernelGGL(scan_kernel<0>, dim3(1), dim3(1024), 0, s, counts, H, offsets);
+    QSAE_LAUNCH_CHECK();
+    if (n_entries > 0) {
+        hipLaunchKernelGGL(bits_fill_kernel, dim3((H + 3) / 4), dim3(256), 0, s, bitmap, prefix, offsets, H, L.W,
+                           static_cast<long long>(n_entries), entries);
+        QSAE_LAUNCH_CHECK();
+    }
+    return QSAE_OK;
+}
+
+constexpr int kMatMaxLevels = 8;
+
+inline size_t dsum_lists_ones_offset(long long n_entries, int H, int D) { return unit_layout(n_entries, H, D).total; }
+
+extern "C" size_t qsae_train_matryoshka_dsum_lists_workspace_bytes(int B, int64_t n_entries, int H, int D) {
+    if (B < 1 || n_entries < 0 || n_entries >= (1LL << 31) || H <= 0 || !train_shape_ok(D)) return 0;
+    return dsum_lists_ones_offset(n_entries, H, D) + align_up(static_cast<size_t>(B) * 4);
+}
+
+extern "C" int qsae_train_matryoshka_dsum_lists(const int32_t* offsets, const int32_t* entries, int64_t n_entries,
+                                                const float* g_levels, int B, int D, int H, int n_bits,
+                                                const int32_t* level_sizes, float* dsum, void* workspace,
+                                                size_t workspace_bytes, qsae_stream_t stream) {
+    QSAE_CHECK_ARG(B >= 1 && D > 0 && H > 0, "B >= 1, D > 0, H > 0 required");
+    QSAE_CHECK_ARG(n_bits >= 1 && n_bits <= kMatMaxLevels && level_sizes, "1 <= n_bits <= 8 and level sizes required");
+    QSAE_CHECK_SUPPORTED(train_shape_ok(D), "D a multiple of 4, at most 4096");
+    QSAE_CHECK_SUPPORTED(n_entries >= 0 && n_entries < (1LL << 31), "0 <= n_entries < 2^31");
+    QSAE_CHECK_ARG(offsets && g_levels && dsum && workspace && (n_entries == 0 || entries), "null pointer");
+    QSAE_CHECK_ARG(aligned16(g_levels) && aligned16(dsum), "g_levels and dsum must be 16-byte aligned");
+    long long sum = 0;
+    for (int i = 0; i < n_bits; ++i) {
+        QSAE_CHECK_ARG(level_sizes[i] >= 0, "negative level size");
+        sum += level_sizes[i];
+    }
+    QSAE_CHECK_ARG(sum == H, "level sizes do not sum to H");
+    if (workspace_bytes < qsae_train_matryoshka_dsum_lists_workspace_bytes(B, n_entries, H, D))
+        return fail(QSAE_ERR_WORKSPACE, "%s: workspace too small", __func__);
+    const UnitLayout L = unit_layout(n_entries, H, D);
+    hipStream_t s = as_stream(stream);
+    char* ws = static_cast<char*>(workspace);
+    int* chunk_off = reinterpret_cast<int*>(ws + L.chunk_off);
+    float* ones = reinterpret_cast<float*>(ws + dsum_lists_ones_offset(n_entries, H, D));
+    hipLaunchKernelGGL(fill_f32_kernel, dim3((B + 255) / 256), dim3(256), 0, s, ones, B, 1.0f);
+    QSAE_LAUNCH_CHECK();
+    const int D4 = D / 4;
+    const int threads = D4 >= 256 ? 256 : ((D4 + 63) / 64) * 64;
+    int h0 = 0;
+    for (int i = 0; i < n_bits; ++i) {
+        const int n = level_sizes[i];
+        if (n == 0) continue;
+        // the lists of this level's units against this level's incoming gradient: entry = row, value 1
+        hipLaunchKernelGGL(scan_kernel<1>, dim3(1), dim3(1024), 0, s, offsets + h0, n, chunk_off);
+        QSAE_LAUNCH_CHECK();
+        UnitArgs a{offsets + h0, entries, chunk_off, ones, ones, B, 1, n, D, 1, nullptr,
+                   g_levels + static_cast<long long>(i) * B * D, nullptr, 1.0f, nullptr, 1.0, nullptr, nullptr, nullptr,
+                   reinterpret_cast<float*>(ws + L.slab), L.slab_rows, L.slab_ld, dsum + static_cast<long long>(h0) * D};
+        const long long grid = static_cast<long long>(n) + (n_entries + kTrainChunk - 1) / kTrainChunk;   // >= number of chunks
+        hipLaunchKernelGGL(unit_chunk_kernel<true>, dim3(static_cast<unsigned>(grid)), dim3(threads), 0, s, a);
+        QSAE_LAUNCH_CHECK();
+        if (n_entries > kTrainChunk) {                     // otherwise no list can be split
+            hipLaunchKernelGGL(unit_final_kernel<true>, dim3(n), dim3(threads), 0, s, a);
+            QSAE_LAUNCH_CHECK();
+        }
+        h0 += n;
+    }
+    return QSAE_OK;
+}
+
+static int logit_grad_grid(int H, int D, long long& total4, unsigned& blocks) {
+    total4 = static_cast<long long>(H) * (D / 4);
+    const long long b = (total4 + 255) / 256;
+    if (b >= (1LL << 31)) return fail(QSAE_ERR_UNSUPPORTED, "%s: unsupported: H * D < 2^41", __func__);
+    blocks = static_cast<unsigned>(b);
+    return QSAE_OK;
+}
+
+extern "C" int qsae_train_matryoshka_sign_rows(const float* w, const float* wm, const int32_t* index, int H, int D,
+                                               float* sign_rows, qsae_stream_t stream) {
+    QSAE_CHECK_ARG(H > 0 && D > 0 && w && wm && sign_rows, "H > 0, D > 0, non-null pointers");
+    QSAE_CHECK_SUPPORTED(D % 4 == 0, "D a multiple of 4");
+    QSAE_CHECK_ARG(aligned16(w) && aligned16(wm) && aligned16(sign_rows), "w, wm and sign_rows must be 16-byte aligned");
+    long long total4;
+    unsigned blocks;
+    const int rc = logit_grad_grid(H, D, total4, blocks);
+    if (rc != QSAE_OK) return rc;
+    hipLaunchKernelGGL(matryoshka_sign_rows_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), w, wm, index, total4, D / 4,
+                       sign_rows);
+    QSAE_LAUNCH_CHECK();
+    return QSAE_OK;
+}
+
+extern "C" int qsae_train_matryoshka_finish(const float* dsum, const float* scale, const int32_t* index, const float* w,
+                                            const float* wm, int H, int D, float* dweight, float* dweight_mirror,
+                                            qsae_stream_t stream) {
+    QSAE_CHECK_ARG(H > 0 && D > 0 && scale && w && wm && dweight && dweight_mirror, "H > 0, D > 0, non-null pointers");
+    QSAE_CHECK_SUPPORTED(D % 4 == 0, "D a multiple of 4");
+    QSAE_CHECK_ARG(aligned16(w) && aligned16(wm) && aligned16(dweight) && aligned16(dweight_mirror) &&
+                   (!dsum || aligned16(dsum)), "dsum, w, wm and the gradients must be 16-byte aligned");
+    long long total4;
+    unsigned blocks;
+    const int rc = logit_grad_grid(H, D, total4, blocks);
+    if (rc != QSAE_OK) return rc;
+    hipLaunchKernelGGL(matryoshka_logit_grad_kernel<false>, dim3(blocks), dim3(256), 0, as_stream(stream), dsum,
+                       static_cast<const long long*>(nullptr), 0.0f, scale, index, w, wm, total4, D / 4, dweight,
+                       dweight_mirror);
+    QSAE_LAUNCH_CHECK();
+    return QSAE_OK;
+}
+
+extern "C" int qsae_train_matryoshka_secant(const int64_t* counts, float c, const float* scale, const int32_t* index,
+                                            const float* w, const float* wm, int H, int D, float* grad_weight,
+                                            float* grad_weight_mirror, qsae_stream_t stream) {
+    QSAE_CHECK_ARG(H > 0 && D > 0 && counts && scale && w && wm && grad_weight && grad_weight_mirror,
+                   "H > 0, D > 0, non-null pointers");
+    QSAE_CHECK_SUPPORTED(D % 4 == 0, "D a multiple of 4");
+    QSAE_CHECK_ARG(aligned16(w) && aligned16(wm) && aligned16(grad_weight) && aligned16(grad_weight_mirror),
+                   "w, wm and the gradients must be 16-byte aligned");
+    long long total4;
+    unsigned blocks;
+    const int rc = logit_grad_grid(H, D, total4, blocks);
+    if (rc != QSAE_OK) return rc;
+    hipLaunchKernelGGL(matryoshka_logit_grad_kernel<true>, dim3(blocks), dim3(256), 0, as_stream(stream),
+                       static_cast<const float*>(nullptr), reinterpret_cast<const long long*>(counts), c, scale, index, w, wm,
+                       total4, D / 4, grad_weight, grad_weight_mirror);
     QSAE_LAUNCH_CHECK();
     return QSAE_OK;
 }

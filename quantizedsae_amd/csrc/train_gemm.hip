@@ -1,0 +1,423 @@
+// train_gemm.hip -- the dense contractions of the QuantizedMatryoshkaSAE backward on the fp32 matrix pipe (reference:
+// sae/quantized_matryoshka.py:47-143 under loss.backward(); the q_sae / rq_sae branches of training/trainer.py:88-142).
+//
+// The latent is binarised with a straight-through estimator, so every sigmoid output of every row receives a gradient:
+//   dz[r][h]   = scale_h <G_i[r], S[h]> + gg_i / B        (h in level i)          NT: both operands K-contiguous (K = D)
+//   dpre[r][h] = dz[r][h] p (1 - p),  p = sigmoid(pre[r][h])                       epilogue of the same kernel, in place
+//   dW_enc[h][d] = sum_r dpre[r][h] x[r][d]                                        TN: K = B is the SLOW axis of both
+//   dSum[h][d]   = sum_r z[r][h] G_i[r][d]     (dense activations)                 TN, A expanded from the z bits
+//
+// The TN operands are staged by loaders that read 16-byte chunks ACROSS the output rows for a fixed k and write them
+// transposed into the LDS image of gemm_mfma_f32.h, so the MFMA loop -- and with it the fmaf chain in ascending r -- is the
+// one of every other contraction in this library.  K beyond B is zero-filled (fma(0, 0, acc) == acc).
+//
+// LDS bank check of the transposed store.  A thread owns 4 output rows (m = 4 mc .. 4 mc + 3) x 4 consecutive k (chunk c),
+// c = tid % 8, mc = tid / 8; after a 4 x 4 register transpose it stores, per row, the chunk as two ds_write_b64 at dword
+// (4 mc + e) 36 + 8 (c >> 1) + 2 (c & 1) (+ 4 for the odd-k pair).  ds_write_b64 is serviced in 4 groups of 16 contiguous
+// lanes, bank = dword mod 32: a group holds c = 0..7 for two consecutive mc, and 144 mc = 16 (mc & 1) (mod 32), so both mc
+// would land on banks {0-3, 8-11, 16-19, 24-27} (+ 4 e): 2-way.  Lanes with odd mc therefore store the odd-k pair FIRST: the
+// first store of a group covers {0-3, 8-11, 16-19, 24-27} (even mc) and {20-23, 28-31, 4-7, 12-15} (odd mc), the second
+// store the complement: 32 different banks per group on either store.  The fragment reads are unchanged (same image).
+#include "gemm_mfma_f32.h"
+
+namespace qsae {
+
+constexpr int kTnMaxLevels = 8;
+constexpr int kTnMaxD = 4096;
+
+// ---- TN operand loaders --------------------------------------------------------------------------------------------
+__device__ __forceinline__ void lds_put_chunk_alt(float* row, int c, f32x4 v, bool odd_first) {
+    float* p = row + perm_pair_offset(c);
+    const f32x2 even{v[0], v[2]}, odd{v[1], v[3]};
+    *reinterpret_cast<f32x2*>(p + (odd_first ? 4 : 0)) = odd_first ? odd : even;
+    *reinterpret_cast<f32x2*>(p + (odd_first ? 0 : 4)) = odd_first ? even : odd;
+}
+
+// fp32 operand with element (m, k) at p[k ld + m]: nrows % 4 == 0, ld % 4 == 0, p 16-byte aligned.  Row chunks at or beyond
+// nrows are clamped to the last chunk (their outputs are never stored), k >= K reads as zero.
+template <int ROWS, int BK>
+struct LoaderTN {
+    using G = TileGeom<BK>;
+    static constexpr int KC = BK / 4;                          // k chunks per slice
+    static constexpr int MC = kGemmThreads / KC;               // row chunks (of 4 rows) per pass
+    static constexpr int PASSES = ROWS / (4 * MC);
+    static_assert(ROWS % (4 * MC) == 0, "tile rows must be a multiple of the rows per pass");
+    struct Args {
+        const float* p;
+        int64_t ld;
+        int nrows;
+    };
+    static constexpr bool kAsmLoads = false;
+    static constexpr int kLoadsPerStep = 4 * PASSES;
+    template <int P> __device__ __forceinline__ void pin() {}
+    const float* colp[PASSES];
+    f32x4 r[2][PASSES][4];
+    Args args;
+    int K, c, mc;
+
+    __device__ __forceinline__ void init(const Args& a, int K_, int tid) {
+        args = a;
+        K = K_;
+        c = tid % KC;
+        mc = tid / KC;
+    }
+    __device__ __forceinline__ void set_rows(int row0) {
+#pragma unroll
+        for (int i = 0; i < PASSES; ++i) {
+            int m = row0 + 4 * (i * MC + mc);
+            m = (m + 3) < args.nrows ? m : args.nrows - 4;
+            colp[i] = args.p + m;
+        }
+    }
+    template <int P>
+    __device__ __forceinline__ void load(int kt) {
+        const int k0 = kt * BK + 4 * c;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool ok = (k0 + j) < K;
+            const int64_t off = ok ? static_cast<int64_t>(k0 + j) * args.ld : 0;
+#pragma unroll
+            for (int i = 0; i < PASSES; ++i) {
+                const f32x4 t = *reinterpret_cast<const f32x4*>(colp[i] + off);
+                r[P][i][j] = ok ? t : f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+        }
+    }
+    template <int P>
+    __device__ __forceinline__ void store(float* tile) const {
+#pragma unroll
+        for (int i = 0; i < PASSES; ++i)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const f32x4 v{r[P][i][0][e], r[P][i][1][e], r[P][i][2][e], r[P][i][3][e]};
+                lds_put_chunk_alt(tile + (4 * (i * MC + mc) + e) * G::LDS_STRIDE, c, v, (mc & 1) != 0);
+            }
+    }
+};
+
+// LoaderTN for the X operand of a contraction that covers all levels in ONE launch: the workgroup's single M tile
+// (sweep = 1) decides the level, and with it which [K][ld] block of p the panel comes from.  Needs every level boundary on
+// a multiple of the tile height, so that a tile never straddles two levels.
+template <int ROWS, int BK>
+struct LoaderTNByLevel : LoaderTN<ROWS, BK> {
+    using Base = LoaderTN<ROWS, BK>;
+    struct Args {
+        const float* p;            // [n][K][ld]
+        int64_t ld;
+        int nrows;
+        int64_t level_stride;      // K * ld
+        int n;
+        int end_tile[kTnMaxLevels];   // exclusive end of each level, in M tiles
+        SweepMap map;              // the map the launch uses (sweep == 1)
+    };
+    __device__ __forceinline__ void init(const Args& a, int K_, int tid) {
+        int tn, m_first, m_last;
+        a.map.locate(blockIdx.x, gridDim.x, tn, m_first, m_last);
+        int level = 0;
+        while (level < a.n - 1 && m_first >= a.end_tile[level]) ++level;
+        Base::init(typename Base::Args{a.p + level * a.level_stride, a.ld, a.nrows}, K_, tid);
+    }
+};
+
+// z bits as a TN operand: element (m, k) = bit (bit0 + m) of row k of zbits [K][words_ld] as 0.0 / 1.0; bit0 % 32 == 0,
+// nrows % 4 == 0.
+template <int ROWS, int BK>
+struct LoaderTNBits {
+    using G = TileGeom<BK>;
+    static constexpr int KC = BK / 4;
+    static constexpr int MC = kGemmThreads / KC;
+    static constexpr int PASSES = ROWS / (4 * MC);
+    static_assert(ROWS % (4 * MC) == 0, "tile rows must be a multiple of the rows per pass");
+    struct Args {
+        const uint32_t* bits;
+        int64_t words_ld;
+        int nrows;
+        int bit0;
+    };
+    static constexpr bool kAsmLoads = false;
+    static constexpr int kLoadsPerStep = 4 * PASSES;
+    template <int P> __device__ __forceinline__ void pin() {}
+    const uint32_t* colp[PASSES];
+    int sh[PASSES];
+    int shs[2][PASSES];             // the shift of the rows a staging set was loaded for: set_rows() moves on before store()
+    uint32_t r[2][PASSES][4];
+    Args args;
+    int K, c, mc;
+
+    __device__ __forceinline__ void init(const Args& a, int K_, int tid) {
+        args = a;
+        K = K_;
+        c = tid % KC;
+        mc = tid / KC;
+    }
+    __device__ __forceinline__ void set_rows(int row0) {
+#pragma unroll
+        for (int i = 0; i < PASSES; ++i) {
+            int m = row0 + 4 * (i * MC + mc);
+            m = (m + 3) < args.nrows ? m : args.nrows - 4;
+            colp[i] = args.bits + ((args.bit0 + m) >> 5);
+            sh[i] = (args.bit0 + m) & 31;
+        }
+    }
+    template <int P>
+    __device__ __forceinline__ void load(int kt) {
+        const int k0 = kt * BK + 4 * c;
+#pragma unroll
+        for (int i = 0; i < PASSES; ++i) shs[P][i] = sh[i];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool ok = (k0 + j) < K;
+            const int64_t off = ok ? static_cast<int64_t>(k0 + j) * args.words_ld : 0;
+#pragma unroll
+            for (int i = 0; i < PASSES; ++i) {
+                const uint32_t t = colp[i][off];
+                r[P][i][j] = ok ? t : 0u;
+            }
+        }
+    }
+    template <int P>
+    __device__ __forceinline__ void store(float* tile) const {
+#pragma unroll
+        for (int i = 0; i < PASSES; ++i)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                f32x4 v;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[j] = ((r[P][i][j] >> (shs[P][i] + e)) & 1u) ? 1.0f : 0.0f;
+                lds_put_chunk_alt(tile + (4 * (i * MC + mc) + e) * G::LDS_STRIDE, c, v, (mc & 1) != 0);
+            }
+    }
+};
+
+// ---- epilogues -----------------------------------------------------------------------------------------------------
+template <int BM, int BN>
+struct EpiTrainBase {
+    static constexpr int MT = BM / 64, NT = BN / 64, WTM = BM / 2, WTN = BN / 2;
+    static constexpr int kCheckpoints = 0;
+    static constexpr int kLdsFloats = 0;
+    static constexpr int kStoresPerFinish = 0;   // conservative: the staged-load wait then also covers them
+    template <class A> __device__ __forceinline__ void end(const A&, const TileCtx&) {}
+    template <class A> __device__ __forceinline__ void init(const A&, f32x16 (&acc)[MT][NT], const TileCtx&) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.0f;
+    }
+    template <class A> __device__ __forceinline__ void checkpoint(const A&, f32x16 (&)[MT][NT], const TileCtx&, int) {}
+};
+
+// C[row][col] = acc
+template <int BM, int BN>
+struct EpiStoreC : EpiTrainBase<BM, BN> {
+    using Base = EpiTrainBase<BM, BN>;
+    static constexpr int MT = Base::MT, NT = Base::NT, WTM = Base::WTM, WTN = Base::WTN;
+    struct Args {
+        float* out;
+        int64_t ld;
+    };
+    __device__ __forceinline__ void begin(const Args&, const TileCtx&) {}
+    __device__ __forceinline__ void finish(const Args& a, f32x16 (&acc)[MT][NT], const TileCtx& c) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = c.m0 + c.wm * WTM + mt * 32 + mfma_row(r, c.lane_half);
+                if (row >= c.M) continue;
+                float* orow = a.out + static_cast<int64_t>(row) * a.ld;
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) {
+                    const int col = c.n0 + c.wn * WTN + nt * 32 + c.lane_col;
+                    if (col < c.N) orow[col] = acc[mt][nt][r];
+                }
+            }
+    }
+};
+
+// pre[row][col] <- (acc scale[col] + gg / B) p (1 - p), p = sigmoid(pre[row][col]): the pre-activation becomes dpre in place
+template <int BM, int BN>
+struct EpiDpre : EpiTrainBase<BM, BN> {
+    using Base = EpiTrainBase<BM, BN>;
+    static constexpr int MT = Base::MT, NT = Base::NT, WTM = Base::WTM, WTN = Base::WTN;
+    struct Args {
+        const float* scale;    // [N], this level's units
+        const float* gg;       // device scalar (incoming gradient of latent_group[i]) or nullptr
+        float batch;           // B
+        float* pre;            // [M][ld], first column = this level's first unit
+        int64_t ld;
+    };
+    float add;
+    __device__ __forceinline__ void begin(const Args& a, const TileCtx&) { add = a.gg ? a.gg[0] / a.batch : 0.0f; }
+    __device__ __forceinline__ void finish(const Args& a, f32x16 (&acc)[MT][NT], const TileCtx& c) {
+        float sc[NT];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const int col = c.n0 + c.wn * WTN + nt * 32 + c.lane_col;
+            sc[nt] = col < c.N ? a.scale[col] : 0.0f;
+        }
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = c.m0 + c.wm * WTM + mt * 32 + mfma_row(r, c.lane_half);
+                if (row >= c.M) continue;
+                float* prow = a.pre + static_cast<int64_t>(row) * a.ld;
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) {
+                    const int col = c.n0 + c.wn * WTN + nt * 32 + c.lane_col;
+                    if (col >= c.N) continue;
+                    const float p = soft_bit_prob(prow[col]);
+                    const float dz = acc[mt][nt][r] * sc[nt] + add;
+                    prow[col] = dz * (p * (1.0f - p));
+                }
+            }
+    }
+};
+
+// no incoming reconstruction gradient: dz = gg / B for every unit of the level
+__global__ void __launch_bounds__(256)
+dpre_const_kernel(float* __restrict__ pre, int64_t ld, int B, int ncols, const float* __restrict__ gg) {
+    const float add = gg ? gg[0] / static_cast<float>(B) : 0.0f;
+    const long long total = static_cast<long long>(B) * ncols;
+    const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
+    for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i < total; i += stride) {
+        float* q = pre + (i / ncols) * ld + (i % ncols);
+        const float p = soft_bit_prob(*q);
+        *q = add * (p * (1.0f - p));
+    }
+}
+
+struct TrainLevels {
+    int n;
+    int begin[kTnMaxLevels], size[kTnMaxLevels];
+};
+
+static int parse_levels(int H, int n_bits, const int32_t* level_sizes, TrainLevels& lv) {
+    if (n_bits < 1 || n_bits > kTnMaxLevels || !level_sizes)
+        return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: 1 <= n_bits <= 8 and level sizes required", __func__);
+    long long acc = 0;
+    lv.n = n_bits;
+    for (int i = 0; i < n_bits; ++i) {
+        if (level_sizes[i] < 0) return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: negative level size", __func__);
+        if (level_sizes[i] % 32 != 0)
+            return fail(QSAE_ERR_UNSUPPORTED, "%s: unsupported: level sizes must be multiples of 32 (pad the levels)", __func__);
+        lv.begin[i] = static_cast<int>(acc);
+        lv.size[i] = level_sizes[i];
+        acc += level_sizes[i];
+    }
+    if (acc != H) return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: level sizes do not sum to H", __func__);
+    return QSAE_OK;
+}
+
+inline bool tn_shape_ok(int D) { return D > 0 && D % 4 == 0 && D <= kTnMaxD; }
+
+template <class LA, class LB, class Epi>
+static int run_tn(const typename LA::Args& la, const typename LB::Args& lb, const typename Epi::Args& ea, int M, int N, int K,
+                  hipStream_t s) {
+    return launch_gemm<LA, LB, Epi, 128, 128, 32>(la, lb, ea, M, N, K, pick_sweep<128, 128>(M, N, K), s);
+}
+
+}  // namespace qsae
+
+using namespace qsae;
+
+extern "C" int qsae_train_matryoshka_dpre(const float* g_levels, const float* g_groups, const float* sign_rows,
+                                          const float* scale, int B, int D, int H, int n_bits, const int32_t* level_sizes,
+                                          float* pre, int64_t pre_ld, qsae_stream_t stream) {
+    QSAE_CHECK_ARG(B >= 1 && D > 0 && H > 0, "B >= 1, D > 0, H > 0 required");
+    QSAE_CHECK_SUPPORTED(tn_shape_ok(D), "D a multiple of 4, at most 4096");
+    TrainLevels lv;
+    const int rc = parse_levels(H, n_bits, level_sizes, lv);
+    if (rc != QSAE_OK) return rc;
+    QSAE_CHECK_ARG(pre && pre_ld >= H, "pre required, pre_ld >= H");
+    QSAE_CHECK_ARG(!g_levels || (sign_rows && scale), "g_levels needs sign_rows and scale");
+    QSAE_CHECK_ARG((!g_levels || aligned16(g_levels)) && (!sign_rows || aligned16(sign_rows)),
+                   "g_levels and sign_rows must be 16-byte aligned");
+    hipStream_t s = as_stream(stream);
+    for (int i = 0; i < n_bits; ++i) {
+        const int n = lv.size[i], h0 = lv.begin[i];
+        if (n == 0) continue;
+        const float* gg = g_groups ? g_groups + i : nullptr;
+        if (!g_levels) {
+            long long blocks = (static_cast<long long>(B) * n + 255) / 256;
+            if (blocks > 65536) blocks = 65536;
+            hipLaunchKernelGGL(dpre_const_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, pre + h0, pre_ld, B, n,
+                               gg);
+            QSAE_LAUNCH_CHECK();
+            continue;
+        }
+        using Epi = EpiDpre<128, 128>;
+        const float* G = g_levels + static_cast<int64_t>(i) * B * D;
+        const float* S = sign_rows + static_cast<int64_t>(h0) * D;
+        typename Epi::Args ea{scale + h0, gg, static_cast<float>(B), pre + h0, pre_ld};
+        // the asm-staged loaders address with 32-bit byte offsets
+        const bool small = static_cast<int64_t>(B) * D < (1LL << 30) && static_cast<int64_t>(n) * D < (1LL << 30);
+        int r;
+        if (D % 32 == 0 && small) {
+            using L = LoaderF32<128, 32, false, true>;
+            r = launch_gemm<L, L, Epi, 128, 128, 32>(typename L::Args{G, D, B}, typename L::Args{S, D, n}, ea, B, n, D,
+                                                     pick_sweep<128, 128>(B, n, D), s);
+        } else {
+            using L = LoaderF32<128, 32, true>;
+            r = launch_gemm<L, L, Epi, 128, 128, 32>(typename L::Args{G, D, B}, typename L::Args{S, D, n}, ea, B, n, D,
+                                                     pick_sweep<128, 128>(B, n, D), s);
+        }
+        if (r != QSAE_OK) return r;
+    }
+    return QSAE_OK;
+}
+
+extern "C" int qsae_train_gemm_tn(const float* A, int64_t lda, const float* X, int64_t ldx, int K, int M, int N, float* C,
+                                  int64_t ldc, qsae_stream_t stream) {
+    QSAE_CHECK_ARG(K >= 1 && M > 0 && N > 0, "K >= 1, M > 0, N > 0 required");
+    QSAE_CHECK_SUPPORTED(M % 4 == 0 && N % 4 == 0 && lda % 4 == 0 && ldx % 4 == 0, "M, N, lda and ldx multiples of 4");
+    QSAE_CHECK_ARG(A && X && C && lda >= M && ldx >= N && ldc >= N, "null pointer or leading dimension too small");
+    QSAE_CHECK_ARG(aligned16(A) && aligned16(X), "A and X must be 16-byte aligned");
+    using LA = LoaderTN<128, 32>;
+    using Epi = EpiStoreC<128, 128>;
+    return run_tn<LA, LA, Epi>(typename LA::Args{A, lda, M}, typename LA::Args{X, ldx, N}, typename Epi::Args{C, ldc}, M, N, K,
+                               as_stream(stream));
+}
+
+extern "C" int qsae_train_matryoshka_dsum_dense(const uint32_t* zbits, int64_t words_ld, const float* g_levels, int B, int D,
+                                                int H, int n_bits, const int32_t* level_sizes, float* dsum,
+                                                qsae_stream_t stream) {
+    QSAE_CHECK_ARG(B >= 1 && D > 0 && H > 0, "B >= 1, D > 0, H > 0 required");
+    QSAE_CHECK_SUPPORTED(tn_shape_ok(D), "D a multiple of 4, at most 4096");
+    TrainLevels lv;
+    const int rc = parse_levels(H, n_bits, level_sizes, lv);
+    if (rc != QSAE_OK) return rc;
+    QSAE_CHECK_ARG(zbits && g_levels && dsum && words_ld >= H / 32, "null pointer or words_ld < H / 32");
+    QSAE_CHECK_ARG(aligned16(g_levels), "g_levels must be 16-byte aligned");
+    hipStream_t s = as_stream(stream);
+    bool on_tiles = true;
+    for (int i = 0; i < n_bits; ++i) on_tiles = on_tiles && lv.size[i] % 128 == 0;
+    if (on_tiles) {
+        // one launch over all levels: a level of a few thousand units alone leaves most of the chip idle for the whole K walk
+        using LA = LoaderTNBits<128, 32>;
+        using LB = LoaderTNByLevel<128, 32>;
+        using Epi = EpiStoreC<128, 128>;
+        typename LB::Args lb{g_levels, D, D, static_cast<int64_t>(B) * D, n_bits, {}, {}};
+        for (int i = 0; i < kTnMaxLevels; ++i) lb.end_tile[i] = (i < n_bits ? lv.begin[i] + lv.size[i] : H) / 128;
+        lb.map.tiles_m = H / 128;
+        lb.map.tiles_n = (D + 127) / 128;
+        lb.map.sweep = 1;
+        lb.map.msplit = lb.map.tiles_m;
+        lb.map.stagger = g_stagger;
+        return launch_gemm<LA, LB, Epi, 128, 128, 32>(typename LA::Args{zbits, words_ld, H, 0}, lb, typename Epi::Args{dsum, D},
+                                                      H, D, B, 1, s);
+    }
+    for (int i = 0; i < n_bits; ++i) {
+        const int n = lv.size[i], h0 = lv.begin[i];
+        if (n == 0) continue;
+        using LA = LoaderTNBits<128, 32>;
+        using LB = LoaderTN<128, 32>;
+        using Epi = EpiStoreC<128, 128>;
+        const int r = run_tn<LA, LB, Epi>(typename LA::Args{zbits, words_ld, n, h0},
+                                          typename LB::Args{g_levels + static_cast<int64_t>(i) * B * D, D, D},
+                                          typename Epi::Args{dsum + static_cast<int64_t>(h0) * D, D}, n, D, B, s);
+        if (r != QSAE_OK) return r;
+    }
+    return QSAE_OK;
+}

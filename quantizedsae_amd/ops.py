@@ -1216,3 +1216,204 @@ def normalize_columns_table(W: torch.Tensor, want_table: bool = True) -> Optiona
     table = torch.empty((H, D), dtype=torch.float32, device=W.device) if want_table else None
     check(_lib.load().qsae_normalize_columns_table(_p(W), D, H, _p(table), _stream()))
     return table
+
+
+# ---- QuantizedMatryoshkaSAE training -------------------------------------------------------------------------------------
+def train_matryoshka_supported(D: int) -> bool:
+    return 0 < D <= TRAIN_MAX_D and D % 4 == 0
+
+
+def _check_matryoshka_shape(D: int) -> None:
+    if not train_matryoshka_supported(D):
+        raise ValueError(f"QuantizedMatryoshkaSAE training kernels take D a multiple of 4 up to {TRAIN_MAX_D} (got D = {D})")
+
+
+def _i32dev(t: Optional[torch.Tensor], name: str) -> Optional[torch.Tensor]:
+    if t is None:
+        return None
+    _dev(t, name)
+    return t.to(torch.int32).contiguous()
+
+
+@_on_tensor_device
+def transpose_rows(src: torch.Tensor) -> torch.Tensor:
+    """[H, D] fp32 -> its transpose [D, H] as a contiguous copy (D a multiple of 4); see qsae_transpose_rows."""
+    src = _f32c(src, "src")
+    H, D = src.shape
+    dst = torch.empty((D, H), dtype=torch.float32, device=src.device)
+    check(_lib.load().qsae_transpose_rows(_p(src), H, D, _p(dst), _stream()))
+    return dst
+
+
+@_on_tensor_device
+def train_pre_bits(pre: torch.Tensor) -> torch.Tensor:
+    """int32-packed z bits [B, H / 32] of a pre-activation [B, H] (H a multiple of 32) by the cutoff every bits path uses;
+    see qsae_train_pre_bits."""
+    _dev(pre, "pre", torch.float32)
+    if pre.dim() != 2 or not pre.is_contiguous() or pre.shape[1] % 32:
+        raise ValueError(f"train_pre_bits: pre must be a contiguous [B, H] tensor with H a multiple of 32, got {tuple(pre.shape)}")
+    B, H = pre.shape
+    z = torch.empty((B, H // 32), dtype=torch.int32, device=pre.device)
+    check(_lib.load().qsae_train_pre_bits(_p(pre), H, B, H, _p(z), H // 32, _stream()))
+    return z
+
+
+@_on_tensor_device
+def train_matryoshka_sign_rows(w: torch.Tensor, wm: torch.Tensor, index: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> S fp32 [slots, D] in {-2, 0, 2} in the packed hidden order (index int32 [slots] or None = the parameters' order)."""
+    w, wm = _f32c(w, "w"), _f32c(wm, "wm")
+    D = w.shape[1]
+    _check_matryoshka_shape(D)
+    index = _i32dev(index, "index")
+    slots = index.numel() if index is not None else w.shape[0]
+    S = torch.empty((slots, D), dtype=torch.float32, device=w.device)
+    check(_lib.load().qsae_train_matryoshka_sign_rows(_p(w), _p(wm), _p(index), slots, D, _p(S), _stream()))
+    return S
+
+
+def _levels_grad(g_levels: Optional[torch.Tensor], n_bits: int, B: int, D: int):
+    if g_levels is None:
+        return None
+    g = _f32c(g_levels, "g_levels")
+    if tuple(g.shape) != (n_bits, B, D):
+        raise ValueError(f"g_levels is {tuple(g.shape)}, expected [{n_bits}, {B}, {D}]")
+    return g
+
+
+@_on_tensor_device
+def train_matryoshka_dpre(pre: torch.Tensor, g_levels: Optional[torch.Tensor], g_groups: Optional[torch.Tensor],
+                          sign_rows: torch.Tensor, scale: torch.Tensor, sizes) -> torch.Tensor:
+    """The pre-activation [B, H] (contiguous fp32, packed hidden order) becomes dpre IN PLACE and is returned; see
+    qsae_train_matryoshka_dpre."""
+    _dev(pre, "pre", torch.float32)
+    if pre.dim() != 2 or not pre.is_contiguous():
+        raise ValueError("train_matryoshka_dpre: pre must be a contiguous [B, H] tensor (it is updated in place)")
+    B, H = pre.shape
+    sign_rows, scale = _f32c(sign_rows, "sign_rows"), _f32c(scale, "scale")
+    D = sign_rows.shape[1]
+    _check_matryoshka_shape(D)
+    n_bits = len(sizes)
+    if sign_rows.shape[0] != H or scale.numel() != H or sum(sizes) != H or B < 1:
+        raise ValueError("train_matryoshka_dpre: inconsistent shapes")
+    G = _levels_grad(g_levels, n_bits, B, D)
+    gg = _f32c(g_groups.reshape(-1), "g_groups") if g_groups is not None else None
+    if gg is not None and gg.numel() != n_bits:
+        raise ValueError(f"g_groups has {gg.numel()} elements, expected {n_bits}")
+    keep, sp = _sizes_arg(sizes, n_bits)
+    check(_lib.load().qsae_train_matryoshka_dpre(_p(G), _p(gg), _p(sign_rows), _p(scale), B, D, H, n_bits, sp, _p(pre), H,
+                                                 _stream()))
+    return pre
+
+
+@_on_tensor_device
+def train_gemm_tn(A: torch.Tensor, X: torch.Tensor) -> torch.Tensor:
+    """A [K, M], X [K, N] -> A^T X [M, N] as one fp32 chain per element in ascending k; see qsae_train_gemm_tn."""
+    A, X = _f32c(A, "A"), _f32c(X, "X")
+    K, M = A.shape
+    N = X.shape[1]
+    if X.shape[0] != K or K < 1 or M % 4 or N % 4:
+        raise ValueError(f"train_gemm_tn: A {tuple(A.shape)}, X {tuple(X.shape)}: equal K >= 1, M and N multiples of 4")
+    out = torch.empty((M, N), dtype=torch.float32, device=A.device)
+    check(_lib.load().qsae_train_gemm_tn(_p(A), M, _p(X), N, K, M, N, _p(out), N, _stream()))
+    return out
+
+
+@_on_tensor_device
+def train_matryoshka_dsum_dense(zbits: torch.Tensor, g_levels: torch.Tensor, H: int, sizes) -> torch.Tensor:
+    """-> dSum fp32 [H, D] from the z bits and the incoming gradients [n, B, D]; see qsae_train_matryoshka_dsum_dense."""
+    _dev(zbits, "zbits", torch.int32)
+    B = zbits.shape[0]
+    n_bits = len(sizes)
+    D = g_levels.shape[2]
+    _check_matryoshka_shape(D)
+    G = _levels_grad(g_levels, n_bits, B, D)
+    if zbits.stride(1) != 1 or zbits.shape[1] * 32 < H or sum(sizes) != H or B < 1:
+        raise ValueError("train_matryoshka_dsum_dense: inconsistent shapes")
+    dsum = torch.empty((H, D), dtype=torch.float32, device=zbits.device)
+    keep, sp = _sizes_arg(sizes, n_bits)
+    check(_lib.load().qsae_train_matryoshka_dsum_dense(_p(zbits), zbits.stride(0), _p(G), B, D, H, n_bits, sp, _p(dsum),
+                                                       _stream()))
+    return dsum
+
+
+def train_bits_csr_supported(B: int, H: int) -> bool:
+    return B >= 1 and H > 0 and H % 32 == 0 and B * H < 2 ** 31
+
+
+@_on_tensor_device
+def train_bits_csr(zbits: torch.Tensor, H: int, n_entries: int):
+    """z bits [B, words] -> (offsets int32 [H + 1], entries int32 [n_entries]): the active rows of every unit, ascending;
+    n_entries is the batch's active-unit count (the decoder's level counts).  See qsae_train_bits_csr."""
+    _dev(zbits, "zbits", torch.int32)
+    B = zbits.shape[0]
+    if not train_bits_csr_supported(B, H) or zbits.stride(1) != 1 or zbits.shape[1] * 32 < H:
+        raise ValueError(f"train_bits_csr: the unit lists take H a multiple of 32 and B * H < 2^31 (got B = {B}, H = {H})")
+    offsets = torch.empty((H + 1,), dtype=torch.int32, device=zbits.device)
+    entries = torch.empty((max(1, int(n_entries)),), dtype=torch.int32, device=zbits.device)
+    lib = _lib.load()
+    ws = _train_ws(lib.qsae_train_bits_csr_workspace_bytes(B, H), zbits.device)
+    check(lib.qsae_train_bits_csr(_p(zbits), zbits.stride(0), B, H, _p(offsets), _p(entries), int(n_entries), _p(ws),
+                                  ws.numel(), _stream()))
+    return offsets, entries
+
+
+@_on_tensor_device
+def train_matryoshka_dsum_lists(offsets: torch.Tensor, entries: torch.Tensor, n_entries: int, g_levels: torch.Tensor,
+                                sizes) -> torch.Tensor:
+    """-> dSum fp32 [H, D] summed over the unit lists of train_bits_csr; see qsae_train_matryoshka_dsum_lists."""
+    _dev(offsets, "offsets", torch.int32)
+    _dev(entries, "entries", torch.int32)
+    n_bits, B, D = g_levels.shape
+    _check_matryoshka_shape(D)
+    H = offsets.shape[0] - 1
+    if len(sizes) != n_bits or sum(sizes) != H or B < 1 or not 0 <= n_entries < 2 ** 31:
+        raise ValueError("train_matryoshka_dsum_lists: inconsistent shapes")
+    G = _levels_grad(g_levels, n_bits, B, D)
+    dsum = torch.empty((H, D), dtype=torch.float32, device=G.device)
+    lib = _lib.load()
+    ws = _train_ws(lib.qsae_train_matryoshka_dsum_lists_workspace_bytes(B, int(n_entries), H, D), G.device)
+    keep, sp = _sizes_arg(sizes, n_bits)
+    check(lib.qsae_train_matryoshka_dsum_lists(_p(offsets.contiguous()), _p(entries.contiguous()), int(n_entries), _p(G), B, D,
+                                               H, n_bits, sp, _p(dsum), _p(ws), ws.numel(), _stream()))
+    return dsum
+
+
+@_on_tensor_device
+def train_matryoshka_finish(dsum: Optional[torch.Tensor], scale: torch.Tensor, index: Optional[torch.Tensor],
+                            w: torch.Tensor, wm: torch.Tensor):
+    """-> (dweight, dweight_mirror) [H, D] in the parameters' order; see qsae_train_matryoshka_finish."""
+    w, wm, scale = _f32c(w, "w"), _f32c(wm, "wm"), _f32c(scale, "scale")
+    D = w.shape[1]
+    _check_matryoshka_shape(D)
+    slots = scale.numel()
+    index = _i32dev(index, "index")
+    if (index is None and slots != w.shape[0]) or (index is not None and index.numel() != slots) or w.shape != wm.shape:
+        raise ValueError("train_matryoshka_finish: inconsistent shapes")
+    ds = _f32c(dsum, "dsum") if dsum is not None else None
+    if ds is not None and tuple(ds.shape) != (slots, D):
+        raise ValueError(f"dsum is {tuple(ds.shape)}, expected [{slots}, {D}]")
+    dw, dwm = torch.empty_like(w), torch.empty_like(wm)
+    check(_lib.load().qsae_train_matryoshka_finish(_p(ds), _p(scale), _p(index), _p(w), _p(wm), slots, D, _p(dw), _p(dwm),
+                                                   _stream()))
+    return dw, dwm
+
+
+@_on_tensor_device
+def train_matryoshka_secant(gw: torch.Tensor, gwm: torch.Tensor, counts: torch.Tensor, c: float, scale: torch.Tensor,
+                            index: Optional[torch.Tensor], w: torch.Tensor, wm: torch.Tensor) -> None:
+    """The secant correction of apply_secant_grad() on the two gradient tensors IN PLACE; see qsae_train_matryoshka_secant."""
+    for t, name in ((gw, "weight.grad"), (gwm, "weight_mirror.grad")):
+        _dev(t, name, torch.float32)
+        if not t.is_contiguous() or t.data_ptr() % 16:
+            raise ValueError(f"train_matryoshka_secant: {name} must be contiguous and 16-byte aligned (it is updated in place)")
+    w, wm, scale = _f32c(w, "w"), _f32c(wm, "wm"), _f32c(scale, "scale")
+    _dev(counts, "counts", torch.int64)
+    D = w.shape[1]
+    _check_matryoshka_shape(D)
+    slots = scale.numel()
+    index = _i32dev(index, "index")
+    if counts.numel() < slots or gw.shape != w.shape or gwm.shape != wm.shape or \
+            (index is None and slots != w.shape[0]) or (index is not None and index.numel() != slots):
+        raise ValueError("train_matryoshka_secant: inconsistent shapes")
+    check(_lib.load().qsae_train_matryoshka_secant(_p(counts.contiguous()), float(c), _p(scale), _p(index), _p(w), _p(wm),
+                                                   slots, D, _p(gw), _p(gwm), _stream()))

@@ -10,10 +10,6 @@ import torch.nn as nn
 from .. import torch_ops as ops          # torch.ops.qsae.* (dispatcher ops over the C ABI)
 from .base import HipEncoder, PackedCache, SparseAutoencoder, require_device_input
 
-_TRAINING_ONLY = ("the secant-gradient correction belongs to the reference's training loop "
-                  "(sae/quantized_matryoshka.py:145-190) and is outside this inference backend")
-
-
 def nested_sizes(in_features: int, n_bits: int) -> List[int]:
     """Level sizes [1,1,2,4,...] scaled to in_features, remainder in the last level
     (sae/quantized_matryoshka.py:25-38)."""
@@ -61,6 +57,8 @@ class QuantizedMatryoshkaDecoder(nn.Module):
         nn.init.xavier_uniform_(self.weight)
         nn.init.xavier_uniform_(self.weight_mirror)
         self._cache = PackedCache()
+        self._train_cache = PackedCache()
+        self._train_ctx = None           # what apply_secant_grad() needs of the last forward_train (the reference's _ctx)
 
     # -- layout ---------------------------------------------------------------------------------
     @property
@@ -135,11 +133,21 @@ class QuantizedMatryoshkaDecoder(nn.Module):
         units only (same outputs as the exact-fp32 chain); None = decide from this batch's own activation density.  The sparse
         walk and the bf16 split decoder round their sums in different orders, so the choice is a function of the z bits and
         the attributes alone -- never of earlier batches or of how far the GPU has got."""
-        st = self.packed()
         B = zbits.shape[0]
         if sparse is None:
-            sparse = ("codes_rows" in st and B > 0 and self.SPARSE_MAX_ACTIVE_FRACTION > 0
-                      and self.active_fraction(zbits) < self.SPARSE_MAX_ACTIVE_FRACTION)
+            sparse = self.sparse_walk_possible(B) and self.active_fraction(zbits) < self.SPARSE_MAX_ACTIVE_FRACTION
+        levels, counts = self._decode_levels(zbits, sparse)
+        groups = (counts.to(torch.float64) / max(B, 1)).to(torch.float32)
+        return [groups[i] for i in range(self.n_bits)], [levels[i] for i in range(self.n_bits)]
+
+    def sparse_walk_possible(self, rows: int) -> bool:
+        """Whether decode_bits looks at the activation density of a batch of ``rows`` rows at all."""
+        return "codes_rows" in self.packed() and rows > 0 and self.SPARSE_MAX_ACTIVE_FRACTION > 0
+
+    def _decode_levels(self, zbits: torch.Tensor, sparse: bool):
+        """-> (levels fp32 [n_bits, B, D], active-unit counts int64 [n_bits]) on the decoder ``sparse`` selects."""
+        st = self.packed()
+        B = zbits.shape[0]
         if sparse and "codes_rows" in st:
             levels, counts = ops.decode_matryoshka_sparse(zbits, st["H"], self.out_features, self.n_bits,
                                                           st["codes_rows"], st["scale"], self.bias.detach(),
@@ -152,8 +160,7 @@ class QuantizedMatryoshkaDecoder(nn.Module):
         else:
             levels, counts = ops.decode_matryoshka(zbits, st["H"], self.out_features, self.n_bits, st["codes"],
                                                    st["scale"], self.bias.detach(), self.allow_bias, st["sizes"])
-        groups = (counts.to(torch.float64) / max(B, 1)).to(torch.float32)
-        return [groups[i] for i in range(self.n_bits)], [levels[i] for i in range(self.n_bits)]
+        return levels, counts
 
     def forward(self, latent):
         with torch.no_grad():
@@ -168,8 +175,34 @@ class QuantizedMatryoshkaDecoder(nn.Module):
                 latent = padded
             return self.decode_bits(ops.pack_bits_gt(latent, 0.5))
 
+    # -- training -------------------------------------------------------------------------------
+    def train_pack(self) -> dict:
+        """What the backward needs besides packed(): the fp32 image S [H_padded, D] of the dictionary in the packed hidden
+        order (the K-contiguous operand of the dz contraction) and the int32 slot -> unit map of a padded model."""
+        def build():
+            st = self.packed()
+            index = st["index"].to(torch.int32) if st["index"] is not None else None
+            return {"S": ops.train_matryoshka_sign_rows(self.weight.detach(), self.weight_mirror.detach(), index),
+                    "index": index}
+        return self._train_cache.get((self.weight, self.weight_mirror), build)
+
     def apply_secant_grad(self):
-        raise NotImplementedError(_TRAINING_ONLY)
+        """The secant correction of the reference's training loop (sae/quantized_matryoshka.py:145-190, joint_gradient=False):
+        ``weight.grad[h, d] -= c cnt_h scale_h^2 Bs[h, d] sw (1 - sw)`` and the same for the mirror, in place, in one HIP
+        pass, with cnt / scale / B of the last ``forward_train`` (c = 1 / (B D))."""
+        tc = self._train_ctx
+        if tc is None:
+            raise RuntimeError("apply_secant_grad() needs the context of a forward_train(); forward() leaves none")
+        if self.weight.grad is None or self.weight_mirror.grad is None:
+            raise RuntimeError("apply_secant_grad() needs decoder.weight.grad and decoder.weight_mirror.grad (run backward first)")
+        if (self.weight._version, self.weight_mirror._version) != tc["versions"]:
+            raise RuntimeError("decoder.weight / weight_mirror changed since the last forward_train(): its signs and scales "
+                               "no longer describe them")
+        with torch.no_grad():
+            counts = ops.activation_counts_bits(tc["zbits"])
+            ops.train_matryoshka_secant(self.weight.grad, self.weight_mirror.grad, counts,
+                                        1.0 / tc["rows"] / self.out_features, tc["scale"], tc["index"],
+                                        self.weight.detach(), self.weight_mirror.detach())
 
 
 class QuantizedMatryoshkaSAE(ops.GraphForwardMixin, SparseAutoencoder):
@@ -288,6 +321,50 @@ class QuantizedMatryoshkaSAE(ops.GraphForwardMixin, SparseAutoencoder):
             path = self.resolved_bits_path(x.shape[0])
             return self.decoder.decode_bits(self.activation_bits(x, path))
 
+    # -- training -------------------------------------------------------------------------------------------------
+    #: "auto" | "dense" | "lists" -- how the backward sums the decoder-logit gradient dSum[h] = sum of G_i[r] over the rows
+    #: r that activate unit h; read per call.  dense: one TN contraction of the z bits against G_i on the matrix pipe,
+    #: whatever the density.  lists: per-unit row lists from a bit transpose of z, summed in list order -- work
+    #: proportional to the number of active (row, unit) pairs.  auto: lists below LISTS_MAX_ACTIVE_FRACTION of active
+    #: units over the same evenly spaced sample of rows that decode_bits decides on (a function of the batch alone).
+    decoder_grad_path = "auto"
+    #: measured at B = 8192, H = 32768, D = 512: the backward on lists takes 8.25 ms at 4.0 % active units and 9.59 ms at
+    #: 6.6 %, on the dense contraction 8.4 to 8.6 ms at any density
+    LISTS_MAX_ACTIVE_FRACTION = 0.04
+    last_decoder_grad_path = None      # "dense" | "lists": what the previous forward_train resolved to (per model)
+
+    def forward_train(self, x):
+        """``(latent_groups, reconstruction_levels)`` as ``forward()`` returns them, same values bit for bit, every element
+        with a ``grad_fn``: the forward the reference trains through (sae/quantized_matryoshka.py:47-143; the q_sae branch
+        of training/trainer.py:88-112), whose backward runs the HIP gradient kernels (csrc/train_gemm.hip, csrc/train.hip;
+        the table in DESIGN.md section 4.12).  ``loss.backward()`` fills the ``.grad`` of encoder.0.weight / .bias,
+        decoder.weight / .weight_mirror / .bias (none for the bias without ``allow_bias``, as in the reference) and of
+        ``x`` if it requires grad; then ``decoder.apply_secant_grad()``.
+
+        The encoder pre-activation [B, H] is kept for the backward, which turns it into its own gradient in place: a
+        second backward through the same graph raises.  Derived weights are keyed on the parameters' version counters,
+        so an optimizer step is picked up by the next call."""
+        path = self.decoder_grad_path
+        if path not in ("auto", "dense", "lists"):
+            raise ValueError(f"decoder_grad_path must be 'auto', 'dense' or 'lists', got {path!r}")
+        D = self.input_dim
+        if not ops.train_matryoshka_supported(D):
+            raise ValueError(f"QuantizedMatryoshkaSAE.forward_train: the gradient kernels take input_dim a multiple of 4 up to "
+                             f"4096 (got input_dim = {D})")
+        if isinstance(x, torch.Tensor) and (x.dim() != 2 or x.shape[1] != D):
+            raise ValueError(f"x is {tuple(x.shape)}, expected [batch, {D}]")
+        x = require_device_input(x, "x")
+        if x.shape[0] < 1:
+            raise ValueError("QuantizedMatryoshkaSAE.forward_train: the batch needs at least one row")
+        Hp = sum(self.decoder.padded_sizes)
+        if path == "lists" and not ops.train_bits_csr_supported(x.shape[0], Hp):
+            raise ValueError(f"QuantizedMatryoshkaSAE.forward_train: decoder_grad_path = 'lists' takes batch * padded hidden "
+                             f"size below 2^31 (got {x.shape[0]} * {Hp})")
+        lin, dec = self.encoder.linear, self.decoder
+        groups, levels = _MatryoshkaTrainStep.apply(self, path, x, lin.weight, lin.bias, dec.weight, dec.weight_mirror,
+                                                    dec.bias)
+        return [groups[i] for i in range(self.n_bits)], [levels[i] for i in range(self.n_bits)]
+
     def forward_submit(self, x, slot: int = 0):
         """Queue one forward without waiting for the GPU (see BinarySAE.forward_submit): the z bits of the fp16 candidate
         sweep are queued here (qsae_encode_bits_prefilter_submit); ``result()`` takes the count of rows that need the
@@ -320,3 +397,79 @@ class _SubmittedMatryoshka:
                     m._dense_regime = True
                 self._outs = m.decoder.decode_bits(z)
             return self._outs
+
+
+class _MatryoshkaTrainStep(torch.autograd.Function):
+    """The QuantizedMatryoshkaSAE forward and its gradient (the table in DESIGN.md section 4.12).  Outputs: latent groups
+    [n] and reconstruction levels [n, B, D] as two tensors (the caller hands out their elements).  The binarisation of the
+    latent and of the decoder logits are straight-through estimators, so the encoder side of the gradient is dense:
+    dz = scale <G_i, S> + gg_i / B for every unit of every row, dpre = dz p (1 - p), dW_enc = dpre^T x."""
+
+    @staticmethod
+    def forward(ctx, model, path, x, W_enc, b_enc, w, wm, bias):
+        dec = model.decoder
+        xf = x.detach()
+        xf = xf if (xf.dtype == torch.float32 and xf.is_contiguous()) else xf.float().contiguous()
+        B = xf.shape[0]
+        Wp, bp = model._encoder_params()
+        st = dec.packed()
+        # the dense exact-fp32 pre-activation, kept for the backward; its bits by the cutoff every bits path uses
+        pre = ops.encode_dense(xf, Wp, bp)
+        zbits = ops.train_pre_bits(pre)
+        frac = dec.active_fraction(zbits)
+        levels, counts = dec._decode_levels(zbits, dec.sparse_walk_possible(B) and frac < dec.SPARSE_MAX_ACTIVE_FRACTION)
+        groups = (counts.to(torch.float64) / B).to(torch.float32)
+        if path == "auto":
+            path = "lists" if (frac < model.LISTS_MAX_ACTIVE_FRACTION and ops.train_bits_csr_supported(B, st["H"])) else "dense"
+        tp = dec.train_pack()
+        dec._train_ctx = {"zbits": zbits, "scale": st["scale"], "index": tp["index"], "rows": B,
+                          "versions": (dec.weight._version, dec.weight_mirror._version)}
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(xf, zbits, counts, st["scale"], tp["S"])
+        ctx.pre = pre
+        ctx.model, ctx.path, ctx.x_dtype = model, path, x.dtype
+        ctx.sizes, ctx.index, ctx.valid = list(st["sizes"]), tp["index"], (st["index"] >= 0 if st["index"] is not None else None)
+        model.last_decoder_grad_path = path
+        return groups, levels
+
+    @staticmethod
+    def backward(ctx, g_groups, g_levels):
+        xf, zbits, counts, scale, S = ctx.saved_tensors
+        model = ctx.model
+        dec = model.decoder
+        need_x, need_W, need_b, need_w, need_wm, need_bias = ctx.needs_input_grad[2:8]
+        sizes, Hp = ctx.sizes, zbits.shape[1] * 32
+        G = None
+        if g_levels is not None:
+            G = g_levels if (g_levels.dtype == torch.float32 and g_levels.is_contiguous()) else g_levels.float().contiguous()
+        dx = dW = db = dw = dwm = dbias = None
+        if need_x or need_W or need_b:
+            if ctx.pre is None:
+                raise RuntimeError("Trying to backward through QuantizedMatryoshkaSAE.forward_train a second time: the saved "
+                                   "pre-activation was turned into its gradient in place by the first backward")
+            dpre = ops.train_matryoshka_dpre(ctx.pre, G, g_groups, S, scale, sizes)
+            ctx.pre = None
+            if need_W:
+                dW = ops.train_gemm_tn(dpre, xf)
+                dW = dW if ctx.valid is None else dW[ctx.valid]
+            if need_b:
+                db = ops.train_col_sum(dpre)
+                db = db if ctx.valid is None else db[ctx.valid]
+            if need_x:
+                Wp, _ = model._encoder_params()
+                dx = ops.encode_dense(dpre, ops.transpose_rows(Wp), None)
+                if dx.dtype != ctx.x_dtype:
+                    dx = dx.to(ctx.x_dtype)
+            del dpre
+        if need_w or need_wm:
+            dsum = None
+            if G is not None and ctx.path == "lists":
+                n_entries = int(counts.sum().item())
+                offsets, entries = ops.train_bits_csr(zbits, Hp, n_entries)
+                dsum = ops.train_matryoshka_dsum_lists(offsets, entries, n_entries, G, sizes)
+            elif G is not None:
+                dsum = ops.train_matryoshka_dsum_dense(zbits, G, Hp, sizes)
+            dw, dwm = ops.train_matryoshka_finish(dsum, scale, ctx.index, dec.weight.detach(), dec.weight_mirror.detach())
+        if need_bias and dec.allow_bias:
+            dbias = ops.train_col_sum(G[0]) if G is not None else torch.zeros_like(dec.bias)
+        return (None, None, dx, dW, db, dw if need_w else None, dwm if need_wm else None, dbias)

@@ -49,6 +49,22 @@ class ResidualQuantizedSAE(ops.GraphForwardMixin, SparseAutoencoder):
                 residual = ops.residual_update(residual, recs[-1], 2.0)          # (residual - reconstruction) * 2
             return groups, levels
 
+    def forward_train(self, x):
+        """``forward()`` with a ``grad_fn`` on every output: the stages' ``forward_train`` chained on the detached, doubled
+        residual (sae/residual_quantized.py:53-69; the rq_sae branch of training/trainer.py:114-142).  Only stage 0 sees
+        ``x`` itself, as in the reference.  Then ``loss.backward()`` and ``apply_secant_grad()``."""
+        residual = require_device_input(x, "x")
+        if residual.dtype != torch.float32:
+            residual = residual.float()
+        groups, levels = [], []
+        for sae in self.saes:
+            g, recs = sae.forward_train(residual)
+            groups.append(g[-1])
+            levels.append(recs[-1])
+            with torch.no_grad():
+                residual = ops.residual_update(residual.detach(), recs[-1].detach(), 2.0)    # (residual - reconstruction) * 2
+        return groups, levels
+
     def apply_secant_grad(self):
         for sae in self.saes:
             sae.decoder.apply_secant_grad()

@@ -913,3 +913,19 @@ def _(x, params, handle):
     m = _module(handle)
     n = len(m.saes) if hasattr(m, "saes") else m.n_bits
     return _f32((n,), x), _f32((n, x.shape[0], m.input_dim), x)
+
+
+# ---- QuantizedMatryoshkaSAE training: called from an autograd.Function's backward and from apply_secant_grad() only (two of
+# them update a tensor in place through its pointer), never traced -- plain functions over ops.py, no dispatcher nodes ------
+train_matryoshka_supported = _ops.train_matryoshka_supported
+train_bits_csr_supported = _ops.train_bits_csr_supported
+train_pre_bits = _ops.train_pre_bits
+transpose_rows = _ops.transpose_rows
+train_matryoshka_sign_rows = _ops.train_matryoshka_sign_rows
+train_matryoshka_dpre = _ops.train_matryoshka_dpre
+train_gemm_tn = _ops.train_gemm_tn
+train_matryoshka_dsum_dense = _ops.train_matryoshka_dsum_dense
+train_bits_csr = _ops.train_bits_csr
+train_matryoshka_dsum_lists = _ops.train_matryoshka_dsum_lists
+train_matryoshka_finish = _ops.train_matryoshka_finish
+train_matryoshka_secant = _ops.train_matryoshka_secant
