@@ -548,6 +548,37 @@ int qsae_train_matryoshka_secant(const int64_t* counts, float c, const float* sc
                                  const float* wm, int H, int D, float* grad_weight, float* grad_weight_mirror,
                                  qsae_stream_t stream);
 
+/* -- TernarySparseAutoencoder training: the gradient of h = relu(x W_enc^T + b), recon = h T^T under the straight-through
+ *    estimator of STEWeights, and the RigL mask maintenance of the decoder (sae/ternary.py:27-90,116-122; the t_sae branch
+ *    of training/trainer.py:157-164).  w / mask are decoder.weight / decoder.mask [D][H].  No float atomics anywhere:
+ *    bitwise reproducible. ------------------------------------------------------------------------------------------ */
+/* t_rows [H][D] = the fp32 image of the ternary dictionary, transposed: sign(w[d][h]) (|w[d][h]| >= 0.5), the rule of
+ * qsae_pack_ternary.  H a multiple of 4, w 16-byte aligned. */
+int qsae_train_ternary_rows(const float* w, int D, int H, float* t_rows, qsae_stream_t stream);
+/* dpre[r][h] = (g_latent[r][h] + <g_recon[r], t_rows[h]>) where h_act[r][h] > 0, else 0, on the fp32 matrix pipe (k
+ * ascending).  g_recon [B][D] / g_latent [B][H] may be NULL (that term is 0); h_act, g_latent and dpre are [B][H]
+ * contiguous and h_act is only read.  D a multiple of 4 up to 4096; B >= 1. */
+int qsae_train_ternary_dpre(const float* g_recon, const float* t_rows, const float* g_latent, const float* h_act, int B, int D,
+                            int H, float* dpre, qsae_stream_t stream);
+/* dweight[d][h] = mask[d][h] sum_r g_recon[r][d] h_act[r][h], r ascending: the TN contraction of qsae_train_gemm_tn with
+ * the mask on the store.  D a multiple of 4 up to 4096, H a multiple of 4, B >= 1. */
+int qsae_train_ternary_dweight(const float* g_recon, const float* h_act, const float* mask, int B, int D, int H,
+                               float* dweight, qsae_stream_t stream);
+/* Device workspace of qsae_train_mask_init / qsae_train_mask_update (0 for a refused shape: D * H not below 2^31 or not a
+ * multiple of 4). */
+size_t qsae_train_mask_workspace_bytes(int D, int H);
+/* init_mask: the n_inactive smallest |w| -- exactly that many, ties at the boundary value in ascending flat index d H + h
+ * -- get mask 0, every other position mask 1; then w *= mask.  In place, nothing is read back.  0 <= n_inactive <= D H. */
+int qsae_train_mask_init(float* w, float* mask, int D, int H, int64_t n_inactive, void* workspace, size_t workspace_bytes,
+                         qsae_stream_t stream);
+/* update_mask: active = (mask != 0).  Drop (n > 0): thr = the n-th smallest |w| over active positions; every active
+ * position with |w| <= thr becomes inactive (n above the active count saturates: all of them drop).  Grow (n > 0, a and
+ * delta given): the n largest |delta[d]| * |a[h]| (one fp32 multiply) over the positions inactive after the drop become
+ * active -- exactly n, ties in ascending flat index; fewer inactive positions than n: all of them.  Then mask = active and
+ * w *= mask, in one pass.  a [H], delta [D] (both NULL: drop only).  In place, nothing is read back.  0 <= n <= D H. */
+int qsae_train_mask_update(float* w, float* mask, const float* a, const float* delta, int D, int H, int64_t n,
+                           void* workspace, size_t workspace_bytes, qsae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -391,6 +391,8 @@ unit_final_kernel(UnitArgs a) {
 constexpr int kTrTile = 32;
 constexpr int kTrTilesD = 2;
 
+// TERNARY: the stored value is sign(v) (|v| >= 0.5) (the rule of qsae_pack_ternary; sae/ternary.py:47-49).
+template <bool TERNARY>
 __global__ void __launch_bounds__(256)
 transpose_rows_kernel(const float* __restrict__ src, int H, int D, float* __restrict__ dst, long long ld, int vec) {
     __shared__ float s_t[kTrTilesD][kTrTile][kTrTile + 1];
@@ -406,7 +408,10 @@ transpose_rows_kernel(const float* __restrict__ src, int H, int D, float* __rest
 #pragma unroll
     for (int j = 0; j < kTrTilesD; ++j)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) s_t[j][hi][4 * lo + e] = v[j][e];
+        for (int e = 0; e < 4; ++e) {
+            const float x = v[j][e];
+            s_t[j][hi][4 * lo + e] = TERNARY ? ((fabsf(x) >= 0.5f) ? (x > 0.0f ? 1.0f : -1.0f) : 0.0f) : x;
+        }
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < kTrTilesD; ++j) {
@@ -917,7 +922,7 @@ extern "C" int qsae_train_table_unit_grad(const int32_t* offsets, const int32_t*
     if (dW_dec) {
         const int vec = (dW_dec_ld % 4 == 0 && aligned16(dW_dec)) ? 1 : 0;
         const dim3 grid((H + kTrTile - 1) / kTrTile, (D + kTrTile * kTrTilesD - 1) / (kTrTile * kTrTilesD));
-        hipLaunchKernelGGL(transpose_rows_kernel, grid, dim3(256), 0, s, dT, H, D, dW_dec,
+        hipLaunchKernelGGL(transpose_rows_kernel<false>, grid, dim3(256), 0, s, dT, H, D, dW_dec,
                            static_cast<long long>(dW_dec_ld), vec);
         QSAE_LAUNCH_CHECK();
     }
@@ -938,6 +943,20 @@ extern "C" int qsae_normalize_columns_table(float* W, int D, int H, float* table
     return QSAE_OK;
 }
 
+// fp32 image of the ternary dictionary, transposed: t_rows [H][D] from decoder.weight w [D][H]
+extern "C" int qsae_train_ternary_rows(const float* w, int D, int H, float* t_rows, qsae_stream_t stream) {
+    QSAE_CHECK_ARG(H > 0 && D > 0 && w && t_rows, "H > 0, D > 0, non-null pointers");
+    QSAE_CHECK_SUPPORTED(H % 4 == 0, "H a multiple of 4");
+    QSAE_CHECK_ARG(aligned16(w), "w must be 16-byte aligned");
+    const int vec = (D % 4 == 0 && aligned16(t_rows)) ? 1 : 0;
+    // the kernel's "rows" are the D rows of w, its "columns" the H units
+    const dim3 grid((D + kTrTile - 1) / kTrTile, (H + kTrTile * kTrTilesD - 1) / (kTrTile * kTrTilesD));
+    hipLaunchKernelGGL(transpose_rows_kernel<true>, grid, dim3(256), 0, as_stream(stream), w, D, H, t_rows,
+                       static_cast<long long>(D), vec);
+    QSAE_LAUNCH_CHECK();
+    return QSAE_OK;
+}
+
 // ---- QuantizedMatryoshkaSAE training (the dense contractions are in train_gemm.hip) ------------------------------------
 extern "C" int qsae_transpose_rows(const float* src, int H, int D, float* dst, qsae_stream_t stream) {
     QSAE_CHECK_ARG(H > 0 && D > 0 && src && dst, "H > 0, D > 0, non-null pointers");
@@ -945,7 +964,7 @@ extern "C" int qsae_transpose_rows(const float* src, int H, int D, float* dst, q
     QSAE_CHECK_ARG(aligned16(src), "src must be 16-byte aligned");
     const int vec = (H % 4 == 0 && aligned16(dst)) ? 1 : 0;
     const dim3 grid((H + kTrTile - 1) / kTrTile, (D + kTrTile * kTrTilesD - 1) / (kTrTile * kTrTilesD));
-    hipLaunchKernelGGL(transpose_rows_kernel, grid, dim3(256), 0, as_stream(stream), src, H, D, dst, static_cast<long long>(H),
+    hipLaunchKernelGGL(transpose_rows_kernel<false>, grid, dim3(256), 0, as_stream(stream), src, H, D, dst, static_cast<long long>(H),
                        vec);
     QSAE_LAUNCH_CHECK();
     return QSAE_OK;

@@ -288,6 +288,74 @@ dpre_const_kernel(float* __restrict__ pre, int64_t ld, int B, int ncols, const f
     }
 }
 
+// TernarySparseAutoencoder: dpre[row][col] = (acc + gh[row][col]) where h[row][col] > 0, else 0 (the ReLU's gradient; gh = the
+// gradient arriving at the latent itself, nullable).  h is read only: the caller owns it.
+template <int BM, int BN>
+struct EpiTernaryDpre : EpiTrainBase<BM, BN> {
+    using Base = EpiTrainBase<BM, BN>;
+    static constexpr int MT = Base::MT, NT = Base::NT, WTM = Base::WTM, WTN = Base::WTN;
+    struct Args {
+        const float* gh;       // [M][ld] or nullptr
+        const float* h;        // [M][ld]
+        float* dpre;           // [M][ld]
+        int64_t ld;
+    };
+    __device__ __forceinline__ void begin(const Args&, const TileCtx&) {}
+    __device__ __forceinline__ void finish(const Args& a, f32x16 (&acc)[MT][NT], const TileCtx& c) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = c.m0 + c.wm * WTM + mt * 32 + mfma_row(r, c.lane_half);
+                if (row >= c.M) continue;
+                const int64_t off = static_cast<int64_t>(row) * a.ld;
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) {
+                    const int col = c.n0 + c.wn * WTN + nt * 32 + c.lane_col;
+                    if (col >= c.N) continue;
+                    const float dh = a.gh ? a.gh[off + col] + acc[mt][nt][r] : acc[mt][nt][r];
+                    a.dpre[off + col] = a.h[off + col] > 0.0f ? dh : 0.0f;
+                }
+            }
+    }
+};
+
+// C[row][col] = acc * mask[row][col]: the RigL mask on the store of the ternary decoder's weight gradient
+template <int BM, int BN>
+struct EpiStoreMasked : EpiTrainBase<BM, BN> {
+    using Base = EpiTrainBase<BM, BN>;
+    static constexpr int MT = Base::MT, NT = Base::NT, WTM = Base::WTM, WTN = Base::WTN;
+    struct Args {
+        float* out;
+        const float* mask;
+        int64_t ld;
+    };
+    __device__ __forceinline__ void begin(const Args&, const TileCtx&) {}
+    __device__ __forceinline__ void finish(const Args& a, f32x16 (&acc)[MT][NT], const TileCtx& c) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = c.m0 + c.wm * WTM + mt * 32 + mfma_row(r, c.lane_half);
+                if (row >= c.M) continue;
+                const int64_t off = static_cast<int64_t>(row) * a.ld;
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) {
+                    const int col = c.n0 + c.wn * WTN + nt * 32 + c.lane_col;
+                    if (col < c.N) a.out[off + col] = acc[mt][nt][r] * a.mask[off + col];
+                }
+            }
+    }
+};
+
+// no incoming reconstruction gradient: dh = gh (or 0)
+__global__ void __launch_bounds__(256)
+ternary_dpre_const_kernel(const float* __restrict__ gh, const float* __restrict__ h, float* __restrict__ dpre, long long total) {
+    const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
+    for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i < total; i += stride)
+        dpre[i] = (gh && h[i] > 0.0f) ? gh[i] : 0.0f;
+}
+
 struct TrainLevels {
     int n;
     int begin[kTnMaxLevels], size[kTnMaxLevels];
@@ -420,4 +488,48 @@ extern "C" int qsae_train_matryoshka_dsum_dense(const uint32_t* zbits, int64_t w
         if (r != QSAE_OK) return r;
     }
     return QSAE_OK;
+}
+
+// ---- TernarySparseAutoencoder training (reference: sae/ternary.py:41-52,116-122 under loss.backward(); the t_sae branch of
+// training/trainer.py:157-164).  The latent is dense (ReLU), so all three contractions are encoder-sized. -------------------
+extern "C" int qsae_train_ternary_dpre(const float* g_recon, const float* t_rows, const float* g_latent, const float* h, int B,
+                                       int D, int H, float* dpre, qsae_stream_t stream) {
+    QSAE_CHECK_ARG(B >= 1 && D > 0 && H > 0, "B >= 1, D > 0, H > 0 required");
+    QSAE_CHECK_SUPPORTED(tn_shape_ok(D), "D a multiple of 4, at most 4096");
+    QSAE_CHECK_ARG(h && dpre, "h and dpre required");
+    QSAE_CHECK_ARG(!g_recon || t_rows, "g_recon needs t_rows");
+    QSAE_CHECK_ARG((!g_recon || aligned16(g_recon)) && (!t_rows || aligned16(t_rows)), "g_recon and t_rows must be 16-byte aligned");
+    hipStream_t s = as_stream(stream);
+    if (!g_recon) {
+        const long long total = static_cast<long long>(B) * H;
+        long long blocks = (total + 255) / 256;
+        if (blocks > 65536) blocks = 65536;
+        hipLaunchKernelGGL(ternary_dpre_const_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, g_latent, h, dpre, total);
+        QSAE_LAUNCH_CHECK();
+        return QSAE_OK;
+    }
+    using Epi = EpiTernaryDpre<128, 128>;
+    typename Epi::Args ea{g_latent, h, dpre, H};
+    // the asm-staged loaders address with 32-bit byte offsets
+    const bool small = static_cast<int64_t>(B) * D < (1LL << 30) && static_cast<int64_t>(H) * D < (1LL << 30);
+    if (D % 32 == 0 && small) {
+        using L = LoaderF32<128, 32, false, true>;
+        return launch_gemm<L, L, Epi, 128, 128, 32>(typename L::Args{g_recon, D, B}, typename L::Args{t_rows, D, H}, ea, B, H, D,
+                                                    pick_sweep<128, 128>(B, H, D), s);
+    }
+    using L = LoaderF32<128, 32, true>;
+    return launch_gemm<L, L, Epi, 128, 128, 32>(typename L::Args{g_recon, D, B}, typename L::Args{t_rows, D, H}, ea, B, H, D,
+                                                pick_sweep<128, 128>(B, H, D), s);
+}
+
+extern "C" int qsae_train_ternary_dweight(const float* g_recon, const float* h, const float* mask, int B, int D, int H,
+                                          float* dweight, qsae_stream_t stream) {
+    QSAE_CHECK_ARG(B >= 1 && D > 0 && H > 0, "B >= 1, D > 0, H > 0 required");
+    QSAE_CHECK_SUPPORTED(tn_shape_ok(D) && H % 4 == 0, "D a multiple of 4, at most 4096; H a multiple of 4");
+    QSAE_CHECK_ARG(g_recon && h && mask && dweight, "null pointer");
+    QSAE_CHECK_ARG(aligned16(g_recon) && aligned16(h), "g_recon and h must be 16-byte aligned");
+    using LA = LoaderTN<128, 32>;
+    using Epi = EpiStoreMasked<128, 128>;
+    return run_tn<LA, LA, Epi>(typename LA::Args{g_recon, D, D}, typename LA::Args{h, H, H}, typename Epi::Args{dweight, mask, H},
+                               D, H, B, as_stream(stream));
 }

@@ -1417,3 +1417,97 @@ def train_matryoshka_secant(gw: torch.Tensor, gwm: torch.Tensor, counts: torch.T
         raise ValueError("train_matryoshka_secant: inconsistent shapes")
     check(_lib.load().qsae_train_matryoshka_secant(_p(counts.contiguous()), float(c), _p(scale), _p(index), _p(w), _p(wm),
                                                    slots, D, _p(gw), _p(gwm), _stream()))
+
+
+# ---- TernarySparseAutoencoder training -------------------------------------------------------------------------------------
+def train_ternary_supported(D: int, H: int) -> bool:
+    return 0 < D <= TRAIN_MAX_D and D % 4 == 0 and H > 0 and H % 4 == 0
+
+
+def train_mask_supported(D: int, H: int) -> bool:
+    return D > 0 and H > 0 and D * H < 2 ** 31 and (D * H) % 4 == 0
+
+
+@_on_tensor_device
+def train_ternary_rows(w: torch.Tensor) -> torch.Tensor:
+    """decoder.weight [D, H] -> the fp32 ternary dictionary transposed, [H, D] in {-1, 0, +1}; see qsae_train_ternary_rows."""
+    w = _f32c(w, "w")
+    D, H = w.shape
+    if H % 4:
+        raise ValueError(f"train_ternary_rows: hidden_dim must be a multiple of 4 (got {H})")
+    out = torch.empty((H, D), dtype=torch.float32, device=w.device)
+    check(_lib.load().qsae_train_ternary_rows(_p(w), D, H, _p(out), _stream()))
+    return out
+
+
+@_on_tensor_device
+def train_ternary_dpre(h: torch.Tensor, g_recon: Optional[torch.Tensor], g_latent: Optional[torch.Tensor],
+                       t_rows: torch.Tensor) -> torch.Tensor:
+    """-> dpre [B, H] (a new tensor; h is only read); see qsae_train_ternary_dpre."""
+    h, t_rows = _f32c(h, "h"), _f32c(t_rows, "t_rows")
+    B, H = h.shape
+    D = t_rows.shape[1]
+    if not train_ternary_supported(D, H) or t_rows.shape[0] != H or B < 1:
+        raise ValueError(f"train_ternary_dpre: D a multiple of 4 up to {TRAIN_MAX_D}, H a multiple of 4 (got D = {D}, H = {H})")
+    G = _f32c(g_recon, "g_recon") if g_recon is not None else None
+    gh = _f32c(g_latent, "g_latent") if g_latent is not None else None
+    if (G is not None and tuple(G.shape) != (B, D)) or (gh is not None and tuple(gh.shape) != (B, H)):
+        raise ValueError("train_ternary_dpre: inconsistent shapes")
+    dpre = torch.empty_like(h)
+    check(_lib.load().qsae_train_ternary_dpre(_p(G), _p(t_rows), _p(gh), _p(h), B, D, H, _p(dpre), _stream()))
+    return dpre
+
+
+@_on_tensor_device
+def train_ternary_dweight(g_recon: torch.Tensor, h: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+    """-> mask * (g_recon^T h) [D, H]; see qsae_train_ternary_dweight."""
+    G, h, mask = _f32c(g_recon, "g_recon"), _f32c(h, "h"), _f32c(mask, "mask")
+    B, D = G.shape
+    H = h.shape[1]
+    if not train_ternary_supported(D, H) or h.shape[0] != B or tuple(mask.shape) != (D, H) or B < 1:
+        raise ValueError(f"train_ternary_dweight: D a multiple of 4 up to {TRAIN_MAX_D}, H a multiple of 4 (got D = {D}, H = {H})")
+    out = torch.empty((D, H), dtype=torch.float32, device=G.device)
+    check(_lib.load().qsae_train_ternary_dweight(_p(G), _p(h), _p(mask), B, D, H, _p(out), _stream()))
+    return out
+
+
+def _mask_operands(w: torch.Tensor, mask: torch.Tensor, what: str):
+    for t, name in ((w, "weight"), (mask, "mask")):
+        _dev(t, name, torch.float32)
+        if t.dim() != 2 or not t.is_contiguous() or t.data_ptr() % 16:
+            raise ValueError(f"{what}: {name} must be a contiguous, 16-byte aligned [D, H] tensor (it is updated in place)")
+    D, H = w.shape
+    if tuple(mask.shape) != (D, H):
+        raise ValueError(f"{what}: mask is {tuple(mask.shape)}, weight {tuple(w.shape)}")
+    if not train_mask_supported(D, H):
+        raise ValueError(f"{what}: the mask kernels take D * H below 2^31 and a multiple of 4 (got D = {D}, H = {H})")
+    return D, H
+
+
+@_on_tensor_device
+def train_mask_init(w: torch.Tensor, mask: torch.Tensor, n_inactive: int) -> None:
+    """init_mask on weight / mask [D, H] IN PLACE; see qsae_train_mask_init."""
+    D, H = _mask_operands(w, mask, "train_mask_init")
+    if not 0 <= n_inactive <= D * H:
+        raise ValueError(f"train_mask_init: {n_inactive} inactive positions of {D * H}")
+    lib = _lib.load()
+    ws = _train_ws(lib.qsae_train_mask_workspace_bytes(D, H), w.device)
+    check(lib.qsae_train_mask_init(_p(w), _p(mask), D, H, int(n_inactive), _p(ws), ws.numel(), _stream()))
+
+
+@_on_tensor_device
+def train_mask_update(w: torch.Tensor, mask: torch.Tensor, a: Optional[torch.Tensor], delta: Optional[torch.Tensor],
+                      n: int) -> None:
+    """update_mask on weight / mask [D, H] IN PLACE (a [H], delta [D], or both None: drop only); see qsae_train_mask_update."""
+    D, H = _mask_operands(w, mask, "train_mask_update")
+    if not 0 <= n <= D * H:
+        raise ValueError(f"train_mask_update: n = {n} is outside 0 .. {D * H}")
+    if (a is None) != (delta is None):
+        raise ValueError("train_mask_update: a and delta are given together or not at all")
+    if a is not None:
+        a, delta = _f32c(a, "a"), _f32c(delta, "delta")
+        if a.numel() != H or delta.numel() != D:
+            raise ValueError(f"train_mask_update: a has {a.numel()} elements (H = {H}), delta {delta.numel()} (D = {D})")
+    lib = _lib.load()
+    ws = _train_ws(lib.qsae_train_mask_workspace_bytes(D, H), w.device)
+    check(lib.qsae_train_mask_update(_p(w), _p(mask), _p(a), _p(delta), D, H, int(n), _p(ws), ws.numel(), _stream()))

@@ -7,8 +7,8 @@ import torch.nn as nn
 from .. import torch_ops as ops          # torch.ops.qsae.* (dispatcher ops over the C ABI)
 from .base import HipEncoder, PackedCache, require_device_input
 
-_TRAINING_ONLY = ("RigL mask maintenance is part of the reference's training loop "
-                  "(sae/ternary.py:27-39,54-90) and is outside this inference backend")
+_GPU_ONLY = ("RigL mask maintenance (sae/ternary.py:27-39,54-90) runs on the GPU only: the decoder's parameters are on the "
+             "host and there is no CPU fallback")
 
 
 class STEWeights(nn.Module):
@@ -23,6 +23,9 @@ class STEWeights(nn.Module):
         self.register_buffer("mask", torch.ones(out_features, in_features))
         self.input_activations = None   # the reference pins the last [B,H] input here; not kept
         self.output_grad = None
+        # what update_mask() reads of them, left by forward_train (plain attributes, not buffers: no state_dict keys)
+        self.activation_mean = None     # a [H] = mean over the batch of the latent, from the last forward_train
+        self.output_grad_mean = None    # delta [D] = mean over the batch of the gradient at the reconstruction, from its backward
         nn.init.kaiming_normal_(self.weight)
         self._cache = PackedCache()
 
@@ -72,14 +75,76 @@ class STEWeights(nn.Module):
                 return ops.decode_ternary_dense_split(x, self.dictionary_bf16(), self.weight.shape[0])
             return ops.decode_ternary_dense(x, self.codes(), self.weight.shape[0])
 
-    def init_mask(self, sparsity):
-        raise NotImplementedError(_TRAINING_ONLY)
+    def ternary_rows(self) -> torch.Tensor:
+        """The fp32 image of the dictionary transposed, [H, D] in {-1, 0, +1}: the K-contiguous operand of the backward's
+        dh contraction (once per weight version, 4 H D bytes)."""
+        st = self._packed()
+        if "tr" not in st:
+            st["tr"] = ops.train_ternary_rows(self.weight.detach())
+        return st["tr"]
 
-    def update_mask(self, f_decay, sparsity_rate=0.7):
-        raise NotImplementedError(_TRAINING_ONLY)
+    def invalidate_packed(self) -> None:
+        """Forget the derived weight copies (2-bit codes, bf16 and fp32 dictionaries): needed after an edit of ``weight``
+        that moves neither its pointer nor its version counter -- the mask methods below do it themselves."""
+        self._cache.clear()
+
+    def _mask_operands(self):
+        w, m = self.weight, self.mask
+        if not (w.is_cuda and m.is_cuda):
+            raise NotImplementedError(_GPU_ONLY)
+        if w.dtype != torch.float32 or m.dtype != torch.float32 or not w.is_contiguous() or not m.is_contiguous():
+            raise ValueError("STEWeights: the mask kernels take contiguous fp32 weight and mask")
+        D, H = w.shape
+        if not ops.train_mask_supported(D, H):
+            raise ValueError(f"STEWeights: the mask kernels take input_dim * hidden_dim below 2^31 and a multiple of 4 "
+                             f"(got {D} x {H})")
+        return w.detach(), m
+
+    def init_mask(self, sparsity):
+        """``int(numel * sparsity)`` positions with the smallest ``|weight|`` get ``mask = 0`` (exactly that many), then
+        ``weight *= mask`` (sae/ternary.py:27-39), in place on the device.  Where the reference leaves the order among
+        equal ``|weight|`` at the boundary to ``torch.topk``, ties are taken in ascending flat index ``d * H + h``."""
+        w, m = self._mask_operands()
+        n = int(w.numel() * sparsity)
+        if not 0 <= n <= w.numel():
+            raise ValueError(f"init_mask: sparsity {sparsity} gives {n} inactive positions of {w.numel()}")
+        ops.train_mask_init(w, m, n)
+        self.invalidate_packed()          # written through the raw pointers: neither data_ptr nor version moved
+
+    def update_mask(self, f_decay, sparsity_rate=0.7, *, check=False):
+        """One RigL step (sae/ternary.py:54-87) in place on the device, ``n = int(f_decay * (1 - sparsity_rate) * numel)``:
+        the drop (every active position with ``|weight|`` <= the n-th smallest active ``|weight|``, ties included), the grow
+        (the n largest ``|delta[d]| * |a[h]|`` among the positions inactive after the drop; exactly n, ties at the boundary in
+        ascending flat index ``d * H + h`` where the reference leaves them to ``torch.topk``; fewer inactive positions than n:
+        all of them), then ``mask = active`` and ``weight *= mask``.  ``a`` / ``delta`` are ``activation_mean`` /
+        ``output_grad_mean`` as the last ``forward_train`` and its backward left them; before the first backward only the
+        drop happens, as in the reference.
+
+        Nothing is read back to the host: n comes from the Python arithmetic above, every selection is made on the device.
+        So an n above the number of active positions -- a RuntimeError from ``kthvalue`` in the reference -- cannot be seen
+        here and saturates: every active position drops.  ``check=True`` spends one host read on the active count and raises
+        ValueError before anything changes."""
+        w, m = self._mask_operands()
+        n = int(f_decay * (1 - sparsity_rate) * w.numel())
+        if not 0 <= n <= w.numel():
+            raise ValueError(f"update_mask: f_decay {f_decay}, sparsity_rate {sparsity_rate} give n = {n} of {w.numel()} positions")
+        if check and n > 0:
+            active = int((m != 0).sum().item())
+            if n > active:
+                raise ValueError(f"update_mask: n = {n} is above the {active} active positions")
+        a, delta = self.activation_mean, self.output_grad_mean
+        if a is None or delta is None:
+            a = delta = None
+        ops.train_mask_update(w, m, a, delta, n)
+        self.invalidate_packed()          # written through the raw pointers: neither data_ptr nor version moved
 
     def mask_grad(self):
-        raise NotImplementedError(_TRAINING_ONLY)
+        """``weight.grad *= mask`` in place (sae/ternary.py:89-90).  forward_train's backward already returns the masked
+        gradient, as the reference's autograd does, so this is idempotent."""
+        if not self.weight.is_cuda:
+            raise NotImplementedError(_GPU_ONLY)
+        if self.weight.grad is not None:
+            self.weight.grad.mul_(self.mask)
 
 
 class TernarySparseAutoencoder(ops.GraphForwardMixin, nn.Module):
@@ -103,9 +168,81 @@ class TernarySparseAutoencoder(ops.GraphForwardMixin, nn.Module):
         h = self.encoder(require_device_input(x, "x"))
         return h, self.decoder(h)
 
+    def forward_train(self, x):
+        """``(h [B,H], recon [B,D])`` with a ``grad_fn``: the forward the reference trains through (sae/ternary.py:41-52,
+        116-122; the t_sae branch of training/trainer.py:157-164), the same bits as ``forward()`` on whichever decoder
+        ``precision`` resolves, whose backward runs the HIP gradient kernels.  ``loss.backward()``
+        fills the ``.grad`` of encoder.0.weight / .bias and decoder.weight (already multiplied by ``decoder.mask``; the mask
+        is a buffer and gets none), and of ``x`` if it requires grad.  A gradient arriving at ``h`` (an L1 term) is added.
+
+        Kept alive between forward and backward: ``x`` (as fp32), ``h`` [B, H] -- the tensor handed to the caller, which
+        the backward only reads -- the decoder's fp32 dictionary rows [H, D] (cached per weight version) and the mask.  The
+        backward allocates its own [B, H] buffer for ``dpre`` (1 GiB at B = 8192, H = 32768).
+
+        For ``decoder.update_mask`` the forward leaves ``decoder.activation_mean`` (a [H], the batch mean of ``h``) and the
+        backward ``decoder.output_grad_mean`` (delta [D], the batch mean of the gradient at ``recon``); the [B, H] tensor the
+        reference pins is not kept."""
+        x = require_device_input(x, "x")
+        lin = self.encoder.linear
+        H, D = lin.weight.shape
+        if not ops.train_ternary_supported(D, H):
+            raise ValueError(f"TernarySparseAutoencoder.forward_train: the gradient kernels take input_dim a multiple of 4 up "
+                             f"to 4096 and hidden_dim a multiple of 4 (got input_dim = {D}, hidden_dim = {H})")
+        if x.shape[1] != D:
+            raise ValueError(f"x is {tuple(x.shape)}, expected [batch, {D}]")
+        if x.shape[0] < 1:
+            raise ValueError("TernarySparseAutoencoder.forward_train: empty batch")
+        return _TernaryTrainStep.apply(self, x, lin.weight, lin.bias, self.decoder.weight)
+
     def forward(self, x):
         if torch.compiler.is_compiling():              # one graph node: torch.ops.qsae.ternary_sae_forward
             with torch.no_grad():
                 lin = self.encoder.linear
                 return torch.ops.qsae.ternary_sae_forward(x, [lin.weight, lin.bias, self.decoder.weight], self._qsae_handle)
         return self._forward_eager(x)
+
+
+class _TernaryTrainStep(torch.autograd.Function):
+    """The TernarySparseAutoencoder forward and its gradient (the table in DESIGN.md section 4.13).  The latent is dense
+    (ReLU, no top-k), so the backward is three encoder-sized fp32 contractions: dh = gh + G T (NT, with the ReLU gate in the
+    epilogue), dw = mask * (G^T h) (TN, the mask on the store), dW_enc = dpre^T x (TN)."""
+
+    @staticmethod
+    def forward(ctx, model, x, W_enc, b_enc, w):
+        dec = model.decoder
+        xf = x.detach()
+        xf = xf if (xf.dtype == torch.float32 and xf.is_contiguous()) else xf.float().contiguous()
+        h = model.encoder(xf)
+        recon = dec(h)
+        dec.activation_mean = ops.train_col_sum(h).div_(h.shape[0])
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(xf, h, dec.ternary_rows(), dec.mask)
+        ctx.model, ctx.x_dtype = model, x.dtype
+        return h, recon
+
+    @staticmethod
+    def backward(ctx, g_h, g_recon):
+        xf, h, t_rows, mask = ctx.saved_tensors
+        model = ctx.model
+        dec = model.decoder
+        need_x, need_W, need_b, need_w = ctx.needs_input_grad[1:5]
+        G = gh = None
+        if g_recon is not None:
+            G = g_recon if (g_recon.dtype == torch.float32 and g_recon.is_contiguous()) else g_recon.float().contiguous()
+            dec.output_grad_mean = ops.train_col_sum(G).div_(G.shape[0])
+        if g_h is not None:
+            gh = g_h if (g_h.dtype == torch.float32 and g_h.is_contiguous()) else g_h.float().contiguous()
+        dx = dW = db = dw = None
+        if need_w:
+            dw = ops.train_ternary_dweight(G, h, mask) if G is not None else torch.zeros_like(dec.weight)
+        if need_x or need_W or need_b:
+            dpre = ops.train_ternary_dpre(h, G, gh, t_rows)
+            if need_W:
+                dW = ops.train_gemm_tn(dpre, xf)
+            if need_b:
+                db = ops.train_col_sum(dpre)
+            if need_x:
+                dx = ops.encode_dense(dpre, ops.transpose_rows(model.encoder.linear.weight.detach()), None)
+                if dx.dtype != ctx.x_dtype:
+                    dx = dx.to(ctx.x_dtype)
+        return (None, dx, dW, db, dw)

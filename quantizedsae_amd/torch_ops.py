@@ -929,3 +929,14 @@ train_bits_csr = _ops.train_bits_csr
 train_matryoshka_dsum_lists = _ops.train_matryoshka_dsum_lists
 train_matryoshka_finish = _ops.train_matryoshka_finish
 train_matryoshka_secant = _ops.train_matryoshka_secant
+
+
+# ---- TernarySparseAutoencoder training: called from an autograd.Function and from the RigL mask methods only (the mask
+# entry points update weight and mask in place through their pointers), never traced -- plain functions over ops.py -----------
+train_ternary_supported = _ops.train_ternary_supported
+train_mask_supported = _ops.train_mask_supported
+train_ternary_rows = _ops.train_ternary_rows
+train_ternary_dpre = _ops.train_ternary_dpre
+train_ternary_dweight = _ops.train_ternary_dweight
+train_mask_init = _ops.train_mask_init
+train_mask_update = _ops.train_mask_update
