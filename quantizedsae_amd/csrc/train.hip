@@ -710,6 +710,30 @@ inline UnitLayout unit_layout(long long Bk, int H, int D) {
 
 inline bool train_shape_ok(int D) { return D > 0 && D % 4 == 0 && D <= kTrainMaxD; }
 
+// The per-unit list sums of a.H lists (a.offsets) that hold n_entries entries in all: scans the chunk offsets into the
+// workspace, sums every chunk, and adds up the partials of the lists that were split.  The caller fills the lists, the
+// operands and the outputs of `a`; chunk_off and the slab come from the workspace (unit_layout) here.  TABLE: the
+// table epilogue (dT) instead of the logit epilogue, which stages dInt[D] in LDS.
+template <bool TABLE>
+hipError_t launch_unit_sums(UnitArgs a, long long n_entries, char* ws, const UnitLayout& L, hipStream_t s) {
+    int* chunk_off = reinterpret_cast<int*>(ws + L.chunk_off);
+    hipLaunchKernelGGL(scan_kernel<1>, dim3(1), dim3(1024), 0, s, a.offsets, a.H, chunk_off);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    a.chunk_off = chunk_off;
+    a.slab = reinterpret_cast<float*>(ws + L.slab);
+    a.slab_rows = L.slab_rows;
+    a.slab_ld = L.slab_ld;
+    const int D4 = a.D / 4;
+    const int threads = D4 >= 256 ? 256 : ((D4 + 63) / 64) * 64;
+    const size_t lds = TABLE ? 0 : static_cast<size_t>(a.D) * 4;
+    const long long grid = static_cast<long long>(a.H) + (n_entries + kTrainChunk - 1) / kTrainChunk;   // >= number of chunks
+    hipLaunchKernelGGL(unit_chunk_kernel<TABLE>, dim3(static_cast<unsigned>(grid)), dim3(threads), lds, s, a);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    if (n_entries > kTrainChunk)                           // otherwise no list can be split
+        hipLaunchKernelGGL(unit_final_kernel<TABLE>, dim3(a.H), dim3(threads), lds, s, a);
+    return hipGetLastError();
+}
+
 }  // namespace qsae
 
 using namespace qsae;
@@ -827,22 +851,26 @@ extern "C" int qsae_train_unit_grad(const int32_t* offsets, const int32_t* entri
     if (workspace_bytes < L.total) return fail(QSAE_ERR_WORKSPACE, "%s: workspace too small", __func__);
     hipStream_t s = as_stream(stream);
     char* ws = static_cast<char*>(workspace);
-    int* chunk_off = reinterpret_cast<int*>(ws + L.chunk_off);
-    hipLaunchKernelGGL(scan_kernel<1>, dim3(1), dim3(1024), 0, s, offsets, H, chunk_off);
-    QSAE_LAUNCH_CHECK();
-    UnitArgs a{offsets, entries, chunk_off, val, gv, Bk, k > 0 ? k : 1, H, D, n_bits, x, Bk > 0 ? g_recon : nullptr,
-               logits, step, g_polarize, static_cast<double>(H) * D * n_bits, dW_enc, db_enc, dlogits,
-               reinterpret_cast<float*>(ws + L.slab), L.slab_rows, L.slab_ld, nullptr};
-    const int D4 = D / 4;
-    const int threads = D4 >= 256 ? 256 : ((D4 + 63) / 64) * 64;
-    const size_t lds = static_cast<size_t>(D) * 4;
-    const long long grid = static_cast<long long>(H) + (Bk + kTrainChunk - 1) / kTrainChunk;   // >= number of chunks
-    hipLaunchKernelGGL(unit_chunk_kernel<false>, dim3(static_cast<unsigned>(grid)), dim3(threads), lds, s, a);
-    QSAE_LAUNCH_CHECK();
-    if (Bk > kTrainChunk) {                                // otherwise no list can be split
-        hipLaunchKernelGGL(unit_final_kernel<false>, dim3(H), dim3(threads), lds, s, a);
-        QSAE_LAUNCH_CHECK();
-    }
+    UnitArgs a{};
+    a.offsets = offsets;
+    a.entries = entries;
+    a.val = val;
+    a.gv = gv;
+    a.Bk = Bk;
+    a.k = k > 0 ? k : 1;
+    a.H = H;
+    a.D = D;
+    a.n = n_bits;
+    a.x = x;
+    a.gR = Bk > 0 ? g_recon : nullptr;
+    a.logits = logits;
+    a.step = step;
+    a.gP = g_polarize;
+    a.pol_count = static_cast<double>(H) * D * n_bits;
+    a.dW = dW_enc;
+    a.db = db_enc;
+    a.dlogit = dlogits;
+    QSAE_HIP(launch_unit_sums<false>(a, Bk, ws, L, s));
     return QSAE_OK;
 }
 
@@ -904,20 +932,24 @@ extern "C" int qsae_train_table_unit_grad(const int32_t* offsets, const int32_t*
     const float* gR = Bk > 0 ? g_recon : nullptr;
     float* dT = (dW_dec && gR) ? reinterpret_cast<float*>(ws + L.total) : nullptr;
     if (dW_enc || db_enc || dT) {
-        int* chunk_off = reinterpret_cast<int*>(ws + L.chunk_off);
-        hipLaunchKernelGGL(scan_kernel<1>, dim3(1), dim3(1024), 0, s, offsets, H, chunk_off);
-        QSAE_LAUNCH_CHECK();
-        UnitArgs a{offsets, entries, chunk_off, val, gv, Bk, k > 0 ? k : 1, H, D, 1, x, gR, nullptr, 1.0f, nullptr, 1.0,
-                   dW_enc, db_enc, nullptr, reinterpret_cast<float*>(ws + L.slab), L.slab_rows, L.slab_ld, dT};
-        const int D4 = D / 4;
-        const int threads = D4 >= 256 ? 256 : ((D4 + 63) / 64) * 64;
-        const long long grid = static_cast<long long>(H) + (Bk + kTrainChunk - 1) / kTrainChunk;   // >= number of chunks
-        hipLaunchKernelGGL(unit_chunk_kernel<true>, dim3(static_cast<unsigned>(grid)), dim3(threads), 0, s, a);
-        QSAE_LAUNCH_CHECK();
-        if (Bk > kTrainChunk) {                            // otherwise no list can be split
-            hipLaunchKernelGGL(unit_final_kernel<true>, dim3(H), dim3(threads), 0, s, a);
-            QSAE_LAUNCH_CHECK();
-        }
+        UnitArgs a{};
+        a.offsets = offsets;
+        a.entries = entries;
+        a.val = val;
+        a.gv = gv;
+        a.Bk = Bk;
+        a.k = k > 0 ? k : 1;
+        a.H = H;
+        a.D = D;
+        a.n = 1;
+        a.x = x;
+        a.gR = gR;
+        a.step = 1.0f;
+        a.pol_count = 1.0;
+        a.dW = dW_enc;
+        a.db = db_enc;
+        a.dT = dT;
+        QSAE_HIP(launch_unit_sums<true>(a, Bk, ws, L, s));
     }
     if (dW_dec) {
         const int vec = (dW_dec_ld % 4 == 0 && aligned16(dW_dec)) ? 1 : 0;
@@ -1056,29 +1088,29 @@ extern "C" int qsae_train_matryoshka_dsum_lists(const int32_t* offsets, const in
     const UnitLayout L = unit_layout(n_entries, H, D);
     hipStream_t s = as_stream(stream);
     char* ws = static_cast<char*>(workspace);
-    int* chunk_off = reinterpret_cast<int*>(ws + L.chunk_off);
     float* ones = reinterpret_cast<float*>(ws + dsum_lists_ones_offset(n_entries, H, D));
     hipLaunchKernelGGL(fill_f32_kernel, dim3((B + 255) / 256), dim3(256), 0, s, ones, B, 1.0f);
     QSAE_LAUNCH_CHECK();
-    const int D4 = D / 4;
-    const int threads = D4 >= 256 ? 256 : ((D4 + 63) / 64) * 64;
     int h0 = 0;
     for (int i = 0; i < n_bits; ++i) {
         const int n = level_sizes[i];
         if (n == 0) continue;
         // the lists of this level's units against this level's incoming gradient: entry = row, value 1
-        hipLaunchKernelGGL(scan_kernel<1>, dim3(1), dim3(1024), 0, s, offsets + h0, n, chunk_off);
-        QSAE_LAUNCH_CHECK();
-        UnitArgs a{offsets + h0, entries, chunk_off, ones, ones, B, 1, n, D, 1, nullptr,
-                   g_levels + static_cast<long long>(i) * B * D, nullptr, 1.0f, nullptr, 1.0, nullptr, nullptr, nullptr,
-                   reinterpret_cast<float*>(ws + L.slab), L.slab_rows, L.slab_ld, dsum + static_cast<long long>(h0) * D};
-        const long long grid = static_cast<long long>(n) + (n_entries + kTrainChunk - 1) / kTrainChunk;   // >= number of chunks
-        hipLaunchKernelGGL(unit_chunk_kernel<true>, dim3(static_cast<unsigned>(grid)), dim3(threads), 0, s, a);
-        QSAE_LAUNCH_CHECK();
-        if (n_entries > kTrainChunk) {                     // otherwise no list can be split
-            hipLaunchKernelGGL(unit_final_kernel<true>, dim3(n), dim3(threads), 0, s, a);
-            QSAE_LAUNCH_CHECK();
-        }
+        UnitArgs a{};
+        a.offsets = offsets + h0;
+        a.entries = entries;
+        a.val = ones;
+        a.gv = ones;
+        a.Bk = B;
+        a.k = 1;
+        a.H = n;
+        a.D = D;
+        a.n = 1;
+        a.gR = g_levels + static_cast<long long>(i) * B * D;
+        a.step = 1.0f;
+        a.pol_count = 1.0;
+        a.dT = dsum + static_cast<long long>(h0) * D;
+        QSAE_HIP(launch_unit_sums<true>(a, n_entries, ws, L, s));
         h0 += n;
     }
     return QSAE_OK;

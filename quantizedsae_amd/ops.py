@@ -483,24 +483,32 @@ def _decode_prefilter_args(x, W, bias, Wq, meta, k, decoder, dec_bias, want_dens
     return cargs, keep, (idx, val, dense, recon)
 
 
+# library symbols of the forward-in-one-call entry points, by the kind of decoder description
+_PREFILTER_FORWARD = {"packed": "qsae_binary_forward_prefilter", "table": "qsae_table_forward_prefilter"}
+_PREFILTER_SUBMIT = {"packed": ("qsae_prefilter_submit", "qsae_prefilter_finish"),
+                     "table": ("qsae_prefilter_submit_table", "qsae_prefilter_finish_table")}
+
+
 @_on_tensor_device
+def _forward_prefilter(x, W, bias, Wq, meta, k, decoder, dec_bias, want_dense, spec_rows, info):
+    cargs, keep, outs = _decode_prefilter_args(x, W, bias, Wq, meta, k, decoder, dec_bias, want_dense, 0, "call")
+    flagged = C.c_int(0)
+    kernel_timer.arm_sweep()
+    check(getattr(_lib.load(), _PREFILTER_FORWARD[decoder[0]])(*cargs, int(spec_rows), C.byref(flagged), _stream()))
+    if info is not None:
+        info["flagged_rows"] = int(flagged.value)
+    return outs
+
+
 def binary_forward_prefilter(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], Wq: torch.Tensor,
                              meta: torch.Tensor, k: int, packed: torch.Tensor, n_bits: int, step: float,
                              dec_bias: Optional[torch.Tensor], want_dense: bool = True, spec_rows: int = 0,
                              info: Optional[dict] = None):
     """encode_topk_prefilter + decode_binary_sparse in one call (rows are decoded by the refinement kernel as it
     ranks them): (idx, val, dense latent or None, reconstruction), bit-identical to the two separate calls."""
-    cargs, keep, outs = _decode_prefilter_args(x, W, bias, Wq, meta, k, ("packed", packed, n_bits, step), dec_bias,
-                                               want_dense, 0, "call")
-    flagged = C.c_int(0)
-    kernel_timer.arm_sweep()
-    check(_lib.load().qsae_binary_forward_prefilter(*cargs, int(spec_rows), C.byref(flagged), _stream()))
-    if info is not None:
-        info["flagged_rows"] = int(flagged.value)
-    return outs
+    return _forward_prefilter(x, W, bias, Wq, meta, k, ("packed", packed, n_bits, step), dec_bias, want_dense, spec_rows, info)
 
 
-@_on_tensor_device
 def table_forward_prefilter(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], Wq: torch.Tensor,
                             meta: torch.Tensor, k: int, table: torch.Tensor, scale: float,
                             dec_bias: Optional[torch.Tensor], want_dense: bool = True, spec_rows: int = 0,
@@ -508,14 +516,7 @@ def table_forward_prefilter(x: torch.Tensor, W: torch.Tensor, bias: Optional[tor
     """encode_topk_prefilter + decode_table_sparse in one call (fp32 dictionary rows [H, D]: the Baseline decoder, the
     soft integers of an unpolarised BinarySAE): (idx, val, dense latent or None, reconstruction), bit-identical to the
     two separate calls."""
-    cargs, keep, outs = _decode_prefilter_args(x, W, bias, Wq, meta, k, ("table", table, scale), dec_bias, want_dense, 0,
-                                               "call")
-    flagged = C.c_int(0)
-    kernel_timer.arm_sweep()
-    check(_lib.load().qsae_table_forward_prefilter(*cargs, int(spec_rows), C.byref(flagged), _stream()))
-    if info is not None:
-        info["flagged_rows"] = int(flagged.value)
-    return outs
+    return _forward_prefilter(x, W, bias, Wq, meta, k, ("table", table, scale), dec_bias, want_dense, spec_rows, info)
 
 
 class PendingForward:
@@ -584,6 +585,15 @@ def _claim_slot(device, slot):
 
 
 @_on_tensor_device
+def _forward_prefilter_submit(x, W, bias, Wq, meta, k, decoder, dec_bias, want_dense, slot, owner) -> PendingForward:
+    slot = (owner, slot)            # slots are per owner (module): two models on one stream do not share workspaces
+    _claim_slot(x.device, slot)
+    cargs, keep, outs = _decode_prefilter_args(x, W, bias, Wq, meta, k, decoder, dec_bias, want_dense, slot, "pending")
+    lib = _lib.load()
+    submit_fn, finish_fn = (getattr(lib, name) for name in _PREFILTER_SUBMIT[decoder[0]])
+    return _submit(submit_fn, finish_fn, cargs, keep, outs, x.device, slot)
+
+
 def binary_forward_prefilter_submit(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], Wq: torch.Tensor,
                                     meta: torch.Tensor, k: int, packed: torch.Tensor, n_bits: int, step: float,
                                     dec_bias: Optional[torch.Tensor], want_dense: bool = True,
@@ -591,26 +601,16 @@ def binary_forward_prefilter_submit(x: torch.Tensor, W: torch.Tensor, bias: Opti
     """The two-call form of binary_forward_prefilter (qsae_prefilter_submit / _finish): nothing in here waits for the
     GPU, so the caller can submit batch i+1 before it finishes batch i.  Batches in flight together on one stream
     need different ``slot`` numbers (each slot is a workspace of its own); finish them in submission order."""
-    slot = (owner, slot)            # slots are per owner (module): two models on one stream do not share workspaces
-    _claim_slot(x.device, slot)
-    cargs, keep, outs = _decode_prefilter_args(x, W, bias, Wq, meta, k, ("packed", packed, n_bits, step), dec_bias,
-                                               want_dense, slot, "pending")
-    lib = _lib.load()
-    return _submit(lib.qsae_prefilter_submit, lib.qsae_prefilter_finish, cargs, keep, outs, x.device, slot)
+    return _forward_prefilter_submit(x, W, bias, Wq, meta, k, ("packed", packed, n_bits, step), dec_bias, want_dense, slot,
+                                     owner)
 
 
-@_on_tensor_device
 def table_forward_prefilter_submit(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], Wq: torch.Tensor,
                                    meta: torch.Tensor, k: int, table: torch.Tensor, scale: float,
                                    dec_bias: Optional[torch.Tensor], want_dense: bool = True,
                                    slot: int = 0, owner: int = 0) -> PendingForward:
     """The two-call form of table_forward_prefilter (qsae_prefilter_submit_table / _finish_table)."""
-    slot = (owner, slot)
-    _claim_slot(x.device, slot)
-    cargs, keep, outs = _decode_prefilter_args(x, W, bias, Wq, meta, k, ("table", table, scale), dec_bias, want_dense, slot,
-                                               "pending")
-    lib = _lib.load()
-    return _submit(lib.qsae_prefilter_submit_table, lib.qsae_prefilter_finish_table, cargs, keep, outs, x.device, slot)
+    return _forward_prefilter_submit(x, W, bias, Wq, meta, k, ("table", table, scale), dec_bias, want_dense, slot, owner)
 
 
 @_on_tensor_device

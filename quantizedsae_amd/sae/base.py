@@ -120,6 +120,27 @@ class SparseAutoencoder(nn.Module):
         return latent, self.decode(latent)
 
 
+def as_f32c(t: torch.Tensor) -> torch.Tensor:
+    """``t`` itself when it is already fp32 and contiguous (no copy, no launch), else an fp32 contiguous copy."""
+    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+
+
+def dense_encoder_backward(dpre, xf, W, need_x: bool, need_W: bool, need_b: bool, x_dtype):
+    """-> (dx, dW, db) of a dense encoder ``pre = x W^T + b`` from ``dpre`` [B, H]: dW = dpre^T x (TN contraction),
+    db = column sums of dpre, dx = dpre W (cast back to the dtype x came in).  What is not needed is None and is not
+    computed; ``W`` [H, D] is read only for dx.  Shared by the Ternary and Matryoshka backwards, whose latents are dense."""
+    dx = dW = db = None
+    if need_W:
+        dW = ops.train_gemm_tn(dpre, xf)
+    if need_b:
+        db = ops.train_col_sum(dpre)
+    if need_x:
+        dx = ops.encode_dense(dpre, ops.transpose_rows(W), None)
+        if dx.dtype != x_dtype:
+            dx = dx.to(x_dtype)
+    return dx, dW, db
+
+
 def require_device_input(x: torch.Tensor, what: str = "input") -> torch.Tensor:
     if not isinstance(x, torch.Tensor):
         raise TypeError(f"{what}: expected a torch.Tensor, got {type(x)}")

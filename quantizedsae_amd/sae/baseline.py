@@ -5,10 +5,11 @@ import torch
 import torch.nn as nn
 
 from .. import torch_ops as ops          # torch.ops.qsae.* (dispatcher ops over the C ABI)
-from .base import HipEncoder, PackedCache, require_device_input
+from .base import HipEncoder, PackedCache, as_f32c, require_device_input
+from .topk import SubmittedForward, TopKCore, sparse_backward
 
 
-class BaselineSparseAutoencoder(ops.GraphForwardMixin, nn.Module):
+class BaselineSparseAutoencoder(ops.GraphForwardMixin, TopKCore, nn.Module):
     def __init__(self, input_dim, hidden_dim):
         super().__init__()
         self.encoder = HipEncoder(nn.Linear(input_dim, hidden_dim))   # no ReLU in the reference either
@@ -16,8 +17,7 @@ class BaselineSparseAutoencoder(ops.GraphForwardMixin, nn.Module):
         self.topk = 32
         self.latent_path = "auto"      # "auto" | "prefilter" | "fused" | "inplace" (see BinarySAE.latent_path)
         self._cache = PackedCache()
-        self._pref_cache = PackedCache()
-        self.last_flagged_rows = 0     # rows of the previous prefilter batch that took the exact fallback (per model)
+        self._init_topk()
         ops.module_handle(self)
 
     def _table(self) -> torch.Tensor:
@@ -25,16 +25,15 @@ class BaselineSparseAutoencoder(ops.GraphForwardMixin, nn.Module):
         return self._cache.get((self.decoder.weight,),
                                lambda: {"t": self.decoder.weight.detach().t().contiguous()})["t"]
 
-    def _prefilter_ok(self, rows: int) -> bool:
-        lin = self.encoder.linear
-        H, D = lin.weight.shape
+    def resolved_latent_path(self, rows: int) -> str:
+        """Which path _run() takes for a batch of this many rows.  Not BinarySAE's rule, and deliberately not aligned with
+        it: ``latent_path`` is not validated here, and an explicit "prefilter" or "fused" on a small batch falls to the
+        in-place path (BinarySAE honours it)."""
+        H, D = self.encoder.linear.weight.shape
         big = rows >= 2048 and H >= 8192
-        return big and self.latent_path in ("auto", "prefilter") and ops.prefilter_supported(rows, D, H, self.topk)
-
-    def _prefilter_weights(self):
-        lin = self.encoder.linear
-        return self._pref_cache.get((lin.weight, lin.bias), lambda: dict(zip(
-            ("Wq", "meta"), ops.prefilter_pack_w(lin.weight.detach(), lin.bias.detach()))))
+        if big and self.latent_path in ("auto", "prefilter") and ops.prefilter_supported(rows, D, H, self.topk):
+            return "prefilter"
+        return "fused" if (big and self.latent_path != "inplace") else "inplace"
 
     def _check_limits(self, rows: int) -> None:
         H, D = self.encoder.linear.weight.shape
@@ -48,31 +47,14 @@ class BaselineSparseAutoencoder(ops.GraphForwardMixin, nn.Module):
         forward_compact()."""
         x = require_device_input(x, "x")
         self._check_limits(x.shape[0])
-        lin = self.encoder.linear
-        H = lin.weight.shape[0]
-        big = x.shape[0] >= 2048 and H >= 8192
-        if self._prefilter_ok(x.shape[0]):
+        path = self.resolved_latent_path(x.shape[0])
+        if path == "prefilter":
             # one call: candidate sweep, exact refinement, and the row's reconstruction from the fp32 decoder rows as soon
             # as the row is ranked (qsae_table_forward_prefilter)
-            pw = self._prefilter_weights()
-            xf = x if (x.dtype == torch.float32 and x.is_contiguous()) else x.float().contiguous()
-            info = {}
-            idx, val, h, recon = ops.table_forward_prefilter(
-                xf, lin.weight.detach(), lin.bias.detach(), pw["Wq"], pw["meta"], self.topk, self._table(), 1.0,
-                self.decoder.bias.detach(), want_dense=want_dense, spec_rows=32 if self.last_flagged_rows > 0 else 0,
-                info=info)
-            self.last_flagged_rows = info["flagged_rows"]
-            return idx, val, h, recon
-        if big and self.latent_path != "inplace" and want_dense:
-            xp, Wp, kperm = self.encoder.operands(x)
-            idx, val, h = ops.encode_topk_latent(xp, Wp, lin.bias, self.topk, kperm=kperm)
-        elif not want_dense:
-            xp, Wp, kperm = self.encoder.operands(x)
-            idx, val = ops.encode_topk(xp, Wp, lin.bias, self.topk, kperm=kperm)
-            h = None
-        else:
-            h = self.encoder(x)
-            idx, val = ops.topk_rows(h, self.topk, zero_rest=True)
+            enc = self._prefilter_operands(x)
+            return self._forward_prefilter(enc, self.topk, ("table", self._table(), 1.0), self.decoder.bias.detach(),
+                                           want_dense)
+        idx, val, h = self._select(x, self.topk, path, want_dense)
         return idx, val, h, ops.decode_table_sparse(idx, val, self._table(), 1.0, self.decoder.bias.detach())
 
     def forward(self, x):
@@ -120,26 +102,23 @@ class BaselineSparseAutoencoder(ops.GraphForwardMixin, nn.Module):
     def forward_submit(self, x, slot: int = 0, want_dense: bool = True):
         """Queue one forward without waiting for the GPU anywhere (see BinarySAE.forward_submit): ``result()`` of the
         returned handle gives ``(h_sparse, reconstruction)`` (``(idx, val, reconstruction)`` with want_dense=False)."""
+        def to_result(idx, val, h, recon):
+            return (h, recon) if want_dense else (idx, val, recon)
         with torch.no_grad():
             xd = require_device_input(x, "x")
             self._check_limits(xd.shape[0])
-            if self._prefilter_ok(xd.shape[0]):
-                lin = self.encoder.linear
-                pw = self._prefilter_weights()
-                xf = xd if (xd.dtype == torch.float32 and xd.is_contiguous()) else xd.float().contiguous()
-                pending = ops.table_forward_prefilter_submit(
-                    xf, lin.weight.detach(), lin.bias.detach(), pw["Wq"], pw["meta"], self.topk, self._table(), 1.0,
-                    self.decoder.bias.detach(), want_dense=want_dense, slot=slot, owner=self._qsae_handle)
-                return _SubmittedBaseline(self, pending, None, want_dense)
-            return _SubmittedBaseline(self, None, self._run(xd, want_dense), want_dense)
+            if self.resolved_latent_path(xd.shape[0]) == "prefilter":
+                enc = self._prefilter_operands(xd)
+                pending = self._submit_prefilter(enc, self.topk, ("table", self._table(), 1.0), self.decoder.bias.detach(),
+                                                 want_dense, slot)
+                return SubmittedForward(self, pending, None, to_result)
+            return SubmittedForward(self, None, self._run(xd, want_dense), to_result)
 
     def invalidate_packed(self) -> None:
         """Forget the derived weight copies (transposed decoder table, fp16 / K-interleaved encoder copies): needed only
         after an in-place edit through ``.data`` -- normalize_decoder_weights() below does it itself."""
         self._cache.clear()
-        self._pref_cache.clear()
-        if hasattr(self.encoder, "_kperm_cache"):
-            self.encoder._kperm_cache.clear()
+        self._clear_encoder_copies()
 
     def apply_topk_activation(self, h):
         """Dense in, dense out: keep the top-k entries of every row (sae/baseline.py:33-40)."""
@@ -168,20 +147,6 @@ class BaselineSparseAutoencoder(ops.GraphForwardMixin, nn.Module):
             self.invalidate_packed()
 
 
-class _SubmittedBaseline:
-    def __init__(self, model, pending, outs, want_dense):
-        self._model, self._pending, self._outs, self._want_dense = model, pending, outs, want_dense
-
-    def result(self):
-        with torch.no_grad():
-            if self._pending is not None:
-                self._outs = self._pending.finish()
-                self._model.last_flagged_rows = self._pending.flagged_rows
-                self._pending = None
-            idx, val, h, recon = self._outs
-            return (h, recon) if self._want_dense else (idx, val, recon)
-
-
 class _BaselineTrainStep(torch.autograd.Function):
     """The baseline forward and its gradient (the table in DESIGN.md section 4.11): the BinarySAE gradient without the
     sigmoid chain.  gv = g_latent[r, h] + <g_recon[r], W_dec[:, h]> on the k selected entries of each row, then per unit
@@ -190,8 +155,7 @@ class _BaselineTrainStep(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, dense_latent, x, W_enc, b_enc, W_dec, b_dec):
-        xf = x.detach()
-        xf = xf if (xf.dtype == torch.float32 and xf.is_contiguous()) else xf.float().contiguous()
+        xf = as_f32c(x.detach())
         idx, val, latent, recon = model._run(xf, dense_latent)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(xf, idx, val, model._table())
@@ -204,21 +168,11 @@ class _BaselineTrainStep(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_latent, g_recon):
         xf, idx, val, table = ctx.saved_tensors
-        model = ctx.model
-        lin, dec = model.encoder.linear, model.decoder
-        need_x, need_W, need_b, need_Wd, need_bd = ctx.needs_input_grad[2:7]
-        H = table.shape[0]
-        want_enc = need_W or need_b
-        dx = dW = db = dWd = dbd = None
-        if need_x or want_enc or need_Wd:
-            gv, dx = ops.train_row_grad(idx, table, 1.0, g_recon, g_latent, lin.weight.detach(), want_dx=need_x)
-            if want_enc or need_Wd:
-                offsets, entries = ops.train_csr(idx, H)
-                dW, db, dWd = ops.train_table_unit_grad(offsets, entries, val, gv, xf, g_recon, want_encoder=want_enc,
-                                                        want_decoder=need_Wd)
-        if need_bd:
-            dbd = ops.train_col_sum(g_recon) if g_recon is not None else torch.zeros_like(dec.bias)
-        if dx is not None and dx.dtype != ctx.x_dtype:
-            dx = dx.to(ctx.x_dtype)
-        return (None, None, dx if need_x else None, dW if need_W else None, db if need_b else None,
-                dWd if need_Wd else None, dbd)
+        lin, dec = ctx.model.encoder.linear, ctx.model.decoder
+        need_W, need_b, need_Wd = ctx.needs_input_grad[3:6]
+
+        def unit_grad(offsets, entries, gv):
+            return ops.train_table_unit_grad(offsets, entries, val, gv, xf, g_recon, want_encoder=need_W or need_b,
+                                             want_decoder=need_Wd)
+        return (None, None) + sparse_backward(idx, table, 1.0, g_recon, g_latent, lin.weight, dec.bias,
+                                              ctx.needs_input_grad[2:7], ctx.x_dtype, unit_grad)

@@ -8,7 +8,8 @@ import torch
 import torch.nn as nn
 
 from .. import torch_ops as ops          # torch.ops.qsae.* (dispatcher ops over the C ABI)
-from .base import HipEncoder, PackedCache, SparseAutoencoder, require_device_input
+from .base import HipEncoder, PackedCache, SparseAutoencoder, as_f32c, require_device_input
+from .topk import SubmittedForward, TopKCore, sparse_backward
 
 
 class binary_decoder(nn.Module):
@@ -128,7 +129,7 @@ class binary_decoder(nn.Module):
             return ops.binary_soft_table(self.weight.detach(), self.out_features, self.n_bits)
 
 
-class BinarySAE(ops.GraphForwardMixin, SparseAutoencoder):
+class BinarySAE(ops.GraphForwardMixin, TopKCore, SparseAutoencoder):
     """``forward(x) -> (sparse_latent [B,H], reconstruction [B,D], polarize_loss [])``
     (sae/binary.py:71-103).  k = int(hidden_dim * self.k) with self.k = 0.002.
 
@@ -147,10 +148,7 @@ class BinarySAE(ops.GraphForwardMixin, SparseAutoencoder):
         nn.init.zeros_(lin.bias)
         self.encoder = HipEncoder(lin)
         self.decoder = binary_decoder(hidden_dim, input_dim, gamma=gamma, n_bits=self.n_bits)
-        self._pref_cache = PackedCache()
-        #: rows of the previous prefilter batch that went through the exact fallback kernels (sizes the next call's
-        #: speculative fallback; per model, not per process)
-        self.last_flagged_rows = 0
+        self._init_topk()
         ops.module_handle(self)
 
     @property
@@ -180,20 +178,11 @@ class BinarySAE(ops.GraphForwardMixin, SparseAutoencoder):
             path = "fused" if big else "inplace"
         return path
 
-    def _prefilter_weights(self):
-        lin = self.encoder.linear
-        def build():
-            Wq, meta = ops.prefilter_pack_w(lin.weight.detach(), lin.bias.detach())
-            return {"Wq": Wq, "meta": meta}
-        return self._pref_cache.get((lin.weight, lin.bias), build)
-
     def invalidate_packed(self) -> None:
         """Forget every derived copy of the weights (packed dictionary, fp16 / K-interleaved encoder copies); see
         binary_decoder.invalidate_packed."""
         self.decoder.invalidate_packed()
-        self._pref_cache.clear()
-        if hasattr(self.encoder, "_kperm_cache"):
-            self.encoder._kperm_cache.clear()
+        self._clear_encoder_copies()
 
     def _check_limits(self, path: str, rows: int) -> None:
         k = self.top_k
@@ -223,47 +212,26 @@ class BinarySAE(ops.GraphForwardMixin, SparseAutoencoder):
         x = require_device_input(x, "x")
         if self.top_k == 0:
             return self._zero_k(x, want_dense)
-        lin = self.encoder.linear
         path = self.resolved_latent_path(x.shape[0])
         self._check_limits(path, x.shape[0])
-        hard = soft_table is None and self.decoder.resolved_decode_mode() == "hard"
-        latent = None
-        if path == "prefilter":
-            pw = self._prefilter_weights()
-            xf = x if (x.dtype == torch.float32 and x.is_contiguous()) else x.float().contiguous()
-            spec = 32 if self.last_flagged_rows > 0 else 0
-            info = {}
-            if self.fuse_decode:
-                # one call: the refinement kernel decodes every row it ranks -- from the packed n-bit dictionary, or from
-                # the fp32 soft-integer table when the checkpoint is not polarised (the reference's own arithmetic)
-                dec = self.decoder
-                if hard:
-                    idx, val, latent, recon = ops.binary_forward_prefilter(
-                        xf, lin.weight.detach(), lin.bias.detach(), pw["Wq"], pw["meta"], self.top_k, dec.packed()["packed"],
-                        dec.n_bits, dec.quantization_step, dec.bias.detach(), want_dense=want_dense, spec_rows=spec, info=info)
-                else:
-                    idx, val, latent, recon = ops.table_forward_prefilter(
-                        xf, lin.weight.detach(), lin.bias.detach(), pw["Wq"], pw["meta"], self.top_k,
-                        dec.soft_table() if soft_table is None else soft_table, dec.quantization_step, dec.bias.detach(),
-                        want_dense=want_dense, spec_rows=spec, info=info)
-                self.last_flagged_rows = info["flagged_rows"]
-                return idx, val, latent, recon
-            idx, val, latent = ops.encode_topk_prefilter(xf, lin.weight.detach(), lin.bias.detach(), pw["Wq"], pw["meta"],
-                                                         self.top_k, want_dense=want_dense, spec_rows=spec, info=info)
-            self.last_flagged_rows = info["flagged_rows"]
-        elif path == "fused" or not want_dense:
-            xp, Wp, kperm = self.encoder.operands(x)
-            if want_dense:
-                idx, val, latent = ops.encode_topk_latent(xp, Wp, lin.bias, self.top_k, kperm=kperm)
-            else:
-                idx, val = ops.encode_topk(xp, Wp, lin.bias, self.top_k, kperm=kperm)
-        else:   # inplace
-            latent = self.encoder(x)
-            idx, val = ops.topk_rows(latent, self.top_k, zero_rest=True)     # latent * mask, in place
+        dec = self.decoder
+        hard = soft_table is None and dec.resolved_decode_mode() == "hard"
+        if path == "prefilter" and self.fuse_decode:
+            enc = self._prefilter_operands(x)
+            return self._forward_prefilter(enc, self.top_k, self._fused_decoder(hard, soft_table), dec.bias.detach(),
+                                           want_dense)
+        idx, val, latent = self._select(x, self.top_k, path, want_dense)
         if soft_table is not None:
-            dec = self.decoder
             return idx, val, latent, ops.decode_table_sparse(idx, val, soft_table, dec.quantization_step, dec.bias.detach())
-        return idx, val, latent, self.decoder.decode_sparse(idx, val)
+        return idx, val, latent, dec.decode_sparse(idx, val)
+
+    def _fused_decoder(self, hard: bool, soft_table=None):
+        """What the refinement kernel decodes every row it ranks from: the packed n-bit dictionary, or the fp32
+        soft-integer table when the checkpoint is not polarised (the reference's own arithmetic)."""
+        dec = self.decoder
+        if hard:
+            return "packed", dec.packed()["packed"], dec.n_bits, dec.quantization_step
+        return "table", dec.soft_table() if soft_table is None else soft_table, dec.quantization_step
 
     def _graph_params(self):
         lin, dec = self.encoder.linear, self.decoder
@@ -317,39 +285,17 @@ class BinarySAE(ops.GraphForwardMixin, SparseAutoencoder):
         an unpolarised checkpoint): submit batch i+1, then
         call ``result()`` of batch i -- the 4-byte read-back of batch i no longer idles the GPU.  Batches in flight
         together need different ``slot`` numbers; other paths compute eagerly and return a finished handle."""
+        def to_result(idx, val, latent, recon):
+            return (latent, recon, self.decoder.packed()["polarize"]) if want_dense else (idx, val, recon)
         with torch.no_grad():
             xd = require_device_input(x, "x")
             if self.top_k > 0 and self.resolved_latent_path(xd.shape[0]) == "prefilter" and self.fuse_decode:
                 self._check_limits("prefilter", xd.shape[0])
-                lin, dec = self.encoder.linear, self.decoder
-                pw = self._prefilter_weights()
-                xf = xd if (xd.dtype == torch.float32 and xd.is_contiguous()) else xd.float().contiguous()
-                if dec.resolved_decode_mode() == "hard":
-                    pending = ops.binary_forward_prefilter_submit(
-                        xf, lin.weight.detach(), lin.bias.detach(), pw["Wq"], pw["meta"], self.top_k, dec.packed()["packed"],
-                        dec.n_bits, dec.quantization_step, dec.bias.detach(), want_dense=want_dense, slot=slot, owner=self._qsae_handle)
-                else:
-                    pending = ops.table_forward_prefilter_submit(
-                        xf, lin.weight.detach(), lin.bias.detach(), pw["Wq"], pw["meta"], self.top_k, dec.soft_table(),
-                        dec.quantization_step, dec.bias.detach(), want_dense=want_dense, slot=slot, owner=self._qsae_handle)
-                return _SubmittedForward(self, pending, None, want_dense)
-            return _SubmittedForward(self, None, self._run(xd, want_dense), want_dense)
-
-
-class _SubmittedForward:
-    def __init__(self, model, pending, outs, want_dense):
-        self._model, self._pending, self._outs, self._want_dense = model, pending, outs, want_dense
-
-    def result(self):
-        with torch.no_grad():
-            if self._pending is not None:
-                self._outs = self._pending.finish()
-                self._model.last_flagged_rows = self._pending.flagged_rows
-                self._pending = None
-            idx, val, latent, recon = self._outs
-            if self._want_dense:
-                return latent, recon, self._model.decoder.packed()["polarize"]
-            return idx, val, recon
+                enc = self._prefilter_operands(xd)
+                decoder = self._fused_decoder(self.decoder.resolved_decode_mode() == "hard")
+                pending = self._submit_prefilter(enc, self.top_k, decoder, self.decoder.bias.detach(), want_dense, slot)
+                return SubmittedForward(self, pending, None, to_result)
+            return SubmittedForward(self, None, self._run(xd, want_dense), to_result)
 
 
 class _BinaryTrainStep(torch.autograd.Function):
@@ -361,8 +307,7 @@ class _BinaryTrainStep(torch.autograd.Function):
     def forward(ctx, model, dense_latent, x, W_enc, b_enc, logits, b_dec):
         dec = model.decoder
         table, pol = ops.binary_soft_table_polarize(logits.detach(), dec.out_features, dec.n_bits)
-        xf = x.detach()
-        xf = xf if (xf.dtype == torch.float32 and xf.is_contiguous()) else xf.float().contiguous()
+        xf = as_f32c(x.detach())
         idx, val, latent, recon = model._run(xf, dense_latent, soft_table=table)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(xf, idx, val, table)
@@ -377,20 +322,10 @@ class _BinaryTrainStep(torch.autograd.Function):
         xf, idx, val, table = ctx.saved_tensors
         model = ctx.model
         lin, dec = model.encoder.linear, model.decoder
-        need_x, need_W, need_b, need_l, need_bd = ctx.needs_input_grad[2:7]
-        H = model.hidden_dim
-        want_enc = need_W or need_b
-        dx = dW = db = dl = dbd = None
-        if need_x or want_enc or need_l:
-            gv, dx = ops.train_row_grad(idx, table, dec.quantization_step, g_recon, g_latent, lin.weight.detach(),
-                                        want_dx=need_x)
-            if want_enc or need_l:
-                offsets, entries = ops.train_csr(idx, H)
-                dW, db, dl = ops.train_unit_grad(offsets, entries, val, gv, xf, g_recon, dec.weight.detach(), dec.n_bits,
-                                                 dec.quantization_step, g_pol, want_encoder=want_enc, want_logits=need_l)
-        if need_bd:
-            dbd = ops.train_col_sum(g_recon) if g_recon is not None else torch.zeros_like(dec.bias)
-        if dx is not None and dx.dtype != ctx.x_dtype:
-            dx = dx.to(ctx.x_dtype)
-        return (None, None, dx if need_x else None, dW if need_W else None, db if need_b else None,
-                dl if need_l else None, dbd)
+        need_W, need_b, need_l = ctx.needs_input_grad[3:6]
+
+        def unit_grad(offsets, entries, gv):
+            return ops.train_unit_grad(offsets, entries, val, gv, xf, g_recon, dec.weight.detach(), dec.n_bits,
+                                       dec.quantization_step, g_pol, want_encoder=need_W or need_b, want_logits=need_l)
+        return (None, None) + sparse_backward(idx, table, dec.quantization_step, g_recon, g_latent, lin.weight, dec.bias,
+                                              ctx.needs_input_grad[2:7], ctx.x_dtype, unit_grad)

@@ -8,7 +8,7 @@ import torch
 import torch.nn as nn
 
 from .. import torch_ops as ops          # torch.ops.qsae.* (dispatcher ops over the C ABI)
-from .base import HipEncoder, PackedCache, SparseAutoencoder, require_device_input
+from .base import HipEncoder, PackedCache, SparseAutoencoder, as_f32c, dense_encoder_backward, require_device_input
 
 def nested_sizes(in_features: int, n_bits: int) -> List[int]:
     """Level sizes [1,1,2,4,...] scaled to in_features, remainder in the last level
@@ -408,8 +408,7 @@ class _MatryoshkaTrainStep(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, path, x, W_enc, b_enc, w, wm, bias):
         dec = model.decoder
-        xf = x.detach()
-        xf = xf if (xf.dtype == torch.float32 and xf.is_contiguous()) else xf.float().contiguous()
+        xf = as_f32c(x.detach())
         B = xf.shape[0]
         Wp, bp = model._encoder_params()
         st = dec.packed()
@@ -441,7 +440,7 @@ class _MatryoshkaTrainStep(torch.autograd.Function):
         sizes, Hp = ctx.sizes, zbits.shape[1] * 32
         G = None
         if g_levels is not None:
-            G = g_levels if (g_levels.dtype == torch.float32 and g_levels.is_contiguous()) else g_levels.float().contiguous()
+            G = as_f32c(g_levels)
         dx = dW = db = dw = dwm = dbias = None
         if need_x or need_W or need_b:
             if ctx.pre is None:
@@ -449,18 +448,12 @@ class _MatryoshkaTrainStep(torch.autograd.Function):
                                    "pre-activation was turned into its gradient in place by the first backward")
             dpre = ops.train_matryoshka_dpre(ctx.pre, G, g_groups, S, scale, sizes)
             ctx.pre = None
-            if need_W:
-                dW = ops.train_gemm_tn(dpre, xf)
-                dW = dW if ctx.valid is None else dW[ctx.valid]
-            if need_b:
-                db = ops.train_col_sum(dpre)
-                db = db if ctx.valid is None else db[ctx.valid]
-            if need_x:
-                Wp, _ = model._encoder_params()
-                dx = ops.encode_dense(dpre, ops.transpose_rows(Wp), None)
-                if dx.dtype != ctx.x_dtype:
-                    dx = dx.to(ctx.x_dtype)
-            del dpre
+            Wp = model._encoder_params()[0] if need_x else None
+            dx, dW, db = dense_encoder_backward(dpre, xf, Wp, need_x, need_W, need_b, ctx.x_dtype)
+            del dpre                                       # 1 GiB at the full shape: gone before the decoder-logit gradients
+            if ctx.valid is not None:                      # padded hidden order -> the model's units
+                dW = dW[ctx.valid] if need_W else None
+                db = db[ctx.valid] if need_b else None
         if need_w or need_wm:
             dsum = None
             if G is not None and ctx.path == "lists":

@@ -5,7 +5,7 @@ import torch
 import torch.nn as nn
 
 from .. import torch_ops as ops          # torch.ops.qsae.* (dispatcher ops over the C ABI)
-from .base import HipEncoder, PackedCache, require_device_input
+from .base import HipEncoder, PackedCache, as_f32c, dense_encoder_backward, require_device_input
 
 _GPU_ONLY = ("RigL mask maintenance (sae/ternary.py:27-39,54-90) runs on the GPU only: the decoder's parameters are on the "
              "host and there is no CPU fallback")
@@ -210,8 +210,7 @@ class _TernaryTrainStep(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, x, W_enc, b_enc, w):
         dec = model.decoder
-        xf = x.detach()
-        xf = xf if (xf.dtype == torch.float32 and xf.is_contiguous()) else xf.float().contiguous()
+        xf = as_f32c(x.detach())
         h = model.encoder(xf)
         recon = dec(h)
         dec.activation_mean = ops.train_col_sum(h).div_(h.shape[0])
@@ -228,21 +227,15 @@ class _TernaryTrainStep(torch.autograd.Function):
         need_x, need_W, need_b, need_w = ctx.needs_input_grad[1:5]
         G = gh = None
         if g_recon is not None:
-            G = g_recon if (g_recon.dtype == torch.float32 and g_recon.is_contiguous()) else g_recon.float().contiguous()
+            G = as_f32c(g_recon)
             dec.output_grad_mean = ops.train_col_sum(G).div_(G.shape[0])
         if g_h is not None:
-            gh = g_h if (g_h.dtype == torch.float32 and g_h.is_contiguous()) else g_h.float().contiguous()
+            gh = as_f32c(g_h)
         dx = dW = db = dw = None
         if need_w:
             dw = ops.train_ternary_dweight(G, h, mask) if G is not None else torch.zeros_like(dec.weight)
         if need_x or need_W or need_b:
             dpre = ops.train_ternary_dpre(h, G, gh, t_rows)
-            if need_W:
-                dW = ops.train_gemm_tn(dpre, xf)
-            if need_b:
-                db = ops.train_col_sum(dpre)
-            if need_x:
-                dx = ops.encode_dense(dpre, ops.transpose_rows(model.encoder.linear.weight.detach()), None)
-                if dx.dtype != ctx.x_dtype:
-                    dx = dx.to(ctx.x_dtype)
+            dx, dW, db = dense_encoder_backward(dpre, xf, model.encoder.linear.weight.detach(), need_x, need_W, need_b,
+                                                ctx.x_dtype)
         return (None, dx, dW, db, dw)

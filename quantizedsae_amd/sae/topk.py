@@ -1,0 +1,120 @@
+"""What BinarySAE and BaselineSparseAutoencoder share: both are "encoder -> top-k -> sparse decode", served by the same
+three selection paths, the same forward-in-one-call / two-call entry points and the same sparse backward.  Each model keeps
+what really differs: its rule for resolving ``latent_path``, its shape limits and messages, and its decoder."""
+from __future__ import annotations
+
+import torch
+
+from .. import torch_ops as ops          # torch.ops.qsae.* (dispatcher ops over the C ABI)
+from .base import PackedCache, as_f32c
+
+# forward-in-one-call entry points by the kind of decoder description (see ops._decode_prefilter_args)
+_FORWARD_PREFILTER = {"packed": ops.binary_forward_prefilter, "table": ops.table_forward_prefilter}
+_FORWARD_PREFILTER_SUBMIT = {"packed": ops.binary_forward_prefilter_submit, "table": ops.table_forward_prefilter_submit}
+
+
+class TopKCore:
+    """Mixin for a module with ``self.encoder`` (a HipEncoder without activation) and a ``_qsae_handle``: the encoder-side
+    state and the top-k selection.  No parameters or buffers of its own.
+
+    A decoder description is ``("packed", packed uint8 [H, row_bytes], n_bits, step)`` or ``("table", fp32 [H, D], scale)``."""
+
+    def _init_topk(self) -> None:
+        self._pref_cache = PackedCache()
+        #: rows of the previous prefilter batch that went through the exact fallback kernels (sizes the next call's
+        #: speculative fallback; per model, not per process)
+        self.last_flagged_rows = 0
+
+    def _prefilter_weights(self):
+        lin = self.encoder.linear
+        def build():
+            Wq, meta = ops.prefilter_pack_w(lin.weight.detach(), lin.bias.detach())
+            return {"Wq": Wq, "meta": meta}
+        return self._pref_cache.get((lin.weight, lin.bias), build)
+
+    def _prefilter_operands(self, x):
+        """-> (x as fp32, W, b, Wq, meta): the encoder arguments of every prefilter entry point.  Taken before the
+        decoder description is put together, so the fp16 copy of new weights is built before the decoder's copies."""
+        lin = self.encoder.linear
+        pw = self._prefilter_weights()
+        return as_f32c(x), lin.weight.detach(), lin.bias.detach(), pw["Wq"], pw["meta"]
+
+    def _spec_rows(self) -> int:
+        """Flagged rows the device recomputes speculatively: only after a batch that had any."""
+        return 32 if self.last_flagged_rows > 0 else 0
+
+    def _clear_encoder_copies(self) -> None:
+        """The encoder half of invalidate_packed(): the fp16 and K-interleaved copies."""
+        self._pref_cache.clear()
+        if hasattr(self.encoder, "_kperm_cache"):
+            self.encoder._kperm_cache.clear()
+
+    def _select(self, x, k: int, path: str, want_dense: bool):
+        """-> (idx, val, dense latent or None) on the resolved path; bit-identical on all three."""
+        lin = self.encoder.linear
+        if path == "prefilter":
+            info = {}
+            idx, val, latent = ops.encode_topk_prefilter(*self._prefilter_operands(x), k, want_dense=want_dense,
+                                                         spec_rows=self._spec_rows(), info=info)
+            self.last_flagged_rows = info["flagged_rows"]
+            return idx, val, latent
+        if path == "fused" or not want_dense:
+            xp, Wp, kperm = self.encoder.operands(x)
+            if want_dense:
+                return ops.encode_topk_latent(xp, Wp, lin.bias, k, kperm=kperm)
+            idx, val = ops.encode_topk(xp, Wp, lin.bias, k, kperm=kperm)
+            return idx, val, None
+        latent = self.encoder(x)                                     # inplace
+        idx, val = ops.topk_rows(latent, k, zero_rest=True)          # latent * mask, in place
+        return idx, val, latent
+
+    def _forward_prefilter(self, enc, k: int, decoder, dec_bias, want_dense: bool):
+        """One call: candidate sweep, exact refinement, and every row's reconstruction as soon as the refinement kernel has
+        ranked it.  ``enc`` = _prefilter_operands(x).  -> (idx, val, dense latent or None, reconstruction)"""
+        info = {}
+        outs = _FORWARD_PREFILTER[decoder[0]](*enc, k, *decoder[1:], dec_bias, want_dense=want_dense,
+                                              spec_rows=self._spec_rows(), info=info)
+        self.last_flagged_rows = info["flagged_rows"]
+        return outs
+
+    def _submit_prefilter(self, enc, k: int, decoder, dec_bias, want_dense: bool, slot: int):
+        """The two-call form of _forward_prefilter: -> ops.PendingForward (nothing in here waits for the GPU)."""
+        return _FORWARD_PREFILTER_SUBMIT[decoder[0]](*enc, k, *decoder[1:], dec_bias, want_dense=want_dense, slot=slot,
+                                                     owner=self._qsae_handle)
+
+
+class SubmittedForward:
+    """What ``forward_submit`` returns: ``pending`` (a batch in flight) or ``outs`` (computed eagerly) as
+    (idx, val, latent, reconstruction); ``to_result`` is the model's function from those four to its return tuple."""
+
+    def __init__(self, model, pending, outs, to_result):
+        self._model, self._pending, self._outs, self._to_result = model, pending, outs, to_result
+
+    def result(self):
+        with torch.no_grad():
+            if self._pending is not None:
+                self._outs = self._pending.finish()
+                self._model.last_flagged_rows = self._pending.flagged_rows
+                self._pending = None
+            return self._to_result(*self._outs)
+
+
+def sparse_backward(idx, table, step: float, g_recon, g_latent, W_enc, dec_bias, needs, x_dtype, unit_grad):
+    """The gradient of encoder -> top-k -> ``step * table`` rows + bias, from the k selected entries of each row:
+    gv = g_latent[r, h] + step <g_recon[r], table[h]> and dx per row, then ``unit_grad(offsets, entries, gv) ->
+    (dW_enc, db_enc, d_decoder)`` per unit over the rows that selected it (the one step that differs between the models),
+    and the decoder bias' column sum.  ``needs`` = (need_x, need_W, need_b, need_decoder, need_dec_bias).
+    -> (dx, dW_enc, db_enc, d_decoder, db_dec), None where not needed."""
+    need_x, need_W, need_b, need_dec, need_bd = needs
+    want_units = need_W or need_b or need_dec
+    dx = dW = db = ddec = dbd = None
+    if need_x or want_units:
+        gv, dx = ops.train_row_grad(idx, table, step, g_recon, g_latent, W_enc.detach(), want_dx=need_x)
+        if want_units:
+            offsets, entries = ops.train_csr(idx, table.shape[0])
+            dW, db, ddec = unit_grad(offsets, entries, gv)
+    if need_bd:
+        dbd = ops.train_col_sum(g_recon) if g_recon is not None else torch.zeros_like(dec_bias)
+    if dx is not None and dx.dtype != x_dtype:
+        dx = dx.to(x_dtype)
+    return (dx if need_x else None, dW if need_W else None, db if need_b else None, ddec if need_dec else None, dbd)
