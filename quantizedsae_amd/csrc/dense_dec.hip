@@ -35,44 +35,6 @@ pack_ternary_kernel(const float* __restrict__ w, int D, int H, int words, uint32
     codes[gid] = word;
 }
 
-template <int BM, int BN>
-struct EpiStore {
-    static constexpr int MT = BM / 64, NT = BN / 64, WTM = BM / 2, WTN = BN / 2;
-    static constexpr int kCheckpoints = 0;
-    static constexpr int kLdsFloats = 0;
-    static constexpr int kStoresPerFinish = 0;   // conservative: the staged-load wait then also covers them
-    template <class A> __device__ __forceinline__ void begin(const A&, const TileCtx&) {}
-    template <class A> __device__ __forceinline__ void end(const A&, const TileCtx&) {}
-    struct Args {
-        float* out;
-        int64_t ld;
-    };
-    __device__ __forceinline__ void init(const Args&, f32x16 (&acc)[MT][NT], const TileCtx&) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.0f;
-    }
-    __device__ __forceinline__ void checkpoint(const Args&, f32x16 (&)[MT][NT], const TileCtx&, int) {}
-    __device__ __forceinline__ void finish(const Args& a, f32x16 (&acc)[MT][NT], const TileCtx& c) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = c.m0 + c.wm * WTM + mt * 32 + mfma_row(r, c.lane_half);
-                if (row >= c.M) continue;
-                float* orow = a.out + static_cast<int64_t>(row) * a.ld;
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const int col = c.n0 + c.wn * WTN + nt * 32 + c.lane_col;
-                    if (col < c.N) orow[col] = acc[mt][nt][r];
-                }
-            }
-    }
-};
-
 // ---- matryoshka -----------------------------------------------------------------------------
 struct LevelTable {
     int n;
@@ -122,40 +84,30 @@ pack_matryoshka_scale_kernel(const float* __restrict__ w, const float* __restric
 }
 
 template <int BM, int BN>
-struct EpiLevels {
-    static constexpr int MT = BM / 64, NT = BN / 64, WTM = BM / 2, WTN = BN / 2;
+struct EpiLevels : EpiTile<BM, BN> {
+    using T = EpiTile<BM, BN>;
+    static constexpr int MT = T::MT, NT = T::NT;
     static constexpr int kCheckpoints = 1;
-    static constexpr int kLdsFloats = 0;
-    static constexpr int kStoresPerFinish = 0;   // conservative: the staged-load wait then also covers them
-    template <class A> __device__ __forceinline__ void begin(const A&, const TileCtx&) {}
-    template <class A> __device__ __forceinline__ void end(const A&, const TileCtx&) {}
     struct Args {
         LevelTable lv;
         const float* bias;     // nullptr when allow_bias == 0
         float* levels;         // [n][B][D]
         int64_t level_stride;  // B * D
     };
-    __device__ __forceinline__ void init(const Args&, f32x16 (&acc)[MT][NT], const TileCtx&) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.0f;
-    }
+    __device__ __forceinline__ void init(const Args&, f32x16 (&acc)[MT][NT], const TileCtx&) { T::fill(acc, 0.0f); }
     __device__ __forceinline__ void write_level(const Args& a, f32x16 (&acc)[MT][NT], const TileCtx& c,
                                                 int level) const {
         float* base = a.levels + static_cast<int64_t>(level) * a.level_stride;
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-            const int col = c.n0 + c.wn * WTN + nt * 32 + c.lane_col;
+            const int col = T::col(c, nt);
             if (col >= c.N) continue;
             const float b = a.bias ? a.bias[col] : 0.0f;
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int row = c.m0 + c.wm * WTM + mt * 32 + mfma_row(r, c.lane_half);
+                    const int row = T::row(c, mt, r);
                     if (row < c.M) base[static_cast<int64_t>(row) * c.N + col] = acc[mt][nt][r] + b;
                 }
         }

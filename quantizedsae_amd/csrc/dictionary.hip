@@ -63,13 +63,11 @@ inline long long tri_map_blocks(int tiles, int sweep) {
 //   column scan: 1 thread per column, 32 rows each: running column keys, kept in registers over the whole sweep
 //                (a workgroup owns one Cm panel) and flushed once in end().
 // Working from LDS keeps the epilogue's registers small beside the accumulators and the in-flight staging sets.
-struct EpiCosine {
+struct EpiCosine : EpiTile<kCosBM, kCosBN> {
+    using T = EpiTile<kCosBM, kCosBN>;
     static constexpr int BM = kCosBM, BN = kCosBN;
-    static constexpr int MT = BM / 64, NT = BN / 64, WTM = BM / 2, WTN = BN / 2;
-    static constexpr int kCheckpoints = 0;
-    static constexpr int kLdsFloats = 0;          // the launcher sizes the epilogue LDS at run time (histogram)
-    // VMEM operations per finish depend on the data (masked rows, dense store or not): keep the conservative 0
-    static constexpr int kStoresPerFinish = 0;
+    // kLdsFloats stays 0: the launcher sizes the epilogue LDS at run time (histogram).  kStoresPerFinish stays the conservative
+    // 0: the VMEM operations per finish depend on the data (masked rows, dense store or not).
     static constexpr int kStride = BN + 4;        // floats per scratch row (64 rows <= the staging buffer)
     static_assert(64 * kStride <= (BM + BN) * (kCosBK + 4), "half a tile must fit one staging buffer");
     struct Args {
@@ -100,7 +98,7 @@ struct EpiCosine {
         lds_red = lds_col + kCosColKeyWords;
         lds_hist = reinterpret_cast<uint32_t*>(lds_red + kCosRedWords);
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) invb[nt] = a.inv_b[c.n0 + c.wn * WTN + nt * 32 + c.lane_col];
+        for (int nt = 0; nt < NT; ++nt) invb[nt] = a.inv_b[T::col(c, nt)];
         colk = 0ull;
         if ((c.tid & 63) == 0)
             for (int w = 0; w < 8; ++w) lds_red[(c.tid >> 6) * 8 + w] = 0ull;
@@ -108,16 +106,7 @@ struct EpiCosine {
         for (int i = c.tid; i < a.bins; i += kGemmThreads) lds_hist[i] = 0u;
     }
 
-    __device__ __forceinline__ void init(const Args&, f32x16 (&acc)[MT][NT], const TileCtx&) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.0f;
-    }
-
-    __device__ __forceinline__ void checkpoint(const Args&, f32x16 (&)[MT][NT], const TileCtx&, int) {}
+    __device__ __forceinline__ void init(const Args&, f32x16 (&acc)[MT][NT], const TileCtx&) { T::fill(acc, 0.0f); }
 
     __device__ __forceinline__ void finish(const Args& a, f32x16 (&acc)[MT][NT], const TileCtx& c) {
         float* lds = c.lds_free;
@@ -471,9 +460,8 @@ extern "C" int qsae_cosine_compare(const float* A, int64_t lda, int Ha, const fl
     ea.bins = bins;
     ea.self = self ? 1 : 0;
 
-    // the asm-staged loader addresses an operand with 32-bit byte offsets; larger operands take the compiler-load form
-    const bool small = static_cast<unsigned long long>(Ha) * lda * 4 < (1ull << 32) &&
-                       static_cast<unsigned long long>(Hb) * ldb * 4 < (1ull << 32);
+    // the asm-staged loader only for operands that fit its 32-bit byte offsets; larger ones take the compiler-load form
+    const bool small = fits_u32_bytes(Ha, lda) && fits_u32_bytes(Hb, ldb);
     if (D % kCosBK == 0 && small) rc = run_cosine<LoaderF32<kCosBM, kCosBK, false, true>>(A, lda, Ha, B, ldb, Hb, D, self, ea, s);
     else rc = run_cosine<LoaderF32<kCosBM, kCosBK, true>>(A, lda, Ha, B, ldb, Hb, D, self, ea, s);
     if (rc != QSAE_OK) return rc;

@@ -272,16 +272,15 @@ static int bits_finish(const float* x, const float* W, const float* bias, int B,
 constexpr int kBandCap = 1024;        // band entries per row (mean ~240 at the cutoff of a zero-mean latent; more -> flagged)
 
 template <int BM, int BN, int WMW, int WNW>
-struct EpiBitsBand {
-    static constexpr int WTM = BM / WMW, WTN = BN / WNW, MT = WTM / 32, NT = WTN / 32;
+struct EpiBitsBand : EpiTile<BM, BN, WMW, WNW> {
+    using T = EpiTile<BM, BN, WMW, WNW>;
+    static constexpr int MT = T::MT, NT = T::NT;
     static constexpr int kThreads = 64 * WMW * WNW;
-    static constexpr int kCheckpoints = 0;
     // Band entries of one tile are collected in LDS and appended to the rows' lists with ONE global atomic per row and
     // tile (a global atomic with return per entry -- 22 M of them at 65536 x 32768, 1 % in the band -- doubled the
     // kernel's time: 3.9 -> 7.5 ms).  Scratch: hits per tile row [BM] | list base per tile row [BM] | total | entries.
     static constexpr int kTileCap = 2048;                     // entries per tile held in LDS (mean ~650 at 1 %); more go direct
     static constexpr int kLdsFloats = 2 * BM + 4 + 3 * kTileCap;
-    static constexpr int kStoresPerFinish = 0;
     struct Args {
         const float* inv;      // [B] 1 / (row scale * weight scale)
         const float* margin;   // [B] 2 eps_b
@@ -292,17 +291,7 @@ struct EpiBitsBand {
         int* cnt;              // [B], zeroed by the caller
         int cap;
     };
-    __device__ __forceinline__ void begin(const Args&, const TileCtx&) {}
-    __device__ __forceinline__ void end(const Args&, const TileCtx&) {}
-    __device__ __forceinline__ void init(const Args&, f32x16 (&acc)[MT][NT], const TileCtx&) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.0f;
-    }
-    __device__ __forceinline__ void checkpoint(const Args&, f32x16 (&)[MT][NT], const TileCtx&, int) {}
+    __device__ __forceinline__ void init(const Args&, f32x16 (&acc)[MT][NT], const TileCtx&) { T::fill(acc, 0.0f); }
     __device__ __forceinline__ void finish(const Args& a, f32x16 (&acc)[MT][NT], const TileCtx& c) {
         const float cut = __uint_as_float(QSAE_SIG_GT_BITS);
         int* lcount = reinterpret_cast<int*>(c.lds_epi);
@@ -316,7 +305,7 @@ struct EpiBitsBand {
         bool col_ok[NT];
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-            const int col = c.n0 + c.wn * WTN + nt * 32 + c.lane_col;
+            const int col = T::col(c, nt);
             col_ok[nt] = col < c.N;
             bcol[nt] = (a.bias && col_ok[nt]) ? a.bias[col] : 0.0f;
         }
@@ -325,7 +314,7 @@ struct EpiBitsBand {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 // lanes 0-31 carry activation row mfma_row(r, 0), lanes 32-63 row mfma_row(r, 1)
-                const int lrow = c.wm * WTM + mt * 32 + mfma_row(r, c.lane_half);
+                const int lrow = T::tile_row(c, mt, r);
                 const int row = c.m0 + lrow;
                 const bool row_ok = row < c.M;
                 const int rr = row_ok ? row : c.M - 1;
@@ -333,7 +322,7 @@ struct EpiBitsBand {
                 const float half = 0.5f * a.margin[rr] * 1.00001f;       // eps_b with slack for the roundings below
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) {
-                    const int col0 = c.n0 + c.wn * WTN + nt * 32;
+                    const int col0 = T::col0(c, nt);
                     const float v = fmaf(acc[mt][nt][r], iv, bcol[nt]);
                     const float d = v - cut;
                     const bool live = row_ok && col_ok[nt];

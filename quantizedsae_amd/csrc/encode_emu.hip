@@ -74,52 +74,35 @@ emu_x_prep_kernel(const float* __restrict__ x, int B, int D, const float* __rest
 }
 
 template <int ACT, int BM, int BN, int WMW, int WNW>
-struct EpiEmuDense {
-    static constexpr int WTM = BM / WMW, WTN = BN / WNW, MT = WTM / 32, NT = WTN / 32;
-    static constexpr int kCheckpoints = 0;
-    static constexpr int kLdsFloats = 0;
-    static constexpr int kStoresPerFinish = 0;
+struct EpiEmuDense : EpiTile<BM, BN, WMW, WNW> {
+    using T = EpiTile<BM, BN, WMW, WNW>;
+    static constexpr int MT = T::MT, NT = T::NT;
     struct Args {
         const float* inv;      // [B]
         const float* bias;     // [H] or nullptr
         float* out;            // [B][ld]
         int64_t ld;
     };
-    __device__ __forceinline__ void begin(const Args&, const TileCtx&) {}
-    __device__ __forceinline__ void end(const Args&, const TileCtx&) {}
-    __device__ __forceinline__ void init(const Args&, f32x16 (&acc)[MT][NT], const TileCtx&) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.0f;
-    }
-    __device__ __forceinline__ void checkpoint(const Args&, f32x16 (&)[MT][NT], const TileCtx&, int) {}
+    __device__ __forceinline__ void init(const Args&, f32x16 (&acc)[MT][NT], const TileCtx&) { T::fill(acc, 0.0f); }
     __device__ __forceinline__ void finish(const Args& a, f32x16 (&acc)[MT][NT], const TileCtx& c) {
         float bcol[NT];
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-            const int col = c.n0 + c.wn * WTN + nt * 32 + c.lane_col;
+            const int col = T::col(c, nt);
             bcol[nt] = (a.bias && col < c.N) ? a.bias[col] : 0.0f;
         }
+        T::for_each_row(c, [=, &acc](int mt, int r, int row) {
+            const float iv = a.inv[row];
+            float* orow = a.out + static_cast<int64_t>(row) * a.ld;
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = c.m0 + c.wm * WTM + mt * 32 + mfma_row(r, c.lane_half);
-                if (row >= c.M) continue;
-                const float iv = a.inv[row];
-                float* orow = a.out + static_cast<int64_t>(row) * a.ld;
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const int col = c.n0 + c.wn * WTN + nt * 32 + c.lane_col;
-                    float v = fmaf(acc[mt][nt][r], iv, bcol[nt]);
-                    if (ACT == QSAE_ACT_RELU) v = v > 0.0f ? v : (v != v ? v : 0.0f);      // (NaN stays NaN, like torch.relu)
-                    if (ACT == QSAE_ACT_SIGMOID) v = 1.0f / (1.0f + expf(-v));
-                    if (col < c.N) orow[col] = v;
-                }
+            for (int nt = 0; nt < NT; ++nt) {
+                const int col = T::col(c, nt);
+                float v = fmaf(acc[mt][nt][r], iv, bcol[nt]);
+                if (ACT == QSAE_ACT_RELU) v = v > 0.0f ? v : (v != v ? v : 0.0f);      // (NaN stays NaN, like torch.relu)
+                if (ACT == QSAE_ACT_SIGMOID) v = 1.0f / (1.0f + expf(-v));
+                if (col < c.N) orow[col] = v;
             }
+        });
     }
 };
 

@@ -407,24 +407,8 @@ static int run_fused(const float* x, const float* W, const float* bias, int B, i
                                    split, cnt_split};
             rc = launch_gemm_dma<EpiD, 256, 128>(W + static_cast<size_t>(P) * D, Hs, x, B, D, ed, s,
                                                  split > 1 ? (tiles + split - 1) / split : 0);
-        } else if (kperm) {
-            using LA = LoaderF32<BM, BK, false, true, true>;
-            using LB = LoaderF32<BN, BK, false, true, true>;
-            typename LA::Args la{W + static_cast<size_t>(P) * D, D, Hs};
-            typename LB::Args lb{x, D, B};
-            rc = launch_gemm<LA, LB, Epi, BM, BN, BK>(la, lb, ea, Hs, B, D, /*sweep=*/0, s);
-        } else if (D % BK == 0) {
-            using LA = LoaderF32<BM, BK, false, true>;
-            using LB = LoaderF32<BN, BK, false, true>;
-            typename LA::Args la{W + static_cast<size_t>(P) * D, D, Hs};
-            typename LB::Args lb{x, D, B};
-            rc = launch_gemm<LA, LB, Epi, BM, BN, BK>(la, lb, ea, Hs, B, D, /*sweep=*/0, s);
         } else {
-            using LA = LoaderF32<BM, BK, true>;
-            using LB = LoaderF32<BN, BK, true>;
-            typename LA::Args la{W + static_cast<size_t>(P) * D, D, Hs};
-            typename LB::Args lb{x, D, B};
-            rc = launch_gemm<LA, LB, Epi, BM, BN, BK>(la, lb, ea, Hs, B, D, /*sweep=*/0, s);
+            rc = launch_nt_rows<Epi, BM, BN, BK, true>(W + static_cast<size_t>(P) * D, D, Hs, x, D, B, D, ea, /*sweep=*/0, s, kperm);
         }
         if (prof.end) QSAE_HIP(hipEventRecord(prof.end, s));
         if (rc != QSAE_OK) return rc;

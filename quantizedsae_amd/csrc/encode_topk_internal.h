@@ -69,10 +69,10 @@ FusedLayout fused_layout(int B, int D, int H, int k);
 // APPROX (fp16 prefilter): the accumulator holds the scaled fp16 contraction; the value compared and
 // stored is fma(acc, inv[row], bias[h]) and the row threshold is tau[row] - margin[row].
 template <int BM, int BN, int WMW = 2, int WNW = 2, bool APPROX = false>
-struct EpiFilter {
-    static constexpr int WTM = BM / WMW, WTN = BN / WNW, MT = WTM / 32, NT = WTN / 32;
+struct EpiFilter : EpiTile<BM, BN, WMW, WNW> {
+    using T = EpiTile<BM, BN, WMW, WNW>;
+    static constexpr int MT = T::MT, NT = T::NT;
     static constexpr int kThreads = 64 * WMW * WNW;
-    static constexpr int kCheckpoints = 0;
     static constexpr int kLdsFloats = BN;      // per-row candidate counters
     static constexpr int kStoresPerFinish = (BM * BN * 4) / (kThreads * 16);   // zero-fill stores per wave
     struct Args {
@@ -104,7 +104,7 @@ struct EpiFilter {
         }
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-            const int col = c.n0 + c.wn * WTN + nt * 32 + c.lane_col;
+            const int col = T::col(c, nt);
             col_ok[nt] = col < c.N;
             tau[nt] = col_ok[nt] ? a.tau[col] : __builtin_huge_valf();
             inv[nt] = 1.0f;
@@ -120,14 +120,13 @@ struct EpiFilter {
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                int h = c.m0 + c.wm * WTM + mt * 32 + mfma_row(r, c.lane_half);
+                int h = T::row(c, mt, r);
                 h = h < c.M ? h : c.M - 1;
                 const float b = (!APPROX && a.bias) ? a.bias[h] : 0.0f;
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) acc[mt][nt][r] = b;
             }
     }
-    __device__ __forceinline__ void checkpoint(const Args&, f32x16 (&)[MT][NT], const TileCtx&, int) {}
     __device__ __forceinline__ void finish(const Args& a, f32x16 (&acc)[MT][NT], const TileCtx& c) {
         int* counters = reinterpret_cast<int*>(c.lds_epi);
         if (a.dense != nullptr) {
@@ -152,14 +151,14 @@ struct EpiFilter {
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    int h = c.m0 + c.wm * WTM + mt * 32 + mfma_row(r, c.lane_half);
+                    int h = T::row(c, mt, r);
                     h = h < c.M ? h : c.M - 1;
                     hb[mt][r] = a.bias ? a.bias[h] : 0.0f;
                 }
         }
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-            const int lcol = c.wn * WTN + nt * 32 + c.lane_col;
+            const int lcol = T::tile_col(c, nt);
             const float t = tau[nt];
             const int cap_part = a.parts > 1 ? a.cap / a.parts : a.cap;
             uint2* list = a.cand + static_cast<int64_t>(c.n0 + lcol) * a.cap + (a.parts > 1 ? c.part * cap_part : 0);
@@ -169,7 +168,7 @@ struct EpiFilter {
                 for (int r = 0; r < 16; ++r) {
                     const float v = APPROX ? fmaf(acc[mt][nt][r], inv[nt], hb[mt][r]) : acc[mt][nt][r];
                     if (!(v < t)) {      // v >= tau, or NaN (which ranks above everything)
-                        const int h = c.m0 + c.wm * WTM + mt * 32 + mfma_row(r, c.lane_half);
+                        const int h = T::row(c, mt, r);
                         if (h < c.M && col_ok[nt]) {
                             const int pos = atomicAdd(&counters[lcol], 1);
                             if (pos < cap_part)

@@ -305,14 +305,16 @@ struct SweepMap {
 };
 
 // -------------------------------------------------------------------------------------
-// The kernel.  Epi provides:
-//   struct Args;  static constexpr int kCheckpoints;
-//   __device__ void begin(args, ctx, smem_epi)   -- once per workgroup, before the sweep
-//   __device__ void init(args, acc, ctx)         -- accumulator seed for the tile at ctx.m0
-//   __device__ void checkpoint(args, acc, ctx, k_done)   (only if kCheckpoints)
-//   __device__ void finish(args, acc, ctx)       -- consume the finished tile
-//   __device__ void end(args, ctx)               -- once per workgroup, after the sweep
-//   static constexpr int kLdsFloats               -- extra LDS the epilogue wants
+// The kernel.  Epi provides (EpiTile below holds the defaults; an epilogue shadows what it needs otherwise):
+//   struct Args;
+//   static constexpr int kCheckpoints             -- 1: checkpoint() runs after every K slice          (default 0)
+//   static constexpr int kLdsFloats               -- extra LDS the epilogue wants                       (default 0)
+//   static constexpr int kStoresPerFinish         -- fire-and-forget VMEM stores per wave of finish()   (default 0)
+//   __device__ void begin(args, ctx)              -- once per workgroup, before the sweep               (default: nothing)
+//   __device__ void init(args, acc, ctx)          -- accumulator seed for the tile at ctx.m0
+//   __device__ void checkpoint(args, acc, ctx, k_done)   (only if kCheckpoints)                         (default: nothing)
+//   __device__ void finish(args, acc, ctx)        -- consume the finished tile
+//   __device__ void end(args, ctx)                -- once per workgroup, after the sweep                (default: nothing)
 // ctx carries tile origin, wave/lane coordinates and problem sizes.
 struct TileCtx {
     int m0, n0;        // tile origin (row of R, row of Cm)
@@ -332,6 +334,89 @@ struct TileCtx {
 __device__ __forceinline__ int mfma_row(int reg, int lane_half) {
     return (reg & 3) + 8 * (reg >> 2) + 4 * lane_half;
 }
+
+// What every epilogue knows about a wave's accumulator block acc[MT][NT] (WMW x WNW waves per workgroup, MT x NT MFMA tiles
+// of 32 x 32 per wave): which output element a (tile, register, lane) holds, and the defaults of the kernel's hooks.  This is
+// the one place that spells the layout out.
+template <int BM, int BN, int WMW = 2, int WNW = 2>
+struct EpiTile {
+    static constexpr int WTM = BM / WMW, WTN = BN / WNW;      // per-wave tile
+    static constexpr int MT = WTM / 32, NT = WTN / 32;        // MFMA tiles per wave
+    static constexpr int kCheckpoints = 0;
+    static constexpr int kLdsFloats = 0;
+    static constexpr int kStoresPerFinish = 0;   // conservative: the staged-load wait then also covers them
+    template <class A> __device__ __forceinline__ void begin(const A&, const TileCtx&) {}
+    template <class A> __device__ __forceinline__ void end(const A&, const TileCtx&) {}
+    template <class A> __device__ __forceinline__ void checkpoint(const A&, f32x16 (&)[MT][NT], const TileCtx&, int) {}
+
+    // output row (row of R) behind register r of MFMA tile row mt, output column (row of Cm) behind this lane in tile column nt
+    __device__ __forceinline__ static int row(const TileCtx& c, int mt, int r) {
+        return c.m0 + tile_row(c, mt, r);
+    }
+    __device__ __forceinline__ static int col(const TileCtx& c, int nt) { return c.n0 + tile_col(c, nt); }
+    // ... and the same two inside the workgroup's BM x BN tile
+    __device__ __forceinline__ static int tile_row(const TileCtx& c, int mt, int r) { return c.wm * WTM + mt * 32 + mfma_row(r, c.lane_half); }
+    __device__ __forceinline__ static int tile_col(const TileCtx& c, int nt) { return c.wn * WTN + nt * 32 + c.lane_col; }
+    // first of the 32 output columns that the lanes of a half-wave hold in tile column nt (one word of a ballot)
+    __device__ __forceinline__ static int col0(const TileCtx& c, int nt) { return c.n0 + c.wn * WTN + nt * 32; }
+
+    __device__ __forceinline__ static void fill(f32x16 (&acc)[MT][NT], float v) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[mt][nt][r] = v;
+    }
+    // seed every accumulator of output column j with bias[j]
+    __device__ __forceinline__ static void seed_bias(const float* bias, f32x16 (&acc)[MT][NT], const TileCtx& c) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const int j = col(c, nt);
+            const float b = (bias != nullptr && j < c.N) ? bias[j] : 0.0f;
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[mt][nt][r] = b;
+        }
+    }
+    // f(mt, r, row) for every accumulator row inside the problem (row < c.M).  Not for epilogues that ballot: lanes whose
+    // row lies outside never reach f.  Callers pass a lambda that captures the accumulators by reference and everything else
+    // by value ([=, &acc]): the args are then read once in front of the walk, as in a written-out loop (same machine code).
+    template <class F>
+    __device__ __forceinline__ static void for_each_row(const TileCtx& c, F&& f) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int rw = row(c, mt, r);
+                if (rw >= c.M) continue;
+                f(mt, r, rw);
+            }
+    }
+};
+
+// C[row][col] = acc
+template <int BM, int BN>
+struct EpiStore : EpiTile<BM, BN> {
+    using T = EpiTile<BM, BN>;
+    static constexpr int MT = T::MT, NT = T::NT;
+    struct Args {
+        float* out;
+        int64_t ld;
+    };
+    __device__ __forceinline__ void init(const Args&, f32x16 (&acc)[MT][NT], const TileCtx&) { T::fill(acc, 0.0f); }
+    __device__ __forceinline__ void finish(const Args& a, f32x16 (&acc)[MT][NT], const TileCtx& c) {
+        T::for_each_row(c, [=, &acc](int mt, int r, int row) {
+            float* orow = a.out + static_cast<int64_t>(row) * a.ld;
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                const int col = T::col(c, nt);
+                if (col < c.N) orow[col] = acc[mt][nt][r];
+            }
+        });
+    }
+};
 
 // 128x128 tiles are sized for two workgroups per CU (LDS 2 x 74 KB, <= 256 registers per lane):
 // the second launch-bounds argument (waves per SIMD) makes the register allocator honour that.
@@ -519,25 +604,73 @@ constexpr size_t gemm_lds_bytes(int epi_floats) {
     return (2ull * (BM + BN) * (BK + 4) + static_cast<size_t>(epi_floats)) * sizeof(float);
 }
 
-// Host-side launcher.  sweep = number of consecutive R tiles per workgroup (<= 0: all of them).
-template <class LA, class LB, class Epi, int BM, int BN, int BK, int ABLATE = 0>
-inline int launch_gemm(const typename LA::Args& la, const typename LB::Args& lb,
-                       const typename Epi::Args& ea, int M, int N, int K, int sweep, hipStream_t stream) {
-    auto kern = gemm_nt_f32_kernel<LA, LB, Epi, BM, BN, BK, ABLATE>;
-    constexpr size_t lds = gemm_lds_bytes<BM, BN, BK>(Epi::kLdsFloats);
-    QSAE_SET_MAX_LDS_ONCE(kern, lds);     // per instantiation and device
+// The workgroup -> work map of an M x N problem in BM x BN tiles; sweep = number of consecutive R tiles per workgroup
+// (<= 0: all of them).
+inline SweepMap make_sweep_map(int M, int N, int BM, int BN, int sweep, int stagger) {
     SweepMap map;
     map.tiles_m = (M + BM - 1) / BM;
     map.tiles_n = (N + BN - 1) / BN;
     map.sweep = (sweep <= 0 || sweep > map.tiles_m) ? map.tiles_m : sweep;
     map.msplit = (map.tiles_m + map.sweep - 1) / map.sweep;
-    map.stagger = g_stagger;
+    map.stagger = stagger;
+    return map;
+}
+
+// Host-side launcher.  `map` must be make_sweep_map(M, N, BM, BN, ...): a loader that locates its own workgroup (train_gemm.hip)
+// takes the same object in its args.
+template <class LA, class LB, class Epi, int BM, int BN, int BK, int ABLATE = 0>
+inline int launch_gemm(const typename LA::Args& la, const typename LB::Args& lb, const typename Epi::Args& ea, int M, int N,
+                       int K, const SweepMap& map, hipStream_t stream) {
+    auto kern = gemm_nt_f32_kernel<LA, LB, Epi, BM, BN, BK, ABLATE>;
+    constexpr size_t lds = gemm_lds_bytes<BM, BN, BK>(Epi::kLdsFloats);
+    QSAE_SET_MAX_LDS_ONCE(kern, lds);     // per instantiation and device
     const long long nblocks = static_cast<long long>(map.tiles_n) * map.msplit;
     if (nblocks <= 0 || nblocks > 0x7FFFFFFFll) return fail(QSAE_ERR_UNSUPPORTED, "%s: tile count out of range", __func__);
     hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(nblocks)), dim3(kGemmThreads), lds, stream, la, lb,
                        ea, M, N, K, map);
     QSAE_LAUNCH_CHECK();
     return QSAE_OK;
+}
+template <class LA, class LB, class Epi, int BM, int BN, int BK, int ABLATE = 0>
+inline int launch_gemm(const typename LA::Args& la, const typename LB::Args& lb,
+                       const typename Epi::Args& ea, int M, int N, int K, int sweep, hipStream_t stream) {
+    return launch_gemm<LA, LB, Epi, BM, BN, BK, ABLATE>(la, lb, ea, M, N, K, make_sweep_map(M, N, BM, BN, sweep, g_stagger),
+                                                        stream);
+}
+
+// LoaderF32's asm-staged forms address an operand with ONE 32-bit byte offset per lane: rows * ld * 4 must stay below 2^32.
+constexpr bool fits_u32_bytes(int64_t rows, int64_t ld) { return rows <= 0 || ld <= ((int64_t{1} << 30) - 1) / rows; }
+static_assert(fits_u32_bytes((1 << 30) - 1, 1) && fits_u32_bytes(1, (1 << 30) - 1), "2^30 - 1 elements fit");
+static_assert(!fits_u32_bytes(1 << 30, 1) && !fits_u32_bytes(1, 1 << 30) && !fits_u32_bytes(1 << 15, 1 << 15), "2^30 elements do not");
+static_assert(fits_u32_bytes(1, 4096) && !fits_u32_bytes((1 << 18) + 128, 4096), "a single row fits; 4 GiB + 2 MiB does not");
+
+// The contraction of two fp32 row operands A [M][lda] and Bm [N][ldb] over K: the one place that decides which staging loader
+// an operand may take.
+//   1. kperm (operands stored K-interleaved, K % BK == 0 checked by the caller; KPERM_FORM instantiations only): the asm loaders
+//      with direct 16-byte LDS writes -- 32-bit byte offsets as well, larger operands are refused;
+//   2. K % BK == 0: the asm-staged loaders -- for the audited spill-free 128 x 128 tile, and only while both operands fit
+//      32-bit byte offsets; the 64-row tile takes the plain compiler loads (64-bit addresses);
+//   3. otherwise the K-tail loaders (compiler loads, 64-bit addresses).
+template <class Epi, int BM, int BN, int BK, bool KPERM_FORM = false>
+inline int launch_nt_rows(const float* A, int64_t lda, int M, const float* Bm, int64_t ldb, int N, int K,
+                          const typename Epi::Args& ea, int sweep, hipStream_t stream, bool kperm = false) {
+    auto run = [&](auto ktail, auto as, auto kp) {
+        using LA = LoaderF32<BM, BK, decltype(ktail)::value, decltype(as)::value, decltype(kp)::value>;
+        using LB = LoaderF32<BN, BK, decltype(ktail)::value, decltype(as)::value, decltype(kp)::value>;
+        return launch_gemm<LA, LB, Epi, BM, BN, BK>(typename LA::Args{A, lda, M}, typename LB::Args{Bm, ldb, N}, ea, M, N, K,
+                                                    sweep, stream);
+    };
+    constexpr bool kAudited = (BM == 128 && BN == 128);
+    const bool fits = fits_u32_bytes(M, lda) && fits_u32_bytes(N, ldb);
+    if (kperm) {
+        // KPERM_FORM: only the entry points that take K-interleaved operands instantiate these kernels
+        QSAE_CHECK_SUPPORTED(KPERM_FORM, "this contraction takes no K-interleaved operands");
+        // interleaved data has no loader with 64-bit addresses: refused, where the 32-bit offsets would wrap
+        QSAE_CHECK_SUPPORTED(fits, "K-interleaved operands must stay below 4 GiB each");
+        if constexpr (KPERM_FORM) return run(std::false_type{}, std::true_type{}, std::true_type{});
+    }
+    if (K % BK == 0 && (fits || !kAudited)) return run(std::false_type{}, std::bool_constant<kAudited>{}, std::false_type{});
+    return run(std::true_type{}, std::false_type{}, std::false_type{});
 }
 
 }  // namespace qsae

@@ -189,12 +189,7 @@ inline int launch_gemm_dma(const float* Rp, int M, const float* Cp, int N, int K
     static_assert(lds <= 160 * 1024, "tile does not fit the 160 KiB LDS");
     QSAE_SET_MAX_LDS_ONCE(kern, lds);     // per instantiation and device
     if (K % kDmaBK != 0) return fail(QSAE_ERR_UNSUPPORTED, "%s: K must be a multiple of 32 words", __func__);
-    SweepMap map;
-    map.tiles_m = (M + BM - 1) / BM;
-    map.tiles_n = (N + BN - 1) / BN;
-    map.sweep = (sweep <= 0 || sweep > map.tiles_m) ? map.tiles_m : sweep;
-    map.msplit = (map.tiles_m + map.sweep - 1) / map.sweep;
-    map.stagger = 0;
+    const SweepMap map = make_sweep_map(M, N, BM, BN, sweep, /*stagger=*/0);
     const long long nblocks = static_cast<long long>(map.tiles_n) * map.msplit;
     hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(nblocks)), dim3(kDmaThreads), lds, stream, Rp, M, Cp, N,
                        K, ea, map);

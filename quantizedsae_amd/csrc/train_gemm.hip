@@ -33,25 +33,19 @@ __device__ __forceinline__ void lds_put_chunk_alt(float* row, int c, f32x4 v, bo
     *reinterpret_cast<f32x2*>(p + (odd_first ? 0 : 4)) = odd_first ? even : odd;
 }
 
-// fp32 operand with element (m, k) at p[k ld + m]: nrows % 4 == 0, ld % 4 == 0, p 16-byte aligned.  Row chunks at or beyond
-// nrows are clamped to the last chunk (their outputs are never stored), k >= K reads as zero.
-template <int ROWS, int BK>
-struct LoaderTN {
+// What the TN loaders share: a thread owns the 4 x 4 block of row chunk mc (4 output rows) and k chunk c (4 consecutive k) in
+// each of PASSES passes over the tile's rows.
+template <int ROWS, int BK, class ArgsT>
+struct LoaderTNBase {
     using G = TileGeom<BK>;
+    using Args = ArgsT;                                        // has nrows (a multiple of 4)
     static constexpr int KC = BK / 4;                          // k chunks per slice
     static constexpr int MC = kGemmThreads / KC;               // row chunks (of 4 rows) per pass
     static constexpr int PASSES = ROWS / (4 * MC);
     static_assert(ROWS % (4 * MC) == 0, "tile rows must be a multiple of the rows per pass");
-    struct Args {
-        const float* p;
-        int64_t ld;
-        int nrows;
-    };
     static constexpr bool kAsmLoads = false;
     static constexpr int kLoadsPerStep = 4 * PASSES;
     template <int P> __device__ __forceinline__ void pin() {}
-    const float* colp[PASSES];
-    f32x4 r[2][PASSES][4];
     Args args;
     int K, c, mc;
 
@@ -61,13 +55,32 @@ struct LoaderTN {
         c = tid % KC;
         mc = tid / KC;
     }
+    // first row of this thread's chunk in pass i of the tile at row0; chunks at or beyond nrows are clamped to the last one
+    __device__ __forceinline__ int first_row(int row0, int i) const {
+        const int m = row0 + 4 * (i * MC + mc);
+        return (m + 3) < args.nrows ? m : args.nrows - 4;
+    }
+};
+
+struct TNArgs {
+    const float* p;
+    int64_t ld;
+    int nrows;
+};
+
+// fp32 operand with element (m, k) at p[k ld + m]: nrows % 4 == 0, ld % 4 == 0, p 16-byte aligned.  Row chunks at or beyond
+// nrows are clamped to the last chunk (their outputs are never stored), k >= K reads as zero.
+template <int ROWS, int BK>
+struct LoaderTN : LoaderTNBase<ROWS, BK, TNArgs> {
+    using Base = LoaderTNBase<ROWS, BK, TNArgs>;
+    using G = typename Base::G;
+    using Base::PASSES, Base::MC, Base::args, Base::K, Base::c, Base::mc;
+    const float* colp[PASSES];
+    f32x4 r[2][PASSES][4];
+
     __device__ __forceinline__ void set_rows(int row0) {
 #pragma unroll
-        for (int i = 0; i < PASSES; ++i) {
-            int m = row0 + 4 * (i * MC + mc);
-            m = (m + 3) < args.nrows ? m : args.nrows - 4;
-            colp[i] = args.p + m;
-        }
+        for (int i = 0; i < PASSES; ++i) colp[i] = args.p + this->first_row(row0, i);
     }
     template <int P>
     __device__ __forceinline__ void load(int kt) {
@@ -108,7 +121,7 @@ struct LoaderTNByLevel : LoaderTN<ROWS, BK> {
         int64_t level_stride;      // K * ld
         int n;
         int end_tile[kTnMaxLevels];   // exclusive end of each level, in M tiles
-        SweepMap map;              // the map the launch uses (sweep == 1)
+        SweepMap map;              // the map the launch uses (sweep == 1): the caller passes this object to launch_gemm
     };
     __device__ __forceinline__ void init(const Args& a, int K_, int tid) {
         int tn, m_first, m_last;
@@ -121,40 +134,27 @@ struct LoaderTNByLevel : LoaderTN<ROWS, BK> {
 
 // z bits as a TN operand: element (m, k) = bit (bit0 + m) of row k of zbits [K][words_ld] as 0.0 / 1.0; bit0 % 32 == 0,
 // nrows % 4 == 0.
+struct TNBitsArgs {
+    const uint32_t* bits;
+    int64_t words_ld;
+    int nrows;
+    int bit0;
+};
+
 template <int ROWS, int BK>
-struct LoaderTNBits {
-    using G = TileGeom<BK>;
-    static constexpr int KC = BK / 4;
-    static constexpr int MC = kGemmThreads / KC;
-    static constexpr int PASSES = ROWS / (4 * MC);
-    static_assert(ROWS % (4 * MC) == 0, "tile rows must be a multiple of the rows per pass");
-    struct Args {
-        const uint32_t* bits;
-        int64_t words_ld;
-        int nrows;
-        int bit0;
-    };
-    static constexpr bool kAsmLoads = false;
-    static constexpr int kLoadsPerStep = 4 * PASSES;
-    template <int P> __device__ __forceinline__ void pin() {}
+struct LoaderTNBits : LoaderTNBase<ROWS, BK, TNBitsArgs> {
+    using Base = LoaderTNBase<ROWS, BK, TNBitsArgs>;
+    using G = typename Base::G;
+    using Base::PASSES, Base::MC, Base::args, Base::K, Base::c, Base::mc;
     const uint32_t* colp[PASSES];
     int sh[PASSES];
     int shs[2][PASSES];             // the shift of the rows a staging set was loaded for: set_rows() moves on before store()
     uint32_t r[2][PASSES][4];
-    Args args;
-    int K, c, mc;
 
-    __device__ __forceinline__ void init(const Args& a, int K_, int tid) {
-        args = a;
-        K = K_;
-        c = tid % KC;
-        mc = tid / KC;
-    }
     __device__ __forceinline__ void set_rows(int row0) {
 #pragma unroll
         for (int i = 0; i < PASSES; ++i) {
-            int m = row0 + 4 * (i * MC + mc);
-            m = (m + 3) < args.nrows ? m : args.nrows - 4;
+            const int m = this->first_row(row0, i);
             colp[i] = args.bits + ((args.bit0 + m) >> 5);
             sh[i] = (args.bit0 + m) & 31;
         }
@@ -190,56 +190,11 @@ struct LoaderTNBits {
 };
 
 // ---- epilogues -----------------------------------------------------------------------------------------------------
-template <int BM, int BN>
-struct EpiTrainBase {
-    static constexpr int MT = BM / 64, NT = BN / 64, WTM = BM / 2, WTN = BN / 2;
-    static constexpr int kCheckpoints = 0;
-    static constexpr int kLdsFloats = 0;
-    static constexpr int kStoresPerFinish = 0;   // conservative: the staged-load wait then also covers them
-    template <class A> __device__ __forceinline__ void end(const A&, const TileCtx&) {}
-    template <class A> __device__ __forceinline__ void init(const A&, f32x16 (&acc)[MT][NT], const TileCtx&) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.0f;
-    }
-    template <class A> __device__ __forceinline__ void checkpoint(const A&, f32x16 (&)[MT][NT], const TileCtx&, int) {}
-};
-
-// C[row][col] = acc
-template <int BM, int BN>
-struct EpiStoreC : EpiTrainBase<BM, BN> {
-    using Base = EpiTrainBase<BM, BN>;
-    static constexpr int MT = Base::MT, NT = Base::NT, WTM = Base::WTM, WTN = Base::WTN;
-    struct Args {
-        float* out;
-        int64_t ld;
-    };
-    __device__ __forceinline__ void begin(const Args&, const TileCtx&) {}
-    __device__ __forceinline__ void finish(const Args& a, f32x16 (&acc)[MT][NT], const TileCtx& c) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = c.m0 + c.wm * WTM + mt * 32 + mfma_row(r, c.lane_half);
-                if (row >= c.M) continue;
-                float* orow = a.out + static_cast<int64_t>(row) * a.ld;
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const int col = c.n0 + c.wn * WTN + nt * 32 + c.lane_col;
-                    if (col < c.N) orow[col] = acc[mt][nt][r];
-                }
-            }
-    }
-};
-
 // pre[row][col] <- (acc scale[col] + gg / B) p (1 - p), p = sigmoid(pre[row][col]): the pre-activation becomes dpre in place
 template <int BM, int BN>
-struct EpiDpre : EpiTrainBase<BM, BN> {
-    using Base = EpiTrainBase<BM, BN>;
-    static constexpr int MT = Base::MT, NT = Base::NT, WTM = Base::WTM, WTN = Base::WTN;
+struct EpiDpre : EpiTile<BM, BN> {
+    using T = EpiTile<BM, BN>;
+    static constexpr int MT = T::MT, NT = T::NT;
     struct Args {
         const float* scale;    // [N], this level's units
         const float* gg;       // device scalar (incoming gradient of latent_group[i]) or nullptr
@@ -249,29 +204,25 @@ struct EpiDpre : EpiTrainBase<BM, BN> {
     };
     float add;
     __device__ __forceinline__ void begin(const Args& a, const TileCtx&) { add = a.gg ? a.gg[0] / a.batch : 0.0f; }
+    __device__ __forceinline__ void init(const Args&, f32x16 (&acc)[MT][NT], const TileCtx&) { T::fill(acc, 0.0f); }
     __device__ __forceinline__ void finish(const Args& a, f32x16 (&acc)[MT][NT], const TileCtx& c) {
         float sc[NT];
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-            const int col = c.n0 + c.wn * WTN + nt * 32 + c.lane_col;
+            const int col = T::col(c, nt);
             sc[nt] = col < c.N ? a.scale[col] : 0.0f;
         }
+        T::for_each_row(c, [=, &acc](int mt, int r, int row) {
+            float* prow = a.pre + static_cast<int64_t>(row) * a.ld;
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = c.m0 + c.wm * WTM + mt * 32 + mfma_row(r, c.lane_half);
-                if (row >= c.M) continue;
-                float* prow = a.pre + static_cast<int64_t>(row) * a.ld;
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const int col = c.n0 + c.wn * WTN + nt * 32 + c.lane_col;
-                    if (col >= c.N) continue;
-                    const float p = soft_bit_prob(prow[col]);
-                    const float dz = acc[mt][nt][r] * sc[nt] + add;
-                    prow[col] = dz * (p * (1.0f - p));
-                }
+            for (int nt = 0; nt < NT; ++nt) {
+                const int col = T::col(c, nt);
+                if (col >= c.N) continue;
+                const float p = soft_bit_prob(prow[col]);
+                const float dz = acc[mt][nt][r] * sc[nt] + add;
+                prow[col] = dz * (p * (1.0f - p));
             }
+        });
     }
 };
 
@@ -291,60 +242,50 @@ dpre_const_kernel(float* __restrict__ pre, int64_t ld, int B, int ncols, const f
 // TernarySparseAutoencoder: dpre[row][col] = (acc + gh[row][col]) where h[row][col] > 0, else 0 (the ReLU's gradient; gh = the
 // gradient arriving at the latent itself, nullable).  h is read only: the caller owns it.
 template <int BM, int BN>
-struct EpiTernaryDpre : EpiTrainBase<BM, BN> {
-    using Base = EpiTrainBase<BM, BN>;
-    static constexpr int MT = Base::MT, NT = Base::NT, WTM = Base::WTM, WTN = Base::WTN;
+struct EpiTernaryDpre : EpiTile<BM, BN> {
+    using T = EpiTile<BM, BN>;
+    static constexpr int MT = T::MT, NT = T::NT;
     struct Args {
         const float* gh;       // [M][ld] or nullptr
         const float* h;        // [M][ld]
         float* dpre;           // [M][ld]
         int64_t ld;
     };
-    __device__ __forceinline__ void begin(const Args&, const TileCtx&) {}
+    __device__ __forceinline__ void init(const Args&, f32x16 (&acc)[MT][NT], const TileCtx&) { T::fill(acc, 0.0f); }
     __device__ __forceinline__ void finish(const Args& a, f32x16 (&acc)[MT][NT], const TileCtx& c) {
+        T::for_each_row(c, [=, &acc](int mt, int r, int row) {
+            const int64_t off = static_cast<int64_t>(row) * a.ld;
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = c.m0 + c.wm * WTM + mt * 32 + mfma_row(r, c.lane_half);
-                if (row >= c.M) continue;
-                const int64_t off = static_cast<int64_t>(row) * a.ld;
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const int col = c.n0 + c.wn * WTN + nt * 32 + c.lane_col;
-                    if (col >= c.N) continue;
-                    const float dh = a.gh ? a.gh[off + col] + acc[mt][nt][r] : acc[mt][nt][r];
-                    a.dpre[off + col] = a.h[off + col] > 0.0f ? dh : 0.0f;
-                }
+            for (int nt = 0; nt < NT; ++nt) {
+                const int col = T::col(c, nt);
+                if (col >= c.N) continue;
+                const float dh = a.gh ? a.gh[off + col] + acc[mt][nt][r] : acc[mt][nt][r];
+                a.dpre[off + col] = a.h[off + col] > 0.0f ? dh : 0.0f;
             }
+        });
     }
 };
 
 // C[row][col] = acc * mask[row][col]: the RigL mask on the store of the ternary decoder's weight gradient
 template <int BM, int BN>
-struct EpiStoreMasked : EpiTrainBase<BM, BN> {
-    using Base = EpiTrainBase<BM, BN>;
-    static constexpr int MT = Base::MT, NT = Base::NT, WTM = Base::WTM, WTN = Base::WTN;
+struct EpiStoreMasked : EpiTile<BM, BN> {
+    using T = EpiTile<BM, BN>;
+    static constexpr int MT = T::MT, NT = T::NT;
     struct Args {
         float* out;
         const float* mask;
         int64_t ld;
     };
-    __device__ __forceinline__ void begin(const Args&, const TileCtx&) {}
+    __device__ __forceinline__ void init(const Args&, f32x16 (&acc)[MT][NT], const TileCtx&) { T::fill(acc, 0.0f); }
     __device__ __forceinline__ void finish(const Args& a, f32x16 (&acc)[MT][NT], const TileCtx& c) {
+        T::for_each_row(c, [=, &acc](int mt, int r, int row) {
+            const int64_t off = static_cast<int64_t>(row) * a.ld;
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = c.m0 + c.wm * WTM + mt * 32 + mfma_row(r, c.lane_half);
-                if (row >= c.M) continue;
-                const int64_t off = static_cast<int64_t>(row) * a.ld;
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const int col = c.n0 + c.wn * WTN + nt * 32 + c.lane_col;
-                    if (col < c.N) a.out[off + col] = acc[mt][nt][r] * a.mask[off + col];
-                }
+            for (int nt = 0; nt < NT; ++nt) {
+                const int col = T::col(c, nt);
+                if (col < c.N) a.out[off + col] = acc[mt][nt][r] * a.mask[off + col];
             }
+        });
     }
 };
 
@@ -419,18 +360,7 @@ extern "C" int qsae_train_matryoshka_dpre(const float* g_levels, const float* g_
         const float* G = g_levels + static_cast<int64_t>(i) * B * D;
         const float* S = sign_rows + static_cast<int64_t>(h0) * D;
         typename Epi::Args ea{scale + h0, gg, static_cast<float>(B), pre + h0, pre_ld};
-        // the asm-staged loaders address with 32-bit byte offsets
-        const bool small = static_cast<int64_t>(B) * D < (1LL << 30) && static_cast<int64_t>(n) * D < (1LL << 30);
-        int r;
-        if (D % 32 == 0 && small) {
-            using L = LoaderF32<128, 32, false, true>;
-            r = launch_gemm<L, L, Epi, 128, 128, 32>(typename L::Args{G, D, B}, typename L::Args{S, D, n}, ea, B, n, D,
-                                                     pick_sweep<128, 128>(B, n, D), s);
-        } else {
-            using L = LoaderF32<128, 32, true>;
-            r = launch_gemm<L, L, Epi, 128, 128, 32>(typename L::Args{G, D, B}, typename L::Args{S, D, n}, ea, B, n, D,
-                                                     pick_sweep<128, 128>(B, n, D), s);
-        }
+        const int r = launch_nt_rows<Epi, 128, 128, 32>(G, D, B, S, D, n, D, ea, pick_sweep<128, 128>(B, n, D), s);
         if (r != QSAE_OK) return r;
     }
     return QSAE_OK;
@@ -443,7 +373,7 @@ extern "C" int qsae_train_gemm_tn(const float* A, int64_t lda, const float* X, i
     QSAE_CHECK_ARG(A && X && C && lda >= M && ldx >= N && ldc >= N, "null pointer or leading dimension too small");
     QSAE_CHECK_ARG(aligned16(A) && aligned16(X), "A and X must be 16-byte aligned");
     using LA = LoaderTN<128, 32>;
-    using Epi = EpiStoreC<128, 128>;
+    using Epi = EpiStore<128, 128>;
     return run_tn<LA, LA, Epi>(typename LA::Args{A, lda, M}, typename LA::Args{X, ldx, N}, typename Epi::Args{C, ldc}, M, N, K,
                                as_stream(stream));
 }
@@ -465,23 +395,18 @@ extern "C" int qsae_train_matryoshka_dsum_dense(const uint32_t* zbits, int64_t w
         // one launch over all levels: a level of a few thousand units alone leaves most of the chip idle for the whole K walk
         using LA = LoaderTNBits<128, 32>;
         using LB = LoaderTNByLevel<128, 32>;
-        using Epi = EpiStoreC<128, 128>;
-        typename LB::Args lb{g_levels, D, D, static_cast<int64_t>(B) * D, n_bits, {}, {}};
+        using Epi = EpiStore<128, 128>;
+        typename LB::Args lb{g_levels, D, D, static_cast<int64_t>(B) * D, n_bits, {}, make_sweep_map(H, D, 128, 128, 1, g_stagger)};
         for (int i = 0; i < kTnMaxLevels; ++i) lb.end_tile[i] = (i < n_bits ? lv.begin[i] + lv.size[i] : H) / 128;
-        lb.map.tiles_m = H / 128;
-        lb.map.tiles_n = (D + 127) / 128;
-        lb.map.sweep = 1;
-        lb.map.msplit = lb.map.tiles_m;
-        lb.map.stagger = g_stagger;
         return launch_gemm<LA, LB, Epi, 128, 128, 32>(typename LA::Args{zbits, words_ld, H, 0}, lb, typename Epi::Args{dsum, D},
-                                                      H, D, B, 1, s);
+                                                      H, D, B, lb.map, s);
     }
     for (int i = 0; i < n_bits; ++i) {
         const int n = lv.size[i], h0 = lv.begin[i];
         if (n == 0) continue;
         using LA = LoaderTNBits<128, 32>;
         using LB = LoaderTN<128, 32>;
-        using Epi = EpiStoreC<128, 128>;
+        using Epi = EpiStore<128, 128>;
         const int r = run_tn<LA, LB, Epi>(typename LA::Args{zbits, words_ld, n, h0},
                                           typename LB::Args{g_levels + static_cast<int64_t>(i) * B * D, D, D},
                                           typename Epi::Args{dsum + static_cast<int64_t>(h0) * D, D}, n, D, B, s);
@@ -510,16 +435,7 @@ extern "C" int qsae_train_ternary_dpre(const float* g_recon, const float* t_rows
     }
     using Epi = EpiTernaryDpre<128, 128>;
     typename Epi::Args ea{g_latent, h, dpre, H};
-    // the asm-staged loaders address with 32-bit byte offsets
-    const bool small = static_cast<int64_t>(B) * D < (1LL << 30) && static_cast<int64_t>(H) * D < (1LL << 30);
-    if (D % 32 == 0 && small) {
-        using L = LoaderF32<128, 32, false, true>;
-        return launch_gemm<L, L, Epi, 128, 128, 32>(typename L::Args{g_recon, D, B}, typename L::Args{t_rows, D, H}, ea, B, H, D,
-                                                    pick_sweep<128, 128>(B, H, D), s);
-    }
-    using L = LoaderF32<128, 32, true>;
-    return launch_gemm<L, L, Epi, 128, 128, 32>(typename L::Args{g_recon, D, B}, typename L::Args{t_rows, D, H}, ea, B, H, D,
-                                                pick_sweep<128, 128>(B, H, D), s);
+    return launch_nt_rows<Epi, 128, 128, 32>(g_recon, D, B, t_rows, D, H, D, ea, pick_sweep<128, 128>(B, H, D), s);
 }
 
 extern "C" int qsae_train_ternary_dweight(const float* g_recon, const float* h, const float* mask, int B, int D, int H,

@@ -974,3 +974,16 @@ def test_refine_sliced_switch_reaches_the_unit_that_launches_the_refinement(fuse
     assert unwritten.sum() == B - flagged2                   # rows that were not flagged still hold -1 ...
     assert np.array_equal(idx2[~unwritten], want_idx[~unwritten])     # ... flagged ones come from the exact kernels
     assert np.array_equal(idx0, want_idx)                    # the one-launch form ignores the bit
+
+
+@pytest.mark.parametrize("K,M,N", [(1, 4, 4), (33, 132, 4), (70, 260, 136)])
+def test_train_gemm_tn_matches_the_oracle_chain(K, M, N):
+    """C = A^T X through the transposing loaders and the plain store epilogue: a single k and a single row chunk, a K tail
+    behind one full slice, a partial second tile in M and in N.  Bit for bit the oracle's fmaf chain in ascending k."""
+    rng = np.random.default_rng(4100 + K)
+    A = rng.standard_normal((K, M)).astype(np.float32)
+    X = rng.standard_normal((K, N)).astype(np.float32)
+    got = host(_ops().train_gemm_tn(dev(A), dev(X)))
+    want = oracle.encode(A.T.copy(), X.T.copy())
+    assert got.shape == (M, N)
+    assert np.array_equal(got, want)

@@ -381,6 +381,28 @@ def test_bits_band_corners(D, H):
     check_bits_oracle_rows(x, W, b, z)
 
 
+def test_encoder_rows_past_4_gib_of_activations():
+    """x of 4 GiB + 2 MiB: the smallest operand at which a 32-bit byte offset per lane wraps (the asm-staged loaders address
+    that way, so operands of this size must take the 64-bit compiler loads).  A wrapped offset lands inside the same
+    allocation, on rows 0..127, whose contents differ from the last 128 rows': the last rows of the big batch must equal
+    the same rows encoded on their own, bit for bit, dense and as z bits."""
+    B, D, H = 2 ** 18 + 128, 4096, 8
+    g = gen(9100)
+    x = torch.zeros((B, D), device=DEV)
+    x[:128] = torch.randn((128, D), device=DEV, generator=g)
+    x[-128:] = torch.randn((128, D), device=DEV, generator=g)
+    W = torch.randn((H, D), device=DEV, generator=g) * (1.0 / 64.0)
+    try:
+        tail = x[-128:].contiguous()
+        dense = ops.encode_dense(x, W, None)[-128:]
+        bits = ops.encode_bits(x, W, None)[-128:]
+        assert bits_equal(dense, ops.encode_dense(tail, W, None))
+        assert bits_equal(bits, ops.encode_bits(tail, W, None))
+    finally:
+        del x
+        torch.cuda.empty_cache()
+
+
 def test_matryoshka_at_h65536_auto_equals_dense_and_fp32():
     B, D, H = 2304, 512, 65536
     with torch.device(DEV):

@@ -175,3 +175,14 @@ def test_baseline_refuses_shapes_no_path_takes():
         m._check_limits(2048)
     BaselineSparseAutoencoder(64, 65536)._check_limits(2048)
     BaselineSparseAutoencoder(64, 32768)._check_limits(0)        # an empty batch is legal everywhere
+
+
+def test_k_interleaved_encoder_operands_of_4_gib_are_refused_before_any_launch():
+    """The K-interleaved loaders address an operand with one 32-bit byte offset per lane and have no form with 64-bit addresses:
+    an operand of 4 GiB or more is refused where the offsets would wrap (natural-order operands of that size take the K-tail
+    loaders instead: tests/test_limits_gpu.py).  x is 4 GiB + 2 MiB, then W."""
+    lib = _lib.load()
+    B, D, H = 2 ** 18 + 128, 4096, 8
+    assert lib.qsae_encode_dense_kperm(FAKE, FAKE, None, B, D, H, ops.ACT_NONE, FAKE, H, None) == _lib.ERR_UNSUPPORTED
+    assert lib.qsae_encode_dense_kperm(FAKE, FAKE, None, H, D, B, ops.ACT_NONE, FAKE, B, None) == _lib.ERR_UNSUPPORTED
+    assert b"below 4 GiB" in lib.qsae_last_error()

@@ -1,12 +1,14 @@
 """Machine code of every kernel of the library, one line per kernel, for comparing two trees with `diff`:
 
-    name  size  sha256(disassembly, addresses stripped)[:16]  vgpr  sgpr  lds  scratch  unit
+    name  size  sha256(disassembly; addresses and the "<symbol+offset>" notes of branch targets stripped)[:16]  vgpr  sgpr  lds  scratch  unit
 
 usage: python tools/kernel_table.py [--debug] [unit.hip ...] > table.txt      (default: every unit of build.SOURCES)
 
 Each unit is compiled device-only with the flags of build.py (--debug: plus -DQSAE_DEBUG_BUILD=1); nothing is written into the
 tree.  A kernel's instructions are bounded by its symbol's st_size, so the padding after the last kernel of an ELF is not
-counted.  Moving a kernel to another unit must change the last column only; a name listed twice is a kernel emitted twice."""
+counted.  A branch's offset stays in the hash through its encoding; its target note is dropped because it repeats the kernel's
+own name, so renaming a kernel changes the first column only.  (Hashes of tables made before that note was dropped do not compare
+with these.)  Moving a kernel to another unit must change the last column only; a name listed twice is a kernel emitted twice."""
 import hashlib
 import re
 import subprocess
@@ -55,7 +57,8 @@ def unit_rows(src: str, debug: bool, tmp: str):
         while ki < len(kernels) and addr >= kernels[ki][1]:
             ki += 1
         if ki < len(kernels) and addr >= kernels[ki][0]:
-            text[kernels[ki][2]].append(m.group(1) + " | " + m.group(3))
+            # (a branch's "<symbol+offset>" target note is dropped: it would put the kernel's own name into its hash)
+            text[kernels[ki][2]].append(m.group(1) + " | " + re.sub(r"\s*<.*>$", "", m.group(3)))
     # resource fields from the code object's metadata note
     meta = {}
     for block in re.split(r"\n  - (?=\.agpr_count)", _run(LLVM / "llvm-readelf", "--notes", elf)):
