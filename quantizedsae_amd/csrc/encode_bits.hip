@@ -1,5 +1,9 @@
 // encode_bits.hip -- threshold bits z = (sigmoid(x W^T + b) > 0.5) from the fp16 candidate sweep
 // (qsae_encode_bits_prefilter*) and, for dense activations, from the fp16 GEMM with an uncertainty band (qsae_encode_bits_band*).
+// The two pipelines share their host side: one BitsCall per call, one bits_entry behind the six entry points.  The exact fp32
+// chain of the uncertain latents is written out in both resolve kernels (sweep form: loads predicated, bit set in LDS; band
+// form: unpredicated, bit set in global memory): as one forced-inline helper it changed both kernels' code, and the band
+// kernel measured 0.35 % slower (profiles/refactor_bits_pipeline.txt).  A change to the chain goes into both.
 #include "encode_topk_internal.h"
 #include "sweep_xstat_f16.h"
 
@@ -24,6 +28,14 @@ __host__ __device__ static inline size_t bits_lds_per_wave(int H) {
     return static_cast<size_t>((H + 31) / 32) * 4 + 64 * kRefTileStride * 4 + kBitsMaxUnc * 4;
 }
 
+// A row the resolve kernels leave to the exact dense kernel: its id is appended to flags[1..], flags[0] counts them.
+__device__ __forceinline__ void flag_row(int* __restrict__ flags, int b, int lane) {
+    if (lane == 0) {
+        const int slot = atomicAdd(&flags[0], 1);
+        flags[1 + slot] = b;
+    }
+}
+
 __global__ void __launch_bounds__(64 * kBitsWaves)
 resolve_bits_kernel(const uint2* __restrict__ cand, const int* __restrict__ cnt, int cap, int parts,
                     const int* __restrict__ cnt_parts, const float* __restrict__ margin, const float* __restrict__ x,
@@ -39,12 +51,6 @@ resolve_bits_kernel(const uint2* __restrict__ cand, const int* __restrict__ cnt,
     uint32_t* zrow = reinterpret_cast<uint32_t*>(mybase);
     float* wt = reinterpret_cast<float*>(mybase + static_cast<size_t>(words) * 4);
     int* hidx = reinterpret_cast<int*>(wt + 64 * kRefTileStride);
-    auto flag_row = [&]() {
-        if (lane == 0) {
-            const int slot = atomicAdd(&flags[0], 1);
-            flags[1 + slot] = b;
-        }
-    };
     auto lds_handoff = [&]() { asm volatile("" ::: "memory"); };       // one wave's LDS operations execute in order
     typedef const __attribute__((address_space(4))) int* cint_t;
     typedef const __attribute__((address_space(4))) float* cflt_t;
@@ -54,7 +60,7 @@ resolve_bits_kernel(const uint2* __restrict__ cand, const int* __restrict__ cnt,
         const int np = p == 0 ? ((cint_t)cnt)[b] : ((cint_t)cnt_parts)[static_cast<size_t>(p - 1) * B + b];
         seg_overflow |= np > cap_part;
     }
-    if (seg_overflow) { flag_row(); return; }
+    if (seg_overflow) { flag_row(flags, b, lane); return; }
     for (int w = lane; w < words; w += 64) zrow[w] = 0u;
     lds_handoff();
     const float c = __uint_as_float(QSAE_SIG_GT_BITS);
@@ -94,7 +100,7 @@ resolve_bits_kernel(const uint2* __restrict__ cand, const int* __restrict__ cnt,
             }
         }
     }
-    if (__any(bad) || m > kBitsMaxUnc) { flag_row(); return; }         // NaN latents / too many: the exact kernel decides
+    if (__any(bad) || m > kBitsMaxUnc) { flag_row(flags, b, lane); return; }   // NaN latents / too many: the exact kernel decides
     lds_handoff();
     // exact fp32 chain of the uncertain latents (ascending k, seeded with the bias): the transposed block gather
     // of refine_topk_kernel.  ~30 latents x 2 KiB of W per row: this gather (3.9 GB per 65536 rows at the headline
@@ -171,94 +177,6 @@ scatter_bit_rows_kernel(const uint32_t* __restrict__ src, const int* __restrict_
     if (gid >= static_cast<long long>(n) * words) return;
     const int r = static_cast<int>(gid / words), w = static_cast<int>(gid % words);
     dst[static_cast<long long>(rows[r]) * words_ld + w] = src[gid];
-}
-
-struct BitsLayout {
-    size_t tau, cnt, cnt_parts, cand, flags, xq, inv, margin, fx, fbits, total;
-};
-static BitsLayout bits_layout(int B, int D, int H, int cap = kBitsCap) {
-    BitsLayout L;
-    size_t off = 0;
-    L.tau = off;       off = align_up(off + static_cast<size_t>(B) * 4, 256);
-    L.cnt = off;       off = align_up(off + static_cast<size_t>(B) * 4, 256);
-    L.cnt_parts = off; off = align_up(off + static_cast<size_t>(B) * 4 * 7, 256);
-    L.cand = off;      off = align_up(off + static_cast<size_t>(B) * cap * 8, 256);
-    L.flags = off;     off = align_up(off + (static_cast<size_t>(B) + 4) * 4, 256);
-    L.xq = off;        off = align_up(off + static_cast<size_t>(B) * D * 2, 256);
-    L.inv = off;       off = align_up(off + static_cast<size_t>(B) * 4, 256);
-    L.margin = off;    off = align_up(off + static_cast<size_t>(B) * 4, 256);
-    L.fx = off;        off = align_up(off + static_cast<size_t>(kBitsChunk) * D * 4, 256);
-    L.fbits = off;     off = align_up(off + static_cast<size_t>(kBitsChunk) * ((H + 31) / 32) * 4, 256);
-    L.total = off;
-    return L;
-}
-
-static bool bits_prefilter_shape_ok(int B, int D, int H) {
-    return B > 0 && xstat_supported(D, H, 0) && D % 64 == 0 && D <= kRefMaxD && H <= (1 << 20) &&
-           bits_lds_per_wave(H) * kBitsWaves <= 160 * 1024;
-}
-
-// Everything up to and including the bit resolution; afterwards flags[0] (device) = rows that need the exact dense
-// kernel, flags[1..] their ids, every other row's bits are final.
-static int bits_submit(const float* x, const float* W, const float* bias, const _Float16* Wq, const float* meta,
-                       int B, int D, int H, uint32_t* zbits, int64_t words_ld, char* ws, qsae_stream_t stream) {
-    hipStream_t s = as_stream(stream);
-    const SweepProfile prof = take_sweep_profile();
-    const BitsLayout L = bits_layout(B, D, H);
-    float* tau = reinterpret_cast<float*>(ws + L.tau);
-    int* cnt = reinterpret_cast<int*>(ws + L.cnt);
-    int* cnt_parts = reinterpret_cast<int*>(ws + L.cnt_parts);
-    uint2* cand = reinterpret_cast<uint2*>(ws + L.cand);
-    int* flags = reinterpret_cast<int*>(ws + L.flags);
-    _Float16* xq = reinterpret_cast<_Float16*>(ws + L.xq);
-    float* inv = reinterpret_cast<float*>(ws + L.inv);
-    float* margin = reinterpret_cast<float*>(ws + L.margin);
-    const int words = (H + 31) / 32;
-    QSAE_HIP(hipMemsetAsync(flags, 0, sizeof(int), s));
-    QSAE_HIP(hipMemsetAsync(cnt, 0, static_cast<size_t>(B) * 4, s));
-    QSAE_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(tau), static_cast<int>(QSAE_SIG_GT_BITS), B, s));
-    if (words_ld > words)
-        QSAE_HIP(hipMemset2DAsync(zbits + words, words_ld * 4, 0, (words_ld - words) * 4, B, s));
-    launch_x_prep(x, B, D, meta, xq, inv, margin, s);
-    QSAE_LAUNCH_CHECK();
-    const int parts = xstat_parts(B, H, kBitsCap);
-    if (prof.begin) QSAE_HIP(hipEventRecord(prof.begin, s));
-    XsArgs xa{xq, Wq, bias, tau, margin, inv, cand, cnt, B, H, kBitsCap, 0, g_xstat_rot, nullptr, nullptr, 0, H, 0, 0, 0,
-              nullptr, nullptr, meta, nullptr, nullptr, parts, cnt_parts};
-    int rc = launch_xstat(D, xa, s, D == 512 ? 9 : 0);      // (nothing to zero-fill here: the build without fill code)
-    if (prof.end) QSAE_HIP(hipEventRecord(prof.end, s));
-    if (rc != QSAE_OK) return rc;
-    const size_t lds = bits_lds_per_wave(H) * kBitsWaves;
-    QSAE_SET_MAX_LDS_ONCE(resolve_bits_kernel, 160 * 1024);
-    hipLaunchKernelGGL(resolve_bits_kernel, dim3((B + kBitsWaves - 1) / kBitsWaves), dim3(64 * kBitsWaves), lds, s,
-                       cand, cnt, kBitsCap, parts, cnt_parts, margin, x, W, bias, B, D, H, zbits, words_ld, flags);
-    QSAE_LAUNCH_CHECK();
-    return QSAE_OK;
-}
-
-// The exact dense kernel on the nflag flagged rows (count known to the host).
-static int bits_finish(const float* x, const float* W, const float* bias, int B, int D, int H, uint32_t* zbits,
-                       int64_t words_ld, char* ws, qsae_stream_t stream, int nflag, int cap = kBitsCap) {
-    if (nflag < 0 || nflag > B) return fail(QSAE_ERR_INVALID_ARG, "%s: flagged-row count out of range", __func__);
-    hipStream_t s = as_stream(stream);
-    const BitsLayout L = bits_layout(B, D, H, cap);
-    const int* flags = reinterpret_cast<const int*>(ws + L.flags);
-    const int words = (H + 31) / 32;
-    float* fx = reinterpret_cast<float*>(ws + L.fx);
-    uint32_t* fbits = reinterpret_cast<uint32_t*>(ws + L.fbits);
-    for (int f0 = 0; f0 < nflag; f0 += kBitsChunk) {
-        const int n = (nflag - f0) < kBitsChunk ? (nflag - f0) : kBitsChunk;
-        const int* rows = flags + 1 + f0;
-        int rc = gather_rows(x, rows, n, D, fx, s);
-        if (rc != QSAE_OK) return rc;
-        rc = qsae_encode_bits(fx, W, bias, n, D, H, fbits, words, stream);
-        if (rc != QSAE_OK) return rc;
-        const long long tw = static_cast<long long>(n) * words;
-        hipLaunchKernelGGL(scatter_bit_rows_kernel, dim3(static_cast<unsigned>((tw + 255) / 256)), dim3(256), 0, s, fbits,
-                           rows, n, words, zbits, words_ld);
-        QSAE_LAUNCH_CHECK();
-    }
-    return QSAE_OK;
 }
 
 // ---- dense activations: classify EVERY latent with the fp16 pass, list only the uncertainty band -------------------------------
@@ -395,13 +313,7 @@ resolve_band_kernel(const uint2* __restrict__ cand, const int* __restrict__ cnt,
             hidx[i] = static_cast<int>(r.y);
         }
     }
-    if (__any(bad)) {                                                  // overflowing band / NaN latents: the exact kernel decides
-        if (lane == 0) {
-            const int slot = atomicAdd(&flags[0], 1);
-            flags[1 + slot] = b;
-        }
-        return;
-    }
+    if (__any(bad)) { flag_row(flags, b, lane); return; }              // overflowing band / NaN latents: the exact kernel decides
     lds_handoff();
     typedef const __attribute__((address_space(4))) f32x4* cvec_t;
     cvec_t xrow = (cvec_t)(x + static_cast<int64_t>(b) * D);
@@ -462,16 +374,100 @@ resolve_band_kernel(const uint2* __restrict__ cand, const int* __restrict__ cnt,
     }
 }
 
-static bool bits_band_shape_ok(int B, int D, int H) {
-    return B > 0 && D % 64 == 0 && D <= kRefMaxD && H % 32 == 0 && H <= (1 << 20);
+// ---- host side: one description of a call, one entry helper ---------------------------------------------------------------------
+// The kind alone decides the list capacity (and with it the workspace layout), the shapes taken and the submit function.
+enum class BitsKind { sweep, band };
+enum class BitsMode { blocking, submit, finish };
+
+struct BitsLayout {
+    size_t tau, cnt, cnt_parts, cand, flags, xq, inv, margin, fx, fbits, total;
+};
+static int bits_cap(BitsKind kind) { return kind == BitsKind::band ? kBandCap : kBitsCap; }
+static BitsLayout bits_layout(BitsKind kind, int B, int D, int H) {
+    const int cap = bits_cap(kind);
+    BitsLayout L;
+    size_t off = 0;
+    L.tau = off;       off = align_up(off + static_cast<size_t>(B) * 4, 256);
+    L.cnt = off;       off = align_up(off + static_cast<size_t>(B) * 4, 256);
+    L.cnt_parts = off; off = align_up(off + static_cast<size_t>(B) * 4 * 7, 256);
+    L.cand = off;      off = align_up(off + static_cast<size_t>(B) * cap * 8, 256);
+    L.flags = off;     off = align_up(off + (static_cast<size_t>(B) + 4) * 4, 256);
+    L.xq = off;        off = align_up(off + static_cast<size_t>(B) * D * 2, 256);
+    L.inv = off;       off = align_up(off + static_cast<size_t>(B) * 4, 256);
+    L.margin = off;    off = align_up(off + static_cast<size_t>(B) * 4, 256);
+    L.fx = off;        off = align_up(off + static_cast<size_t>(kBitsChunk) * D * 4, 256);
+    L.fbits = off;     off = align_up(off + static_cast<size_t>(kBitsChunk) * ((H + 31) / 32) * 4, 256);
+    L.total = off;
+    return L;
 }
 
-// Everything up to and including the band resolution (flags[0] = rows for the exact dense kernel afterwards).
-static int bits_band_submit(const float* x, const float* W, const float* bias, const _Float16* Wq, const float* meta,
-                            int B, int D, int H, uint32_t* zbits, int64_t words_ld, char* ws, qsae_stream_t stream) {
-    hipStream_t s = as_stream(stream);
+static bool bits_shape_ok(BitsKind kind, int B, int D, int H) {
+    if (kind == BitsKind::band) return B > 0 && D % 64 == 0 && D <= kRefMaxD && H % 32 == 0 && H <= (1 << 20);
+    return B > 0 && xstat_supported(D, H, 0) && D % 64 == 0 && D <= kRefMaxD && H <= (1 << 20) &&
+           bits_lds_per_wave(H) * kBitsWaves <= 160 * 1024;
+}
+static size_t bits_workspace_bytes(BitsKind kind, int B, int D, int H) {
+    return bits_shape_ok(kind, B, D, H) ? bits_layout(kind, B, D, H).total : 0;
+}
+
+// One call: the arguments of the entry point and the layout that follows from them.
+struct BitsCall {
+    const float* x; const float* W; const float* bias; const _Float16* Wq; const float* meta;
+    int B, D, H;
+    uint32_t* zbits; int64_t words_ld;
+    char* ws; qsae_stream_t stream;
+    BitsKind kind;
+    BitsLayout L;
+};
+
+// The candidate sweep up to and including the bit resolution; afterwards flags[0] (device) = rows that need the exact dense
+// kernel, flags[1..] their ids, every other row's bits are final.
+static int bits_sweep_submit(const BitsCall& c) {
+    hipStream_t s = as_stream(c.stream);
     const SweepProfile prof = take_sweep_profile();
-    const BitsLayout L = bits_layout(B, D, H, kBandCap);
+    const BitsLayout& L = c.L;
+    const int B = c.B, D = c.D, H = c.H;
+    char* ws = c.ws;
+    float* tau = reinterpret_cast<float*>(ws + L.tau);
+    int* cnt = reinterpret_cast<int*>(ws + L.cnt);
+    int* cnt_parts = reinterpret_cast<int*>(ws + L.cnt_parts);
+    uint2* cand = reinterpret_cast<uint2*>(ws + L.cand);
+    int* flags = reinterpret_cast<int*>(ws + L.flags);
+    _Float16* xq = reinterpret_cast<_Float16*>(ws + L.xq);
+    float* inv = reinterpret_cast<float*>(ws + L.inv);
+    float* margin = reinterpret_cast<float*>(ws + L.margin);
+    const int words = (H + 31) / 32;
+    QSAE_HIP(hipMemsetAsync(flags, 0, sizeof(int), s));
+    QSAE_HIP(hipMemsetAsync(cnt, 0, static_cast<size_t>(B) * 4, s));
+    QSAE_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(tau), static_cast<int>(QSAE_SIG_GT_BITS), B, s));
+    if (c.words_ld > words)
+        QSAE_HIP(hipMemset2DAsync(c.zbits + words, c.words_ld * 4, 0, (c.words_ld - words) * 4, B, s));
+    launch_x_prep(c.x, B, D, c.meta, xq, inv, margin, s);
+    QSAE_LAUNCH_CHECK();
+    const int parts = xstat_parts(B, H, kBitsCap);
+    if (prof.begin) QSAE_HIP(hipEventRecord(prof.begin, s));
+    XsArgs xa{};                                            // (no offset, no dense latent, no in-kernel pilot or x prep: zero)
+    xa.xq = xq;  xa.wq = c.Wq;  xa.bias = c.bias;  xa.tau = tau;  xa.margin = margin;  xa.inv = inv;
+    xa.cand = cand;  xa.cnt = cnt;  xa.B = B;  xa.Hs = H;  xa.cap = kBitsCap;  xa.rot_mul = g_xstat_rot;
+    xa.H = H;  xa.meta = c.meta;  xa.parts = parts;  xa.cnt_parts = cnt_parts;
+    int rc = launch_xstat(D, xa, s, D == 512 ? 9 : 0);      // (nothing to zero-fill here: the build without fill code)
+    if (prof.end) QSAE_HIP(hipEventRecord(prof.end, s));
+    if (rc != QSAE_OK) return rc;
+    const size_t lds = bits_lds_per_wave(H) * kBitsWaves;
+    QSAE_SET_MAX_LDS_ONCE(resolve_bits_kernel, 160 * 1024);
+    hipLaunchKernelGGL(resolve_bits_kernel, dim3((B + kBitsWaves - 1) / kBitsWaves), dim3(64 * kBitsWaves), lds, s,
+                       cand, cnt, kBitsCap, parts, cnt_parts, margin, c.x, c.W, c.bias, B, D, H, c.zbits, c.words_ld, flags);
+    QSAE_LAUNCH_CHECK();
+    return QSAE_OK;
+}
+
+// The band classification up to and including the band resolution (flags[0] = rows for the exact dense kernel afterwards).
+static int bits_band_submit(const BitsCall& c) {
+    hipStream_t s = as_stream(c.stream);
+    const SweepProfile prof = take_sweep_profile();
+    const BitsLayout& L = c.L;
+    const int B = c.B, D = c.D, H = c.H;
+    char* ws = c.ws;
     int* cnt = reinterpret_cast<int*>(ws + L.cnt);
     uint2* cand = reinterpret_cast<uint2*>(ws + L.cand);
     int* flags = reinterpret_cast<int*>(ws + L.flags);
@@ -481,44 +477,98 @@ static int bits_band_submit(const float* x, const float* W, const float* bias, c
     const int words = (H + 31) / 32;
     QSAE_HIP(hipMemsetAsync(flags, 0, sizeof(int), s));
     QSAE_HIP(hipMemsetAsync(cnt, 0, static_cast<size_t>(B) * 4, s));
-    if (words_ld > words)
-        QSAE_HIP(hipMemset2DAsync(zbits + words, words_ld * 4, 0, (words_ld - words) * 4, B, s));
-    launch_x_prep(x, B, D, meta, xq, inv, margin, s);
+    if (c.words_ld > words)
+        QSAE_HIP(hipMemset2DAsync(c.zbits + words, c.words_ld * 4, 0, (c.words_ld - words) * 4, B, s));
+    launch_x_prep(c.x, B, D, c.meta, xq, inv, margin, s);
     QSAE_LAUNCH_CHECK();
     using Epi = EpiBitsBand<256, 256, 4, 2>;
-    typename Epi::Args ea{inv, margin, bias, zbits, words_ld, cand, cnt, kBandCap};
+    typename Epi::Args ea{inv, margin, c.bias, c.zbits, c.words_ld, cand, cnt, kBandCap};
     if (prof.begin) QSAE_HIP(hipEventRecord(prof.begin, s));
-    int rc = launch_gemm_dma<Epi, 256, 256, true, 2>(reinterpret_cast<const float*>(xq), B, reinterpret_cast<const float*>(Wq), H,
+    int rc = launch_gemm_dma<Epi, 256, 256, true, 2>(reinterpret_cast<const float*>(xq), B, reinterpret_cast<const float*>(c.Wq), H,
                                                      D / 2, ea, s, /*sweep=*/8);
     if (prof.end) QSAE_HIP(hipEventRecord(prof.end, s));
     if (rc != QSAE_OK) return rc;
     const size_t lds = kBandLdsPerWave * kBitsWaves;
     QSAE_SET_MAX_LDS_ONCE(resolve_band_kernel, 160 * 1024);
     hipLaunchKernelGGL(resolve_band_kernel, dim3((B + kBitsWaves - 1) / kBitsWaves), dim3(64 * kBitsWaves), lds, s,
-                       cand, cnt, x, W, bias, B, D, H, zbits, words_ld, flags);
+                       cand, cnt, c.x, c.W, c.bias, B, D, H, c.zbits, c.words_ld, flags);
     QSAE_LAUNCH_CHECK();
     return QSAE_OK;
 }
 
-// Blocking form: submit, the count through this thread's pinned word (one host round trip), finish.
-static int run_bits_prefilter(const float* x, const float* W, const float* bias, const _Float16* Wq, const float* meta,
-                              int B, int D, int H, uint32_t* zbits, int64_t words_ld, char* ws, qsae_stream_t stream,
-                              int* flagged_rows) {
-    hipStream_t s = as_stream(stream);
-    int rc = bits_submit(x, W, bias, Wq, meta, B, D, H, zbits, words_ld, ws, stream);
+// The exact dense kernel on the nflag flagged rows (count known to the host).
+static int bits_finish(const BitsCall& c, int nflag) {
+    if (nflag < 0 || nflag > c.B) return fail(QSAE_ERR_INVALID_ARG, "%s: flagged-row count out of range", __func__);
+    hipStream_t s = as_stream(c.stream);
+    const int* flags = reinterpret_cast<const int*>(c.ws + c.L.flags);
+    const int words = (c.H + 31) / 32;
+    float* fx = reinterpret_cast<float*>(c.ws + c.L.fx);
+    uint32_t* fbits = reinterpret_cast<uint32_t*>(c.ws + c.L.fbits);
+    for (int f0 = 0; f0 < nflag; f0 += kBitsChunk) {
+        const int n = (nflag - f0) < kBitsChunk ? (nflag - f0) : kBitsChunk;
+        const int* rows = flags + 1 + f0;
+        int rc = gather_rows(c.x, rows, n, c.D, fx, s);
+        if (rc != QSAE_OK) return rc;
+        rc = qsae_encode_bits(fx, c.W, c.bias, n, c.D, c.H, fbits, words, c.stream);
+        if (rc != QSAE_OK) return rc;
+        const long long tw = static_cast<long long>(n) * words;
+        hipLaunchKernelGGL(scatter_bit_rows_kernel, dim3(static_cast<unsigned>((tw + 255) / 256)), dim3(256), 0, s, fbits,
+                           rows, n, words, c.zbits, c.words_ld);
+        QSAE_LAUNCH_CHECK();
+    }
+    return QSAE_OK;
+}
+
+// What the six entry points share: the shape checks, the empty batch, the argument checks, and then one of blocking
+// (out = flagged_rows or NULL: submit, the count through this thread's pinned word -- one host round trip --, finish),
+// submit (out = flagged_host) or finish (n = flagged).  A short workspace is QSAE_ERR_INVALID_ARG to the blocking forms
+// and QSAE_ERR_WORKSPACE to the two-call forms.
+static int bits_entry(const char* who, BitsKind kind, BitsMode mode, const float* x, const float* W, const float* bias,
+                      const void* Wq, const float* meta, int B, int D, int H, uint32_t* zbits, int64_t words_ld, void* workspace,
+                      size_t workspace_bytes, int n, int* out, qsae_stream_t stream) {
+    if (!(B >= 0 && D > 0 && H > 0)) return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: B >= 0, D > 0, H > 0 required", who);
+    if (mode == BitsMode::submit && !out)
+        return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: flagged_host must point to a host int", who);
+    if (out && (mode == BitsMode::blocking || B == 0)) *out = 0;
+    if (B == 0) return QSAE_OK;
+    if (!(x && W && Wq && meta && zbits)) return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: null pointer", who);
+    if (words_ld < (H + 31) / 32) return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: words_ld < ceil(H/32)", who);
+    if (!bits_shape_ok(kind, B, D, H))
+        return kind == BitsKind::band
+                   ? fail(QSAE_ERR_UNSUPPORTED,
+                          "%s: unsupported: shape not covered (D %% 64 == 0, H %% 32 == 0; use qsae_encode_bits)", who)
+                   : fail(QSAE_ERR_UNSUPPORTED,
+                          "%s: unsupported: shape not covered by the fp16 candidate sweep (D in {128,256,512}, H %% 64 == 0)", who);
+    if (!(aligned16(x) && aligned16(W) && aligned16(Wq)))
+        return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: x, W and Wq must be 16-byte aligned", who);
+    BitsCall c{};
+    c.x = x;  c.W = W;  c.bias = bias;  c.Wq = static_cast<const _Float16*>(Wq);  c.meta = meta;  c.B = B;  c.D = D;  c.H = H;
+    c.zbits = zbits;  c.words_ld = words_ld;  c.ws = static_cast<char*>(workspace);  c.stream = stream;  c.kind = kind;
+    c.L = bits_layout(kind, B, D, H);
+    if (!(workspace && workspace_bytes >= c.L.total))
+        return mode == BitsMode::blocking ? fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: workspace too small", who)
+                                          : fail(QSAE_ERR_WORKSPACE, "%s: workspace too small", who);
+    if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0)
+        return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: workspace must be 256-byte aligned", who);
+    if (mode == BitsMode::finish) return bits_finish(c, n);
+    int rc = kind == BitsKind::band ? bits_band_submit(c) : bits_sweep_submit(c);
     if (rc != QSAE_OK) return rc;
-    const BitsLayout L = bits_layout(B, D, H);
+    hipStream_t s = as_stream(stream);
+    if (mode == BitsMode::submit) {
+        QSAE_HIP(hipMemcpyAsync(out, c.ws + c.L.flags, sizeof(int), hipMemcpyDeviceToHost, s));
+        return QSAE_OK;
+    }
     ThreadDeviceCtx* ctx = nullptr;
     rc = thread_device_ctx(&ctx);
     if (rc != QSAE_OK) return rc;
     *ctx->pinned = 0;
-    QSAE_HIP(hipMemcpyAsync(ctx->pinned, ws + L.flags, sizeof(int), hipMemcpyDeviceToHost, s));
+    QSAE_HIP(hipMemcpyAsync(ctx->pinned, c.ws + c.L.flags, sizeof(int), hipMemcpyDeviceToHost, s));
     QSAE_HIP(hipEventRecord(ctx->ev_copied, s));
     QSAE_HIP(hipEventSynchronize(ctx->ev_copied));
     const int nflag = *ctx->pinned;
-    if (flagged_rows) *flagged_rows = nflag;
-    if (nflag < 0 || nflag > B) return fail(QSAE_ERR_HIP, "%s: corrupt flagged-row count", __func__);
-    return bits_finish(x, W, bias, B, D, H, zbits, words_ld, ws, stream, nflag);
+    if (out) *out = nflag;
+    if (nflag < 0 || nflag > B) return fail(QSAE_ERR_HIP, "%s: corrupt flagged-row count", who);
+    return bits_finish(c, nflag);
 }
 
 }  // namespace qsae
@@ -526,129 +576,55 @@ static int run_bits_prefilter(const float* x, const float* W, const float* bias,
 using namespace qsae;
 
 extern "C" size_t qsae_encode_bits_prefilter_workspace_bytes(int B, int D, int H) {
-    if (!bits_prefilter_shape_ok(B, D, H)) return 0;
-    return bits_layout(B, D, H).total;
+    return bits_workspace_bytes(BitsKind::sweep, B, D, H);
 }
 
 extern "C" int qsae_encode_bits_prefilter(const float* x, const float* W, const float* bias, const void* Wq,
                                           const float* meta, int B, int D, int H, uint32_t* zbits, int64_t words_ld,
                                           void* workspace, size_t workspace_bytes, int* flagged_rows,
                                           qsae_stream_t stream) {
-    QSAE_CHECK_ARG(B >= 0 && D > 0 && H > 0, "B >= 0, D > 0, H > 0 required");
-    if (flagged_rows) *flagged_rows = 0;
-    if (B == 0) return QSAE_OK;
-    QSAE_CHECK_ARG(x && W && Wq && meta && zbits, "null pointer");
-    QSAE_CHECK_ARG(words_ld >= (H + 31) / 32, "words_ld < ceil(H/32)");
-    QSAE_CHECK_SUPPORTED(bits_prefilter_shape_ok(B, D, H), "shape not covered by the fp16 candidate sweep (D in {128,256,512}, H %% 64 == 0)");
-    QSAE_CHECK_ARG(aligned16(x) && aligned16(W) && aligned16(Wq), "x, W and Wq must be 16-byte aligned");
-    QSAE_CHECK_ARG(workspace && workspace_bytes >= bits_layout(B, D, H).total, "workspace too small");
-    QSAE_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, "workspace must be 256-byte aligned");
-    return run_bits_prefilter(x, W, bias, static_cast<const _Float16*>(Wq), meta, B, D, H, zbits, words_ld,
-                              static_cast<char*>(workspace), stream, flagged_rows);
+    return bits_entry(__func__, BitsKind::sweep, BitsMode::blocking, x, W, bias, Wq, meta, B, D, H, zbits, words_ld, workspace,
+                      workspace_bytes, 0, flagged_rows, stream);
 }
 
-/* the two-call forms (see qsae_prefilter_submit / _finish); band: qsae_encode_bits_band_*, else qsae_encode_bits_prefilter_* */
-static int bits_args_ok(const char* who, bool band, const float* x, const float* W, const void* Wq, const float* meta, int B, int D,
-                        int H, const uint32_t* zbits, int64_t words_ld, const void* workspace, size_t workspace_bytes) {
-    if (!(x && W && Wq && meta && zbits)) return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: null pointer", who);
-    if (words_ld < (H + 31) / 32) return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: words_ld < ceil(H/32)", who);
-    if (band && !bits_band_shape_ok(B, D, H))
-        return fail(QSAE_ERR_UNSUPPORTED, "%s: unsupported: shape not covered (D %% 64 == 0, H %% 32 == 0; use qsae_encode_bits)", who);
-    if (!band && !bits_prefilter_shape_ok(B, D, H))
-        return fail(QSAE_ERR_UNSUPPORTED, "%s: unsupported: shape not covered by the fp16 candidate sweep (D in {128,256,512}, H %% 64 == 0)", who);
-    if (!(aligned16(x) && aligned16(W) && aligned16(Wq)))
-        return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: x, W and Wq must be 16-byte aligned", who);
-    if (!(workspace && workspace_bytes >= bits_layout(B, D, H, band ? kBandCap : kBitsCap).total))
-        return fail(QSAE_ERR_WORKSPACE, "%s: workspace too small", who);
-    if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0)
-        return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: workspace must be 256-byte aligned", who);
-    return QSAE_OK;
-}
-
+/* the two-call forms (see qsae_prefilter_submit / _finish) */
 extern "C" int qsae_encode_bits_prefilter_submit(const float* x, const float* W, const float* bias, const void* Wq,
                                                  const float* meta, int B, int D, int H, uint32_t* zbits, int64_t words_ld,
                                                  void* workspace, size_t workspace_bytes, int* flagged_host,
                                                  qsae_stream_t stream) {
-    QSAE_CHECK_ARG(B >= 0 && D > 0 && H > 0, "B >= 0, D > 0, H > 0 required");
-    QSAE_CHECK_ARG(flagged_host != nullptr, "flagged_host must point to a host int");
-    if (B == 0) { *flagged_host = 0; return QSAE_OK; }
-    int rc = bits_args_ok(__func__, false, x, W, Wq, meta, B, D, H, zbits, words_ld, workspace, workspace_bytes);
-    if (rc != QSAE_OK) return rc;
-    char* ws = static_cast<char*>(workspace);
-    rc = bits_submit(x, W, bias, static_cast<const _Float16*>(Wq), meta, B, D, H, zbits, words_ld, ws, stream);
-    if (rc != QSAE_OK) return rc;
-    QSAE_HIP(hipMemcpyAsync(flagged_host, ws + bits_layout(B, D, H).flags, sizeof(int), hipMemcpyDeviceToHost, as_stream(stream)));
-    return QSAE_OK;
+    return bits_entry(__func__, BitsKind::sweep, BitsMode::submit, x, W, bias, Wq, meta, B, D, H, zbits, words_ld, workspace,
+                      workspace_bytes, 0, flagged_host, stream);
 }
 
 extern "C" int qsae_encode_bits_prefilter_finish(const float* x, const float* W, const float* bias, const void* Wq,
                                                  const float* meta, int B, int D, int H, uint32_t* zbits, int64_t words_ld,
                                                  void* workspace, size_t workspace_bytes, int flagged, qsae_stream_t stream) {
-    QSAE_CHECK_ARG(B >= 0 && D > 0 && H > 0, "B >= 0, D > 0, H > 0 required");
-    if (B == 0) return QSAE_OK;
-    const int rc = bits_args_ok(__func__, false, x, W, Wq, meta, B, D, H, zbits, words_ld, workspace, workspace_bytes);
-    if (rc != QSAE_OK) return rc;
-    return bits_finish(x, W, bias, B, D, H, zbits, words_ld, static_cast<char*>(workspace), stream, flagged);
+    return bits_entry(__func__, BitsKind::sweep, BitsMode::finish, x, W, bias, Wq, meta, B, D, H, zbits, words_ld, workspace,
+                      workspace_bytes, flagged, nullptr, stream);
 }
 
 /* dense activations: every latent classified by the fp16 pass, the uncertainty band resolved exactly */
 extern "C" size_t qsae_encode_bits_band_workspace_bytes(int B, int D, int H) {
-    if (!bits_band_shape_ok(B, D, H)) return 0;
-    return bits_layout(B, D, H, kBandCap).total;
+    return bits_workspace_bytes(BitsKind::band, B, D, H);
 }
 
 extern "C" int qsae_encode_bits_band(const float* x, const float* W, const float* bias, const void* Wq, const float* meta,
                                      int B, int D, int H, uint32_t* zbits, int64_t words_ld, void* workspace,
                                      size_t workspace_bytes, int* flagged_rows, qsae_stream_t stream) {
-    QSAE_CHECK_ARG(B >= 0 && D > 0 && H > 0, "B >= 0, D > 0, H > 0 required");
-    if (flagged_rows) *flagged_rows = 0;
-    if (B == 0) return QSAE_OK;
-    QSAE_CHECK_ARG(x && W && Wq && meta && zbits, "null pointer");
-    QSAE_CHECK_ARG(words_ld >= (H + 31) / 32, "words_ld < ceil(H/32)");
-    QSAE_CHECK_SUPPORTED(bits_band_shape_ok(B, D, H), "shape not covered (D %% 64 == 0, H %% 32 == 0; use qsae_encode_bits)");
-    QSAE_CHECK_ARG(aligned16(x) && aligned16(W) && aligned16(Wq), "x, W and Wq must be 16-byte aligned");
-    QSAE_CHECK_ARG(workspace && workspace_bytes >= bits_layout(B, D, H, kBandCap).total, "workspace too small");
-    QSAE_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, "workspace must be 256-byte aligned");
-    char* ws = static_cast<char*>(workspace);
-    hipStream_t s = as_stream(stream);
-    int rc = bits_band_submit(x, W, bias, static_cast<const _Float16*>(Wq), meta, B, D, H, zbits, words_ld, ws, stream);
-    if (rc != QSAE_OK) return rc;
-    const BitsLayout L = bits_layout(B, D, H, kBandCap);
-    ThreadDeviceCtx* ctx = nullptr;
-    rc = thread_device_ctx(&ctx);
-    if (rc != QSAE_OK) return rc;
-    *ctx->pinned = 0;
-    QSAE_HIP(hipMemcpyAsync(ctx->pinned, ws + L.flags, sizeof(int), hipMemcpyDeviceToHost, s));
-    QSAE_HIP(hipEventRecord(ctx->ev_copied, s));
-    QSAE_HIP(hipEventSynchronize(ctx->ev_copied));
-    const int nflag = *ctx->pinned;
-    if (flagged_rows) *flagged_rows = nflag;
-    if (nflag < 0 || nflag > B) return fail(QSAE_ERR_HIP, "%s: corrupt flagged-row count", __func__);
-    return bits_finish(x, W, bias, B, D, H, zbits, words_ld, ws, stream, nflag, kBandCap);
+    return bits_entry(__func__, BitsKind::band, BitsMode::blocking, x, W, bias, Wq, meta, B, D, H, zbits, words_ld, workspace,
+                      workspace_bytes, 0, flagged_rows, stream);
 }
 
 extern "C" int qsae_encode_bits_band_submit(const float* x, const float* W, const float* bias, const void* Wq, const float* meta,
                                             int B, int D, int H, uint32_t* zbits, int64_t words_ld, void* workspace,
                                             size_t workspace_bytes, int* flagged_host, qsae_stream_t stream) {
-    QSAE_CHECK_ARG(B >= 0 && D > 0 && H > 0, "B >= 0, D > 0, H > 0 required");
-    QSAE_CHECK_ARG(flagged_host != nullptr, "flagged_host must point to a host int");
-    if (B == 0) { *flagged_host = 0; return QSAE_OK; }
-    int rc = bits_args_ok(__func__, true, x, W, Wq, meta, B, D, H, zbits, words_ld, workspace, workspace_bytes);
-    if (rc != QSAE_OK) return rc;
-    char* ws = static_cast<char*>(workspace);
-    rc = bits_band_submit(x, W, bias, static_cast<const _Float16*>(Wq), meta, B, D, H, zbits, words_ld, ws, stream);
-    if (rc != QSAE_OK) return rc;
-    QSAE_HIP(hipMemcpyAsync(flagged_host, ws + bits_layout(B, D, H, kBandCap).flags, sizeof(int), hipMemcpyDeviceToHost,
-                            as_stream(stream)));
-    return QSAE_OK;
+    return bits_entry(__func__, BitsKind::band, BitsMode::submit, x, W, bias, Wq, meta, B, D, H, zbits, words_ld, workspace,
+                      workspace_bytes, 0, flagged_host, stream);
 }
 
 extern "C" int qsae_encode_bits_band_finish(const float* x, const float* W, const float* bias, const void* Wq, const float* meta,
                                             int B, int D, int H, uint32_t* zbits, int64_t words_ld, void* workspace,
                                             size_t workspace_bytes, int flagged, qsae_stream_t stream) {
-    QSAE_CHECK_ARG(B >= 0 && D > 0 && H > 0, "B >= 0, D > 0, H > 0 required");
-    if (B == 0) return QSAE_OK;
-    const int rc = bits_args_ok(__func__, true, x, W, Wq, meta, B, D, H, zbits, words_ld, workspace, workspace_bytes);
-    if (rc != QSAE_OK) return rc;
-    return bits_finish(x, W, bias, B, D, H, zbits, words_ld, static_cast<char*>(workspace), stream, flagged, kBandCap);
+    return bits_entry(__func__, BitsKind::band, BitsMode::finish, x, W, bias, Wq, meta, B, D, H, zbits, words_ld, workspace,
+                      workspace_bytes, flagged, nullptr, stream);
 }

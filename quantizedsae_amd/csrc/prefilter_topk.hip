@@ -453,10 +453,13 @@ static int prefilter_submit(const PrefCall& c) {
         typename EpiS::Args es{c.bias ? c.bias + P : nullptr, tau, cand, cnt, kCandCap, P, fused_fill, c.dense_ld, inv, margin};
         if (prof.begin) QSAE_HIP(hipEventRecord(prof.begin, s));
         if (xstat) {
-            XsArgs xa{xq + 0, c.Wq + static_cast<size_t>(hoff) * D, c.bias ? c.bias + hoff : nullptr, tau, margin, inv, cand, cnt,
-                      B, Hs, kCandCap, hoff, g_xstat_rot, g_xstat_stamps, fill_in_sweep ? c.dense : nullptr, c.dense_ld, H,
-                      fill_cw, inkernel ? P / kXsHT : 0, g_inkernel_rank > 0 ? g_inkernel_rank : inkernel_rank(k), tau,
-                      fuse_prep ? c.x : nullptr, c.meta, inv, margin, parts, cnt_parts};
+            XsArgs xa{};
+            xa.xq = xq;  xa.wq = c.Wq + static_cast<size_t>(hoff) * D;  xa.bias = c.bias ? c.bias + hoff : nullptr;  xa.tau = tau;
+            xa.margin = margin;  xa.inv = inv;  xa.cand = cand;  xa.cnt = cnt;  xa.B = B;  xa.Hs = Hs;  xa.cap = kCandCap;
+            xa.hidden_offset = hoff;  xa.rot_mul = g_xstat_rot;  xa.stamps = g_xstat_stamps;  xa.H = H;  xa.fill_cw = fill_cw;
+            xa.dense = fill_in_sweep ? c.dense : nullptr;  xa.dense_ld = c.dense_ld;  xa.pilot_stages = inkernel ? P / kXsHT : 0;
+            xa.pilot_rank = g_inkernel_rank > 0 ? g_inkernel_rank : inkernel_rank(k);  xa.tau_out = tau;  xa.meta = c.meta;
+            xa.x32 = fuse_prep ? c.x : nullptr;  xa.inv_out = inv;  xa.margin_out = margin;  xa.parts = parts;  xa.cnt_parts = cnt_parts;
             if (fill_co) QSAE_HIP(hipEventRecord(ctx->ev_fork, s));     // everything before the sweep (x prep, earlier users of `dense`)
             // (the build without fill code whenever this launch has no zeros to write itself)
             rc = launch_xstat(D, xa, s, (g_xstat_ablate == 0 && D == 512 && !fill_in_sweep) ? 9 : g_xstat_ablate);

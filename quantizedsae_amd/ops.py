@@ -213,62 +213,70 @@ def encode_bits(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor]) 
     return z
 
 
-def encode_bits_prefilter_supported(B: int, D: int, H: int) -> bool:
-    return B > 0 and int(_lib.load().qsae_encode_bits_prefilter_workspace_bytes(B, D, H)) > 0
+# The two fp16 routes to the z bits: kind -> (workspace sizer, blocking, submit and finish entry point, refusal text).
+_BITS_FP16 = {
+    "prefilter": ("qsae_encode_bits_prefilter_workspace_bytes", "qsae_encode_bits_prefilter", "qsae_encode_bits_prefilter_submit",
+                  "qsae_encode_bits_prefilter_finish", "shape not supported by the fp16 candidate sweep"),
+    "band": ("qsae_encode_bits_band_workspace_bytes", "qsae_encode_bits_band", "qsae_encode_bits_band_submit",
+             "qsae_encode_bits_band_finish", "shape not supported by the fp16 band classification"),
+}
+
+
+def _encode_bits_fp16_supported(kind: str, B: int, D: int, H: int) -> bool:
+    return B > 0 and int(getattr(_lib.load(), _BITS_FP16[kind][0])(B, D, H)) > 0
+
+
+def _encode_bits_fp16_operands(kind: str, x, W, bias):
+    """-> (x, W, bias checked, B, D, H, workspace bytes) for the entry points of ``kind``; refuses a shape they do not take."""
+    x, W = _f32c(x, "x"), _f32c(W, "W")
+    B, D = x.shape
+    H = W.shape[0]
+    b = _f32c(bias, "bias") if bias is not None else None
+    need = int(getattr(_lib.load(), _BITS_FP16[kind][0])(B, D, H)) if B > 0 else 1
+    if need == 0:
+        raise ValueError(_BITS_FP16[kind][4])
+    return x, W, b, B, D, H, need
+
+
+def _encode_bits_fp16_cargs(x, W, b, Wq, meta, B, D, H, ws):
+    """-> (C arguments up to workspace_bytes, tensors they point into, zbits)."""
+    words = (H + 31) // 32
+    z = torch.empty((B, words), dtype=torch.int32, device=x.device)
+    return (_p(x), _p(W), _p(b), _p(Wq), _p(meta), B, D, H, _p(z), words, _p(ws), ws.numel()), (x, W, b, Wq, meta, ws), z
 
 
 @_on_tensor_device
+def _encode_bits_fp16(kind: str, x, W, bias, Wq, meta) -> Tuple[torch.Tensor, int]:
+    x, W, b, B, D, H, need = _encode_bits_fp16_operands(kind, x, W, bias)
+    if B == 0:
+        return torch.empty((0, (H + 31) // 32), dtype=torch.int32, device=x.device), 0
+    cargs, _keep, z = _encode_bits_fp16_cargs(x, W, b, Wq, meta, B, D, H, _workspace(x.device, need))
+    flagged = C.c_int(0)
+    kernel_timer.arm_sweep()
+    check(getattr(_lib.load(), _BITS_FP16[kind][1])(*cargs, C.byref(flagged), _stream()))
+    return z, int(flagged.value)
+
+
+def encode_bits_prefilter_supported(B: int, D: int, H: int) -> bool:
+    return _encode_bits_fp16_supported("prefilter", B, D, H)
+
+
+def encode_bits_band_supported(B: int, D: int, H: int) -> bool:
+    return _encode_bits_fp16_supported("band", B, D, H)
+
+
 def encode_bits_prefilter(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], Wq: torch.Tensor,
                           meta: torch.Tensor) -> Tuple[torch.Tensor, int]:
     """z bits identical to encode_bits, from the fp16 candidate sweep + exact re-evaluation of the latents near the
     cutoff.  Returns (zbits int32 [B, ceil(H/32)], rows that went through the exact dense kernel)."""
-    x, W = _f32c(x, "x"), _f32c(W, "W")
-    B, D = x.shape
-    H = W.shape[0]
-    b = _f32c(bias, "bias") if bias is not None else None
-    lib = _lib.load()
-    if B == 0:
-        return torch.empty((0, (H + 31) // 32), dtype=torch.int32, device=x.device), 0
-    need = int(lib.qsae_encode_bits_prefilter_workspace_bytes(B, D, H))
-    if need == 0:
-        raise ValueError("shape not supported by the fp16 candidate sweep")
-    ws = _workspace(x.device, need)
-    words = (H + 31) // 32
-    z = torch.empty((B, words), dtype=torch.int32, device=x.device)
-    flagged = C.c_int(0)
-    kernel_timer.arm_sweep()
-    check(lib.qsae_encode_bits_prefilter(_p(x), _p(W), _p(b), _p(Wq), _p(meta), B, D, H, _p(z), words, _p(ws),
-                                         ws.numel(), C.byref(flagged), _stream()))
-    return z, int(flagged.value)
+    return _encode_bits_fp16("prefilter", x, W, bias, Wq, meta)
 
 
-def encode_bits_band_supported(B: int, D: int, H: int) -> bool:
-    return B > 0 and int(_lib.load().qsae_encode_bits_band_workspace_bytes(B, D, H)) > 0
-
-
-@_on_tensor_device
 def encode_bits_band(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], Wq: torch.Tensor,
                      meta: torch.Tensor) -> Tuple[torch.Tensor, int]:
     """z bits identical to encode_bits for DENSE activations: every latent classified by an fp16 MFMA pass, the
     uncertainty band around the cutoff re-evaluated exactly.  Returns (zbits, rows that went through the exact kernel)."""
-    x, W = _f32c(x, "x"), _f32c(W, "W")
-    B, D = x.shape
-    H = W.shape[0]
-    b = _f32c(bias, "bias") if bias is not None else None
-    lib = _lib.load()
-    if B == 0:
-        return torch.empty((0, (H + 31) // 32), dtype=torch.int32, device=x.device), 0
-    need = int(lib.qsae_encode_bits_band_workspace_bytes(B, D, H))
-    if need == 0:
-        raise ValueError("shape not supported by the fp16 band classification")
-    ws = _workspace(x.device, need)
-    words = (H + 31) // 32
-    z = torch.empty((B, words), dtype=torch.int32, device=x.device)
-    flagged = C.c_int(0)
-    kernel_timer.arm_sweep()
-    check(lib.qsae_encode_bits_band(_p(x), _p(W), _p(b), _p(Wq), _p(meta), B, D, H, _p(z), words, _p(ws), ws.numel(),
-                                    C.byref(flagged), _stream()))
-    return z, int(flagged.value)
+    return _encode_bits_fp16("band", x, W, bias, Wq, meta)
 
 
 @_on_tensor_device
@@ -277,26 +285,13 @@ def encode_bits_prefilter_submit(x: torch.Tensor, W: torch.Tensor, bias: Optiona
     """The two-call form of encode_bits_prefilter (qsae_encode_bits_prefilter_submit / _finish) or, with ``band``, of
     encode_bits_band: ``finish()`` returns the z bits; ``flagged_rows`` of the handle is the number of rows that went
     through the exact dense kernel."""
-    x, W = _f32c(x, "x"), _f32c(W, "W")
-    B, D = x.shape
-    H = W.shape[0]
-    b = _f32c(bias, "bias") if bias is not None else None
-    lib = _lib.load()
-    sizer = lib.qsae_encode_bits_band_workspace_bytes if band else lib.qsae_encode_bits_prefilter_workspace_bytes
-    need = int(sizer(B, D, H)) if B > 0 else 1
-    if need == 0:
-        raise ValueError("shape not supported by the fp16 candidate sweep")
+    kind = "band" if band else "prefilter"
+    x, W, b, B, D, H, need = _encode_bits_fp16_operands(kind, x, W, bias)
     slot = (owner, slot)
     _claim_slot(x.device, slot)
-    ws = _workspace(x.device, need, slot, "pending")
-    words = (H + 31) // 32
-    z = torch.empty((B, words), dtype=torch.int32, device=x.device)
-    cargs = (_p(x), _p(W), _p(b), _p(Wq), _p(meta), B, D, H, _p(z), words, _p(ws), ws.numel())
-    if band:
-        return _submit(lib.qsae_encode_bits_band_submit, lib.qsae_encode_bits_band_finish, cargs, (x, W, b, Wq, meta, ws), z,
-                       x.device, slot)
-    return _submit(lib.qsae_encode_bits_prefilter_submit, lib.qsae_encode_bits_prefilter_finish, cargs,
-                   (x, W, b, Wq, meta, ws), z, x.device, slot)
+    cargs, keep, z = _encode_bits_fp16_cargs(x, W, b, Wq, meta, B, D, H, _workspace(x.device, need, slot, "pending"))
+    lib = _lib.load()
+    return _submit(getattr(lib, _BITS_FP16[kind][2]), getattr(lib, _BITS_FP16[kind][3]), cargs, keep, z, x.device, slot)
 
 
 @_on_tensor_device

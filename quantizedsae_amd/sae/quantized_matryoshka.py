@@ -293,16 +293,13 @@ class QuantizedMatryoshkaSAE(ops.GraphForwardMixin, SparseAutoencoder):
             W, b = self._encoder_params()
             x = require_device_input(x, "x")
             path = path or self.resolved_bits_path(x.shape[0])
-            if path == "prefilter":
+            if path in ("prefilter", "band"):
                 pw = self._prefilter_weights()
-                z, flagged = ops.encode_bits_prefilter(x.float(), W, b, pw["Wq"], pw["meta"])
+                fn = ops.encode_bits_prefilter if path == "prefilter" else ops.encode_bits_band
+                z, flagged = fn(x.float(), W, b, pw["Wq"], pw["meta"])
                 self.last_flagged_rows = flagged
-                if flagged * 2 > x.shape[0]:                  # the exact fallback of half the rows costs what the dense kernel does
+                if path == "prefilter" and flagged * 2 > x.shape[0]:   # the exact fallback of half the rows costs what the dense kernel does
                     self._dense_regime = True
-                return z
-            if path == "band":
-                pw = self._prefilter_weights()
-                z, self.last_flagged_rows = ops.encode_bits_band(x.float(), W, b, pw["Wq"], pw["meta"])
                 return z
             return ops.encode_bits(x, W, b)
 

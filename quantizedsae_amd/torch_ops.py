@@ -98,26 +98,22 @@ def _(x, W, bias):
     return _i32((x.shape[0], (W.shape[0] + 31) // 32), x)
 
 
-@_op("encode_bits_prefilter")
-def _encode_bits_prefilter(x: Tensor, W: Tensor, bias: Optional[Tensor], Wq: Tensor, meta: Tensor) -> Tuple[Tensor, Tensor]:
-    z, flagged = _ops.encode_bits_prefilter(x, W, bias, Wq, meta)
-    return z, torch.tensor(flagged, dtype=torch.int64)
+def _register_bits_fp16(kind):
+    """torch.ops.qsae.encode_bits_<kind> -> (z bits, host count of the rows that took the exact kernel), and its fake."""
+    fn = getattr(_ops, f"encode_bits_{kind}")
+
+    @_op(f"encode_bits_{kind}")
+    def op(x: Tensor, W: Tensor, bias: Optional[Tensor], Wq: Tensor, meta: Tensor) -> Tuple[Tensor, Tensor]:
+        z, flagged = fn(x, W, bias, Wq, meta)
+        return z, torch.tensor(flagged, dtype=torch.int64)
+
+    @op.register_fake
+    def _(x, W, bias, Wq, meta):
+        return _i32((x.shape[0], (W.shape[0] + 31) // 32), x), _host_count()
 
 
-@_encode_bits_prefilter.register_fake
-def _(x, W, bias, Wq, meta):
-    return _i32((x.shape[0], (W.shape[0] + 31) // 32), x), _host_count()
-
-
-@_op("encode_bits_band")
-def _encode_bits_band(x: Tensor, W: Tensor, bias: Optional[Tensor], Wq: Tensor, meta: Tensor) -> Tuple[Tensor, Tensor]:
-    z, flagged = _ops.encode_bits_band(x, W, bias, Wq, meta)
-    return z, torch.tensor(flagged, dtype=torch.int64)
-
-
-@_encode_bits_band.register_fake
-def _(x, W, bias, Wq, meta):
-    return _i32((x.shape[0], (W.shape[0] + 31) // 32), x), _host_count()
+_register_bits_fp16("prefilter")
+_register_bits_fp16("band")
 
 
 @_op("topk_rows", mutates=("latent",))
@@ -597,14 +593,16 @@ def encode_bits(x, W, bias):
     return Q.encode_bits(x, W, bias)
 
 
-def encode_bits_prefilter(x, W, bias, Wq, meta):
-    z, flagged = Q.encode_bits_prefilter(x, W, bias, Wq, meta)
-    return z, int(flagged)
+def _bits_fp16(kind):
+    def call(x, W, bias, Wq, meta):
+        z, flagged = getattr(Q, f"encode_bits_{kind}")(x, W, bias, Wq, meta)
+        return z, int(flagged)
+    call.__name__ = call.__qualname__ = f"encode_bits_{kind}"
+    return call
 
 
-def encode_bits_band(x, W, bias, Wq, meta):
-    z, flagged = Q.encode_bits_band(x, W, bias, Wq, meta)
-    return z, int(flagged)
+encode_bits_prefilter = _bits_fp16("prefilter")
+encode_bits_band = _bits_fp16("band")
 
 
 def topk_rows(latent, k, zero_rest):

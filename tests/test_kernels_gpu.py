@@ -318,6 +318,79 @@ def test_encode_bits_prefilter_nonfinite_rows():
     assert 2 <= flagged < 64
 
 
+def _bits_fp16_inputs(kind, B, D, H, shift):
+    """x with rows of very different norm and one NaN row, W and a bias `shift` standard deviations of the latent below 0:
+    the sweep's as in test_encode_bits_prefilter_matches_exact, the band's as in test_encode_bits_band_matches_exact."""
+    if kind == "prefilter":
+        x = S.activations(81, B, D)
+        x[3] *= 40.0
+        x[5] *= 1e-3
+        W = S.xavier_uniform(81, H, D, stream=1)
+        sigma = float(np.sqrt(D) * np.sqrt(6.0 / (D + H)) / np.sqrt(3.0))
+        bias = (S.normal(81, (H,), stream=3, std=0.05 * sigma) + shift * sigma).astype(np.float32)
+    else:
+        sd = S.matryoshka_sae_params(300, D, H, enc_bias_sigmas=shift)
+        W, bias = sd["encoder.0.weight"], sd["encoder.0.bias"]
+        x = S.activations(301, B, D)
+        x[::9] *= 50.0
+        x[1::9] *= 1e-3
+    x[7, 3] = np.nan
+    return dev(x), dev(W), dev(bias)
+
+
+@pytest.mark.parametrize("kind,B,D,H,shift", [("prefilter", 700, 128, 2048, -1.5), ("band", 300, 512, 4128, -2.5)])
+def test_encode_bits_two_call_forms_equal_blocking(kind, B, D, H, shift):
+    """submit + finish == the blocking call == the exact dense kernel, bits and flagged-row count, for the candidate sweep
+    and for the band; the NaN row gives the finish step a row to recompute.  An empty batch through all three forms."""
+    ops = _ops()
+    blocking = getattr(ops, f"encode_bits_{kind}")
+    xd, Wd, bd = _bits_fp16_inputs(kind, B, D, H, shift)
+    Wq, meta = ops.prefilter_pack_w(Wd, bd)
+    want = ops.encode_bits(xd, Wd, bd)
+    got, flagged = blocking(xd, Wd, bd, Wq, meta)
+    pending = ops.encode_bits_prefilter_submit(xd, Wd, bd, Wq, meta, band=(kind == "band"))
+    got2 = pending.finish()
+    print(f"{kind}: {flagged} of {B} rows flagged (blocking), {pending.flagged_rows} (two-call)")
+    assert torch.equal(got, want) and torch.equal(got2, want)
+    assert pending.flagged_rows == flagged and flagged >= 1
+    x0 = torch.empty((0, D), device=DEV)
+    z0, f0 = blocking(x0, Wd, bd, Wq, meta)
+    p0 = ops.encode_bits_prefilter_submit(x0, Wd, bd, Wq, meta, band=(kind == "band"))
+    for z in (z0, p0.finish(), ops.encode_bits(x0, Wd, bd)):
+        assert z.shape == (0, (H + 31) // 32) and z.dtype == torch.int32
+    assert f0 == 0 and p0.flagged_rows == 0
+
+
+@pytest.mark.parametrize("widen", [1.0, 16.0])
+@pytest.mark.parametrize("D", [64, 128])
+def test_encode_bits_band_chain_loop_forms(D, widen):
+    """The band's exact chain where its loops change form: D = 64 is D/32 = 2 blocks, fewer than the three staging sets
+    (the prologue's guard, no refill); D = 128 is 4 blocks, one partial refill round.  H = 2080 is a multiple of 32 but not
+    of 64, the bias is 0 (half of the units fire).  The band is eps_b ~ 2^-10 |x| max_h |W_h| wide, ~2^-10 sqrt(D) of the
+    latent's standard deviation: measured 1 ... 15 (D = 64) and 3 ... 21 (D = 128) of the 2080 units per row, less than one
+    pass of 64.  widen = 16 scales ONE unit's weights and, through max_h |W_h|, every row's band sixteenfold: measured
+    66 ... 127 and 107 ... 172 entries per row (cap 1024), i.e. more than one pass and a last pass with idle lanes in every
+    row (in 291 of 300 at D = 128).  No row is flagged in any of the four cases.  The lengths depend on the seeds, on
+    synthetic.py and on the error bound in meta (max_h |W_h|), so the widened cases read them back from the call's workspace
+    (the per-row counts follow the B cutoffs, 256-byte aligned) and insist on what they are there for."""
+    ops = _ops()
+    B, H = 300, 2080
+    sd = S.matryoshka_sae_params(310, D, H, enc_bias_sigmas=0.0)
+    W, bias = sd["encoder.0.weight"], sd["encoder.0.bias"]
+    W[17] *= widen
+    xd, Wd, bd = dev(S.activations(311, B, D)), dev(W), dev(bias)
+    assert ops.encode_bits_band_supported(B, D, H)
+    Wq, meta = ops.prefilter_pack_w(Wd, bd)
+    z, flagged = ops.encode_bits_band(xd, Wd, bd, Wq, meta)
+    off = (4 * B + 255) // 256 * 256
+    m = ops._workspace(xd.device, 1)[off:off + 4 * B].view(torch.int32)
+    print(f"D = {D}, widen = {widen}: {flagged} of {B} rows flagged, band lists of {int(m.min())} ... {int(m.max())} entries")
+    if widen > 1.0:
+        assert int(m.min()) > 64 and bool((m % 64 != 0).any())   # more than one pass of 64, a last pass with idle lanes
+    assert torch.equal(z, ops.encode_bits(xd, Wd, bd))
+    assert flagged < B                                     # the band path, not the fallback, produced the bits
+
+
 @pytest.mark.parametrize("B,D,H,n_bits,density", [(300, 512, 4096, 4, 0.01), (1000, 512, 32768, 4, 0.006),
                                                    (257, 64, 1024, 4, 0.05), (130, 256, 2048, 3, 0.5),
                                                    (64, 1024, 4096, 8, 0.02), (33, 128, 512, 1, 0.1)])

@@ -173,7 +173,6 @@ def test_encode_bits_band_matches_exact(B, Dm, H, shift):
     want = ops.encode_bits(xd, W, b)
     assert torch.equal(z, want)
     assert 2 <= flagged <= 2 + B // 50                      # the two non-finite rows (+ rows whose band overflows: none expected)
-    dens = float(torch.ops.qsae.encode_bits(xd, W, b).view(torch.uint8).to(torch.int32).sum()) if False else None
 
 
 # ---- fp32-accurate encoder on the fp16 matrix pipe (opt-in) -----------------------------------------------------------------
