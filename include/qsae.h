@@ -416,6 +416,29 @@ size_t qsae_coactivation_bits_workspace_bytes(int B, int nbits);
 int qsae_coactivation_bits(const uint32_t* zbits, int64_t words_ld, int B, int nbits, const int32_t* index, int H,
                            int32_t* coact, int64_t ld, void* workspace, size_t workspace_bytes, qsae_stream_t stream);
 
+/* -- token overlap between two SAEs (scripts/analysis/summarize_stats.py:100-156, 320-378) -------------------- */
+/* The script scores every pair (a, b) of live features of two SAEs as |A & B| / |A | B| over their top-k token sets and
+ * keeps every score.  A score is fixed by (inter, union) with inter <= k and union <= 2k, so the whole result is the
+ * table hist[k + 1][2k + 1] (int64, device, accumulated into -- the caller zeroes it):
+ *   hist[i][u] += #{(a, b) : asize[a] > 0, bsize[b] > 0, |A_a & B_b| = i, asize[a] + bsize[b] - i = u},
+ * pairs with an empty intersection included, at (0, asize + bsize).  The intersections of all pairs are the product of
+ * the two 0/1 membership matrices, formed on the int8 matrix pipe from the packed bits; no [Na][Nb] matrix exists.
+ * asets uint32 [Na][a_ld]: bit t & 31 of word t >> 5 of row i = token t is in the set of feature i; a_ld >= ceil(V / 32);
+ * bits at or past V in the last word are masked, they need not be zero.  asize[i] (int32, device) is the true size of
+ * the set -- passed, not popcounted, because the caller may have dropped tokens that cannot be in any intersection --
+ * and 0 means no set: that feature takes part in no pair.  bsets / b_ld / bsize / Nb: the same for the other side.
+ * A pair that contradicts itself is not counted and touches no memory: a size above k or below 0, or an intersection
+ * larger than either size (sizes smaller than the bits say).  Callers see that as sum(hist) falling short of
+ * #{asize > 0} * #{bsize > 0}.
+ * 1 <= k <= 128, otherwise QSAE_ERR_UNSUPPORTED.  Na == 0 or Nb == 0: nothing to do, no pointer is looked at.
+ * workspace: 16-byte aligned, qsae_token_overlap_hist_workspace_bytes(Na, Nb, V) = (Na + Nb) * ceil(V / 256) * 32
+ * bytes (both bitsets re-tiled by 256-token chunk; 0 for an invalid shape).  QSAE_ERR_INVALID_ARG before any HIP call;
+ * QSAE_ERR_WORKSPACE when the workspace is too small. */
+size_t qsae_token_overlap_hist_workspace_bytes(int Na, int Nb, int V);
+int qsae_token_overlap_hist(const uint32_t* asets, int64_t a_ld, const int32_t* asize, int Na, const uint32_t* bsets,
+                            int64_t b_ld, const int32_t* bsize, int Nb, int V, int k, int64_t* hist, void* workspace,
+                            size_t workspace_bytes, qsae_stream_t stream);
+
 /* -- activation quantizer of the binary datasets (src/quantized_sae/data/dataset.py:76-102) ----------------- */
 /* bits[b][d*n + j] = bit j (LSB first, as 0.0 / 1.0) of the n-bit code of x[b][d]:
  *   is_signed = 0 (quantize):        int(round(clamp((x * sf) * 2 + 2^(n-1), 0, 2^n - 1)))

@@ -8,3 +8,10 @@ from .framework import (  # noqa: F401
     load_sae,
 )
 from .dictionary import compare_decoders, decoder_atoms, decoder_cosine_similarity  # noqa: F401,E402
+from .token_overlap import (  # noqa: F401,E402
+    JaccardHistogram,
+    TokenSets,
+    average_unique_tokens_per_active_feature,
+    jaccard_histogram,
+    top_token_sets,
+)

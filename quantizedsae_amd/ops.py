@@ -974,6 +974,48 @@ def coactivation_bits(zbits: torch.Tensor, H: int, index: Optional[torch.Tensor]
     return coact
 
 
+def _bitsets(sets: torch.Tensor, size: torch.Tensor, words: int, name: str):
+    _dev(sets, f"{name}sets", torch.int32)
+    _dev(size, f"{name}size", torch.int32)
+    if sets.dim() != 2 or sets.shape[1] < words or size.shape != (sets.shape[0],):
+        raise ValueError(f"{name}sets: expected int32 [N, >= {words}] with {name}size int32 [N]")
+    if sets.shape[0] and sets.stride(1) != 1:
+        sets = sets.contiguous()
+    return sets, size.contiguous()
+
+
+@_on_tensor_device
+def token_overlap_hist(asets: torch.Tensor, asize: torch.Tensor, bsets: torch.Tensor, bsize: torch.Tensor, V: int, k: int,
+                       hist: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """hist[i, u] += #pairs (a, b) with asize[a] > 0, bsize[b] > 0, |A_a & B_b| = i and asize[a] + bsize[b] - i = u: every
+    Jaccard score i / u between the token sets of two SAEs as one table (int64 [k + 1, 2k + 1]), from the packed sets on
+    the int8 matrix pipe.  asets / bsets int32 [N, >= ceil(V / 32)]: bit t & 31 of word t >> 5 = token t is in the set
+    (a column slice of a wider tensor is read in place; bits at or past V are ignored); asize / bsize int32 [N]: the
+    true set sizes, 0 = no set.  1 <= k <= 128.  Pairs whose sizes contradict the bits, or exceed k, are not counted."""
+    V, k = int(V), int(k)
+    if V <= 0:
+        raise ValueError("V must be positive")
+    words = (V + 31) // 32
+    asets, asize = _bitsets(asets, asize, words, "a")
+    bsets, bsize = _bitsets(bsets, bsize, words, "b")
+    if hist is None:
+        if not 1 <= k <= 128:
+            raise ValueError("token_overlap_hist: 1 <= k <= 128 required")
+        hist = torch.zeros((k + 1, 2 * k + 1), dtype=torch.int64, device=asets.device)
+    else:
+        _dev(hist, "hist", torch.int64)
+        if hist.shape != (k + 1, 2 * k + 1) or not hist.is_contiguous():
+            raise ValueError(f"hist: expected a contiguous int64 [{k + 1}, {2 * k + 1}] tensor")
+    Na, Nb = asets.shape[0], bsets.shape[0]
+    lib = _lib.load()
+    need = int(lib.qsae_token_overlap_hist_workspace_bytes(Na, Nb, V)) if Na and Nb else 0
+    ws = _workspace(asets.device, max(need, 1))
+    check(lib.qsae_token_overlap_hist(_p(asets), asets.stride(0) if Na else words, _p(asize), Na,
+                                      _p(bsets), bsets.stride(0) if Nb else words, _p(bsize), Nb, V, k, _p(hist),
+                                      _p(ws), ws.numel(), _stream()))
+    return hist
+
+
 @_on_tensor_device
 def quantize_bits(x: torch.Tensor, n_bits: int, scale_factor: float, signed: bool = True) -> torch.Tensor:
     """n-bit code of every activation as LSB-first 0/1 floats, [B, D * n_bits] (data/dataset.py:76-102)."""

@@ -438,6 +438,16 @@ def _(zbits, index, coact):
     return None
 
 
+@_op("token_overlap_hist", mutates=("hist",))
+def _token_overlap_hist(asets: Tensor, asize: Tensor, bsets: Tensor, bsize: Tensor, V: int, k: int, hist: Tensor) -> None:
+    _ops.token_overlap_hist(asets, asize, bsets, bsize, V, k, hist)
+
+
+@_token_overlap_hist.register_fake
+def _(asets, asize, bsets, bsize, V, k, hist):
+    return None
+
+
 @_op("quantize_bits")
 def _quantize_bits(x: Tensor, n_bits: int, scale_factor: float, signed: bool) -> Tensor:
     return _ops.quantize_bits(x, n_bits, scale_factor, signed)
@@ -763,6 +773,13 @@ def coactivation_bits(zbits, H, index=None, coact=None):
         return _ops.coactivation_bits(zbits, H, index, coact)
     Q.coactivation_bits(zbits, index, coact)
     return coact
+
+
+def token_overlap_hist(asets, asize, bsets, bsize, V, k, hist=None):
+    if hist is None:
+        hist = torch.zeros((int(k) + 1, 2 * int(k) + 1), dtype=torch.int64, device=asets.device)
+    Q.token_overlap_hist(asets, asize, bsets, bsize, int(V), int(k), hist)
+    return hist
 
 
 def quantize_bits(x, n_bits, scale_factor, signed=True):
