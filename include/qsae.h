@@ -416,6 +416,47 @@ size_t qsae_coactivation_bits_workspace_bytes(int B, int nbits);
 int qsae_coactivation_bits(const uint32_t* zbits, int64_t words_ld, int B, int nbits, const int32_t* index, int H,
                            int32_t* coact, int64_t ld, void* workspace, size_t workspace_bytes, qsae_stream_t stream);
 
+/* -- tokens per feature as ordered CSR lists (scripts/analysis/dynamic_analysis.py:283-306) -------------------- */
+/* tokens_per_feature[f] of the reference holds the token of every row whose mask bit f is set, in ascending row order
+ * (the order of mask.nonzero()), batch after batch.  Here it is a CSR pair on the device: offsets int64 [H + 1] with
+ * offsets[0] = 0 and tokens int32 [offsets[H]], feature f in tokens[offsets[f] .. offsets[f + 1]).  A batch is built in
+ * two calls -- a count that leaves the batch's offsets (so that the caller can size the token buffer from offsets[H])
+ * and a unit-major row bitmap in the workspace, then qsae_token_lists_fill from that same, untouched workspace -- and
+ * the batches are joined by qsae_token_lists_regroup.  List positions are prefix counts over the bitmap, never an
+ * atomic counter: the result does not depend on scheduling.  No [B, H] mask of bytes is formed; the scratch is the
+ * bitmap, qsae_token_lists_workspace_bytes(B, H) = align256(H * 2 ceil(B / 64) * 4) + align256(H * 4) bytes (one bit per
+ * row and unit; 0 for an invalid shape: B < 0 or H <= 0).  The workspace must be 16-byte aligned.
+ * Limits: every index into the bitmap and into tokens is 64-bit, so B * H and the number of entries may exceed 2^31
+ * (B = 65536 at H = 32768 is one call); the compact form requires B * k < 2^31 and the bits form nbits <= 134215680,
+ * otherwise QSAE_ERR_UNSUPPORTED.  QSAE_ERR_INVALID_ARG before any HIP call; QSAE_ERR_WORKSPACE when the workspace is
+ * missing or too small.  B == 0 leaves all-zero offsets and needs no workspace. */
+size_t qsae_token_lists_workspace_bytes(int B, int H);
+/* Compact form (top-k models): row r is active in unit idx[r][j] when val[r][j] > 0 (NaN, 0.0 and -0.0 are not; val ==
+ * NULL: every entry, as in qsae_activation_counts).  Entries outside [0, H) are dropped; a unit listed twice in one row
+ * counts once (the mask has one bit). */
+int qsae_token_lists_count(const int32_t* idx, const float* val, int B, int k, int H, int64_t* offsets, void* workspace,
+                           size_t workspace_bytes, qsae_stream_t stream);
+/* Bits form (threshold models): zbits uint32 [B][words_ld], bit j of word w = packed position 32 w + j; nbits a
+ * positive multiple of 32, words_ld >= nbits / 32.  index[nbits] (int32, device) follows qsae_coactivation_bits: the
+ * destination unit of a packed position, -1 = inert pad slot, whose bits are ignored and need not be zero (values >= H
+ * are dropped too); two positions must not map to one unit.  index == NULL: identity, requires nbits <= H.  offsets
+ * come out in unit order. */
+int qsae_token_lists_count_bits(const uint32_t* zbits, int64_t words_ld, int B, int nbits, const int32_t* index, int H,
+                                int64_t* offsets, void* workspace, size_t workspace_bytes, qsae_stream_t stream);
+/* tokens[offsets[u] + rank] = row_tokens[r] for every active (r, u) of the batch whose count call left `workspace` and
+ * `offsets`; rank = active rows of u before r.  row_tokens int32 [B]: the token id of each row, written as it is (no
+ * row number that a second pass would gather).  n_entries = the capacity of tokens, normally offsets[H]; nothing is
+ * written at or past it.  B == 0 or n_entries == 0: nothing to do. */
+int qsae_token_lists_fill(const void* workspace, size_t workspace_bytes, const int64_t* offsets, const int32_t* row_tokens,
+                          int B, int H, int32_t* tokens, int64_t n_entries, qsae_stream_t stream);
+/* Joins nb batches: batch_offsets int64 [nb][H + 1] (each row as a count call left it) and segments int32
+ * [n_entries], the batches' token buffers back to back in batch order -> offsets int64 [H + 1] of the whole dataset and
+ * tokens int32 [n_entries] feature-major, the segments of a feature in batch order.  n_entries must be the sum of the
+ * batches' totals; reads and writes stay inside [0, n_entries) whatever batch_offsets holds.  nb == 0: all-zero
+ * offsets. */
+int qsae_token_lists_regroup(const int64_t* batch_offsets, int nb, int H, const int32_t* segments, int64_t n_entries,
+                             int64_t* offsets, int32_t* tokens, qsae_stream_t stream);
+
 /* -- token overlap between two SAEs (scripts/analysis/summarize_stats.py:100-156, 320-378) -------------------- */
 /* The script scores every pair (a, b) of live features of two SAEs as |A & B| / |A | B| over their top-k token sets and
  * keeps every score.  A score is fixed by (inter, union) with inter <= k and union <= 2k, so the whole result is the

@@ -19,6 +19,7 @@
 // Every sum runs in a fixed order (no float atomics): gradients are bitwise reproducible.  The only atomics are the
 // integer ORs that mark (unit, row) pairs in the CSR build, whose result does not depend on their order.
 #include "common.h"
+#include "csr_lists.h"
 
 namespace qsae {
 
@@ -30,7 +31,6 @@ constexpr size_t kTrainAlign = 256;
 
 typedef float tr_f32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ int clamp_unit(int h, int H) { return h < 0 ? 0 : (h >= H ? H - 1 : h); }
 __device__ __forceinline__ tr_f32x4 ld4(const float* p) { return *reinterpret_cast<const tr_f32x4*>(p); }
 __device__ __forceinline__ void st4(float* p, tr_f32x4 v) { *reinterpret_cast<tr_f32x4*>(p) = v; }
 __device__ __forceinline__ tr_f32x4 fma4(float a, tr_f32x4 w, tr_f32x4 acc) {
@@ -86,66 +86,14 @@ pol_final_kernel(const double* __restrict__ partial, int nb, double count, float
 // ---- top-k lists by unit (CSR) ----------------------------------------------------------------------------------------
 // bitmap[h][w] bit (r & 31) of word w = r >> 5: row r selected unit h.  prefix[h][w] = set bits of row h before word w.
 // The position of entry (r, j) in unit h's list is offsets[h] + (rows before r that selected h): lists come out ordered by
-// row, whatever order the threads ran in.
-__global__ void __launch_bounds__(256)
-csr_mark_kernel(const int32_t* __restrict__ idx, long long Bk, int k, int H, int W, uint32_t* __restrict__ bitmap) {
-    const long long e = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (e >= Bk) return;
-    const int h = clamp_unit(idx[e], H);
-    const int r = static_cast<int>(e / k);
-    atomicOr(bitmap + static_cast<long long>(h) * W + (r >> 5), 1u << (r & 31));
-}
-
-// one wave per unit: inclusive wave scan of the word popcounts, carried across rounds of 64 words
-__global__ void __launch_bounds__(256)
-csr_count_kernel(const uint32_t* __restrict__ bitmap, int H, int W, int* __restrict__ prefix, int* __restrict__ counts) {
-    const int lane = threadIdx.x & 63;
-    const int h = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (h >= H) return;                                    // wave-uniform
-    const uint32_t* row = bitmap + static_cast<long long>(h) * W;
-    int* pre = prefix + static_cast<long long>(h) * W;
-    int carry = 0;
-    for (int w0 = 0; w0 < W; w0 += 64) {                   // every lane runs every round
-        const int w = w0 + lane;
-        const int c = w < W ? __popc(row[w]) : 0;
-        int incl = c;
-        for (int off = 1; off < 64; off <<= 1) {
-            const int t = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += t;
-        }
-        if (w < W) pre[w] = carry + incl - c;
-        carry += __shfl(incl, 63, 64);
-    }
-    if (lane == 0) counts[h] = carry;
-}
+// row, whatever order the threads ran in.  csr_mark_kernel, csr_count_kernel and the scan are in csr_lists.h.
 
 // Exclusive scan of n values into out[0..n] (out[n] = total), one workgroup.  MODE 0: the values are in[i]; MODE 1: the
 // number of chunks of list i, from the list offsets in[0..n].
 template <int MODE>
 __global__ void __launch_bounds__(1024)
 scan_kernel(const int* __restrict__ in, int n, int* __restrict__ out) {
-    __shared__ int s_w[16];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int per = (n + 1023) / 1024;
-    const int beg = min(n, t * per), end = min(n, beg + per);
-    auto value = [&](int i) { return MODE == 0 ? in[i] : list_chunks(in[i + 1] - in[i]); };
-    int s = 0;
-    for (int i = beg; i < end; ++i) s += value(i);
-    int incl = s;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int u = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += u;
-    }
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; ++w) base += s_w[w];
-    int run = base + incl - s;
-    for (int i = beg; i < end; ++i) {
-        out[i] = run;
-        run += value(i);
-    }
-    if (t == 1023) out[n] = run;
+    scan_block<int>([&](int i) { return MODE == 0 ? in[i] : list_chunks(in[i + 1] - in[i]); }, n, out);
 }
 
 __global__ void __launch_bounds__(256)
@@ -789,7 +737,8 @@ extern "C" int qsae_train_csr(const int32_t* idx, int B, int k, int H, int32_t* 
     } else {
         QSAE_HIP(hipMemsetAsync(bitmap, 0, static_cast<size_t>(H) * L.W * 4, s));
         const unsigned eb = static_cast<unsigned>((Bk + 255) / 256);
-        hipLaunchKernelGGL(csr_mark_kernel, dim3(eb), dim3(256), 0, s, idx, Bk, k, H, L.W, bitmap);
+        hipLaunchKernelGGL(csr_mark_kernel<false>, dim3(eb), dim3(256), 0, s, idx, static_cast<const float*>(nullptr), Bk, k, H,
+                           L.W, bitmap);
         QSAE_LAUNCH_CHECK();
         hipLaunchKernelGGL(csr_count_kernel, dim3((H + 3) / 4), dim3(256), 0, s, bitmap, H, L.W, prefix, counts);
         QSAE_LAUNCH_CHECK();

@@ -15,3 +15,4 @@ from .token_overlap import (  # noqa: F401,E402
     jaccard_histogram,
     top_token_sets,
 )
+from .token_lists import TokenLists, token_lists_to_python  # noqa: F401,E402

@@ -6,19 +6,22 @@ the dense [B, H] latent to a boolean mask and forms ``mask.sum(0)`` and ``mask.T
 product per batch); here the top-k variants work from the compact ``(idx, val)`` output of
 ``forward_compact`` -- k and k^2 integer increments per row (``qsae_activation_counts``,
 ``qsae_coactivation_sparse``) -- and the threshold variants from the bit-packed encoder output: per-unit popcounts
-(``qsae_activation_counts_bits``) and the int8-MFMA rank-B update of ``qsae_coactivation_bits``, with no [B, H] mask
-in memory unless the caller asks for the tokens per feature.
+(``qsae_activation_counts_bits``) and the int8-MFMA rank-B update of ``qsae_coactivation_bits``.  The tokens per feature
+come in two forms: ``with_tokens="csr"`` builds them on the device as ordered CSR lists (``TokenLists``,
+``qsae_token_lists_*``) from the same ``(idx, val)`` or packed bits, with no [B, H] mask in memory for any model;
+``with_tokens=True`` returns the reference's list of Python lists and, for the threshold models, goes through the mask.
 """
 from __future__ import annotations
 
 import weakref
-from typing import Any, Dict, Iterable, List, Optional
+from typing import Any, Dict, Iterable, List, Optional, Union
 
 import torch
 
 from .. import torch_ops as ops          # torch.ops.qsae.* (dispatcher ops over the C ABI)
 from ..sae import (BaselineSparseAutoencoder, BinarySAE, QuantizedMatryoshkaSAE, ResidualQuantizedSAE)
 from .framework import SAEWrapper, _ensure_tensor, compute_reconstruction_error  # noqa: F401  (re-export)
+from .token_lists import TokenLists, check_token_ids
 
 
 def _hidden_dim(sae: SAEWrapper) -> int:
@@ -103,14 +106,28 @@ def _packed_index(stages) -> Optional[torch.Tensor]:
     return torch.cat(maps).to(torch.int32)
 
 
-def _threshold_stats(model, x: torch.Tensor, H: int, counts: torch.Tensor, coact: torch.Tensor,
-                     with_tokens: bool) -> Optional[torch.Tensor]:
-    """counts / coact += this batch's activation statistics of a threshold model, from the packed bits.  Returns the
-    bool mask [B, H] (on the device) when the tokens per feature are wanted, else None: nothing else needs it."""
+def _threshold_stats(model, x: torch.Tensor, H: int, counts: torch.Tensor, coact: torch.Tensor, with_tokens: bool,
+                     lists: Optional[TokenLists] = None, batch_tok: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """counts / coact += this batch's activation statistics of a threshold model, from the packed bits; ``lists`` takes
+    the batch's tokens per feature from the same bits.  Returns the bool mask [B, H] (on the device) when the tokens per
+    feature are wanted as Python lists, else None: nothing else needs it."""
     zb, index = _packed_bits(model, x)
     counts += _packed_counts_to_units(ops.activation_counts_bits(zb), index, H)
     ops.coactivation_bits(zb, H, index, coact)
+    if lists is not None:
+        lists.add_bits(zb, index, batch_tok)
     return _bits_to_mask(zb, index, H) if with_tokens else None
+
+
+def _token_lists_mode(with_tokens, token_ids: torch.Tensor) -> bool:
+    """True for ``with_tokens="csr"``, False for a bool; any other value raises.  The CSR form stores token ids as int32,
+    so ``token_ids`` is checked here, once."""
+    if isinstance(with_tokens, bool):
+        return False
+    if not (isinstance(with_tokens, str) and with_tokens == "csr"):
+        raise ValueError(f'with_tokens: expected True, False or "csr", got {with_tokens!r}')
+    check_token_ids(token_ids)
+    return True
 
 
 def activation_indices(sae: SAEWrapper, x: torch.Tensor):
@@ -210,9 +227,12 @@ def _tokens_per_feature(feat: torch.Tensor, tok: torch.Tensor, H: int, into: Lis
 
 def compute_activation_stats(sae: SAEWrapper, loader: Iterable[Any], *, token_ids: torch.Tensor,
                              tokens_per_context: int, device: Optional[Any] = None,
-                             with_tokens: bool = True) -> Dict[str, Any]:
+                             with_tokens: Union[bool, str] = True) -> Dict[str, Any]:
     """activation_counts [H] (int64), coactivation [H,H] (int32, mask^T mask) and tokens_per_feature
-    (dynamic_analysis.py:255-311).  Counts are accumulated on the device and copied to the host once."""
+    (dynamic_analysis.py:255-311).  Counts are accumulated on the device and copied to the host once.
+    ``with_tokens="csr"``: tokens_per_feature is the tuple (offsets int64 [H + 1], tokens int32 [nnz]) on the SAE's device,
+    in the reference's order, as ``top_token_sets`` / ``jaccard_histogram`` take it."""
+    csr = _token_lists_mode(with_tokens, token_ids)
     if device is not None:
         sae.to(device)
     sae.eval()
@@ -221,7 +241,9 @@ def compute_activation_stats(sae: SAEWrapper, loader: Iterable[Any], *, token_id
     dev = sae.device
     counts = torch.zeros((H,), dtype=torch.int64, device=dev)
     coact = torch.zeros((H, H), dtype=torch.int32, device=dev)
-    tokens_per_feature: List[List[int]] = [[] for _ in range(H)]
+    lists = TokenLists(H, dev) if csr else None
+    tokens_per_feature: List[List[int]] = [] if csr else [[] for _ in range(H)]
+    with_lists = with_tokens is True
     global_index = 0
     compact = isinstance(model, (BinarySAE, BaselineSparseAutoencoder))
     with torch.no_grad():
@@ -234,7 +256,9 @@ def compute_activation_stats(sae: SAEWrapper, loader: Iterable[Any], *, token_id
                 idx, val = activation_indices(sae, x)
                 ops.activation_counts(idx, val, H, counts)
                 ops.coactivation_sparse(idx, val, H, coact)
-                if with_tokens:
+                if csr:
+                    lists.add_compact(idx, val, batch_tok)
+                elif with_lists:
                     on = val > 0
                     rows = torch.arange(B, device=dev).unsqueeze(1).expand_as(idx)[on]
                     _tokens_per_feature(idx[on].long(), batch_tok.to(dev)[rows], H, tokens_per_feature)
@@ -242,12 +266,13 @@ def compute_activation_stats(sae: SAEWrapper, loader: Iterable[Any], *, token_id
                 # threshold variants: hundreds to thousands of active units per row, so mask^T mask is a dense rank-B
                 # update (dynamic_analysis.py:405-415) -- of single bits: formed from the packed encoder output on the
                 # int8 matrix pipe (qsae_coactivation_bits), exact in int32, without a [B, H] mask in memory
-                mask = _threshold_stats(model, x, H, counts, coact, with_tokens)
-                if with_tokens:
+                mask = _threshold_stats(model, x, H, counts, coact, with_lists, lists, batch_tok)
+                if with_lists:
                     nz = mask.nonzero(as_tuple=False)
                     _tokens_per_feature(nz[:, 1], batch_tok.to(dev)[nz[:, 0]], H, tokens_per_feature)
             global_index += B
-    return {"activation_counts": counts.cpu(), "coactivation": coact.cpu(), "tokens_per_feature": tokens_per_feature}
+    return {"activation_counts": counts.cpu(), "coactivation": coact.cpu(),
+            "tokens_per_feature": lists.finish() if csr else tokens_per_feature}
 
 
 def compute_reconstruction_error_by_level(sae: SAEWrapper, loader: Iterable[Any], device: Optional[Any] = None) -> torch.Tensor:
@@ -282,12 +307,14 @@ def compute_reconstruction_error_by_level(sae: SAEWrapper, loader: Iterable[Any]
 
 
 def analyze_dataset(sae: SAEWrapper, loader: Iterable[Any], *, token_ids: torch.Tensor, tokens_per_context: int,
-                    device: Optional[Any] = None, with_tokens: bool = True) -> Dict[str, Any]:
+                    device: Optional[Any] = None, with_tokens: Union[bool, str] = True) -> Dict[str, Any]:
     """One pass over the data: final reconstruction MSE, activation counts, co-activation matrix and tokens per
     feature (dynamic_analysis.py:317-440; same result keys, ``mse_per_level`` / ``l0_per_level`` are None there
     too).  Top-k variants run ``forward_compact`` once per batch and feed its (idx, val, reconstruction) to the
     integer kernels and the fp64 squared-error sum; the threshold variants take the reconstruction from the
-    forward pass and the masks from the bit-packed encoder output."""
+    forward pass and the masks from the bit-packed encoder output.  ``with_tokens="csr"``: tokens_per_feature is the
+    CSR tuple on the SAE's device (see ``compute_activation_stats``), built without a mask or a Python list."""
+    csr = _token_lists_mode(with_tokens, token_ids)
     if device is not None:
         sae.to(device)
     sae.eval()
@@ -297,7 +324,9 @@ def analyze_dataset(sae: SAEWrapper, loader: Iterable[Any], *, token_ids: torch.
     counts = torch.zeros((H,), dtype=torch.int64, device=dev)
     coact = torch.zeros((H, H), dtype=torch.int32, device=dev)
     sq = torch.zeros((), dtype=torch.float64, device=dev)
-    tokens_per_feature: List[List[int]] = [[] for _ in range(H)]
+    lists = TokenLists(H, dev) if csr else None
+    tokens_per_feature: List[List[int]] = [] if csr else [[] for _ in range(H)]
+    with_lists = with_tokens is True
     global_index, n_elements = 0, 0
     compact = isinstance(model, (BinarySAE, BaselineSparseAutoencoder))
     with torch.no_grad():
@@ -312,17 +341,20 @@ def analyze_dataset(sae: SAEWrapper, loader: Iterable[Any], *, token_ids: torch.
                 ops.sq_err_sum(recon, x, sq)
                 ops.activation_counts(idx, val, H, counts)
                 ops.coactivation_sparse(idx, val, H, coact)
-                if with_tokens:
+                if csr:
+                    lists.add_compact(idx, val, batch_tok)
+                elif with_lists:
                     on = val > 0
                     rows = torch.arange(B, device=dev).unsqueeze(1).expand_as(idx)[on]
                     _tokens_per_feature(idx[on].long(), batch_tok.to(dev)[rows], H, tokens_per_feature)
             else:
                 ops.sq_err_sum(sae(x)["reconstruction"].to(dev).contiguous(), x, sq)
-                mask = _threshold_stats(model, x, H, counts, coact, with_tokens)
-                if with_tokens:
+                mask = _threshold_stats(model, x, H, counts, coact, with_lists, lists, batch_tok)
+                if with_lists:
                     nz = mask.nonzero(as_tuple=False)
                     _tokens_per_feature(nz[:, 1], batch_tok.to(dev)[nz[:, 0]], H, tokens_per_feature)
             global_index += B
             n_elements += x.numel()
     return {"mse_final": float(sq.item()) / max(n_elements, 1), "mse_per_level": None, "l0_per_level": None,
-            "activation_counts": counts.cpu(), "coactivation": coact.cpu(), "tokens_per_feature": tokens_per_feature}
+            "activation_counts": counts.cpu(), "coactivation": coact.cpu(),
+            "tokens_per_feature": lists.finish() if csr else tokens_per_feature}

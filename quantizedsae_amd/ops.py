@@ -1016,6 +1016,103 @@ def token_overlap_hist(asets: torch.Tensor, asize: torch.Tensor, bsets: torch.Te
     return hist
 
 
+# ---- tokens per feature as ordered CSR lists ---------------------------------------------------------------
+def token_lists_workspace_bytes(B: int, H: int) -> int:
+    """Bytes of the row bitmap that a token_lists_count* call leaves for token_lists_fill (the formula of
+    qsae_token_lists_workspace_bytes, in Python so that a fake registration can size the tensor); 0 for an invalid shape."""
+    if B < 0 or H <= 0:
+        return 0
+    W = max(2, 2 * ((B + 63) // 64))
+    return (H * W * 4 + 255) // 256 * 256 + (H * 4 + 255) // 256 * 256
+
+
+def _token_lists_out(B: int, H: int, device):
+    if H <= 0:
+        raise ValueError("H must be positive")
+    offsets = torch.empty((H + 1,), dtype=torch.int64, device=device)
+    # zeroed, not empty: the workspace is an output of the dispatcher op, and its alignment gaps would otherwise differ
+    # from call to call; one pass over a bit per (row, unit)
+    ws = torch.zeros((token_lists_workspace_bytes(B, H),), dtype=torch.uint8, device=device)
+    return offsets, ws
+
+
+@_on_tensor_device
+def token_lists_count(idx: torch.Tensor, val: Optional[torch.Tensor], H: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """First half of a batch's tokens per feature, compact form: -> (offsets int64 [H + 1], workspace uint8).  Row r is
+    active in unit idx[r, j] when val[r, j] > 0 (every entry when val is None); offsets[u + 1] - offsets[u] = active rows
+    of unit u.  The workspace holds the row bitmap for token_lists_fill.  See qsae_token_lists_count."""
+    _dev(idx, "idx", torch.int32)
+    if idx.dim() != 2:
+        raise ValueError("idx: expected int32 [B, k]")
+    B, k = idx.shape
+    if val is not None:
+        _dev(val, "val", torch.float32)
+        if val.shape != idx.shape:
+            raise ValueError("val: expected the shape of idx")
+        val = val.contiguous()
+    idx = idx.contiguous()
+    offsets, ws = _token_lists_out(B, int(H), idx.device)
+    check(_lib.load().qsae_token_lists_count(_p(idx), _p(val), B, k, int(H), _p(offsets), _p(ws), ws.numel(), _stream()))
+    return offsets, ws
+
+
+@_on_tensor_device
+def token_lists_count_bits(zbits: torch.Tensor, H: int, index: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """First half of a batch's tokens per feature, bits form: -> (offsets int64 [H + 1], workspace uint8), offsets in unit
+    order.  zbits int32 [B, words] and ``index`` as in coactivation_bits: packed position -> unit, -1 = pad slot (its
+    bits are ignored); None = identity (32 * words <= H).  See qsae_token_lists_count_bits."""
+    _dev(zbits, "zbits", torch.int32)
+    if zbits.dim() != 2:
+        raise ValueError("zbits: expected int32 [B, words]")
+    B, words = zbits.shape
+    if zbits.stride(1) != 1:
+        zbits = zbits.contiguous()
+    if index is not None:
+        if index.dtype not in (torch.int32, torch.int64):
+            raise TypeError("index: expected int32 or int64")
+        if index.numel() != 32 * words:
+            raise ValueError(f"index: expected {32 * words} entries (one per packed position), got {index.numel()}")
+        index = _dev(index.to(torch.int32).contiguous(), "index", torch.int32)
+    offsets, ws = _token_lists_out(B, int(H), zbits.device)
+    check(_lib.load().qsae_token_lists_count_bits(_p(zbits), zbits.stride(0) if B else words, B, 32 * words, _p(index), int(H),
+                                                  _p(offsets), _p(ws), ws.numel(), _stream()))
+    return offsets, ws
+
+
+@_on_tensor_device
+def token_lists_fill(workspace: torch.Tensor, offsets: torch.Tensor, row_tokens: torch.Tensor, n_entries: int) -> torch.Tensor:
+    """Second half: -> tokens int32 [n_entries], tokens[offsets[u] + rank] = row_tokens[r] for every active (r, u) of the
+    batch whose count call returned (offsets, workspace); n_entries = int(offsets[-1]).  row_tokens int32 [B]."""
+    _dev(workspace, "workspace", torch.uint8)
+    _dev(offsets, "offsets", torch.int64)
+    _dev(row_tokens, "row_tokens", torch.int32)
+    if offsets.dim() != 1 or offsets.numel() < 2 or row_tokens.dim() != 1 or int(n_entries) < 0:
+        raise ValueError("token_lists_fill: offsets int64 [H + 1], row_tokens int32 [B] and n_entries >= 0 expected")
+    B, H = row_tokens.shape[0], offsets.numel() - 1
+    tokens = torch.empty((int(n_entries),), dtype=torch.int32, device=offsets.device)
+    check(_lib.load().qsae_token_lists_fill(_p(workspace), workspace.numel(), _p(offsets.contiguous()),
+                                            _p(row_tokens.contiguous()), B, H, _p(tokens), int(n_entries), _stream()))
+    return tokens
+
+
+@_on_tensor_device
+def token_lists_regroup(batch_offsets: torch.Tensor, segments: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Joins batches: batch_offsets int64 [nb, H + 1] (one row per batch) and segments int32 [nnz] (the batches' tokens
+    back to back, in batch order) -> (offsets int64 [H + 1], tokens int32 [nnz]) feature-major, a feature's segments in
+    batch order.  See qsae_token_lists_regroup."""
+    _dev(batch_offsets, "batch_offsets", torch.int64)
+    _dev(segments, "segments", torch.int32)
+    if batch_offsets.dim() != 2 or batch_offsets.shape[1] < 2 or segments.dim() != 1:
+        raise ValueError("token_lists_regroup: batch_offsets int64 [nb, H + 1] and segments int32 [nnz] expected")
+    nb, H = batch_offsets.shape[0], batch_offsets.shape[1] - 1
+    batch_offsets, segments = batch_offsets.contiguous(), segments.contiguous()
+    offsets = torch.empty((H + 1,), dtype=torch.int64, device=batch_offsets.device)
+    tokens = torch.empty_like(segments)
+    check(_lib.load().qsae_token_lists_regroup(_p(batch_offsets), nb, H, _p(segments), segments.numel(), _p(offsets),
+                                               _p(tokens), _stream()))
+    return offsets, tokens
+
+
 @_on_tensor_device
 def quantize_bits(x: torch.Tensor, n_bits: int, scale_factor: float, signed: bool = True) -> torch.Tensor:
     """n-bit code of every activation as LSB-first 0/1 floats, [B, D * n_bits] (data/dataset.py:76-102)."""

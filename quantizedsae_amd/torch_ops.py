@@ -448,6 +448,52 @@ def _(asets, asize, bsets, bsize, V, k, hist):
     return None
 
 
+@_op("token_lists_count")
+def _token_lists_count(idx: Tensor, val: Optional[Tensor], H: int) -> Tuple[Tensor, Tensor]:
+    return _ops.token_lists_count(idx, val, H)
+
+
+@_op("token_lists_count_bits")
+def _token_lists_count_bits(zbits: Tensor, index: Optional[Tensor], H: int) -> Tuple[Tensor, Tensor]:
+    return _ops.token_lists_count_bits(zbits, H, index)
+
+
+def _token_lists_count_fake(rows, H, like):
+    return (torch.empty((H + 1,), dtype=torch.int64, device=like.device),
+            torch.empty((_ops.token_lists_workspace_bytes(rows, H),), dtype=torch.uint8, device=like.device))
+
+
+@_token_lists_count.register_fake
+def _(idx, val, H):
+    return _token_lists_count_fake(idx.shape[0], H, idx)
+
+
+@_token_lists_count_bits.register_fake
+def _(zbits, index, H):
+    return _token_lists_count_fake(zbits.shape[0], H, zbits)
+
+
+@_op("token_lists_fill")
+def _token_lists_fill(workspace: Tensor, offsets: Tensor, row_tokens: Tensor, n_entries: int) -> Tensor:
+    return _ops.token_lists_fill(workspace, offsets, row_tokens, n_entries)
+
+
+@_token_lists_fill.register_fake
+def _(workspace, offsets, row_tokens, n_entries):
+    return _i32((n_entries,), offsets)
+
+
+@_op("token_lists_regroup")
+def _token_lists_regroup(batch_offsets: Tensor, segments: Tensor) -> Tuple[Tensor, Tensor]:
+    return _ops.token_lists_regroup(batch_offsets, segments)
+
+
+@_token_lists_regroup.register_fake
+def _(batch_offsets, segments):
+    return (torch.empty((batch_offsets.shape[1],), dtype=torch.int64, device=batch_offsets.device),
+            _i32(segments.shape, segments))
+
+
 @_op("quantize_bits")
 def _quantize_bits(x: Tensor, n_bits: int, scale_factor: float, signed: bool) -> Tensor:
     return _ops.quantize_bits(x, n_bits, scale_factor, signed)
@@ -780,6 +826,25 @@ def token_overlap_hist(asets, asize, bsets, bsize, V, k, hist=None):
         hist = torch.zeros((int(k) + 1, 2 * int(k) + 1), dtype=torch.int64, device=asets.device)
     Q.token_overlap_hist(asets, asize, bsets, bsize, int(V), int(k), hist)
     return hist
+
+
+def token_lists_count(idx, val, H):
+    return Q.token_lists_count(idx, val, int(H))
+
+
+def token_lists_count_bits(zbits, H, index=None):
+    return Q.token_lists_count_bits(zbits, index, int(H))
+
+
+def token_lists_fill(workspace, offsets, row_tokens, n_entries):
+    return Q.token_lists_fill(workspace, offsets, row_tokens, int(n_entries))
+
+
+def token_lists_regroup(batch_offsets, segments):
+    return Q.token_lists_regroup(batch_offsets, segments)
+
+
+token_lists_workspace_bytes = _ops.token_lists_workspace_bytes
 
 
 def quantize_bits(x, n_bits, scale_factor, signed=True):
