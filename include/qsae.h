@@ -416,6 +416,45 @@ size_t qsae_coactivation_bits_workspace_bytes(int B, int nbits);
 int qsae_coactivation_bits(const uint32_t* zbits, int64_t words_ld, int B, int nbits, const int32_t* index, int H,
                            int32_t* coact, int64_t ld, void* workspace, size_t workspace_bytes, qsae_stream_t stream);
 
+/* -- co-activation partner sets: one bit per pair (scripts/analysis/summarize_stats.py:37-70) -------------------- */
+/* average_coactivating_features reads `coactivation > 0` only: for every feature, how many other features ever fired
+ * with it.  That is one bit per pair of state, OR-accumulated over calls, instead of an int32 count.
+ * partners is uint32 [P][ld_words] on the device, P = the number of packed positions; bit q & 31 of word q >> 5 of row p
+ * = positions p and q were active in the same row at least once.  The diagonal is included: bit (p, p) = p was active
+ * at all.  ld_words >= P / 32.  The caller zeroes the state; every call ORs into it and clears nothing.  The state
+ * stays in packed-position space; a position -> unit map is applied once, by qsae_coactivation_partner_counts.
+ *
+ * Bits form (threshold models): zbits, words_ld, B, nbits, index and the workspace as in qsae_coactivation_bits (same
+ * bit transpose, same int8-MFMA main loop, same qsae_coactivation_bits_workspace_bytes(B, nbits)); P = nbits.  index is
+ * used only to mask: positions with index[p] < 0 are inert (their bits are ignored and need not be zero, their rows and
+ * columns of partners stay as they are); index == NULL masks nothing.  Rows and words at or past nbits are not
+ * written.  QSAE_ERR_INVALID_ARG before any HIP call; QSAE_ERR_WORKSPACE when the workspace is missing or too small;
+ * B == 0 does nothing. */
+int qsae_coactivation_partners_bits(const uint32_t* zbits, int64_t words_ld, int B, int nbits, const int32_t* index,
+                                    uint32_t* partners, int64_t ld_words, void* workspace, size_t workspace_bytes,
+                                    qsae_stream_t stream);
+/* Compact form (top-k models): positions are units, P = H rounded up to a multiple of 32, ld_words >= ceil(H / 32); bits
+ * at columns >= H are never set.  Row r is active in unit idx[r][j] when val[r][j] > 0 (NaN, 0.0 and -0.0 are not; val
+ * == NULL: every entry); entries outside [0, H) are dropped; 1 <= k <= 256 (QSAE_ERR_INVALID_ARG otherwise).  Bit c of
+ * row a is set for every ordered pair (a, c) of a row's active units.  A unit listed twice in one row sets its bits
+ * once, as the mask has one bit -- unlike qsae_coactivation_sparse, which counts such a unit twice.  B == 0 does
+ * nothing. */
+int qsae_coactivation_partners_sparse(const int32_t* idx, const float* val, int B, int k, int H, uint32_t* partners,
+                                      int64_t ld_words, qsae_stream_t stream);
+/* counts[u(p)] = popcount(row p of partners over words [0, P / 32)) - bit(p, p): the number of other positions that
+ * were ever active together with p, for every p < P whose unit u(p) = index[p] lies in [0, H).  index == NULL: the
+ * identity, over rows p < min(P, H).  counts is int32 [H]; the call clears it on the stream first, so units without a
+ * position get 0.  P a positive multiple of 32, ld_words >= P / 32; two positions must not map to one unit. */
+int qsae_coactivation_partner_counts(const uint32_t* partners, int P, int64_t ld_words, const int32_t* index, int H,
+                                     int32_t* counts, qsae_stream_t stream);
+/* The same count from co-activation counts that already exist as an int32 matrix (a saved dynamic_stats_*.pt, or the
+ * result of qsae_coactivation_bits / _sparse): counts[i] = #{j < H, j != row0 + i : coact[i][j] > 0} for the R rows
+ * row0 .. row0 + R - 1 of the [H][H] matrix, given as a slab int32 [R][ld], ld >= H -- so a matrix that lives on the
+ * host can be streamed through the device slab by slab.  counts is int32 [R], written, not accumulated.  R == 0 does
+ * nothing. */
+int qsae_coactivation_partner_counts_dense(const int32_t* coact, int64_t ld, int R, int H, int64_t row0, int32_t* counts,
+                                           qsae_stream_t stream);
+
 /* -- tokens per feature as ordered CSR lists (scripts/analysis/dynamic_analysis.py:283-306) -------------------- */
 /* tokens_per_feature[f] of the reference holds the token of every row whose mask bit f is set, in ascending row order
  * (the order of mask.nonzero()), batch after batch.  Here it is a CSR pair on the device: offsets int64 [H + 1] with

@@ -103,6 +103,10 @@ SIGNATURES = {
     "qsae_coactivation_sparse": (_i, [_vp, _vp, _i, _i, _i, _vp, _i64, _vp]),
     "qsae_coactivation_bits_workspace_bytes": (_sz, [_i, _i]),
     "qsae_coactivation_bits": (_i, [_vp, _i64, _i, _i, _vp, _i, _vp, _i64, _vp, _sz, _vp]),
+    "qsae_coactivation_partners_bits": (_i, [_vp, _i64, _i, _i, _vp, _vp, _i64, _vp, _sz, _vp]),
+    "qsae_coactivation_partners_sparse": (_i, [_vp, _vp, _i, _i, _i, _vp, _i64, _vp]),
+    "qsae_coactivation_partner_counts": (_i, [_vp, _i, _i64, _vp, _i, _vp, _vp]),
+    "qsae_coactivation_partner_counts_dense": (_i, [_vp, _i64, _i, _i, _i64, _vp, _vp]),
     "qsae_token_lists_workspace_bytes": (_sz, [_i, _i]),
     "qsae_token_lists_count": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "qsae_token_lists_count_bits": (_i, [_vp, _i64, _i, _i, _vp, _i, _vp, _vp, _sz, _vp]),

@@ -9,7 +9,8 @@
 //   2 s + (r >> 5)), zero past B and zero for pad slots (index == -1), so nothing downstream depends on what the
 //   encoder left in them.
 //   One wave transposes 64 rows x 32 units with one __ballot per unit.
-// Stage 2 (coact_bits_mfma_kernel): symmetric rank-B update with v_mfma_i32_32x32x32_i8.  A workgroup of four waves
+// Stage 2 (coact_bits_mfma_kernel, in coactivation_bits.h with the epilogue as a policy; the one here is CoactCountsOut,
+//   coactivation_partners.hip has the other): symmetric rank-B update with v_mfma_i32_32x32x32_i8.  A workgroup of four waves
 //   owns one 256 x 256 tile of packed positions with tile_row <= tile_col, each wave 128 x 128 of it as 4 x 4
 //   accumulator tiles (256 registers).  Per chunk a lane loads 16 bytes per 32-row fragment (a wave reads 1 KiB
 //   contiguous) and expands them to eight 16-byte operands of 0/1 bytes in registers: (word >> d) & 0x01010101, two
@@ -20,17 +21,9 @@
 //   dense update that also rewrites the elements it adds zero to.
 //   When the triangle has too few tiles to fill the chip, chunks are split over gridDim.y and the update is an
 //   int32 atomicAdd (exact, order-free).
-#include "common.h"
+#include "coactivation_bits.h"
 
 namespace qsae {
-
-constexpr int kCoactChunkRows = 256;                        // batch rows per chunk of T
-constexpr int kCoactChunkWords = kCoactChunkRows / 32;      // 8 words = 32 bytes per (chunk, unit)
-constexpr int kCoactTile = 256;                             // packed positions per workgroup tile edge
-constexpr int kCoactTransposeWords = 32;                    // word columns per transpose workgroup
-
-using i32x4 = __attribute__((ext_vector_type(4))) int;
-using i32x16 = __attribute__((ext_vector_type(16))) int;
 
 // T[(chunk * nbits + p) * 8 + 2 s + {0, 1}] = ballot over rows chunk * 256 + 64 s + (0..63) of bit p
 __global__ void __launch_bounds__(256)
@@ -77,140 +70,74 @@ __device__ __forceinline__ int coact_unit(const int32_t* __restrict__ index, int
     return u < H ? u : -1;
 }
 
-// operand `step` (0..7) of a fragment's 16 raw bytes: bits {d, d + 8, d + 16, d + 24} of one word per dword
-__device__ __forceinline__ i32x4 coact_expand(const uint4& raw, int step) {
-    const uint32_t w = (step >> 1) == 0 ? raw.x : (step >> 1) == 1 ? raw.y : (step >> 1) == 2 ? raw.z : raw.w;
-    const int sh = 4 * (step & 1);
-    i32x4 f;
-    f.x = static_cast<int>((w >> sh) & 0x01010101u);
-    f.y = static_cast<int>((w >> (sh + 1)) & 0x01010101u);
-    f.z = static_cast<int>((w >> (sh + 2)) & 0x01010101u);
-    f.w = static_cast<int>((w >> (sh + 3)) & 0x01010101u);
-    return f;
-}
-
-// One 32 x 32 accumulator tile, rows pa.. (A side) by columns pb.. (B side), added to coact and, when `mirror`, its
-// transpose to the mirrored position.  C/D map of the 32x32 MFMA: register t of lane (r, h) is
-// D[i = (t & 3) + 8 (t >> 2) + 4 h][j = r].  `mirror` is uniform over the workgroup (the barriers sit under it).
+// Epilogue of the counts: one 32 x 32 accumulator tile, rows pa.. (A side) by columns pb.. (B side), added to coact and,
+// when `mirror`, its transpose to the mirrored position (C/D map and `mirror`: see coact_bits_mfma_kernel).
 template <bool ATOMIC>
-__device__ __forceinline__ void coact_tile_out(const i32x16& a, int pa, int pb, int r, int h, bool mirror, int* lds,
-                                               const int32_t* __restrict__ index, int nbits, int H,
-                                               int32_t* __restrict__ coact, int64_t ld) {
-    {
-        const int uq = coact_unit(index, pb + r, nbits, H);
-#pragma unroll
-        for (int t = 0; t < 16; ++t) {
-            const int up = coact_unit(index, pa + (t & 3) + 8 * (t >> 2) + 4 * h, nbits, H);
-            if (up >= 0 && uq >= 0) coact_add<ATOMIC>(coact + static_cast<int64_t>(up) * ld + uq, a[t]);
-        }
-    }
-    if (mirror) {
-        __syncthreads();
-#pragma unroll
-        for (int t = 0; t < 16; ++t) lds[((t & 3) + 8 * (t >> 2) + 4 * h) * 33 + r] = a[t];
-        __syncthreads();
-        const int up = coact_unit(index, pa + r, nbits, H);
-#pragma unroll
-        for (int t = 0; t < 16; ++t) {
-            const int j = (t & 3) + 8 * (t >> 2) + 4 * h;
-            const int uq = coact_unit(index, pb + j, nbits, H);
-            if (up >= 0 && uq >= 0) coact_add<ATOMIC>(coact + static_cast<int64_t>(uq) * ld + up, lds[r * 33 + j]);
-        }
-    }
-}
+struct CoactCountsOut {
+    const int32_t* __restrict__ index;
+    int nbits, H;
+    int32_t* __restrict__ coact;
+    int64_t ld;
 
-template <bool ATOMIC>
-__global__ void __launch_bounds__(256)
-coact_bits_mfma_kernel(const uint4* __restrict__ T, int nbits, int nchunks, int chunks_per_split, int ntiles,
-                       const int32_t* __restrict__ index, int H, int32_t* __restrict__ coact, int64_t ld) {
-    __shared__ int xpose[4][32 * 33];
-    // upper-triangular tile (tr <= tc) of this workgroup, row by row
-    int id = blockIdx.x, tr = 0, rowlen = ntiles;
-    while (id >= rowlen) {
-        id -= rowlen;
-        ++tr;
-        --rowlen;
-    }
-    const int tc = tr + id;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int pA0 = tr * kCoactTile + (wave >> 1) * 128, pB0 = tc * kCoactTile + (wave & 1) * 128;
-    const int k0 = blockIdx.y * chunks_per_split;
-    const int k1 = min(nchunks, k0 + chunks_per_split);
-
-    // rows past nbits are clamped to a valid row: what they accumulate is never written
-    int64_t offA[4], offB[4];
+    __device__ __forceinline__ void tile(const i32x16& a, int pa, int pb, int r, int h, bool mirror, int* lds) const {
+        {
+            const int uq = coact_unit(index, pb + r, nbits, H);
 #pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        offA[m] = static_cast<int64_t>(min(pA0 + 32 * m + r, nbits - 1)) * 2 + h;
-        offB[m] = static_cast<int64_t>(min(pB0 + 32 * m + r, nbits - 1)) * 2 + h;
-    }
-    i32x16 acc[4][4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int n = 0; n < 4; ++n) acc[m][n] = i32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-
-    uint4 ra[4], rb[4];
-    if (k0 < k1) {
-        const uint4* base = T + static_cast<int64_t>(k0) * nbits * 2;
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            ra[m] = base[offA[m]];
-            rb[m] = base[offB[m]];
-        }
-    }
-    for (int kc = k0; kc < k1; ++kc) {
-        // next chunk's raw bits (the last iteration reloads its own)
-        const uint4* next = T + static_cast<int64_t>(min(kc + 1, k1 - 1)) * nbits * 2;
-        uint4 na[4], nb[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            na[m] = next[offA[m]];
-            nb[m] = next[offB[m]];
-        }
-        __builtin_amdgcn_sched_barrier(0);                  // keep the prefetch ahead of this chunk's MFMAs
-#pragma unroll
-        for (int step = 0; step < 8; ++step) {
-            i32x4 fa[4], fb[4];
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                fa[m] = coact_expand(ra[m], step);
-                fb[m] = coact_expand(rb[m], step);
+            for (int t = 0; t < 16; ++t) {
+                const int up = coact_unit(index, pa + (t & 3) + 8 * (t >> 2) + 4 * h, nbits, H);
+                if (up >= 0 && uq >= 0) coact_add<ATOMIC>(coact + static_cast<int64_t>(up) * ld + uq, a[t]);
             }
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-#pragma unroll
-                for (int n = 0; n < 4; ++n)
-                    acc[m][n] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[m], fb[n], acc[m][n], 0, 0, 0);
         }
+        if (mirror) {
+            __syncthreads();
 #pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            ra[m] = na[m];
-            rb[m] = nb[m];
+            for (int t = 0; t < 16; ++t) lds[((t & 3) + 8 * (t >> 2) + 4 * h) * 33 + r] = a[t];
+            __syncthreads();
+            const int up = coact_unit(index, pa + r, nbits, H);
+#pragma unroll
+            for (int t = 0; t < 16; ++t) {
+                const int j = (t & 3) + 8 * (t >> 2) + 4 * h;
+                const int uq = coact_unit(index, pb + j, nbits, H);
+                if (up >= 0 && uq >= 0) coact_add<ATOMIC>(coact + static_cast<int64_t>(uq) * ld + up, lds[r * 33 + j]);
+            }
         }
     }
+};
 
-    // every accumulator is named by constants here: a loop over (m, n) that hipcc does not unroll would index the 256
-    // accumulators at run time and so move them all through private memory
-    const bool mirror = tr != tc;                           // a diagonal workgroup tile holds both halves itself
-    int* lds = xpose[wave];
-#define QSAE_COACT_OUT(m, n) \
-    coact_tile_out<ATOMIC>(acc[m][n], pA0 + 32 * (m), pB0 + 32 * (n), r, h, mirror, lds, index, nbits, H, coact, ld)
-#define QSAE_COACT_OUT_ROW(m) \
-    QSAE_COACT_OUT(m, 0);     \
-    QSAE_COACT_OUT(m, 1);     \
-    QSAE_COACT_OUT(m, 2);     \
-    QSAE_COACT_OUT(m, 3)
-    QSAE_COACT_OUT_ROW(0);
-    QSAE_COACT_OUT_ROW(1);
-    QSAE_COACT_OUT_ROW(2);
-    QSAE_COACT_OUT_ROW(3);
-#undef QSAE_COACT_OUT_ROW
-#undef QSAE_COACT_OUT
+int coact_bits_stage(const char* who, const uint32_t* zbits, int64_t words_ld, int B, int nbits, const int32_t* index,
+                     void* workspace, size_t workspace_bytes, qsae_stream_t stream, CoactBitsPlan* plan) {
+    const size_t need = qsae_coactivation_bits_workspace_bytes(B, nbits);
+    if (!workspace || workspace_bytes < need)
+        return fail(QSAE_ERR_WORKSPACE, "%s: workspace too small (%lld < %lld bytes)", who,
+                    static_cast<long long>(workspace_bytes), static_cast<long long>(need));
+    if (!aligned16(workspace))
+        return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: workspace must be 16-byte aligned", who);
+    const int words = nbits / 32;
+    const int nchunks = static_cast<int>(coact_bits_chunks(B));
+    const int wgroups = (words + kCoactTransposeWords - 1) / kCoactTransposeWords;
+    const int ntiles = (nbits + kCoactTile - 1) / kCoactTile;
+    const long long ntri = static_cast<long long>(ntiles) * (ntiles + 1) / 2;
+    if (!(wgroups <= 65535 && ntri <= 0x7FFFFFFFll))
+        return fail(QSAE_ERR_UNSUPPORTED, "%s: unsupported: nbits too large", who);
+
+    hipLaunchKernelGGL(coact_bits_transpose_kernel, dim3(static_cast<unsigned>(nchunks), wgroups), dim3(256), 0,
+                       as_stream(stream), zbits, words_ld, B, words, index, static_cast<uint32_t*>(workspace));
+    QSAE_LAUNCH_CHECK();
+
+    // a triangle too small to fill the chip: split the chunks over gridDim.y (at least 4 chunks per split, about two
+    // workgroups per CU in all) and combine with atomics
+    int splits = 1;
+    if (ntri < 256) {
+        const long long want = (512 + ntri - 1) / ntri;
+        const long long most = (nchunks + 3) / 4;
+        splits = static_cast<int>(want < most ? want : most);
+        if (splits < 1) splits = 1;
+    }
+    const int per = (nchunks + splits - 1) / splits;
+    splits = (nchunks + per - 1) / per;
+    *plan = CoactBitsPlan{nchunks, ntiles, splits, per, ntri};
+    return QSAE_OK;
 }
-
-inline size_t coact_bits_chunks(int B) { return (static_cast<size_t>(B) + kCoactChunkRows - 1) / kCoactChunkRows; }
 
 }  // namespace qsae
 
@@ -231,41 +158,17 @@ extern "C" int qsae_coactivation_bits(const uint32_t* zbits, int64_t words_ld, i
     QSAE_CHECK_ARG(index || nbits <= H, "index == NULL requires nbits <= H");
     if (B == 0) return QSAE_OK;
     QSAE_CHECK_ARG(zbits && coact, "null pointer");
-    const size_t need = qsae_coactivation_bits_workspace_bytes(B, nbits);
-    if (!workspace || workspace_bytes < need)
-        return fail(QSAE_ERR_WORKSPACE, "%s: workspace too small (%lld < %lld bytes)", __func__,
-                    static_cast<long long>(workspace_bytes), static_cast<long long>(need));
-    QSAE_CHECK_ARG(aligned16(workspace), "workspace must be 16-byte aligned");
-    const int words = nbits / 32;
-    const size_t nchunks_sz = coact_bits_chunks(B);
-    const int nchunks = static_cast<int>(nchunks_sz);
-    const int wgroups = (words + kCoactTransposeWords - 1) / kCoactTransposeWords;
-    const int ntiles = (nbits + kCoactTile - 1) / kCoactTile;
-    const long long ntri = static_cast<long long>(ntiles) * (ntiles + 1) / 2;
-    QSAE_CHECK_SUPPORTED(wgroups <= 65535 && ntri <= 0x7FFFFFFFll, "nbits too large");
-
-    hipLaunchKernelGGL(coact_bits_transpose_kernel, dim3(static_cast<unsigned>(nchunks), wgroups), dim3(256), 0,
-                       as_stream(stream), zbits, words_ld, B, words, index, static_cast<uint32_t*>(workspace));
-    QSAE_LAUNCH_CHECK();
-
-    // a triangle too small to fill the chip: split the chunks over gridDim.y (at least 4 chunks per split, about two
-    // workgroups per CU in all) and add with int32 atomics
-    int splits = 1;
-    if (ntri < 256) {
-        const long long want = (512 + ntri - 1) / ntri;
-        const long long most = (nchunks + 3) / 4;
-        splits = static_cast<int>(want < most ? want : most);
-        if (splits < 1) splits = 1;
-    }
-    const int per = (nchunks + splits - 1) / splits;
-    splits = (nchunks + per - 1) / per;
+    CoactBitsPlan plan;
+    const int rc = coact_bits_stage(__func__, zbits, words_ld, B, nbits, index, workspace, workspace_bytes, stream, &plan);
+    if (rc != QSAE_OK) return rc;
     const uint4* T = static_cast<const uint4*>(workspace);
-    if (splits > 1)
-        hipLaunchKernelGGL(coact_bits_mfma_kernel<true>, dim3(static_cast<unsigned>(ntri), splits), dim3(256), 0,
-                           as_stream(stream), T, nbits, nchunks, per, ntiles, index, H, coact, ld);
+    const dim3 grid(static_cast<unsigned>(plan.ntri), plan.splits);
+    if (plan.splits > 1)                                    // int32 atomicAdd: exact, order-free
+        hipLaunchKernelGGL(coact_bits_mfma_kernel<CoactCountsOut<true>>, grid, dim3(256), 0, as_stream(stream), T, nbits,
+                           plan.nchunks, plan.per, plan.ntiles, CoactCountsOut<true>{index, nbits, H, coact, ld});
     else
-        hipLaunchKernelGGL(coact_bits_mfma_kernel<false>, dim3(static_cast<unsigned>(ntri), 1), dim3(256), 0,
-                           as_stream(stream), T, nbits, nchunks, per, ntiles, index, H, coact, ld);
+        hipLaunchKernelGGL(coact_bits_mfma_kernel<CoactCountsOut<false>>, grid, dim3(256), 0, as_stream(stream), T, nbits,
+                           plan.nchunks, plan.per, plan.ntiles, CoactCountsOut<false>{index, nbits, H, coact, ld});
     QSAE_LAUNCH_CHECK();
     return QSAE_OK;
 }

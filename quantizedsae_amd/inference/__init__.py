@@ -16,3 +16,11 @@ from .token_overlap import (  # noqa: F401,E402
     top_token_sets,
 )
 from .token_lists import TokenLists, token_lists_to_python  # noqa: F401,E402
+from .coactivation_partners import CoactivationPartners  # noqa: F401,E402
+from .summary import (  # noqa: F401,E402
+    average_coactivating_features,
+    count_below_threshold,
+    level_sizes,
+    summarize_activation_counts,
+    summarize_sae,
+)

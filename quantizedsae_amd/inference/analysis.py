@@ -21,6 +21,7 @@ import torch
 from .. import torch_ops as ops          # torch.ops.qsae.* (dispatcher ops over the C ABI)
 from ..sae import (BaselineSparseAutoencoder, BinarySAE, QuantizedMatryoshkaSAE, ResidualQuantizedSAE)
 from .framework import SAEWrapper, _ensure_tensor, compute_reconstruction_error  # noqa: F401  (re-export)
+from .coactivation_partners import CoactivationPartners
 from .token_lists import TokenLists, check_token_ids
 
 
@@ -106,14 +107,19 @@ def _packed_index(stages) -> Optional[torch.Tensor]:
     return torch.cat(maps).to(torch.int32)
 
 
-def _threshold_stats(model, x: torch.Tensor, H: int, counts: torch.Tensor, coact: torch.Tensor, with_tokens: bool,
-                     lists: Optional[TokenLists] = None, batch_tok: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+def _threshold_stats(model, x: torch.Tensor, H: int, counts: torch.Tensor, coact: Optional[torch.Tensor], with_tokens: bool,
+                     lists: Optional[TokenLists] = None, batch_tok: Optional[torch.Tensor] = None,
+                     partners: Optional[CoactivationPartners] = None) -> Optional[torch.Tensor]:
     """counts / coact += this batch's activation statistics of a threshold model, from the packed bits; ``lists`` takes
-    the batch's tokens per feature from the same bits.  Returns the bool mask [B, H] (on the device) when the tokens per
-    feature are wanted as Python lists, else None: nothing else needs it."""
+    the batch's tokens per feature and ``partners`` its co-activation bits from the same bits (``coact`` None: no
+    counts matrix).  Returns the bool mask [B, H] (on the device) when the tokens per feature are wanted as Python
+    lists, else None: nothing else needs it."""
     zb, index = _packed_bits(model, x)
     counts += _packed_counts_to_units(ops.activation_counts_bits(zb), index, H)
-    ops.coactivation_bits(zb, H, index, coact)
+    if coact is not None:
+        ops.coactivation_bits(zb, H, index, coact)
+    if partners is not None:
+        partners.add_bits(zb, index)
     if lists is not None:
         lists.add_bits(zb, index, batch_tok)
     return _bits_to_mask(zb, index, H) if with_tokens else None
@@ -128,6 +134,25 @@ def _token_lists_mode(with_tokens, token_ids: torch.Tensor) -> bool:
         raise ValueError(f'with_tokens: expected True, False or "csr", got {with_tokens!r}')
     check_token_ids(token_ids)
     return True
+
+
+def _coactivation_mode(coactivation, H: int, dev):
+    """(int32 [H, H] counts or None, CoactivationPartners or None) for ``coactivation="counts" | "partners" | None``"""
+    if coactivation is None:
+        return None, None
+    if coactivation == "counts":
+        return torch.zeros((H, H), dtype=torch.int32, device=dev), None
+    if coactivation == "partners":
+        return None, CoactivationPartners(H, dev)
+    raise ValueError(f'coactivation: expected "counts", "partners" or None, got {coactivation!r}')
+
+
+def _coactivation_result(coact: Optional[torch.Tensor], partners: Optional[CoactivationPartners]) -> Dict[str, Any]:
+    out: Dict[str, Any] = {"coactivation": None if coact is None else coact.cpu()}
+    if partners is not None:
+        out["coactivation_partner_counts"] = partners.counts().cpu()
+        out["coactivation_partners"] = partners
+    return out
 
 
 def activation_indices(sae: SAEWrapper, x: torch.Tensor):
@@ -227,11 +252,16 @@ def _tokens_per_feature(feat: torch.Tensor, tok: torch.Tensor, H: int, into: Lis
 
 def compute_activation_stats(sae: SAEWrapper, loader: Iterable[Any], *, token_ids: torch.Tensor,
                              tokens_per_context: int, device: Optional[Any] = None,
-                             with_tokens: Union[bool, str] = True) -> Dict[str, Any]:
+                             with_tokens: Union[bool, str] = True,
+                             coactivation: Optional[str] = "counts") -> Dict[str, Any]:
     """activation_counts [H] (int64), coactivation [H,H] (int32, mask^T mask) and tokens_per_feature
     (dynamic_analysis.py:255-311).  Counts are accumulated on the device and copied to the host once.
     ``with_tokens="csr"``: tokens_per_feature is the tuple (offsets int64 [H + 1], tokens int32 [nnz]) on the SAE's device,
-    in the reference's order, as ``top_token_sets`` / ``jaccard_histogram`` take it."""
+    in the reference's order, as ``top_token_sets`` / ``jaccard_histogram`` take it.
+    ``coactivation="partners"``: the [H, H] matrix is never allocated; ``coactivation`` is None and the result has
+    ``coactivation_partner_counts`` (int64 [H] on the host: the number of other features each feature ever fired
+    with, what ``summary.average_coactivating_features`` needs) and ``coactivation_partners`` (the
+    ``CoactivationPartners`` state on the device).  ``coactivation=None`` skips co-activation altogether."""
     csr = _token_lists_mode(with_tokens, token_ids)
     if device is not None:
         sae.to(device)
@@ -240,7 +270,7 @@ def compute_activation_stats(sae: SAEWrapper, loader: Iterable[Any], *, token_id
     H = _hidden_dim(sae)
     dev = sae.device
     counts = torch.zeros((H,), dtype=torch.int64, device=dev)
-    coact = torch.zeros((H, H), dtype=torch.int32, device=dev)
+    coact, partners = _coactivation_mode(coactivation, H, dev)
     lists = TokenLists(H, dev) if csr else None
     tokens_per_feature: List[List[int]] = [] if csr else [[] for _ in range(H)]
     with_lists = with_tokens is True
@@ -255,7 +285,10 @@ def compute_activation_stats(sae: SAEWrapper, loader: Iterable[Any], *, token_id
             if compact:
                 idx, val = activation_indices(sae, x)
                 ops.activation_counts(idx, val, H, counts)
-                ops.coactivation_sparse(idx, val, H, coact)
+                if coact is not None:
+                    ops.coactivation_sparse(idx, val, H, coact)
+                if partners is not None:
+                    partners.add_compact(idx, val)
                 if csr:
                     lists.add_compact(idx, val, batch_tok)
                 elif with_lists:
@@ -266,12 +299,12 @@ def compute_activation_stats(sae: SAEWrapper, loader: Iterable[Any], *, token_id
                 # threshold variants: hundreds to thousands of active units per row, so mask^T mask is a dense rank-B
                 # update (dynamic_analysis.py:405-415) -- of single bits: formed from the packed encoder output on the
                 # int8 matrix pipe (qsae_coactivation_bits), exact in int32, without a [B, H] mask in memory
-                mask = _threshold_stats(model, x, H, counts, coact, with_lists, lists, batch_tok)
+                mask = _threshold_stats(model, x, H, counts, coact, with_lists, lists, batch_tok, partners)
                 if with_lists:
                     nz = mask.nonzero(as_tuple=False)
                     _tokens_per_feature(nz[:, 1], batch_tok.to(dev)[nz[:, 0]], H, tokens_per_feature)
             global_index += B
-    return {"activation_counts": counts.cpu(), "coactivation": coact.cpu(),
+    return {"activation_counts": counts.cpu(), **_coactivation_result(coact, partners),
             "tokens_per_feature": lists.finish() if csr else tokens_per_feature}
 
 
@@ -307,13 +340,16 @@ def compute_reconstruction_error_by_level(sae: SAEWrapper, loader: Iterable[Any]
 
 
 def analyze_dataset(sae: SAEWrapper, loader: Iterable[Any], *, token_ids: torch.Tensor, tokens_per_context: int,
-                    device: Optional[Any] = None, with_tokens: Union[bool, str] = True) -> Dict[str, Any]:
+                    device: Optional[Any] = None, with_tokens: Union[bool, str] = True,
+                    coactivation: Optional[str] = "counts") -> Dict[str, Any]:
     """One pass over the data: final reconstruction MSE, activation counts, co-activation matrix and tokens per
     feature (dynamic_analysis.py:317-440; same result keys, ``mse_per_level`` / ``l0_per_level`` are None there
     too).  Top-k variants run ``forward_compact`` once per batch and feed its (idx, val, reconstruction) to the
     integer kernels and the fp64 squared-error sum; the threshold variants take the reconstruction from the
     forward pass and the masks from the bit-packed encoder output.  ``with_tokens="csr"``: tokens_per_feature is the
-    CSR tuple on the SAE's device (see ``compute_activation_stats``), built without a mask or a Python list."""
+    CSR tuple on the SAE's device (see ``compute_activation_stats``), built without a mask or a Python list.
+    ``coactivation``: "counts" (the int32 matrix), "partners" (one bit per pair on the device and the partner counts) or
+    None, as in ``compute_activation_stats``."""
     csr = _token_lists_mode(with_tokens, token_ids)
     if device is not None:
         sae.to(device)
@@ -322,7 +358,7 @@ def analyze_dataset(sae: SAEWrapper, loader: Iterable[Any], *, token_ids: torch.
     H = _hidden_dim(sae)
     dev = sae.device
     counts = torch.zeros((H,), dtype=torch.int64, device=dev)
-    coact = torch.zeros((H, H), dtype=torch.int32, device=dev)
+    coact, partners = _coactivation_mode(coactivation, H, dev)
     sq = torch.zeros((), dtype=torch.float64, device=dev)
     lists = TokenLists(H, dev) if csr else None
     tokens_per_feature: List[List[int]] = [] if csr else [[] for _ in range(H)]
@@ -340,7 +376,10 @@ def analyze_dataset(sae: SAEWrapper, loader: Iterable[Any], *, token_ids: torch.
                 idx, val, recon = model.forward_compact(x)
                 ops.sq_err_sum(recon, x, sq)
                 ops.activation_counts(idx, val, H, counts)
-                ops.coactivation_sparse(idx, val, H, coact)
+                if coact is not None:
+                    ops.coactivation_sparse(idx, val, H, coact)
+                if partners is not None:
+                    partners.add_compact(idx, val)
                 if csr:
                     lists.add_compact(idx, val, batch_tok)
                 elif with_lists:
@@ -349,12 +388,12 @@ def analyze_dataset(sae: SAEWrapper, loader: Iterable[Any], *, token_ids: torch.
                     _tokens_per_feature(idx[on].long(), batch_tok.to(dev)[rows], H, tokens_per_feature)
             else:
                 ops.sq_err_sum(sae(x)["reconstruction"].to(dev).contiguous(), x, sq)
-                mask = _threshold_stats(model, x, H, counts, coact, with_lists, lists, batch_tok)
+                mask = _threshold_stats(model, x, H, counts, coact, with_lists, lists, batch_tok, partners)
                 if with_lists:
                     nz = mask.nonzero(as_tuple=False)
                     _tokens_per_feature(nz[:, 1], batch_tok.to(dev)[nz[:, 0]], H, tokens_per_feature)
             global_index += B
             n_elements += x.numel()
     return {"mse_final": float(sq.item()) / max(n_elements, 1), "mse_per_level": None, "l0_per_level": None,
-            "activation_counts": counts.cpu(), "coactivation": coact.cpu(),
+            "activation_counts": counts.cpu(), **_coactivation_result(coact, partners),
             "tokens_per_feature": lists.finish() if csr else tokens_per_feature}

@@ -974,6 +974,98 @@ def coactivation_bits(zbits: torch.Tensor, H: int, index: Optional[torch.Tensor]
     return coact
 
 
+def _partners_state(partners: Optional[torch.Tensor], P: int, device) -> torch.Tensor:
+    """the partner-set state int32 [P, >= P / 32] (int32 words stand in for uint32), allocated zeroed when None"""
+    if partners is None:
+        return torch.zeros((P, P // 32), dtype=torch.int32, device=device)
+    _dev(partners, "partners", torch.int32)
+    if partners.dim() != 2 or partners.shape[0] != P or partners.shape[1] < P // 32 or partners.stride(1) != 1:
+        raise ValueError(f"partners: expected an int32 [{P}, >= {P // 32}] matrix with unit column stride")
+    return partners
+
+
+def _packed_index_arg(index: Optional[torch.Tensor], nbits: int) -> Optional[torch.Tensor]:
+    if index is None:
+        return None
+    if index.dtype not in (torch.int32, torch.int64):
+        raise TypeError("index: expected int32 or int64")
+    if index.numel() != nbits:
+        raise ValueError(f"index: expected {nbits} entries (one per packed position), got {index.numel()}")
+    return _dev(index.to(torch.int32).contiguous(), "index", torch.int32)
+
+
+@_on_tensor_device
+def coactivation_partners_bits(zbits: torch.Tensor, index: Optional[torch.Tensor] = None,
+                               partners: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """partners |= "packed positions p and q were set in the same row": bit q & 31 of word q >> 5 of row p, diagonal
+    included (qsae_coactivation_partners_bits; the main loop of coactivation_bits with a one-bit epilogue).  zbits int32
+    [B, words], a column slice of a wider tensor is read in place; ``index`` (int32 / int64 [32 * words]) only masks:
+    positions with index < 0 are inert.  The state is int32 [32 * words, >= words] in packed-position order, zeroed by
+    the caller (allocated when None); ``coactivation_partner_counts`` applies the map."""
+    _dev(zbits, "zbits", torch.int32)
+    B, words = zbits.shape
+    if zbits.stride(1) != 1:
+        zbits = zbits.contiguous()
+    index = _packed_index_arg(index, 32 * words)
+    partners = _partners_state(partners, 32 * words, zbits.device)
+    lib = _lib.load()
+    need = int(lib.qsae_coactivation_bits_workspace_bytes(B, 32 * words)) if B > 0 else 0
+    ws = _workspace(zbits.device, max(need, 1))
+    check(lib.qsae_coactivation_partners_bits(_p(zbits), zbits.stride(0) if B else words, B, 32 * words, _p(index),
+                                              _p(partners), partners.stride(0), _p(ws), ws.numel(), _stream()))
+    return partners
+
+
+@_on_tensor_device
+def coactivation_partners_sparse(idx: torch.Tensor, val: Optional[torch.Tensor], H: int,
+                                 partners: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """partners |= "units a and c were active in the same row" from the compact (idx, val) form (active: val > 0; every
+    listed entry when val is None; entries outside [0, H) are dropped; a unit listed twice sets its bits once).
+    int32 [P, >= P / 32] with P = H rounded up to 32; 1 <= k <= 256."""
+    _dev(idx, "idx", torch.int32)
+    B, k = idx.shape
+    if val is not None:
+        _dev(val, "val", torch.float32)
+    H = int(H)
+    partners = _partners_state(partners, (H + 31) // 32 * 32, idx.device)
+    check(_lib.load().qsae_coactivation_partners_sparse(_p(idx.contiguous()),
+                                                        _p(val.contiguous()) if val is not None else None, B, k, H,
+                                                        _p(partners), partners.stride(0), _stream()))
+    return partners
+
+
+@_on_tensor_device
+def coactivation_partner_counts(partners: torch.Tensor, H: int, index: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int64 [H]: for every unit, the number of other units that were ever active together with it -- the popcount of
+    its row of ``partners`` minus the diagonal bit, in unit order (``index``: packed position -> unit, -1 = none; None =
+    identity).  Units without a position get 0."""
+    _dev(partners, "partners", torch.int32)
+    if partners.dim() != 2 or partners.shape[0] % 32 or partners.shape[1] < partners.shape[0] // 32 or partners.stride(1) != 1:
+        raise ValueError("partners: expected an int32 [P, >= P / 32] matrix, P a multiple of 32, with unit column stride")
+    P, H = partners.shape[0], int(H)
+    index = _packed_index_arg(index, P)
+    counts = torch.empty((H,), dtype=torch.int32, device=partners.device)
+    check(_lib.load().qsae_coactivation_partner_counts(_p(partners), P, partners.stride(0), _p(index), H, _p(counts),
+                                                       _stream()))
+    return counts.long()
+
+
+@_on_tensor_device
+def coactivation_partner_counts_dense(coact: torch.Tensor, row0: int = 0) -> torch.Tensor:
+    """int64 [R]: counts[i] = #{j != row0 + i : coact[i, j] > 0} for the slab ``coact`` int32 [R, H] of rows row0 ..
+    row0 + R - 1 of an [H, H] co-activation matrix (the partner counts of statistics that exist as counts)."""
+    _dev(coact, "coact", torch.int32)
+    if coact.dim() != 2 or coact.shape[1] == 0:
+        raise ValueError("coact: expected an int32 [R, H] matrix")
+    if coact.stride(1) != 1:
+        coact = coact.contiguous()
+    R, H = coact.shape
+    counts = torch.empty((R,), dtype=torch.int32, device=coact.device)
+    check(_lib.load().qsae_coactivation_partner_counts_dense(_p(coact), coact.stride(0) if R > 1 else H, R, H, int(row0),
+                                                             _p(counts), _stream()))
+    return counts.long()
+
+
 def _bitsets(sets: torch.Tensor, size: torch.Tensor, words: int, name: str):
     _dev(sets, f"{name}sets", torch.int32)
     _dev(size, f"{name}size", torch.int32)

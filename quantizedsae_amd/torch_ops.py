@@ -438,6 +438,46 @@ def _(zbits, index, coact):
     return None
 
 
+@_op("coactivation_partners_bits", mutates=("partners",))
+def _coactivation_partners_bits(zbits: Tensor, index: Optional[Tensor], partners: Tensor) -> None:
+    _ops.coactivation_partners_bits(zbits, index, partners)
+
+
+@_coactivation_partners_bits.register_fake
+def _(zbits, index, partners):
+    return None
+
+
+@_op("coactivation_partners_sparse", mutates=("partners",))
+def _coactivation_partners_sparse(idx: Tensor, val: Optional[Tensor], H: int, partners: Tensor) -> None:
+    _ops.coactivation_partners_sparse(idx, val, H, partners)
+
+
+@_coactivation_partners_sparse.register_fake
+def _(idx, val, H, partners):
+    return None
+
+
+@_op("coactivation_partner_counts")
+def _coactivation_partner_counts(partners: Tensor, H: int, index: Optional[Tensor]) -> Tensor:
+    return _ops.coactivation_partner_counts(partners, H, index)
+
+
+@_coactivation_partner_counts.register_fake
+def _(partners, H, index):
+    return torch.empty((H,), dtype=torch.int64, device=partners.device)
+
+
+@_op("coactivation_partner_counts_dense")
+def _coactivation_partner_counts_dense(coact: Tensor, row0: int) -> Tensor:
+    return _ops.coactivation_partner_counts_dense(coact, row0)
+
+
+@_coactivation_partner_counts_dense.register_fake
+def _(coact, row0):
+    return torch.empty((coact.shape[0],), dtype=torch.int64, device=coact.device)
+
+
 @_op("token_overlap_hist", mutates=("hist",))
 def _token_overlap_hist(asets: Tensor, asize: Tensor, bsets: Tensor, bsize: Tensor, V: int, k: int, hist: Tensor) -> None:
     _ops.token_overlap_hist(asets, asize, bsets, bsize, V, k, hist)
@@ -819,6 +859,29 @@ def coactivation_bits(zbits, H, index=None, coact=None):
         return _ops.coactivation_bits(zbits, H, index, coact)
     Q.coactivation_bits(zbits, index, coact)
     return coact
+
+
+def coactivation_partners_bits(zbits, index=None, partners=None):
+    if partners is None:
+        partners = torch.zeros((32 * zbits.shape[1], zbits.shape[1]), dtype=torch.int32, device=zbits.device)
+    Q.coactivation_partners_bits(zbits, index, partners)
+    return partners
+
+
+def coactivation_partners_sparse(idx, val, H, partners=None):
+    if partners is None:
+        words = (int(H) + 31) // 32
+        partners = torch.zeros((32 * words, words), dtype=torch.int32, device=idx.device)
+    Q.coactivation_partners_sparse(idx, val, int(H), partners)
+    return partners
+
+
+def coactivation_partner_counts(partners, H, index=None):
+    return Q.coactivation_partner_counts(partners, int(H), index)
+
+
+def coactivation_partner_counts_dense(coact, row0=0):
+    return Q.coactivation_partner_counts_dense(coact, int(row0))
 
 
 def token_overlap_hist(asets, asize, bsets, bsize, V, k, hist=None):
