@@ -550,6 +550,30 @@ int qsae_cosine_compare(const float* A, int64_t lda, int Ha, const float* B, int
                         unsigned long long* counts, unsigned long long* hist, float* out, int64_t out_ld,
                         void* workspace, size_t workspace_bytes, qsae_stream_t stream);
 
+/* -- nearest atoms of an integer dictionary (src/quantized_sae/utils/inspector.py:47-67, 110-121) ------------- */
+/* The k nearest atoms (cosine) of every atom of A among the atoms of B, for int8 dictionaries (ternary, n-bit two's
+ * complement), without the [Na][Nb] matrix.  a [Na][a_ld], b [Nb][b_ld] int8 on the device; b == NULL is self mode
+ * (B = A; b_ld and Nb are ignored).  Arithmetic, exact and order-free:
+ *   nsq[i] = sum_d a[i][d]^2 (int32);  inv[i] = fp32(1 / sqrt(fp64(nsq[i]))), 1.0f for an all-zero atom (cosine 0 with
+ *   everything, itself included);  dot(i, j) exact in int32;  c(i, j) = fp32(dot) * (inva[i] * invb[j]) -- the two
+ *   inverse norms multiplied first, so c(i, j) and c(j, i) of one dictionary are the same bits.
+ * keys [Na][k] (u64, overwritten): row i holds its k largest keys (order-preserving bits of c) << 32 | ~j in
+ * descending order -- largest cosine first, equal bits to the lowest index; 0 = none, where fewer than k candidates
+ * exist.  Keys of a row are distinct, so the result does not depend on tiling, grid or column split.
+ * exclude_self != 0 skips j == i.  duplicate_of (int32 [Na], nullable, overwritten): the lowest j with atom j
+ * identical to atom i (i itself when there is none lower), tested as dot(i, j) == nsq[i] == nsq[j]; all-zero atoms
+ * are identical among themselves.  Both need self mode: QSAE_ERR_INVALID_ARG otherwise.
+ * Limits: 1 <= k <= 64, D a multiple of 32 in [32, 4096] (zero-pad: padding changes no dot product and no norm),
+ * otherwise QSAE_ERR_UNSUPPORTED; strides >= D and multiples of 16, pointers 16-byte aligned.  Bytes of a row at or
+ * past D are not read.  Na == 0 or Nb == 0: nothing to do, no pointer is looked at.  QSAE_ERR_INVALID_ARG /
+ * QSAE_ERR_UNSUPPORTED before any HIP call; QSAE_ERR_WORKSPACE when the workspace is missing or too small.
+ * workspace: 16-byte aligned, qsae_nearest_atoms_i8_workspace_bytes(Na, Nb, D, k) bytes (norms of both sides and the
+ * partial lists of a column split; self mode: pass Nb = Na; 0 for an invalid shape; monotone in Na, Nb and k). */
+size_t qsae_nearest_atoms_i8_workspace_bytes(int Na, int Nb, int D, int k);
+int qsae_nearest_atoms_i8(const int8_t* a, int64_t a_ld, int Na, const int8_t* b, int64_t b_ld, int Nb, int D, int k,
+                          int exclude_self, uint64_t* keys, int32_t* duplicate_of, void* workspace,
+                          size_t workspace_bytes, qsae_stream_t stream);
+
 /* -- BinarySAE training: the gradient of the soft-decoder forward (sae/binary.py:24-47, 91-103) ----------------- */
 /* Device workspace of qsae_binary_soft_table_polarize (0 for an invalid shape). */
 size_t qsae_binary_soft_table_polarize_workspace_bytes(int H, int D);

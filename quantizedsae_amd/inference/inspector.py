@@ -1,0 +1,158 @@
+"""Inspection of an integer dictionary on the GPU: the k nearest atoms of every atom, duplicates, value counts.
+
+Reference: src/quantized_sae/utils/inspector.py (``TernarySparseAutoencoderInspector``).  Its nearest-feature query
+forms the [H, H] fp32 cosine matrix with ``torch.mm``, copies it to numpy and hands it to sklearn; here one call of
+``qsae_nearest_atoms_i8`` (csrc/dictionary_neighbors.hip) contracts the int8 atoms on the matrix pipe and keeps k keys
+per row, so no [H, H] matrix exists.  The dictionaries are integers (ternary {-1, 0, +1}; BinarySAE's n-bit two's
+complement table), so every dot product and every squared norm is exact and the ranking needs no tolerance: the
+arithmetic is spelled out in DESIGN.md 4.18.  Two deliberate differences from the reference: the k columns are
+returned and not the matrix, and equal cosines are ordered by the lowest index (sklearn's order there is unspecified).
+For fp32 dictionaries (baseline, matryoshka, residual) use ``compare_decoders``.
+"""
+from __future__ import annotations
+
+from typing import Any, Dict, Sequence
+
+import torch
+
+from .. import torch_ops as T
+from ..sae.binary import BinarySAE
+from ..sae.ternary import STEWeights, TernarySparseAutoencoder
+from .dictionary import _decode_keys, _model
+
+__all__ = ["integer_atoms", "nearest_atoms", "DictionaryInspector"]
+
+
+def _pad32(a: torch.Tensor) -> torch.Tensor:
+    pad = -a.shape[1] % 32
+    return torch.nn.functional.pad(a, (0, pad)) if pad else a
+
+
+def _integer_atoms(sae) -> torch.Tensor:
+    """integer_atoms without the padding."""
+    if isinstance(sae, torch.Tensor):
+        if sae.dtype != torch.int8 or sae.dim() != 2:
+            raise TypeError(f"integer_atoms: a tensor must be int8 [N, D], got {sae.dtype} {tuple(sae.shape)}")
+        return sae
+    model = _model(sae)
+    with torch.no_grad():
+        if isinstance(model, BinarySAE):
+            if model.n_bits > 8:
+                raise TypeError(f"integer_atoms: BinarySAE with n_bits = {model.n_bits} > 8 does not fit int8; "
+                                "use compare_decoders (fp32)")
+            return model.decoder.quantized_int_weights().to(torch.int8)
+        ste = model.decoder if isinstance(model, TernarySparseAutoencoder) else model
+        if isinstance(ste, STEWeights):
+            w = ste.weight.detach()
+            hard = torch.sign(w) * (torch.abs(w) >= ste.threshold)
+            return hard.t().to(torch.int8).contiguous()
+    raise TypeError(f"integer_atoms: {type(model).__name__} has no integer dictionary; use compare_decoders for the "
+                    "fp32 dictionaries")
+
+
+def integer_atoms(sae) -> torch.Tensor:
+    """The dictionary as int8 ``[N, Dp]`` on the model's device, D zero-padded to a multiple of 32 (padding changes
+    no dot product and no norm).
+
+      * BinarySAE with ``n_bits <= 8``: ``decoder.quantized_int_weights()``;
+      * TernarySparseAutoencoder or ``STEWeights``: ``sign(w) * (|w| >= threshold)`` transposed to ``[H, D]``
+        (inspector.py:32-39);
+      * an int8 tensor ``[N, D]`` passes through (padded).
+    Any other model raises TypeError: its dictionary is fp32, ``compare_decoders`` is the route."""
+    return _pad32(_integer_atoms(sae))
+
+
+def nearest_atoms(lhs, rhs=None, k: int = 10, *, include_self: bool = True) -> Dict[str, Any]:
+    """The ``k`` nearest atoms (cosine) of every atom of ``lhs`` among the atoms of ``rhs`` (None: ``lhs`` itself).
+    ``lhs`` / ``rhs`` are SAEs with an integer dictionary or int8 atom tensors (``integer_atoms``).
+
+    Result (tensors on the device):
+      similarity  fp32 [Na, k]   c = fp32(dot) * (inv_a * inv_b), largest first; an all-zero atom has cosine 0 with
+                                 everything, itself included (the reference's safe_norms)
+      index       int64 [Na, k]  equal cosine bits go to the lowest index; past the candidates: -inf / -1
+      distance    fp32 [Na, k]   clamp(1 - similarity, min=0) (inspector.py:57-58)
+    self mode only:
+      duplicate_of        int32 [Na]  the lowest index holding an identical atom (the atom's own where none is lower)
+      n_duplicate_groups  int         distinct atoms that occur more than once (what ``count_duplicates`` returns)
+    ``include_self=True`` keeps j == i in self mode, as sklearn on a precomputed matrix does (the reference's callers
+    drop column 0 themselves); ``include_self=False`` is valid in self mode only.  A different D or device raises
+    ValueError."""
+    a = integer_atoms(lhs)
+    b = None
+    if rhs is not None:
+        b = integer_atoms(rhs)
+        if a.device != b.device:
+            raise ValueError(f"atoms live on different devices ({a.device} vs {b.device})")
+        if a.shape[1] != b.shape[1]:
+            raise ValueError(f"atoms have different sizes (D = {a.shape[1]} vs {b.shape[1]})")
+        if not include_self:
+            raise ValueError("include_self=False is valid in self mode only (rhs=None)")
+    keys, dup = T.nearest_atoms_i8(a, b, int(k), exclude_self=not include_self, want_duplicates=b is None)
+    sim, idx = _decode_keys(keys)
+    out: Dict[str, Any] = {"similarity": sim, "index": idx, "distance": torch.clamp(1.0 - sim, min=0.0)}
+    if b is None:
+        out["duplicate_of"] = dup
+        out["n_duplicate_groups"] = int(torch.unique(dup[dup != torch.arange(dup.numel(), device=dup.device)]).numel())
+    return out
+
+
+class DictionaryInspector:
+    """``TernarySparseAutoencoderInspector`` (utils/inspector.py) for any integer dictionary, with the reference's
+    method names and meanings.  ``sae`` is an SAE (wrapper or module) with an integer dictionary, or int8 atoms."""
+
+    def __init__(self, sae):
+        self.atoms = _integer_atoms(sae)                    # int8 [N, D], unpadded (the kernel call pads)
+        self.dictionary_in_ternary = self.atoms             # the reference's attribute name
+
+    def get_feature(self, feature_idx):
+        return self.atoms[feature_idx]
+
+    def calculate_k_nearest_features_cluster(self, k, type="cosine"):
+        """-> ``(distances [N, k], indices [N, k])``: each atom's k nearest atoms, itself included (column 0 unless a
+        duplicate with a lower index precedes it).  Unlike the reference, ``distances`` holds the k columns that belong
+        to ``indices`` and not the [N, N] matrix, and equal distances are ordered by index.  ``type="cosine"``:
+        ``clamp(1 - c, 0)``; ``type="euclidean"``: the distance of the normalised atoms, ``sqrt(clamp(2 - 2c, 0))`` --
+        with an all-zero atom the reference's ``cdist`` ordering is no longer a function of the cosine: ValueError."""
+        if type not in ("cosine", "euclidean"):
+            raise ValueError(f"type must be 'cosine' or 'euclidean', got {type!r}")
+        if type == "euclidean" and self.zero_entries() > 0:
+            raise ValueError("euclidean neighbours are not defined by the cosine when the dictionary has an all-zero atom")
+        res = nearest_atoms(self.atoms, None, k)
+        if type == "cosine":
+            return res["distance"], res["index"]
+        return torch.sqrt(torch.clamp(2.0 - 2.0 * res["similarity"], min=0.0)), res["index"]
+
+    def _unit(self, f) -> torch.Tensor:
+        v = self.atoms[f].to(torch.float32)
+        n = torch.linalg.norm(v)
+        return v / torch.where(n == 0, torch.ones_like(n), n)
+
+    def distance(self, f1, f2, type="cosine"):
+        u, v = self._unit(f1), self._unit(f2)
+        if type == "cosine":
+            return 1 - u @ v
+        if type == "euclidean":
+            return torch.sqrt(torch.sum((u - v) ** 2))
+        raise ValueError(f"type must be 'cosine' or 'euclidean', got {type!r}")
+
+    def analyze_ternary_distribution(self) -> Dict[int, int]:
+        """{value: count} for whatever integer values occur (the reference prints the counts of -1, 0 and +1)."""
+        vals, counts = torch.unique(self.atoms, return_counts=True)
+        return {int(v): int(c) for v, c in zip(vals.tolist(), counts.tolist())}
+
+    def zero_entries(self) -> int:
+        return int((self.atoms == 0).all(dim=1).sum().item())
+
+    def count_duplicates(self) -> int:
+        return nearest_atoms(self.atoms, None, 1)["n_duplicate_groups"]
+
+    def check_same_entries(self, indices: Sequence[int]):
+        if len(indices) < 2:
+            return []
+        matching = self.atoms[indices[0]] == self.atoms[indices[1]]
+        for i in indices[2:]:
+            matching = (self.atoms[i] == self.atoms[indices[0]]) & matching
+        return int(matching.sum().item()), torch.nonzero(matching, as_tuple=True)
+
+    def sparsity_rate(self) -> float:
+        return float((self.atoms == 0).sum().item()) / self.atoms.numel()

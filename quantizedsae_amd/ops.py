@@ -1293,6 +1293,60 @@ def cosine_compare(A: torch.Tensor, B: Optional[torch.Tensor], thresholds=(), bi
     return row_best, col_best, moments, extrema, counts, hist, matrix
 
 
+# ---- nearest atoms of an int8 dictionary ---------------------------------------------------------------------------
+NEAREST_MAX_K, NEAREST_MAX_D = 64, 4096
+
+
+def _atoms_i8(t: torch.Tensor, name: str) -> torch.Tensor:
+    """int8 [N, D] atoms as the kernel reads them: unit inner stride, row stride a multiple of 16 bytes, 16-byte aligned
+    (a column slice of a wider aligned tensor is read in place; anything else is copied)."""
+    _dev(t, name, torch.int8)
+    if t.dim() != 2:
+        raise ValueError(f"{name}: expected [N, D] atoms, got shape {tuple(t.shape)}")
+    if t.shape[0] and (t.stride(1) != 1 or t.stride(0) % 16 or t.stride(0) < t.shape[1] or t.data_ptr() % 16):
+        t = t.contiguous()
+        if t.data_ptr() % 16:
+            t = t.clone()
+    return t
+
+
+@_on_tensor_device
+def nearest_atoms_i8(a: torch.Tensor, b: Optional[torch.Tensor] = None, k: int = 10, exclude_self: bool = False,
+                     want_duplicates: bool = False):
+    """The k nearest atoms (cosine) of every row of a among the rows of b (None: a itself), int8 [N, D] with D a
+    multiple of 32 in [32, 4096], on the int8 matrix pipe (qsae_nearest_atoms_i8; the arithmetic is spelled out in
+    include/qsae.h).  Returns (keys int64 [Na, k], duplicate_of int32 [Na] or None): a row's keys descend, 0 = none.
+    exclude_self and want_duplicates need self mode."""
+    k = int(k)
+    self_mode = b is None
+    a = _atoms_i8(a, "a")
+    if not self_mode:
+        if b.device != a.device:
+            raise ValueError(f"a and b are on different devices ({a.device}, {b.device})")
+        b = _atoms_i8(b, "b")
+        if b.shape[1] != a.shape[1]:
+            raise ValueError(f"a and b must be [N, D] atoms of the same D ({tuple(a.shape)}, {tuple(b.shape)})")
+        if exclude_self or want_duplicates:
+            raise ValueError("nearest_atoms_i8: exclude_self / want_duplicates need self mode (b=None)")
+    if not 1 <= k <= NEAREST_MAX_K:
+        raise ValueError(f"nearest_atoms_i8: 1 <= k <= {NEAREST_MAX_K} required")
+    Na, D = a.shape
+    if D % 32 or not 32 <= D <= NEAREST_MAX_D:
+        raise ValueError(f"nearest_atoms_i8: D must be a multiple of 32 in [32, {NEAREST_MAX_D}] (zero-pad), got {D}")
+    Nb = Na if self_mode else b.shape[0]
+    keys = torch.empty((Na, k), dtype=torch.int64, device=a.device)
+    dup = torch.empty((Na,), dtype=torch.int32, device=a.device) if want_duplicates else None
+    lib = _lib.load()
+    need = int(lib.qsae_nearest_atoms_i8_workspace_bytes(Na, Nb, D, k)) if Na and Nb else 0
+    ws = _workspace(a.device, max(need, 1))
+    check(lib.qsae_nearest_atoms_i8(_p(a), a.stride(0) if Na else D, Na, None if self_mode else _p(b),
+                                    (b.stride(0) if Nb else D) if not self_mode else 0, Nb, D, k,
+                                    1 if exclude_self else 0, _p(keys), _p(dup), _p(ws), ws.numel(), _stream()))
+    if Na and not Nb:
+        keys.zero_()
+    return keys, dup
+
+
 # ---- BinarySAE training (the gradient of the soft-decoder forward) ---------------------------------------------------
 # Workspaces come from the caching allocator per call (not the shared _workspaces cache: a backward may run on another
 # thread than the forward).

@@ -564,6 +564,20 @@ def _(A, B, thresholds, bins, want_matrix):
             _f32((Ha, Hb) if want_matrix else (0, 0), A))
 
 
+@_op("nearest_atoms_i8")
+def _nearest_atoms_i8(a: Tensor, b: Optional[Tensor], k: int, exclude_self: bool,
+                      want_duplicates: bool) -> Tuple[Tensor, Tensor]:
+    """-> (keys int64 [Na, k], duplicate_of int32 [Na] or [0]); keys as in qsae_nearest_atoms_i8"""
+    keys, dup = _ops.nearest_atoms_i8(a, b, k, exclude_self, want_duplicates)
+    return keys, (dup if dup is not None else _i32((0,), a))
+
+
+@_nearest_atoms_i8.register_fake
+def _(a, b, k, exclude_self, want_duplicates):
+    return (torch.empty((a.shape[0], k), dtype=torch.int64, device=a.device),
+            _i32((a.shape[0] if want_duplicates else 0,), a))
+
+
 # ---- BinarySAE training ----------------------------------------------------------------------------------------------
 @_op("binary_soft_table_polarize")
 def _binary_soft_table_polarize(logits: Tensor, D: int, n_bits: int) -> Tuple[Tensor, Tensor]:
@@ -916,6 +930,11 @@ def quantize_bits(x, n_bits, scale_factor, signed=True):
 
 def cosine_compare(A, B=None, thresholds=(), bins=0, want_matrix=False):
     return Q.cosine_compare(A, B, [float(t) for t in thresholds], int(bins), bool(want_matrix))
+
+
+def nearest_atoms_i8(a, b=None, k=10, exclude_self=False, want_duplicates=False):
+    keys, dup = Q.nearest_atoms_i8(a, b, int(k), bool(exclude_self), bool(want_duplicates))
+    return keys, (dup if want_duplicates else None)
 
 
 def binary_soft_table_polarize(logits, D, n_bits):
