@@ -574,6 +574,32 @@ int qsae_nearest_atoms_i8(const int8_t* a, int64_t a_ld, int Na, const int8_t* b
                           int exclude_self, uint64_t* keys, int32_t* duplicate_of, void* workspace,
                           size_t workspace_bytes, qsae_stream_t stream);
 
+/* -- nearest atoms of an fp32 dictionary (scripts/analysis/analyze_sae.py:59-91 followed by a top-k) ----------- */
+/* The k nearest atoms (cosine) of every atom of A among the atoms of B, for fp32 dictionaries, without the [Na][Nb]
+ * matrix.  a [Na][a_ld], b [Nb][b_ld] fp32 on the device; b == NULL is self mode (B = A; b_ld and Nb are ignored).
+ * Arithmetic, every step fixed:
+ *   inv[i] = what qsae_atom_inv_norms computes: fp32(1 / max(sqrt(fp64 sum of squares), 1e-12)), so an all-zero atom
+ *   has cosine +0 with everything, itself included;  acc(i, j) = the fmaf chain over d ascending from +0 (the bits of
+ *   qsae_cosine_compare's accumulator);  c(i, j) = acc * (inva[i] * invb[j]) -- the two inverse norms multiplied
+ *   first, so c(i, j) and c(j, i) of one dictionary are the same bits.
+ * keys [Na][k] (u64, overwritten): row i holds its k largest keys (order-preserving bits of c, -0 as +0) << 32 | ~j in
+ * descending order -- largest cosine first, equal bits to the lowest index; 0 = none, where fewer than k candidates
+ * exist.  Keys of a row are distinct, so the result does not depend on tiling, grid or candidate split.
+ * exclude_self != 0 skips j == i and needs self mode: QSAE_ERR_INVALID_ARG otherwise.  There is no duplicate_of here:
+ * identity of fp32 vectors cannot be decided from rounded dot products.  Atoms with a non-finite component give
+ * unspecified neighbours for the rows and columns they touch (never an access out of range).
+ * Limits: 1 <= k <= 64 and D a positive multiple of 4 (zero-pad), otherwise QSAE_ERR_UNSUPPORTED; strides >= D and
+ * multiples of 4, pointers 16-byte aligned.  Floats of a row at or past D are not read.  Na == 0 or Nb == 0: nothing
+ * to do, no pointer is looked at.  QSAE_ERR_INVALID_ARG / QSAE_ERR_UNSUPPORTED before any HIP call;
+ * QSAE_ERR_WORKSPACE when the workspace is missing or too small.
+ * workspace: 16-byte aligned, qsae_nearest_atoms_f32_workspace_bytes(Na, Nb, D, k) bytes (inverse norms of both sides
+ * and the partial lists of a candidate split; self mode: pass Nb = Na; 0 for an invalid shape; monotone in Na, Nb
+ * and k). */
+size_t qsae_nearest_atoms_f32_workspace_bytes(int Na, int Nb, int D, int k);
+int qsae_nearest_atoms_f32(const float* a, int64_t a_ld, int Na, const float* b, int64_t b_ld, int Nb, int D, int k,
+                           int exclude_self, uint64_t* keys, void* workspace, size_t workspace_bytes,
+                           qsae_stream_t stream);
+
 /* -- BinarySAE training: the gradient of the soft-decoder forward (sae/binary.py:24-47, 91-103) ----------------- */
 /* Device workspace of qsae_binary_soft_table_polarize (0 for an invalid shape). */
 size_t qsae_binary_soft_table_polarize_workspace_bytes(int H, int D);

@@ -369,7 +369,8 @@ static int run_cosine(const float* A, int64_t lda, int Ha, const float* B, int64
     return launch_cosine<LA>(A, lda, Ha, B, ldb, Hb, D, ea, map, static_cast<long long>(map.tiles_n) * map.msplit, s);
 }
 
-static int launch_inv_norms(const float* atoms, int64_t ld, int H, int Hpad, int D, float* inv, hipStream_t s) {
+// also called by dictionary_neighbors_f32.hip
+int launch_inv_norms(const float* atoms, int64_t ld, int H, int Hpad, int D, float* inv, hipStream_t s) {
     hipLaunchKernelGGL(atom_inv_norms_kernel, dim3(static_cast<unsigned>((Hpad + 3) / 4)), dim3(256), 0, s, atoms, ld, H,
                        Hpad, D, inv);
     QSAE_LAUNCH_CHECK();

@@ -1,7 +1,8 @@
 // topk_lists.h -- per-row top-k lists of 64-bit keys kept in LDS by one workgroup, and the merge of partial lists.
 // Nothing here knows what a key means beyond "larger wins, keys of one row are distinct, 0 = none" (full_key() of
 // common.h: order-preserving bits of an fp32 value << 32 | ~index), so any contraction whose epilogue can form such
-// keys can feed it (dictionary_neighbors.hip: the int8 cosine; an fp32 instantiation would sit on gemm_nt_f32_kernel).
+// keys can feed it (dictionary_neighbors.hip: the int8 cosine; dictionary_neighbors_f32.hip: the fp32 cosine as an epilogue
+// of gemm_nt_f32_kernel).
 //
 // A workgroup of 256 threads owns kTopkListRows rows.  Between two merges a row can take at most kTopkListBuf
 // appends: the CALLER bounds that by construction (it merges after every slab of the tile that offers a row no more
@@ -10,6 +11,9 @@
 // into the new sorted list and refreshes the row's fp32 threshold (the k-th value once the list is full), which is
 // what the caller's cheap filter `value >= thr[row]` compares against.  The filter is only conservative: the merge is
 // an exact top-k of distinct keys, so the result does not depend on the order of appends, tiles or splits.
+// The buffer's capacity is a template parameter of append and merge (kBuf, default kTopkListBuf): a caller that keeps the
+// buffer somewhere smaller than topk_lists_carve() lays out points L.buf there itself and offers a row no more than kBuf
+// products per round.
 #pragma once
 #include "common.h"
 
@@ -22,7 +26,7 @@ constexpr int kTopkMergeMaxSplits = 8;  // partial lists per row that topk_lists
 
 struct TopkLists {
     unsigned long long* list;           // [rows][k] descending, the first nlist[row] valid
-    unsigned long long* buf;            // [rows][kTopkListBuf] unordered appends since the last merge
+    unsigned long long* buf;            // [rows][kBuf] unordered appends since the last merge
     float* thr;                         // -inf until the list is full, then the value of its k-th key; +inf: dead row
     int* cnt;                           // appends since the last merge
     int* nlist;
@@ -60,15 +64,18 @@ __device__ __forceinline__ void topk_lists_init(const TopkLists& L, int rows) {
     __syncthreads();
 }
 
+template <int kBuf = kTopkListBuf>
 __device__ __forceinline__ void topk_lists_append(const TopkLists& L, int row, unsigned long long key) {
     const int slot = atomicAdd(L.cnt + row, 1);
-    if (slot < kTopkListBuf) L.buf[row * kTopkListBuf + slot] = key;   // always true under the caller's bound
+    if (slot < kBuf) L.buf[row * kBuf + slot] = key;   // always true under the caller's bound
 }
 
 // All 256 threads.  Wave w merges rows 32 w .. 32 w + 31 that took an append: every lane holds up to two keys of
 // list + buffer, ranks them by counting the larger ones (the loop reads are wave-uniform LDS broadcasts) and writes
 // the keys of rank < k back to the list.  Barriers on both sides.
+template <int kBuf = kTopkListBuf>
 __device__ __forceinline__ void topk_lists_merge(const TopkLists& L) {
+    static_assert(kTopkListMaxK + kBuf <= 128, "list + buffer must fit two keys per lane");
     __syncthreads();
     const int lane = threadIdx.x & 63, row0 = (threadIdx.x >> 6) * 32;
     const int k = L.k;
@@ -76,9 +83,9 @@ __device__ __forceinline__ void topk_lists_merge(const TopkLists& L) {
     while (todo) {
         const int rl = row0 + __ffsll(static_cast<long long>(todo)) - 1;
         todo &= todo - 1;
-        const int n = L.nlist[rl], c = min(L.cnt[rl], kTopkListBuf), total = n + c;
+        const int n = L.nlist[rl], c = min(L.cnt[rl], kBuf), total = n + c;
         unsigned long long* list = L.list + rl * k;
-        const unsigned long long* buf = L.buf + rl * kTopkListBuf;
+        const unsigned long long* buf = L.buf + rl * kBuf;
         const int x1 = lane + 64;
         const unsigned long long e0 = lane < total ? (lane < n ? list[lane] : buf[lane - n]) : 0ull;
         const unsigned long long e1 = x1 < total ? (x1 < n ? list[x1] : buf[x1 - n]) : 0ull;
@@ -118,7 +125,8 @@ __device__ __forceinline__ void topk_lists_store(const TopkLists& L, int rows, u
 
 // partial [S][N][k] (each list descending, 0-padded) -> out [N][k]: the k largest of a row's S k distinct keys,
 // descending, 0-padded.  One wave per row, four rows per workgroup; S <= kTopkMergeMaxSplits, k <= kTopkListMaxK.
-__global__ void __launch_bounds__(256)
+// static: every unit that includes this header has its own copy.
+static __global__ void __launch_bounds__(256)
 topk_lists_merge_kernel(const unsigned long long* __restrict__ partial, int S, int N, int k,
                         unsigned long long* __restrict__ out) {
     __shared__ unsigned long long keys[4][kTopkMergeMaxSplits * kTopkListMaxK];

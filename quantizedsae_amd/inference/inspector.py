@@ -1,4 +1,4 @@
-"""Inspection of an integer dictionary on the GPU: the k nearest atoms of every atom, duplicates, value counts.
+"""Inspection of a dictionary on the GPU: the k nearest atoms of every atom, duplicates, value counts.
 
 Reference: src/quantized_sae/utils/inspector.py (``TernarySparseAutoencoderInspector``).  Its nearest-feature query
 forms the [H, H] fp32 cosine matrix with ``torch.mm``, copies it to numpy and hands it to sklearn; here one call of
@@ -7,7 +7,9 @@ per row, so no [H, H] matrix exists.  The dictionaries are integers (ternary {-1
 complement table), so every dot product and every squared norm is exact and the ranking needs no tolerance: the
 arithmetic is spelled out in DESIGN.md 4.18.  Two deliberate differences from the reference: the k columns are
 returned and not the matrix, and equal cosines are ordered by the lowest index (sklearn's order there is unspecified).
-For fp32 dictionaries (baseline, matryoshka, residual) use ``compare_decoders``.
+fp32 dictionaries (baseline, matryoshka, residual, a BinarySAE wider than 8 bits, or any pair with one such side) take
+``qsae_nearest_atoms_f32`` (csrc/dictionary_neighbors_f32.hip): the same keys from the exact-fp32 contraction that
+``compare_decoders`` uses, k per row instead of one.
 """
 from __future__ import annotations
 
@@ -18,7 +20,7 @@ import torch
 from .. import torch_ops as T
 from ..sae.binary import BinarySAE
 from ..sae.ternary import STEWeights, TernarySparseAutoencoder
-from .dictionary import _decode_keys, _model
+from .dictionary import _decode_keys, _model, decoder_atoms
 
 __all__ = ["integer_atoms", "nearest_atoms", "DictionaryInspector"]
 
@@ -62,9 +64,57 @@ def integer_atoms(sae) -> torch.Tensor:
     return _pad32(_integer_atoms(sae))
 
 
-def nearest_atoms(lhs, rhs=None, k: int = 10, *, include_self: bool = True) -> Dict[str, Any]:
+def _is_integer(side) -> bool:
+    """Whether ``integer_atoms`` accepts this side."""
+    if isinstance(side, torch.Tensor):
+        return side.dtype == torch.int8
+    model = _model(side)
+    if isinstance(model, BinarySAE):
+        return model.n_bits <= 8
+    return isinstance(model.decoder if isinstance(model, TernarySparseAutoencoder) else model, STEWeights)
+
+
+def _fp32_atoms(side) -> torch.Tensor:
+    """The dictionary as fp32 ``[N, D]``, unpadded: ``decoder_atoms`` of a model; an fp32 tensor passes through, an
+    int8 tensor is converted."""
+    if isinstance(side, torch.Tensor):
+        if side.dtype not in (torch.float32, torch.int8) or side.dim() != 2:
+            raise TypeError(f"nearest_atoms: a tensor must be fp32 or int8 [N, D], got {side.dtype} {tuple(side.shape)}")
+        return side.float() if side.dtype == torch.int8 else side
+    return decoder_atoms(side)
+
+
+def _pad4(a: torch.Tensor) -> torch.Tensor:
+    pad = -a.shape[1] % 4
+    return torch.nn.functional.pad(a, (0, pad)) if pad else a
+
+
+def _nearest_atoms_fp32(lhs, rhs, k: int, include_self: bool) -> Dict[str, Any]:
+    a = _fp32_atoms(lhs)
+    b = None
+    if rhs is not None:
+        b = _fp32_atoms(rhs)
+        if a.device != b.device:
+            raise ValueError(f"atoms live on different devices ({a.device} vs {b.device})")
+        if a.shape[1] != b.shape[1]:
+            raise ValueError(f"atoms have different sizes (D = {a.shape[1]} vs {b.shape[1]})")
+        if not include_self:
+            raise ValueError("include_self=False is valid in self mode only (rhs=None)")
+        b = _pad4(b)                                         # a zero column changes no chain and no norm
+    keys = T.nearest_atoms_f32(_pad4(a), b, int(k), exclude_self=not include_self)
+    sim, idx = _decode_keys(keys)
+    return {"similarity": sim, "index": idx, "distance": torch.clamp(1.0 - sim, min=0.0)}
+
+
+def nearest_atoms(lhs, rhs=None, k: int = 10, *, include_self: bool = True, atoms: str = "auto") -> Dict[str, Any]:
     """The ``k`` nearest atoms (cosine) of every atom of ``lhs`` among the atoms of ``rhs`` (None: ``lhs`` itself).
-    ``lhs`` / ``rhs`` are SAEs with an integer dictionary or int8 atom tensors (``integer_atoms``).
+    ``lhs`` / ``rhs`` are SAEs or atom tensors ``[N, D]`` (int8 or fp32).
+
+    ``atoms="auto"``: when both sides are integer (int8 tensors, or models ``integer_atoms`` accepts) the int8 path
+    below; otherwise, and always with ``atoms="fp32"``, the fp32 path on ``decoder_atoms`` (an int8 tensor is converted,
+    D is zero-padded to a multiple of 4): ``c = acc * (inv_a * inv_b)`` with the exact fmaf chain and the inverse norms
+    of ``compare_decoders``.  The fp32 result has ``similarity``, ``index`` and ``distance`` and no
+    ``duplicate_of`` / ``n_duplicate_groups``: identity of fp32 vectors is not decidable from rounded dot products.
 
     Result (tensors on the device):
       similarity  fp32 [Na, k]   c = fp32(dot) * (inv_a * inv_b), largest first; an all-zero atom has cosine 0 with
@@ -77,6 +127,10 @@ def nearest_atoms(lhs, rhs=None, k: int = 10, *, include_self: bool = True) -> D
     ``include_self=True`` keeps j == i in self mode, as sklearn on a precomputed matrix does (the reference's callers
     drop column 0 themselves); ``include_self=False`` is valid in self mode only.  A different D or device raises
     ValueError."""
+    if atoms not in ("auto", "fp32"):
+        raise ValueError(f"atoms must be 'auto' or 'fp32', got {atoms!r}")
+    if atoms == "fp32" or not (_is_integer(lhs) and (rhs is None or _is_integer(rhs))):
+        return _nearest_atoms_fp32(lhs, rhs, k, include_self)
     a = integer_atoms(lhs)
     b = None
     if rhs is not None:
@@ -97,11 +151,13 @@ def nearest_atoms(lhs, rhs=None, k: int = 10, *, include_self: bool = True) -> D
 
 
 class DictionaryInspector:
-    """``TernarySparseAutoencoderInspector`` (utils/inspector.py) for any integer dictionary, with the reference's
-    method names and meanings.  ``sae`` is an SAE (wrapper or module) with an integer dictionary, or int8 atoms."""
+    """``TernarySparseAutoencoderInspector`` (utils/inspector.py) for any dictionary, with the reference's method names
+    and meanings.  ``sae`` is an SAE (wrapper or module) or atoms ``[N, D]``: an integer dictionary (or int8 atoms) is
+    held as int8, any other as fp32 (``decoder_atoms``)."""
 
     def __init__(self, sae):
-        self.atoms = _integer_atoms(sae)                    # int8 [N, D], unpadded (the kernel call pads)
+        # int8 or fp32 [N, D], unpadded (the kernel call pads)
+        self.atoms = _integer_atoms(sae) if _is_integer(sae) else _fp32_atoms(sae)
         self.dictionary_in_ternary = self.atoms             # the reference's attribute name
 
     def get_feature(self, feature_idx):
@@ -137,6 +193,8 @@ class DictionaryInspector:
 
     def analyze_ternary_distribution(self) -> Dict[int, int]:
         """{value: count} for whatever integer values occur (the reference prints the counts of -1, 0 and +1)."""
+        if self.atoms.dtype != torch.int8:
+            raise TypeError("analyze_ternary_distribution: the dictionary is fp32, not integer")
         vals, counts = torch.unique(self.atoms, return_counts=True)
         return {int(v): int(c) for v, c in zip(vals.tolist(), counts.tolist())}
 
@@ -144,6 +202,9 @@ class DictionaryInspector:
         return int((self.atoms == 0).all(dim=1).sum().item())
 
     def count_duplicates(self) -> int:
+        if self.atoms.dtype != torch.int8:
+            _, counts = torch.unique(self.atoms, dim=0, return_counts=True)
+            return int((counts > 1).sum().item())
         return nearest_atoms(self.atoms, None, 1)["n_duplicate_groups"]
 
     def check_same_entries(self, indices: Sequence[int]):

@@ -1347,6 +1347,55 @@ def nearest_atoms_i8(a: torch.Tensor, b: Optional[torch.Tensor] = None, k: int =
     return keys, dup
 
 
+# ---- nearest atoms of an fp32 dictionary ---------------------------------------------------------------------------
+def _atoms_f32(t: torch.Tensor, name: str) -> torch.Tensor:
+    """fp32 [N, D] atoms as the kernel reads them: unit inner stride, row stride a multiple of 4 floats, 16-byte aligned
+    (a column slice of a wider aligned tensor is read in place; anything else is copied)."""
+    _dev(t, name, torch.float32)
+    if t.dim() != 2:
+        raise ValueError(f"{name}: expected [N, D] atoms, got shape {tuple(t.shape)}")
+    if t.shape[0] and (t.stride(1) != 1 or t.stride(0) % 4 or t.stride(0) < t.shape[1] or t.data_ptr() % 16):
+        t = t.contiguous()
+        if t.data_ptr() % 16:
+            t = t.clone()
+    return t
+
+
+@_on_tensor_device
+def nearest_atoms_f32(a: torch.Tensor, b: Optional[torch.Tensor] = None, k: int = 10,
+                      exclude_self: bool = False) -> torch.Tensor:
+    """The k nearest atoms (cosine) of every row of a among the rows of b (None: a itself), fp32 [N, D] with D a
+    multiple of 4, on the exact-fp32 matrix pipe (qsae_nearest_atoms_f32; the arithmetic is spelled out in
+    include/qsae.h).  Returns keys int64 [Na, k]: a row's keys descend, 0 = none.  exclude_self needs self mode."""
+    k = int(k)
+    self_mode = b is None
+    a = _atoms_f32(a, "a")
+    if not self_mode:
+        if b.device != a.device:
+            raise ValueError(f"a and b are on different devices ({a.device}, {b.device})")
+        b = _atoms_f32(b, "b")
+        if b.shape[1] != a.shape[1]:
+            raise ValueError(f"a and b must be [N, D] atoms of the same D ({tuple(a.shape)}, {tuple(b.shape)})")
+        if exclude_self:
+            raise ValueError("nearest_atoms_f32: exclude_self needs self mode (b=None)")
+    if not 1 <= k <= NEAREST_MAX_K:
+        raise ValueError(f"nearest_atoms_f32: 1 <= k <= {NEAREST_MAX_K} required")
+    Na, D = a.shape
+    if D <= 0 or D % 4:
+        raise ValueError(f"nearest_atoms_f32: D must be a positive multiple of 4 (zero-pad), got {D}")
+    Nb = Na if self_mode else b.shape[0]
+    keys = torch.empty((Na, k), dtype=torch.int64, device=a.device)
+    lib = _lib.load()
+    need = int(lib.qsae_nearest_atoms_f32_workspace_bytes(Na, Nb, D, k)) if Na and Nb else 0
+    ws = _workspace(a.device, max(need, 1))
+    check(lib.qsae_nearest_atoms_f32(_p(a), a.stride(0) if Na else D, Na, None if self_mode else _p(b),
+                                     (b.stride(0) if Nb else D) if not self_mode else 0, Nb, D, k,
+                                     1 if exclude_self else 0, _p(keys), _p(ws), ws.numel(), _stream()))
+    if Na and not Nb:
+        keys.zero_()
+    return keys
+
+
 # ---- BinarySAE training (the gradient of the soft-decoder forward) ---------------------------------------------------
 # Workspaces come from the caching allocator per call (not the shared _workspaces cache: a backward may run on another
 # thread than the forward).

@@ -578,6 +578,17 @@ def _(a, b, k, exclude_self, want_duplicates):
             _i32((a.shape[0] if want_duplicates else 0,), a))
 
 
+@_op("nearest_atoms_f32")
+def _nearest_atoms_f32(a: Tensor, b: Optional[Tensor], k: int, exclude_self: bool) -> Tensor:
+    """-> keys int64 [Na, k] as in qsae_nearest_atoms_f32"""
+    return _ops.nearest_atoms_f32(a, b, k, exclude_self)
+
+
+@_nearest_atoms_f32.register_fake
+def _(a, b, k, exclude_self):
+    return torch.empty((a.shape[0], k), dtype=torch.int64, device=a.device)
+
+
 # ---- BinarySAE training ----------------------------------------------------------------------------------------------
 @_op("binary_soft_table_polarize")
 def _binary_soft_table_polarize(logits: Tensor, D: int, n_bits: int) -> Tuple[Tensor, Tensor]:
@@ -930,6 +941,10 @@ def quantize_bits(x, n_bits, scale_factor, signed=True):
 
 def cosine_compare(A, B=None, thresholds=(), bins=0, want_matrix=False):
     return Q.cosine_compare(A, B, [float(t) for t in thresholds], int(bins), bool(want_matrix))
+
+
+def nearest_atoms_f32(a, b=None, k=10, exclude_self=False):
+    return Q.nearest_atoms_f32(a, b, int(k), bool(exclude_self))
 
 
 def nearest_atoms_i8(a, b=None, k=10, exclude_self=False, want_duplicates=False):
