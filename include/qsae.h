@@ -600,6 +600,41 @@ int qsae_nearest_atoms_f32(const float* a, int64_t a_ld, int Na, const float* b,
                            int exclude_self, uint64_t* keys, void* workspace, size_t workspace_bytes,
                            qsae_stream_t stream);
 
+/* -- k-means over dictionary atoms (utils/inspector.py:137-165 k_means_analysis) ------------------------------- */
+/* The assign step of Lloyd's algorithm without the [N][C] matrix.  atoms [N][a_ld], centers [C][c_ld] fp32 on the
+ * device.  keys [N] (u64, overwritten): keys[i] = the largest (order-preserving bits of s(i, j), -0 as +0) << 32 | ~j
+ * over j < C -- the largest score, equal bits to the lowest center; 0 = every score of the atom was NaN.
+ * Scores, every step fixed:  acc(i, j) = the fmaf chain over d ascending from +0;
+ *   metric 0 (cosine):     s = acc * (inv_a[i] * inv_c[j]), inv = what qsae_atom_inv_norms computes -- the bits of
+ *                          qsae_nearest_atoms_f32(atoms, centers, k = 1); an all-zero atom or center has cosine +0;
+ *   metric 1 (euclidean):  s = acc - h[j], h[j] = fp32(0.5 * nsq64[j]), nsq64 = the fp64 sum of squares of center j in
+ *                          qsae_atom_inv_norms' order; one separately rounded subtraction.  The largest s is the
+ *                          smallest |atom - center|^2.
+ * The result does not depend on tiling, grid or the split of the centers (a maximum of distinct integers).
+ * Limits: D a positive multiple of 4 (zero-pad), otherwise QSAE_ERR_UNSUPPORTED; C >= 1; strides >= D and multiples
+ * of 4; atoms, centers and workspace 16-byte aligned.  Floats of a row at or past D are not read.  N == 0: nothing to
+ * do, no pointer is looked at.  QSAE_ERR_INVALID_ARG / QSAE_ERR_UNSUPPORTED before any HIP call; QSAE_ERR_WORKSPACE when
+ * the workspace is missing or too small.
+ * workspace: qsae_kmeans_assign_f32_workspace_bytes(N, C, D) bytes (per-atom and per-center scale, padded to the tile;
+ * 0 for an invalid shape; monotone in N, C and D). */
+size_t qsae_kmeans_assign_f32_workspace_bytes(int N, int C, int D);
+int qsae_kmeans_assign_f32(const float* atoms, int64_t a_ld, int N, const float* centers, int64_t c_ld, int C, int D,
+                           int metric, uint64_t* keys, void* workspace, size_t workspace_bytes, qsae_stream_t stream);
+/* The update step.  labels [N] int32: the cluster of every atom; a label outside [0, C) belongs to no cluster.
+ * counts [C] int32, centers_new [C][new_ld], stats [2] double = {center_shift, n_empty}: all overwritten (floats of a
+ * centers_new row at or past D are not written).  Members of a cluster are taken in ascending atom index; sum64[c][d] is
+ * built from chunks of 64 consecutive members, each an fp64 chain from 0.0 in member order, the chunk partials added in
+ * chunk order from 0.0; centers_new[c][d] = fp32(sum64 / count).  An empty cluster keeps centers_old[c] and counts in
+ * n_empty.  center_shift = sum over c of sqrt(sum over d of (double(new) - double(old))^2) in fp64, in the fixed orders
+ * DESIGN.md 4.20 states.  No float atomics: the same bits every run.
+ * Limits, alignment, N == 0 and error codes as above; the three row strides are checked alike.
+ * workspace: qsae_kmeans_update_f32_workspace_bytes(N, C, D) bytes (member bitmap C * ceil(N / 32) words, member
+ * lists, chunk partials (N / 64 + C) * D doubles; 0 for an invalid shape; monotone in N, C and D). */
+size_t qsae_kmeans_update_f32_workspace_bytes(int N, int C, int D);
+int qsae_kmeans_update_f32(const float* atoms, int64_t a_ld, int N, int D, const int32_t* labels, int C,
+                           const float* centers_old, int64_t old_ld, float* centers_new, int64_t new_ld, int32_t* counts,
+                           double* stats, void* workspace, size_t workspace_bytes, qsae_stream_t stream);
+
 /* -- BinarySAE training: the gradient of the soft-decoder forward (sae/binary.py:24-47, 91-103) ----------------- */
 /* Device workspace of qsae_binary_soft_table_polarize (0 for an invalid shape). */
 size_t qsae_binary_soft_table_polarize_workspace_bytes(int H, int D);

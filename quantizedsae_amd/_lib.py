@@ -123,6 +123,10 @@ SIGNATURES = {
     "qsae_nearest_atoms_i8": (_i, [_vp, _i64, _i, _vp, _i64, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "qsae_nearest_atoms_f32_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "qsae_nearest_atoms_f32": (_i, [_vp, _i64, _i, _vp, _i64, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "qsae_kmeans_assign_f32_workspace_bytes": (_sz, [_i, _i, _i]),
+    "qsae_kmeans_assign_f32": (_i, [_vp, _i64, _i, _vp, _i64, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "qsae_kmeans_update_f32_workspace_bytes": (_sz, [_i, _i, _i]),
+    "qsae_kmeans_update_f32": (_i, [_vp, _i64, _i, _i, _vp, _i, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "qsae_binary_soft_table_polarize_workspace_bytes": (_sz, [_i, _i]),
     "qsae_binary_soft_table_polarize": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "qsae_train_csr_workspace_bytes": (_sz, [_i, _i, _i]),

@@ -9,6 +9,7 @@ from .framework import (  # noqa: F401
 )
 from .dictionary import compare_decoders, decoder_atoms, decoder_cosine_similarity  # noqa: F401,E402
 from .inspector import DictionaryInspector, integer_atoms, nearest_atoms  # noqa: F401,E402
+from .clustering import kmeans_atoms  # noqa: F401,E402
 from .token_overlap import (  # noqa: F401,E402
     JaccardHistogram,
     TokenSets,

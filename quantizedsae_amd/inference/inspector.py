@@ -9,7 +9,8 @@ arithmetic is spelled out in DESIGN.md 4.18.  Two deliberate differences from th
 returned and not the matrix, and equal cosines are ordered by the lowest index (sklearn's order there is unspecified).
 fp32 dictionaries (baseline, matryoshka, residual, a BinarySAE wider than 8 bits, or any pair with one such side) take
 ``qsae_nearest_atoms_f32`` (csrc/dictionary_neighbors_f32.hip): the same keys from the exact-fp32 contraction that
-``compare_decoders`` uses, k per row instead of one.
+``compare_decoders`` uses, k per row instead of one.  ``k_means_analysis`` clusters the atoms with
+``kmeans_atoms`` (inference/clustering.py) in place of ``kmeans_pytorch`` on the CPU.
 """
 from __future__ import annotations
 
@@ -217,3 +218,53 @@ class DictionaryInspector:
 
     def sparsity_rate(self) -> float:
         return float((self.atoms == 0).sum().item()) / self.atoms.numel()
+
+    def k_means_analysis(self, num_clusters, type="cosine", **kmeans_kwargs):
+        """-> ``(cluster_ids_x [N], cluster_centers [C, D], cluster_ids_by_group, center_features)`` as
+        inspector.py:137-165, with ``kmeans_atoms`` (inference/clustering.py) in place of ``kmeans_pytorch`` on the CPU;
+        ``kmeans_kwargs`` go to it (seed, tol, max_iter, init_indices, ...).  ``cluster_ids_by_group[c]`` is the
+        ascending list of members of cluster c; ``center_features[c]`` is the member with the smallest
+        ``1 - atom . center`` on the raw vectors (cosine, inspector.py:155) or ``|atom - center|`` (euclidean, the intent
+        of :157; ranked by ``|atom|^2 / 2 - atom . center``, the same order), evaluated in fp64, the lowest index among
+        equals, -1 for an empty cluster."""
+        from .clustering import kmeans_atoms
+        if type not in ("cosine", "euclidean"):
+            raise ValueError(f"type must be 'cosine' or 'euclidean', got {type!r}")
+        res = kmeans_atoms(self.atoms, num_clusters, distance=type, **kmeans_kwargs)
+        labels, centers = res["labels"], res["centers"]
+        groups, center_features = _groups_and_center_features(_fp32_atoms(self.atoms), labels, centers, type)
+        return labels, centers, groups, center_features
+
+
+def _groups_and_center_features(atoms: torch.Tensor, labels: torch.Tensor, centers: torch.Tensor, type: str):
+    """What inspector.py:143-163 computes around its kmeans call, by segment reductions on the device: the members of
+    every cluster in ascending order, and per cluster the member nearest to the center (see ``k_means_analysis``)."""
+    N, C = atoms.shape[0], centers.shape[0]
+    ok = labels >= 0
+    lab = labels.clamp(min=0)
+    a64, own = atoms.double(), centers[lab].double()
+    dot = (a64 * own).sum(1)
+    if type == "cosine":
+        rank = dist = 1.0 - dot
+    else:
+        # ranked by |a|^2 / 2 - a . c, which orders the members as |a - c| does and, unlike the sum of squared
+        # differences, is exact in fp64 for an integer dictionary: members at the same distance compare equal
+        rank = 0.5 * (a64 * a64).sum(1) - dot
+        dist = torch.sqrt(torch.clamp(2.0 * rank + (own * own).sum(1), min=0.0))
+    # the reference starts its search at min_distance = 99999: a member at or beyond that (or NaN) is never chosen
+    valid = ok & (dist < 99999.0)
+    rank = torch.where(valid, rank, torch.full_like(rank, float("inf")))
+    best = torch.full((C,), float("inf"), dtype=torch.float64, device=atoms.device)
+    best = best.scatter_reduce(0, lab, rank, "amin")
+    index = torch.arange(N, device=atoms.device)
+    cand = torch.where(valid & (rank == best[lab]), index, torch.full_like(index, N))
+    first = torch.full((C,), N, dtype=torch.int64, device=atoms.device).scatter_reduce(0, lab, cand, "amin")
+    center_features = [int(i) if i < N else -1 for i in first.tolist()]
+    order = torch.argsort(torch.where(ok, labels, torch.full_like(labels, C)), stable=True)
+    sizes = torch.bincount(labels[ok], minlength=C).tolist()
+    members = order.tolist()
+    groups, at = [], 0
+    for n in sizes:
+        groups.append(members[at:at + n])
+        at += n
+    return groups, center_features

@@ -1396,6 +1396,73 @@ def nearest_atoms_f32(a: torch.Tensor, b: Optional[torch.Tensor] = None, k: int 
     return keys
 
 
+# ---- k-means over dictionary atoms -----------------------------------------------------------------------------------
+KMEANS_METRICS = {"cosine": 0, "euclidean": 1}
+
+
+def _kmeans_pair(atoms: torch.Tensor, centers: torch.Tensor, fn: str):
+    atoms = _atoms_f32(atoms, "atoms")
+    if not isinstance(centers, torch.Tensor) or centers.device != atoms.device:
+        raise ValueError(f"{fn}: atoms and centers are on different devices")
+    centers = _atoms_f32(centers, "centers")
+    if centers.shape[1] != atoms.shape[1]:
+        raise ValueError(f"{fn}: atoms and centers must be [N, D] and [C, D] of the same D ({tuple(atoms.shape)}, "
+                         f"{tuple(centers.shape)})")
+    D = atoms.shape[1]
+    if D <= 0 or D % 4:
+        raise ValueError(f"{fn}: D must be a positive multiple of 4 (zero-pad), got {D}")
+    if centers.shape[0] < 1:
+        raise ValueError(f"{fn}: at least one center required")
+    return atoms, centers
+
+
+@_on_tensor_device
+def kmeans_assign(atoms: torch.Tensor, centers: torch.Tensor, metric: str = "cosine") -> torch.Tensor:
+    """The assign step of k-means: keys int64 [N], keys[i] = the largest score of atom i over the centers and its center
+    (bits of the score << 32 | ~center; equal scores go to the lowest center; 0 = every score was NaN).  fp32 [N, D] and
+    [C, D] with D a multiple of 4, on the exact-fp32 matrix pipe (qsae_kmeans_assign_f32; the scores of both metrics are
+    spelled out in include/qsae.h).  ``metric``: "cosine" or "euclidean"."""
+    if metric not in KMEANS_METRICS:
+        raise ValueError(f"kmeans_assign: metric must be 'cosine' or 'euclidean', got {metric!r}")
+    atoms, centers = _kmeans_pair(atoms, centers, "kmeans_assign")
+    (N, D), Cn = atoms.shape, centers.shape[0]
+    keys = torch.empty((N,), dtype=torch.int64, device=atoms.device)
+    if N == 0:
+        return keys
+    lib = _lib.load()
+    ws = _workspace(atoms.device, max(int(lib.qsae_kmeans_assign_f32_workspace_bytes(N, Cn, D)), 1))
+    check(lib.qsae_kmeans_assign_f32(_p(atoms), atoms.stride(0), N, _p(centers), centers.stride(0), Cn, D,
+                                     KMEANS_METRICS[metric], _p(keys), _p(ws), ws.numel(), _stream()))
+    return keys
+
+
+@_on_tensor_device
+def kmeans_update(atoms: torch.Tensor, labels: torch.Tensor, centers_old: torch.Tensor):
+    """The update step of k-means -> (centers_new fp32 [C, D], counts int32 [C], stats fp64 [2] = {center_shift,
+    n_empty}).  ``labels`` [N] (int32 or int64): a label outside [0, C) belongs to no cluster.  A center is the fp64 mean
+    of its members in a fixed order (qsae_kmeans_update_f32), rounded once; an empty cluster keeps its old center."""
+    atoms, centers_old = _kmeans_pair(atoms, centers_old, "kmeans_update")
+    (N, D), Cn = atoms.shape, centers_old.shape[0]
+    _dev(labels, "labels")
+    if labels.device != atoms.device or labels.shape != (N,) or labels.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"kmeans_update: labels must be int32 or int64 [{N}] on the atoms' device")
+    if labels.dtype == torch.int64:                         # out-of-range values stay out of range: no wrap-around
+        labels = labels.clamp(-1, Cn).to(torch.int32)
+    labels = labels.contiguous()
+    if N == 0:
+        return (centers_old.clone(), torch.zeros((Cn,), dtype=torch.int32, device=atoms.device),
+                torch.tensor([0.0, float(Cn)], dtype=torch.float64, device=atoms.device))
+    centers_new = torch.empty((Cn, D), dtype=torch.float32, device=atoms.device)
+    counts = torch.empty((Cn,), dtype=torch.int32, device=atoms.device)
+    stats = torch.empty((2,), dtype=torch.float64, device=atoms.device)
+    lib = _lib.load()
+    ws = _workspace(atoms.device, max(int(lib.qsae_kmeans_update_f32_workspace_bytes(N, Cn, D)), 1))
+    check(lib.qsae_kmeans_update_f32(_p(atoms), atoms.stride(0), N, D, _p(labels), Cn, _p(centers_old),
+                                     centers_old.stride(0), _p(centers_new), D, _p(counts), _p(stats), _p(ws), ws.numel(),
+                                     _stream()))
+    return centers_new, counts, stats
+
+
 # ---- BinarySAE training (the gradient of the soft-decoder forward) ---------------------------------------------------
 # Workspaces come from the caching allocator per call (not the shared _workspaces cache: a backward may run on another
 # thread than the forward).

@@ -589,6 +589,30 @@ def _(a, b, k, exclude_self):
     return torch.empty((a.shape[0], k), dtype=torch.int64, device=a.device)
 
 
+@_op("kmeans_assign")
+def _kmeans_assign(atoms: Tensor, centers: Tensor, metric: str) -> Tensor:
+    """-> keys int64 [N] as in qsae_kmeans_assign_f32"""
+    return _ops.kmeans_assign(atoms, centers, metric)
+
+
+@_kmeans_assign.register_fake
+def _(atoms, centers, metric):
+    return torch.empty((atoms.shape[0],), dtype=torch.int64, device=atoms.device)
+
+
+@_op("kmeans_update")
+def _kmeans_update(atoms: Tensor, labels: Tensor, centers_old: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """-> (centers_new fp32 [C, D], counts int32 [C], stats fp64 [2]) as in qsae_kmeans_update_f32"""
+    return _ops.kmeans_update(atoms, labels, centers_old)
+
+
+@_kmeans_update.register_fake
+def _(atoms, labels, centers_old):
+    C = centers_old.shape[0]
+    return (_f32((C, centers_old.shape[1]), atoms), _i32((C,), atoms),
+            torch.empty((2,), dtype=torch.float64, device=atoms.device))
+
+
 # ---- BinarySAE training ----------------------------------------------------------------------------------------------
 @_op("binary_soft_table_polarize")
 def _binary_soft_table_polarize(logits: Tensor, D: int, n_bits: int) -> Tuple[Tensor, Tensor]:
@@ -945,6 +969,14 @@ def cosine_compare(A, B=None, thresholds=(), bins=0, want_matrix=False):
 
 def nearest_atoms_f32(a, b=None, k=10, exclude_self=False):
     return Q.nearest_atoms_f32(a, b, int(k), bool(exclude_self))
+
+
+def kmeans_assign(atoms, centers, metric="cosine"):
+    return Q.kmeans_assign(atoms, centers, str(metric))
+
+
+def kmeans_update(atoms, labels, centers_old):
+    return Q.kmeans_update(atoms, labels, centers_old)
 
 
 def nearest_atoms_i8(a, b=None, k=10, exclude_self=False, want_duplicates=False):
