@@ -635,6 +635,41 @@ int qsae_kmeans_update_f32(const float* atoms, int64_t a_ld, int N, int D, const
                            const float* centers_old, int64_t old_ld, float* centers_new, int64_t new_ld, int32_t* counts,
                            double* stats, void* workspace, size_t workspace_bytes, qsae_stream_t stream);
 
+/* -- strongest activations per feature as streaming top-n lists (utils/inspector.py linguistic_analyze, ------- */
+/*    print_feature_activations_overview: the examples its labelling prompt is built from) */
+/* State: keys u64 [H][n] on the device, 1 <= n <= 64, every row descending and 0-padded; 0 = none.  The caller zeroes
+ * it before the first batch and passes it to every update of one dataset.  A candidate of feature h is a pair (value,
+ * position) with value > floor (NaN never is; at floor = 0 neither are 0.0, -0.0 and negatives: the reference's
+ * `latent > 0`); position = base + row, a global token index below 2^32.  Its key is (order-preserving bits of the
+ * value) << 32 | ~position: larger values win, equal values go to the lower position.  After an update keys[h] holds
+ * the n largest of (old keys[h]) + (candidates of h in this batch).  Keys of one feature are distinct when positions
+ * are, so the result depends only on the set of (value, position) pairs: not on batch boundaries, tiling, grid or
+ * scheduling (no float atomics, no atomic counter decides a position).  Offering the same (value, position) pair
+ * twice is outside the contract: the merge ranks distinct keys.
+ * Errors: QSAE_ERR_INVALID_ARG (negative sizes, n < 1, NaN floor, base + B > 2^32, ld < H, null pointers) and
+ * QSAE_ERR_UNSUPPORTED (n > 64, B * k >= 2^31) before any HIP call; QSAE_ERR_WORKSPACE when the workspace is missing or
+ * too small; it must be 16-byte aligned.  B == 0 (or k == 0): nothing to do, no pointer is looked at.
+ * The workspace sizes are 0 for an invalid shape and monotone in their arguments. */
+/* Compact form: idx int32 [B][k], val fp32 [B][k] (NULL: every in-range entry is a candidate with value 1.0).  Entries
+ * with idx outside [0, H) are skipped.  Precondition: the units of one row are distinct, as the top-k kernels produce
+ * them; of a unit listed twice in one row, one entry is offered (which one is not fixed) and nothing is read or written
+ * out of bounds.  The per-entry work is proportional to B k; every call also clears, counts and prefix-scans a bitmap
+ * of one bit per (row, unit), whatever the entries hold.  qsae_top_examples_compact_workspace_bytes(B, k, H) = two
+ * H * ceil(B / 32) word arrays (bitmap and prefix), 2 H + 1 and B k ints, each rounded up to 256 bytes: about 530 MiB
+ * at B = 65536, k = 65, H = 32768, of which 512 MiB are written and read per call. */
+size_t qsae_top_examples_compact_workspace_bytes(int B, int k, int H);
+int qsae_top_examples_compact(const int32_t* idx, const float* val, int B, int k, int H, int n, float floor, uint32_t base,
+                              uint64_t* keys, void* workspace, size_t workspace_bytes, qsae_stream_t stream);
+/* Dense form: latent fp32 [B][ld], ld >= H; floats of a row at or past H are not read.  The workspace holds the
+ * partial lists when the rows are split over several workgroups (0 bytes for B <= 64, where they never are). */
+size_t qsae_top_examples_dense_workspace_bytes(int B, int H, int n);
+int qsae_top_examples_dense(const float* latent, int64_t ld, int B, int H, int n, float floor, uint32_t base,
+                            uint64_t* keys, void* workspace, size_t workspace_bytes, qsae_stream_t stream);
+/* keys -> values fp32 [H][n] (0.0 for none), positions int64 [H][n] (-1 for none), counts int32 [H] (filled slots).
+ * Needs no workspace. */
+int qsae_top_examples_decode(const uint64_t* keys, int H, int n, float* values, int64_t* positions, int32_t* counts,
+                             qsae_stream_t stream);
+
 /* -- BinarySAE training: the gradient of the soft-decoder forward (sae/binary.py:24-47, 91-103) ----------------- */
 /* Device workspace of qsae_binary_soft_table_polarize (0 for an invalid shape). */
 size_t qsae_binary_soft_table_polarize_workspace_bytes(int H, int D);

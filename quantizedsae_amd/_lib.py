@@ -127,6 +127,11 @@ SIGNATURES = {
     "qsae_kmeans_assign_f32": (_i, [_vp, _i64, _i, _vp, _i64, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "qsae_kmeans_update_f32_workspace_bytes": (_sz, [_i, _i, _i]),
     "qsae_kmeans_update_f32": (_i, [_vp, _i64, _i, _i, _vp, _i, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "qsae_top_examples_compact_workspace_bytes": (_sz, [_i, _i, _i]),
+    "qsae_top_examples_compact": (_i, [_vp, _vp, _i, _i, _i, _i, _f, C.c_uint32, _vp, _vp, _sz, _vp]),
+    "qsae_top_examples_dense_workspace_bytes": (_sz, [_i, _i, _i]),
+    "qsae_top_examples_dense": (_i, [_vp, _i64, _i, _i, _i, _f, C.c_uint32, _vp, _vp, _sz, _vp]),
+    "qsae_top_examples_decode": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "qsae_binary_soft_table_polarize_workspace_bytes": (_sz, [_i, _i]),
     "qsae_binary_soft_table_polarize": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "qsae_train_csr_workspace_bytes": (_sz, [_i, _i, _i]),

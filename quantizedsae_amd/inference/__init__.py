@@ -8,7 +8,7 @@ from .framework import (  # noqa: F401
     load_sae,
 )
 from .dictionary import compare_decoders, decoder_atoms, decoder_cosine_similarity  # noqa: F401,E402
-from .inspector import DictionaryInspector, integer_atoms, nearest_atoms  # noqa: F401,E402
+from .inspector import DictionaryInspector, FeatureOverview, integer_atoms, nearest_atoms  # noqa: F401,E402
 from .clustering import kmeans_atoms  # noqa: F401,E402
 from .token_overlap import (  # noqa: F401,E402
     JaccardHistogram,
@@ -18,6 +18,7 @@ from .token_overlap import (  # noqa: F401,E402
     top_token_sets,
 )
 from .token_lists import TokenLists, token_lists_to_python  # noqa: F401,E402
+from .top_examples import TopExamples, examples_to_python  # noqa: F401,E402
 from .coactivation_partners import CoactivationPartners  # noqa: F401,E402
 from .summary import (  # noqa: F401,E402
     average_coactivating_features,

@@ -23,6 +23,7 @@ from ..sae import (BaselineSparseAutoencoder, BinarySAE, QuantizedMatryoshkaSAE,
 from .framework import SAEWrapper, _ensure_tensor, compute_reconstruction_error  # noqa: F401  (re-export)
 from .coactivation_partners import CoactivationPartners
 from .token_lists import TokenLists, check_token_ids
+from .top_examples import TopExamples
 
 
 def _hidden_dim(sae: SAEWrapper) -> int:
@@ -155,6 +156,25 @@ def _coactivation_result(coact: Optional[torch.Tensor], partners: Optional[Coact
     return out
 
 
+def _top_examples_mode(top_examples: Optional[int], model, H: int, dev) -> Optional[TopExamples]:
+    """A ``TopExamples`` state for ``top_examples=n``, None for None.  Only the top-k models feed it here (from their
+    compact output); the threshold models keep one bit per unit, so there is nothing to rank by, and a model with a dense
+    latent goes through ``DictionaryInspector.top_examples``: TypeError for both."""
+    if top_examples is None:
+        return None
+    if isinstance(model, (QuantizedMatryoshkaSAE, ResidualQuantizedSAE)):
+        raise TypeError(f"top_examples: {type(model).__name__} is a threshold model -- its activations are one bit per unit "
+                        "and have no magnitude to rank by; only BinarySAE and BaselineSparseAutoencoder are supported")
+    if not isinstance(model, (BinarySAE, BaselineSparseAutoencoder)):
+        raise TypeError(f"top_examples: {type(model).__name__} has no compact top-k output; for a model with a dense latent "
+                        "use DictionaryInspector(model).top_examples(dataset, n)")
+    return TopExamples(H, int(top_examples), dev)
+
+
+def _top_examples_result(examples: Optional[TopExamples]) -> Dict[str, Any]:
+    return {} if examples is None else {"top_examples": examples.finish()}
+
+
 def activation_indices(sae: SAEWrapper, x: torch.Tensor):
     """Compact activation set of the top-k variants: (idx int32 [B,k], val fp32 [B,k]); an entry is active
     when val > 0 (the reference's ``latent > 0``)."""
@@ -253,7 +273,8 @@ def _tokens_per_feature(feat: torch.Tensor, tok: torch.Tensor, H: int, into: Lis
 def compute_activation_stats(sae: SAEWrapper, loader: Iterable[Any], *, token_ids: torch.Tensor,
                              tokens_per_context: int, device: Optional[Any] = None,
                              with_tokens: Union[bool, str] = True,
-                             coactivation: Optional[str] = "counts") -> Dict[str, Any]:
+                             coactivation: Optional[str] = "counts",
+                             top_examples: Optional[int] = None) -> Dict[str, Any]:
     """activation_counts [H] (int64), coactivation [H,H] (int32, mask^T mask) and tokens_per_feature
     (dynamic_analysis.py:255-311).  Counts are accumulated on the device and copied to the host once.
     ``with_tokens="csr"``: tokens_per_feature is the tuple (offsets int64 [H + 1], tokens int32 [nnz]) on the SAE's device,
@@ -261,7 +282,10 @@ def compute_activation_stats(sae: SAEWrapper, loader: Iterable[Any], *, token_id
     ``coactivation="partners"``: the [H, H] matrix is never allocated; ``coactivation`` is None and the result has
     ``coactivation_partner_counts`` (int64 [H] on the host: the number of other features each feature ever fired
     with, what ``summary.average_coactivating_features`` needs) and ``coactivation_partners`` (the
-    ``CoactivationPartners`` state on the device).  ``coactivation=None`` skips co-activation altogether."""
+    ``CoactivationPartners`` state on the device).  ``coactivation=None`` skips co-activation altogether.
+    ``top_examples=n`` (top-k models only, TypeError otherwise): the result gains ``top_examples``, the ``n`` strongest
+    activations of every feature from the same ``(idx, val)`` (``TopExamples.finish()``: values, positions, counts on the
+    device; positions are the global row index that ``token_ids`` is indexed by)."""
     csr = _token_lists_mode(with_tokens, token_ids)
     if device is not None:
         sae.to(device)
@@ -272,6 +296,7 @@ def compute_activation_stats(sae: SAEWrapper, loader: Iterable[Any], *, token_id
     counts = torch.zeros((H,), dtype=torch.int64, device=dev)
     coact, partners = _coactivation_mode(coactivation, H, dev)
     lists = TokenLists(H, dev) if csr else None
+    examples = _top_examples_mode(top_examples, model, H, dev)
     tokens_per_feature: List[List[int]] = [] if csr else [[] for _ in range(H)]
     with_lists = with_tokens is True
     global_index = 0
@@ -289,6 +314,8 @@ def compute_activation_stats(sae: SAEWrapper, loader: Iterable[Any], *, token_id
                     ops.coactivation_sparse(idx, val, H, coact)
                 if partners is not None:
                     partners.add_compact(idx, val)
+                if examples is not None:
+                    examples.add_compact(idx, val, global_index)
                 if csr:
                     lists.add_compact(idx, val, batch_tok)
                 elif with_lists:
@@ -305,7 +332,7 @@ def compute_activation_stats(sae: SAEWrapper, loader: Iterable[Any], *, token_id
                     _tokens_per_feature(nz[:, 1], batch_tok.to(dev)[nz[:, 0]], H, tokens_per_feature)
             global_index += B
     return {"activation_counts": counts.cpu(), **_coactivation_result(coact, partners),
-            "tokens_per_feature": lists.finish() if csr else tokens_per_feature}
+            "tokens_per_feature": lists.finish() if csr else tokens_per_feature, **_top_examples_result(examples)}
 
 
 def compute_reconstruction_error_by_level(sae: SAEWrapper, loader: Iterable[Any], device: Optional[Any] = None) -> torch.Tensor:
@@ -341,7 +368,7 @@ def compute_reconstruction_error_by_level(sae: SAEWrapper, loader: Iterable[Any]
 
 def analyze_dataset(sae: SAEWrapper, loader: Iterable[Any], *, token_ids: torch.Tensor, tokens_per_context: int,
                     device: Optional[Any] = None, with_tokens: Union[bool, str] = True,
-                    coactivation: Optional[str] = "counts") -> Dict[str, Any]:
+                    coactivation: Optional[str] = "counts", top_examples: Optional[int] = None) -> Dict[str, Any]:
     """One pass over the data: final reconstruction MSE, activation counts, co-activation matrix and tokens per
     feature (dynamic_analysis.py:317-440; same result keys, ``mse_per_level`` / ``l0_per_level`` are None there
     too).  Top-k variants run ``forward_compact`` once per batch and feed its (idx, val, reconstruction) to the
@@ -349,7 +376,8 @@ def analyze_dataset(sae: SAEWrapper, loader: Iterable[Any], *, token_ids: torch.
     forward pass and the masks from the bit-packed encoder output.  ``with_tokens="csr"``: tokens_per_feature is the
     CSR tuple on the SAE's device (see ``compute_activation_stats``), built without a mask or a Python list.
     ``coactivation``: "counts" (the int32 matrix), "partners" (one bit per pair on the device and the partner counts) or
-    None, as in ``compute_activation_stats``."""
+    None, as in ``compute_activation_stats``.  ``top_examples=n``: the ``n`` strongest activations per feature, as in
+    ``compute_activation_stats`` (top-k models only)."""
     csr = _token_lists_mode(with_tokens, token_ids)
     if device is not None:
         sae.to(device)
@@ -361,6 +389,7 @@ def analyze_dataset(sae: SAEWrapper, loader: Iterable[Any], *, token_ids: torch.
     coact, partners = _coactivation_mode(coactivation, H, dev)
     sq = torch.zeros((), dtype=torch.float64, device=dev)
     lists = TokenLists(H, dev) if csr else None
+    examples = _top_examples_mode(top_examples, model, H, dev)
     tokens_per_feature: List[List[int]] = [] if csr else [[] for _ in range(H)]
     with_lists = with_tokens is True
     global_index, n_elements = 0, 0
@@ -380,6 +409,8 @@ def analyze_dataset(sae: SAEWrapper, loader: Iterable[Any], *, token_ids: torch.
                     ops.coactivation_sparse(idx, val, H, coact)
                 if partners is not None:
                     partners.add_compact(idx, val)
+                if examples is not None:
+                    examples.add_compact(idx, val, global_index)
                 if csr:
                     lists.add_compact(idx, val, batch_tok)
                 elif with_lists:
@@ -396,4 +427,4 @@ def analyze_dataset(sae: SAEWrapper, loader: Iterable[Any], *, token_ids: torch.
             n_elements += x.numel()
     return {"mse_final": float(sq.item()) / max(n_elements, 1), "mse_per_level": None, "l0_per_level": None,
             "activation_counts": counts.cpu(), **_coactivation_result(coact, partners),
-            "tokens_per_feature": lists.finish() if csr else tokens_per_feature}
+            "tokens_per_feature": lists.finish() if csr else tokens_per_feature, **_top_examples_result(examples)}

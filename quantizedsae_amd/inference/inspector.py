@@ -11,19 +11,28 @@ fp32 dictionaries (baseline, matryoshka, residual, a BinarySAE wider than 8 bits
 ``qsae_nearest_atoms_f32`` (csrc/dictionary_neighbors_f32.hip): the same keys from the exact-fp32 contraction that
 ``compare_decoders`` uses, k per row instead of one.  ``k_means_analysis`` clusters the atoms with
 ``kmeans_atoms`` (inference/clustering.py) in place of ``kmeans_pytorch`` on the CPU.
+The activation side of the reference's ``linguistic_*`` block (``linguistic_analyze``,
+``print_feature_activations_overview``, ``check_sensitivity`` / ``check_specificity``) runs on the device too, with
+``top_examples`` for the strongest activations per feature; ``evaluate_feature`` and ``feature_labeling``
+call an external API and are not ported.
 """
 from __future__ import annotations
 
-from typing import Any, Dict, Sequence
+from typing import Any, Dict, Iterator, List, Sequence, Tuple
 
 import torch
 
 from .. import torch_ops as T
+from ..sae.base import HipEncoder
 from ..sae.binary import BinarySAE
 from ..sae.ternary import STEWeights, TernarySparseAutoencoder
 from .dictionary import _decode_keys, _model, decoder_atoms
+from .token_lists import TokenLists
+from .top_examples import TopExamples
 
-__all__ = ["integer_atoms", "nearest_atoms", "DictionaryInspector"]
+__all__ = ["integer_atoms", "nearest_atoms", "DictionaryInspector", "FeatureOverview"]
+
+_ROWS_PER_CALL = 8192        # rows of a [lines, tokens, D] dataset encoded at once (a dense [rows, H] latent per call)
 
 
 def _pad32(a: torch.Tensor) -> torch.Tensor:
@@ -151,15 +160,139 @@ def nearest_atoms(lhs, rhs=None, k: int = 10, *, include_self: bool = True, atom
     return out
 
 
+class FeatureOverview:
+    """What ``print_feature_activations_overview`` returns: for every feature how often it was the most activated one
+    (``counts`` int64 [F]) and where, as CSR -- ``positions[offsets[f] : offsets[f + 1]]`` are the flat positions
+    ``line * tokens_per_line + pos`` of feature f in ascending order, the order the reference's loop appends them in."""
+
+    def __init__(self, counts: torch.Tensor, offsets: torch.Tensor, positions: torch.Tensor, tokens_per_line: int):
+        self.counts, self.offsets, self.positions = counts, offsets, positions
+        self.tokens_per_line = int(tokens_per_line)
+
+    def to_python(self) -> Dict[int, Dict[str, Any]]:
+        """The reference's ``feature_dict``: ``{id: {"cnt": n, "pos": [(line, pos), ...]}}`` for the features that won at
+        least once.  Two host copies."""
+        bounds, flat, t = self.offsets.cpu().tolist(), self.positions.cpu().tolist(), self.tokens_per_line
+        return {f: {"cnt": bounds[f + 1] - bounds[f], "pos": [(g // t, g % t) for g in flat[bounds[f]:bounds[f + 1]]]}
+                for f in range(len(bounds) - 1) if bounds[f + 1] > bounds[f]}
+
+
+def _activation_table(feature_activations) -> torch.Tensor:
+    """[lines, tokens] integer tensor from the reference's list of per-line lists (or a tensor, returned as it is)."""
+    fa = feature_activations if isinstance(feature_activations, torch.Tensor) else torch.as_tensor(feature_activations)
+    if fa.dim() != 2 or fa.dtype in (torch.float16, torch.bfloat16, torch.float32, torch.float64, torch.bool):
+        raise ValueError(f"feature_activations: expected integer feature ids [lines, tokens], got {fa.dtype} {tuple(fa.shape)}")
+    return fa
+
+
+def _match_mask(match_mask, fa: torch.Tensor) -> torch.Tensor:
+    m = match_mask if isinstance(match_mask, torch.Tensor) else torch.as_tensor(match_mask)
+    if m.dtype != torch.bool or m.shape != fa.shape:
+        raise ValueError(f"match_mask: expected bool {tuple(fa.shape)}, got {m.dtype} {tuple(m.shape)}")
+    return m.to(fa.device)
+
+
 class DictionaryInspector:
     """``TernarySparseAutoencoderInspector`` (utils/inspector.py) for any dictionary, with the reference's method names
     and meanings.  ``sae`` is an SAE (wrapper or module) or atoms ``[N, D]``: an integer dictionary (or int8 atoms) is
-    held as int8, any other as fp32 (``decoder_atoms``)."""
+    held as int8, any other as fp32 (``decoder_atoms``).  The methods that read activations (``linguistic_analyze``,
+    ``top_examples``) need the model, not only its atoms."""
 
     def __init__(self, sae):
         # int8 or fp32 [N, D], unpadded (the kernel call pads)
         self.atoms = _integer_atoms(sae) if _is_integer(sae) else _fp32_atoms(sae)
         self.dictionary_in_ternary = self.atoms             # the reference's attribute name
+        self.model = None if isinstance(sae, torch.Tensor) else _model(sae)
+
+    # ---- activations (inspector.py:173-208, 266-292) ------------------------------------------------------------------
+    def _encoder(self) -> HipEncoder:
+        enc = getattr(self.model, "encoder", None)
+        if not isinstance(enc, HipEncoder) or enc._act != T.ACT_RELU:
+            raise TypeError("this method reads activations: the inspector must be built from a model with a linear + ReLU "
+                            "encoder (TernarySparseAutoencoder), not from atoms")
+        return enc
+
+    def _batches(self, dataset) -> Iterator[Tuple[torch.Tensor, int]]:
+        """(rows fp32 [r, D] on the model's device, lines they complete) of a dataset: a tensor [lines, tokens, D] in
+        chunks of whole lines, or an iterable of contexts [tokens, D] one by one, as the reference walks it."""
+        dev = self._encoder().linear.weight.device
+        if isinstance(dataset, torch.Tensor) and dataset.dim() == 3:
+            lines, tokens, D = dataset.shape
+            step = max(1, _ROWS_PER_CALL // max(tokens, 1))
+            for l0 in range(0, lines, step):
+                part = dataset[l0:l0 + step]
+                yield part.reshape(-1, D).to(dev, torch.float32).contiguous(), part.shape[0]
+            return
+        for context in dataset:
+            yield torch.as_tensor(context).to(dev, torch.float32).contiguous(), 1
+
+    def linguistic_analyze(self, dataset) -> torch.Tensor:
+        """The most activated feature of every token: int64 [lines, tokens] on the device (``.tolist()`` is the
+        reference's list of lists).  One ``encode_topk`` with k = 1 per batch on the exact encoder, no dense latent: the
+        largest pre-activation, equal values to the lowest index (``torch.max``'s documented choice); where it is not
+        above 0 the ReLU row is all zero and the result is index 0, as ``argmax`` of such a row is."""
+        lin = self._encoder().linear
+        out: List[torch.Tensor] = []
+        with torch.no_grad():
+            for x, n_lines in self._batches(dataset):
+                idx, val = T.encode_topk(x, lin.weight.detach(), None if lin.bias is None else lin.bias.detach(), 1)
+                win = torch.where(val[:, 0] > 0, idx[:, 0], torch.zeros_like(idx[:, 0])).long()
+                out.append(win.reshape(n_lines, -1))
+        if not out:
+            return torch.zeros((0, 0), dtype=torch.int64, device=lin.weight.device)
+        return torch.cat(out, dim=0)
+
+    def top_examples(self, dataset, n: int, floor: float = 0.0) -> Dict[str, torch.Tensor]:
+        """The ``n`` strongest activations of every feature over ``dataset`` (``TopExamples.finish()``: values, positions,
+        counts), from the model's dense ReLU latent; position = ``line * tokens + pos``."""
+        enc = self._encoder()
+        state = TopExamples(enc.linear.weight.shape[0], n, enc.linear.weight.device, floor)
+        base = 0
+        with torch.no_grad():
+            for x, _ in self._batches(dataset):
+                state.add_dense(enc(x), base)
+                base += x.shape[0]
+        return state.finish()
+
+    def print_feature_activations_overview(self, feature_activations) -> FeatureOverview:
+        """How often and where each feature was the most activated one, from ``linguistic_analyze``'s table (tensor or
+        list of lists): a ``FeatureOverview`` on the device, built by ``TokenLists`` with positions in place of tokens;
+        ``.to_python()`` is the reference's dict.  Ids outside [0, number of atoms) are dropped."""
+        fa = _activation_table(feature_activations)
+        lines, tokens = fa.shape
+        if lines * tokens >= 2 ** 31:
+            raise ValueError("print_feature_activations_overview: positions are stored as int32")
+        dev = self.atoms.device
+        F = self.atoms.shape[0]
+        ids = fa.reshape(-1, 1).to(dev)
+        ids = torch.where((ids >= 0) & (ids < F), ids, torch.full_like(ids, -1)).to(torch.int32)
+        lists = TokenLists(F, dev)
+        lists.add_compact(ids, None, torch.arange(lines * tokens, dtype=torch.int32, device=dev))
+        offsets, positions = lists.finish()
+        return FeatureOverview(offsets[1:] - offsets[:-1], offsets, positions, tokens)
+
+    @staticmethod
+    def check_sensitivity(feature_activations, match_mask, feature_id: int) -> float:
+        """Of the tokens that match the targets (``match_mask`` bool [lines, tokens]: the caller's
+        ``any(t in token for t in target_tokens)``), the share whose most activated feature is ``feature_id``
+        (inspector.py:266-280).  No matching token: ZeroDivisionError, as there."""
+        fa = _activation_table(feature_activations)
+        m = _match_mask(match_mask, fa)
+        return int((m & (fa == int(feature_id))).sum()) / int(m.sum())
+
+    @staticmethod
+    def check_specificity(overview: FeatureOverview, match_mask, feature_id: int) -> float:
+        """Of the positions where ``feature_id`` was the most activated feature, the share that matches the targets
+        (inspector.py:282-292).  A feature that never won: KeyError, as the reference's dict lookup."""
+        f = int(feature_id)
+        beg, end = int(overview.offsets[f]), int(overview.offsets[f + 1])
+        if end == beg:
+            raise KeyError(f)
+        m = match_mask if isinstance(match_mask, torch.Tensor) else torch.as_tensor(match_mask)
+        if m.dtype != torch.bool or m.dim() != 2 or m.shape[1] != overview.tokens_per_line:
+            raise ValueError(f"match_mask: expected bool [lines, {overview.tokens_per_line}], got {m.dtype} {tuple(m.shape)}")
+        pos = overview.positions[beg:end].long()
+        return int(m.reshape(-1).to(pos.device)[pos].sum()) / (end - beg)
 
     def get_feature(self, feature_idx):
         return self.atoms[feature_idx]

@@ -1205,6 +1205,82 @@ def token_lists_regroup(batch_offsets: torch.Tensor, segments: torch.Tensor) -> 
     return offsets, tokens
 
 
+# ---- strongest activations per feature as streaming top-n lists ----------------------------------------------
+TOP_EXAMPLES_MAX_N = 64
+
+
+def _top_examples_keys(keys: torch.Tensor) -> Tuple[int, int]:
+    """(H, n) of the state: int64 [H, n] (the bits of the u64 keys), contiguous, on the device, 1 <= n <= 64."""
+    _dev(keys, "keys", torch.int64)
+    if keys.dim() != 2 or not keys.is_contiguous() or keys.shape[0] < 1 or not 1 <= keys.shape[1] <= TOP_EXAMPLES_MAX_N:
+        raise ValueError(f"keys: expected a contiguous int64 [H, n] tensor with 1 <= n <= {TOP_EXAMPLES_MAX_N}, "
+                         f"got {tuple(keys.shape)}")
+    return keys.shape[0], keys.shape[1]
+
+
+def _top_examples_base(base: int, B: int) -> int:
+    base = int(base)
+    if base < 0 or base + B > 2 ** 32:
+        raise ValueError(f"top_examples: positions base .. base + B must lie in [0, 2^32], got base = {base}, B = {B}")
+    return base
+
+
+@_on_tensor_device
+def top_examples_compact(idx: torch.Tensor, val: Optional[torch.Tensor], floor: float, base: int, keys: torch.Tensor) -> None:
+    """keys[h] <- the n largest of keys[h] and this batch's candidates of feature h, in place.  idx int32 [B, k], val fp32
+    [B, k] or None (every in-range entry at 1.0); a candidate has val > floor, its position is base + row.  See
+    qsae_top_examples_compact."""
+    _dev(idx, "idx", torch.int32)
+    if idx.dim() != 2:
+        raise ValueError("idx: expected int32 [B, k]")
+    B, k = idx.shape
+    H, n = _top_examples_keys(keys)
+    base = _top_examples_base(base, B)
+    if val is not None:
+        _dev(val, "val", torch.float32)
+        if val.shape != idx.shape:
+            raise ValueError("val: expected the shape of idx")
+        val = val.contiguous()
+    idx = idx.contiguous()
+    lib = _lib.load()
+    need = int(lib.qsae_top_examples_compact_workspace_bytes(B, k, H))
+    if need == 0:
+        raise ValueError(f"top_examples_compact: B * k = {B * k} is outside what the kernels run (B * k < 2^31)")
+    ws = _workspace(idx.device, need)
+    check(lib.qsae_top_examples_compact(_p(idx), _p(val), B, k, H, n, float(floor), base, _p(keys), _p(ws), ws.numel(),
+                                        _stream()))
+
+
+@_on_tensor_device
+def top_examples_dense(latent: torch.Tensor, floor: float, base: int, keys: torch.Tensor) -> None:
+    """The same update from a dense latent fp32 [B, H] (any row stride; a column slice of a wider tensor is read in
+    place, and nothing at or past column H is read).  See qsae_top_examples_dense."""
+    _dev(latent, "latent", torch.float32)
+    H, n = _top_examples_keys(keys)
+    if latent.dim() != 2 or latent.shape[1] != H:
+        raise ValueError(f"latent: expected fp32 [B, {H}], got {tuple(latent.shape)}")
+    B = latent.shape[0]
+    base = _top_examples_base(base, B)
+    if B and (latent.stride(1) != 1 or latent.stride(0) < H):
+        latent = latent.contiguous()
+    lib = _lib.load()
+    need = int(lib.qsae_top_examples_dense_workspace_bytes(B, H, n))
+    ws = _workspace(latent.device, max(need, 16))
+    check(lib.qsae_top_examples_dense(_p(latent), latent.stride(0) if B else H, B, H, n, float(floor), base, _p(keys), _p(ws),
+                                      ws.numel(), _stream()))
+
+
+@_on_tensor_device
+def top_examples_decode(keys: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """keys int64 [H, n] -> (values fp32 [H, n], 0.0 for none; positions int64 [H, n], -1 for none; counts int32 [H])."""
+    H, n = _top_examples_keys(keys)
+    values = torch.empty((H, n), dtype=torch.float32, device=keys.device)
+    positions = torch.empty((H, n), dtype=torch.int64, device=keys.device)
+    counts = torch.empty((H,), dtype=torch.int32, device=keys.device)
+    check(_lib.load().qsae_top_examples_decode(_p(keys), H, n, _p(values), _p(positions), _p(counts), _stream()))
+    return values, positions, counts
+
+
 @_on_tensor_device
 def quantize_bits(x: torch.Tensor, n_bits: int, scale_factor: float, signed: bool = True) -> torch.Tensor:
     """n-bit code of every activation as LSB-first 0/1 floats, [B, D * n_bits] (data/dataset.py:76-102)."""

@@ -534,6 +534,37 @@ def _(batch_offsets, segments):
             _i32(segments.shape, segments))
 
 
+@_op("top_examples_compact", mutates=("keys",))
+def _top_examples_compact(idx: Tensor, val: Optional[Tensor], floor: float, base: int, keys: Tensor) -> None:
+    _ops.top_examples_compact(idx, val, floor, base, keys)
+
+
+@_top_examples_compact.register_fake
+def _(idx, val, floor, base, keys):
+    return None
+
+
+@_op("top_examples_dense", mutates=("keys",))
+def _top_examples_dense(latent: Tensor, floor: float, base: int, keys: Tensor) -> None:
+    _ops.top_examples_dense(latent, floor, base, keys)
+
+
+@_top_examples_dense.register_fake
+def _(latent, floor, base, keys):
+    return None
+
+
+@_op("top_examples_decode")
+def _top_examples_decode(keys: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    return _ops.top_examples_decode(keys)
+
+
+@_top_examples_decode.register_fake
+def _(keys):
+    return (_f32(keys.shape, keys), torch.empty(keys.shape, dtype=torch.int64, device=keys.device),
+            _i32((keys.shape[0],), keys))
+
+
 @_op("quantize_bits")
 def _quantize_bits(x: Tensor, n_bits: int, scale_factor: float, signed: bool) -> Tensor:
     return _ops.quantize_bits(x, n_bits, scale_factor, signed)
@@ -957,6 +988,23 @@ def token_lists_regroup(batch_offsets, segments):
 
 
 token_lists_workspace_bytes = _ops.token_lists_workspace_bytes
+
+
+def top_examples_compact(idx, val, floor, base, keys):
+    Q.top_examples_compact(idx, val, float(floor), int(base), keys)
+    return keys
+
+
+def top_examples_dense(latent, floor, base, keys):
+    Q.top_examples_dense(latent, float(floor), int(base), keys)
+    return keys
+
+
+def top_examples_decode(keys):
+    return Q.top_examples_decode(keys)
+
+
+TOP_EXAMPLES_MAX_N = _ops.TOP_EXAMPLES_MAX_N
 
 
 def quantize_bits(x, n_bits, scale_factor, signed=True):
