@@ -670,6 +670,51 @@ int qsae_top_examples_dense(const float* latent, int64_t ld, int B, int H, int n
 int qsae_top_examples_decode(const uint64_t* keys, int H, int n, float* values, int64_t* positions, int32_t* counts,
                              qsae_stream_t stream);
 
+/* -- evaluation reports (scripts/evaluation/estimate_quantization_error.py, estimate_baseline_error.py) --------- */
+/* Quantization error of a BinarySAE decoder: statistics of W_quant - W_float in one pass over the logits [H][D * n_bits]
+ * (column d * n_bits + b is bit b of output d), without any [H][D] temporary.  Per entry (h, d), in registers:
+ *   soft = what qsae_binary_soft_table computes (same helper, same order, fp32);  hard = the two's-complement integer of
+ *   the sigmoid(logit) > 0.5 bits, as qsae_pack_binary packs it;  w_float = fp32(step * soft), w_quant = fp32(step * hard),
+ *   diff = fp32(w_quant - w_float).
+ * result: QSAE_QUANT_ERROR_WORDS 64-bit words on the device, overwritten:
+ *   [0..5]  fp64 sums over all entries: diff^2, |diff|, w_float, w_float^2, w_quant, w_quant^2
+ *   [6..9]  fp64 images of min w_float, max w_float, min w_quant, max w_quant (NaN entries are passed over)
+ *   [10]    u64 key of the largest |diff|: (order-preserving bits of the fp32 value, NaN above +inf) << 32 | ~(h D + d),
+ *           so equal values go to the lowest flat index
+ *   [11]    int64 number of NaN logits (NaNs propagate into the sums)
+ *   [16+b]  fp64 sum of |logit| over bit plane b;  [24+b] fp64 sum of p (1 - p), p = sigmoid(logit), over plane b;
+ *   [32+b]  int64 number of logits of plane b with |logit| < margin_logit (the raw logit; NaN never is)
+ *   [40+b]  the n_bits logits of the entry behind the key, as fp64;  every other word is 0.
+ * unit_err_sq [H] fp64, overwritten: sum over d of diff^2 of unit h.
+ * Every sum has a fixed order: within a unit, lane l of one wave adds d = l, l + 64, ... in ascending order and the 64
+ * lane sums are joined by a butterfly (xor 32, 16, ..., 1); across units, thread t of 256 adds h = t, t + 256, ... in
+ * ascending order and the thread sums are added in ascending t.  No float atomics: the same bits on every run.
+ * Limits: 1 <= n_bits <= 8 and H * D < 2^31, otherwise QSAE_ERR_UNSUPPORTED (answered from the sizes alone, before any
+ * pointer is looked at); H, D >= 1.  N = 4 and 8 read one and two 16-byte vectors per entry when logits is 16-byte
+ * aligned.  workspace: 8-byte aligned, qsae_quantization_error_workspace_bytes(H, D, n_bits) = (11 + 3 n_bits) * H * 8
+ * bytes rounded up to 256 (the per-unit partials); 0 for an invalid shape. */
+#define QSAE_QUANT_ERROR_WORDS 48
+size_t qsae_quantization_error_workspace_bytes(int H, int D, int n_bits);
+int qsae_quantization_error(const float* logits, int H, int D, int n_bits, float step, float margin_logit, double* result,
+                            double* unit_err_sq, void* workspace, size_t workspace_bytes, qsae_stream_t stream);
+/* Dataset moments: adds the rows of x [B][D] (dtype 0 = fp32, 1 = fp16, 2 = bf16, converted in registers; contiguous)
+ * to a caller-owned running state.  recon (nullable): fp32 [B][D], contiguous.  The rows of one call are cut into groups
+ * of group_rows from the call's first row (the last group may be short).  A group holding a NaN in x contributes nothing
+ * and its rows are counted as skipped (the reference's `if torch.isnan(batch).any(): continue` per DataLoader batch);
+ * inf is summed.  State: sums fp64 [3][D] = per column sum x, sum x^2 (squared in fp64, exact) and sum fp32((recon - x)^2) (difference
+ * and square in fp32, the terms of qsae_sq_err_sum; row 2 is touched only when recon is given), counts int64 [2] = {rows kept, rows skipped}; the caller zeroes both before the first call.
+ * Order of every sum: inside a group, row lane r of 16 adds rows r, r + 16, ... in ascending order and the 16 lane sums
+ * are added in ascending r; the unflagged groups are then added to the state in ascending group order -- the same bits
+ * on every run, and whether the same rows arrive in one call or in several cut at multiples of group_rows.
+ * Four columns per thread are read as one vector when D % 4 == 0 and x / recon are 4-element aligned.
+ * Errors: QSAE_ERR_INVALID_ARG (B < 0, D < 1, group_rows < 1, null or misaligned pointers), QSAE_ERR_UNSUPPORTED (unknown
+ * dtype, D > 16 * 65535) before any HIP call; QSAE_ERR_WORKSPACE.  B == 0: nothing to do, no pointer is looked at.
+ * workspace: 8-byte aligned, qsae_dataset_moments_workspace_bytes(B, D, group_rows, with_recon) = the per-group partials
+ * (2 or 3) * G * D * 8 and G flag words, each rounded up to 256 bytes, G = ceil(B / group_rows); 0 for an invalid shape. */
+size_t qsae_dataset_moments_workspace_bytes(int B, int D, int group_rows, int with_recon);
+int qsae_dataset_moments_add(const void* x, int dtype, const float* recon, int B, int D, int group_rows, double* sums,
+                             int64_t* counts, void* workspace, size_t workspace_bytes, qsae_stream_t stream);
+
 /* -- BinarySAE training: the gradient of the soft-decoder forward (sae/binary.py:24-47, 91-103) ----------------- */
 /* Device workspace of qsae_binary_soft_table_polarize (0 for an invalid shape). */
 size_t qsae_binary_soft_table_polarize_workspace_bytes(int H, int D);

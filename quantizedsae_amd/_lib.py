@@ -132,6 +132,10 @@ SIGNATURES = {
     "qsae_top_examples_dense_workspace_bytes": (_sz, [_i, _i, _i]),
     "qsae_top_examples_dense": (_i, [_vp, _i64, _i, _i, _i, _f, C.c_uint32, _vp, _vp, _sz, _vp]),
     "qsae_top_examples_decode": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "qsae_quantization_error_workspace_bytes": (_sz, [_i, _i, _i]),
+    "qsae_quantization_error": (_i, [_vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _sz, _vp]),
+    "qsae_dataset_moments_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "qsae_dataset_moments_add": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "qsae_binary_soft_table_polarize_workspace_bytes": (_sz, [_i, _i]),
     "qsae_binary_soft_table_polarize": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "qsae_train_csr_workspace_bytes": (_sz, [_i, _i, _i]),

@@ -20,7 +20,7 @@ DEBUG_LIB = LIBDIR / "libqsae_hip_debug.so"      # same sources + -DQSAE_DEBUG_B
 OBJDIR = PKG / "lib" / "obj"
 
 SOURCES = ["encode.hip", "topk.hip", "binary.hip", "dense_dec.hip", "encode_topk.hip", "prefilter_topk.hip", "encode_bits.hip",
-           "encode_emu.hip", "misc.hip", "analysis.hip", "coactivation_bits.hip", "coactivation_partners.hip", "token_overlap.hip", "token_lists.hip", "dictionary.hip", "dictionary_neighbors.hip", "dictionary_neighbors_f32.hip", "kmeans.hip", "top_examples.hip", "train.hip", "train_gemm.hip",
+           "encode_emu.hip", "misc.hip", "analysis.hip", "coactivation_bits.hip", "coactivation_partners.hip", "token_overlap.hip", "token_lists.hip", "dictionary.hip", "dictionary_neighbors.hip", "dictionary_neighbors_f32.hip", "kmeans.hip", "top_examples.hip", "evaluation.hip", "train.hip", "train_gemm.hip",
            "train_mask.hip"]
 HEADERS = sorted(p.name for p in (Path(__file__).resolve().parent / "csrc").glob("*.h"))   # every header: all sources rebuild
 ARCH = "gfx950"

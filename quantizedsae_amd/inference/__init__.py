@@ -20,6 +20,13 @@ from .token_overlap import (  # noqa: F401,E402
 from .token_lists import TokenLists, token_lists_to_python  # noqa: F401,E402
 from .top_examples import TopExamples, examples_to_python  # noqa: F401,E402
 from .coactivation_partners import CoactivationPartners  # noqa: F401,E402
+from .evaluation import (  # noqa: F401,E402
+    DatasetMoments,
+    estimate_baseline_error,
+    evaluate_dataset,
+    format_quantization_report,
+    quantization_error,
+)
 from .summary import (  # noqa: F401,E402
     average_coactivating_features,
     count_below_threshold,

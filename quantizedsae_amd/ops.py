@@ -1281,6 +1281,63 @@ def top_examples_decode(keys: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor,
     return values, positions, counts
 
 
+# ---- evaluation reports: quantization error of a BinarySAE decoder, moments of a dataset --------------------------------
+QUANT_ERROR_WORDS = 48          # QSAE_QUANT_ERROR_WORDS: the result block of qsae_quantization_error, 64-bit words
+MOMENTS_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+
+
+@_on_tensor_device
+def quantization_error(logits: torch.Tensor, D: int, n_bits: int, step: float, margin_logit: float):
+    """-> (result fp64 [48], unit_err_sq fp64 [H]), both on the device: the statistics of W_quant - W_float of a
+    BinarySAE decoder's logits fp32 [H, D * n_bits] in one pass.  The layout of ``result`` (some words are int64 / u64
+    bits: ``result.view(torch.int64)``) is the one of qsae_quantization_error in include/qsae.h."""
+    logits = _f32c(logits, "logits")
+    D, n_bits = int(D), int(n_bits)
+    if logits.dim() != 2 or logits.shape[1] != D * n_bits:
+        raise ValueError(f"logits is {tuple(logits.shape)}, expected [H, {D * n_bits}]")
+    H = logits.shape[0]
+    lib = _lib.load()
+    result = torch.empty((QUANT_ERROR_WORDS,), dtype=torch.float64, device=logits.device)
+    unit_err_sq = torch.empty((H,), dtype=torch.float64, device=logits.device)
+    ws = _workspace(logits.device, max(int(lib.qsae_quantization_error_workspace_bytes(H, D, n_bits)), 16))
+    check(lib.qsae_quantization_error(_p(logits), H, D, n_bits, float(step), float(margin_logit), _p(result),
+                                      _p(unit_err_sq), _p(ws), ws.numel(), _stream()))
+    return result, unit_err_sq
+
+
+@_on_tensor_device
+def dataset_moments_add(x: torch.Tensor, recon: Optional[torch.Tensor], group_rows: int, sums: torch.Tensor,
+                        counts: torch.Tensor) -> None:
+    """sums fp64 [3, D] (per column: sum x, sum x^2, sum (recon - x)^2) and counts int64 [2] (rows kept, rows skipped)
+    += the rows of x [B, D] (fp32, fp16 or bf16), in place; groups of ``group_rows`` rows holding a NaN are skipped.
+    recon: fp32 [B, D] or None.  See qsae_dataset_moments_add."""
+    _dev(x, "x")
+    if x.dtype not in MOMENTS_DTYPES:
+        raise TypeError(f"x: expected fp32, fp16 or bf16, got {x.dtype}")
+    if x.dim() != 2:
+        raise ValueError(f"x: expected [B, D], got {tuple(x.shape)}")
+    B, D = x.shape
+    _dev(sums, "sums", torch.float64)
+    _dev(counts, "counts", torch.int64)
+    if tuple(sums.shape) != (3, D) or tuple(counts.shape) != (2,) or not sums.is_contiguous() or not counts.is_contiguous():
+        raise ValueError(f"state: expected contiguous sums fp64 [3, {D}] and counts int64 [2], got {tuple(sums.shape)} and "
+                         f"{tuple(counts.shape)}")
+    if sums.device != x.device or counts.device != x.device:
+        raise ValueError("x, sums and counts must live on one device")
+    if recon is not None:
+        recon = _f32c(recon, "recon")
+        if recon.shape != x.shape or recon.device != x.device:
+            raise ValueError(f"recon: expected the shape and device of x, got {tuple(recon.shape)} on {recon.device}")
+    x = x.contiguous()
+    group_rows = int(group_rows)
+    if group_rows < 1:
+        raise ValueError(f"group_rows must be >= 1, got {group_rows}")
+    lib = _lib.load()
+    ws = _workspace(x.device, max(int(lib.qsae_dataset_moments_workspace_bytes(B, D, group_rows, int(recon is not None))), 16))
+    check(lib.qsae_dataset_moments_add(_p(x), MOMENTS_DTYPES[x.dtype], _p(recon), B, D, group_rows, _p(sums), _p(counts),
+                                       _p(ws), ws.numel(), _stream()))
+
+
 @_on_tensor_device
 def quantize_bits(x: torch.Tensor, n_bits: int, scale_factor: float, signed: bool = True) -> torch.Tensor:
     """n-bit code of every activation as LSB-first 0/1 floats, [B, D * n_bits] (data/dataset.py:76-102)."""

@@ -565,6 +565,28 @@ def _(keys):
             _i32((keys.shape[0],), keys))
 
 
+@_op("quantization_error")
+def _quantization_error(logits: Tensor, D: int, n_bits: int, step: float, margin_logit: float) -> Tuple[Tensor, Tensor]:
+    """-> (result fp64 [48], unit_err_sq fp64 [H]) as in qsae_quantization_error"""
+    return _ops.quantization_error(logits, D, n_bits, step, margin_logit)
+
+
+@_quantization_error.register_fake
+def _(logits, D, n_bits, step, margin_logit):
+    f64 = dict(dtype=torch.float64, device=logits.device)
+    return torch.empty((_ops.QUANT_ERROR_WORDS,), **f64), torch.empty((logits.shape[0],), **f64)
+
+
+@_op("dataset_moments_add", mutates=("sums", "counts"))
+def _dataset_moments_add(x: Tensor, recon: Optional[Tensor], group_rows: int, sums: Tensor, counts: Tensor) -> None:
+    _ops.dataset_moments_add(x, recon, group_rows, sums, counts)
+
+
+@_dataset_moments_add.register_fake
+def _(x, recon, group_rows, sums, counts):
+    return None
+
+
 @_op("quantize_bits")
 def _quantize_bits(x: Tensor, n_bits: int, scale_factor: float, signed: bool) -> Tensor:
     return _ops.quantize_bits(x, n_bits, scale_factor, signed)
@@ -1002,6 +1024,14 @@ def top_examples_dense(latent, floor, base, keys):
 
 def top_examples_decode(keys):
     return Q.top_examples_decode(keys)
+
+
+def quantization_error(logits, D, n_bits, step, margin_logit):
+    return Q.quantization_error(logits, int(D), int(n_bits), float(step), float(margin_logit))
+
+
+def dataset_moments_add(x, recon, group_rows, sums, counts):
+    Q.dataset_moments_add(x, recon, int(group_rows), sums, counts)
 
 
 TOP_EXAMPLES_MAX_N = _ops.TOP_EXAMPLES_MAX_N
