@@ -862,6 +862,25 @@ int qsae_train_mask_init(float* w, float* mask, int D, int H, int64_t n_inactive
 int qsae_train_mask_update(float* w, float* mask, const float* a, const float* delta, int D, int H, int64_t n,
                            void* workspace, size_t workspace_bytes, qsae_stream_t stream);
 
+/* -- Optimizer: the Adam step in one pass.  Per element, every line one IEEE fp32 operation, no
+ *    contraction -- the op sequence of torch's single-tensor Adam with amsgrad, maximize and weight decay off:
+ *        d = g - m;       m' = m + d * one_minus_b1
+ *        a = v * b2;      q = g * g;          v' = a + q * one_minus_b2
+ *        s = sqrtf(v');   r = s / bc2_sqrt;   den = r + eps
+ *        u = m' / den;    p' = p - step_size * u
+ *    The caller computes the scalars in double (step_size = lr / (1 - b1^t), bc2_sqrt = sqrt(1 - b2^t), one_minus_b1 =
+ *    1 - b1, one_minus_b2 = 1 - b2) and rounds each to fp32 once.  NaN and inf propagate as the operations dictate. -- */
+/* p, m, v [n] updated in place from g [n].  16-byte loads when all four pointers are 16-byte aligned, else element-wise;
+ * both give the same bits.  n = 0 returns QSAE_OK without a launch, whatever the pointers (an empty tensor's are NULL). */
+int qsae_adam_step(float* p, const float* g, float* m, float* v, long long n, float one_minus_b1, float b2,
+                   float one_minus_b2, float bc2_sqrt, float eps, float step_size, qsae_stream_t stream);
+/* The same step on the encoder weight W [H][D] and (all four non-NULL, or all four NULL) its bias [H], leaving Wq (fp16
+ * [H][D]) and meta (4 device floats) bit-identical to what qsae_prefilter_pack_w(W', bias', H, D, Wq, meta) writes for the
+ * updated values.  W and Wq 16-byte aligned.  No workspace: meta[0] carries max |W'| between the launches of the call. */
+int qsae_adam_step_prefilter(float* W, const float* gW, float* mW, float* vW, float* bias, const float* gb, float* mb,
+                             float* vb, int H, int D, float one_minus_b1, float b2, float one_minus_b2, float bc2_sqrt,
+                             float eps, float step_size, void* Wq, float* meta, qsae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,3 +17,4 @@ from .sae import (  # noqa: F401
     TernarySparseAutoencoder,
 )
 from .inference import SAE_REGISTRY, SAEWrapper, available_saes, load_sae  # noqa: F401
+from . import optim  # noqa: F401  (optim.Adam: the optimizer step in HIP)

@@ -167,6 +167,8 @@ SIGNATURES = {
     "qsae_train_mask_workspace_bytes": (_sz, [_i, _i]),
     "qsae_train_mask_init": (_i, [_vp, _vp, _i, _i, _i64, _vp, _sz, _vp]),
     "qsae_train_mask_update": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _sz, _vp]),
+    "qsae_adam_step": (_i, [_vp, _vp, _vp, _vp, C.c_longlong, _f, _f, _f, _f, _f, _f, _vp]),
+    "qsae_adam_step_prefilter": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp]),
 }
 
 

@@ -28,6 +28,42 @@ __device__ __forceinline__ float fp16_input_error(float v, float scaled, float b
     return e;
 }
 
+// ---- the fp16 copy of the encoder weight: what qsae_prefilter_pack_w (prefilter_topk.hip) and the Adam step that leaves
+// the same copy behind (optim.hip) both compute, bit for bit.  One wave per hidden unit; lane l walks d = l, l + 64, ...
+// with one pref_w_*_step per element (an fmaf chain per lane), then the xor-shuffle tree joins the 64 lanes.  The
+// order of both is part of the result: meta[1] and meta[3] are maxima over rows of these fp32 sums.
+__device__ __forceinline__ void pref_w_stat_step(float w, float& mx, float& ss) {
+    const float a = fabsf(w);
+    mx = (a > mx || a != a) ? a : mx;       // NaN propagates (a != a)
+    ss = fmaf(w, w, ss);
+}
+__device__ __forceinline__ void pref_w_stat_join(float& mx, float& ss) {
+    for (int off = 32; off > 0; off >>= 1) {
+        const float o = __shfl_xor(mx, off, 64);
+        mx = (o > mx || o != o) ? o : mx;
+        ss += __shfl_xor(ss, off, 64);
+    }
+}
+// a row's contribution to meta[1] from its joined sum of squares
+__device__ __forceinline__ float pref_w_row_norm(float ss) { return sqrtf(ss) * 1.000001f; }
+// the fp16 copy of one weight under the power-of-two scale sw: exact scaling, one RNE rounding.  The + 0 spells out what
+// the gfx950 code of the plain product computed (v_fma_mixlo_f16 with a +0 addend): a product that is exactly zero comes
+// out as +0 whatever its sign.  The code is now multiply, add, convert; the bits are those of the fused instruction
+// wherever w * sw is a normal fp32 number or an exact zero.  They differ in one corner: a negative product that underflows
+// the fp32 range (a subnormal weight under a scale far below 1, i.e. beside a max |W| near the top of the range) was
+// fp16 -0 and is +0 now.  The matrix core reads both as zero and fp16_input_error takes |.|: no result depends on it.
+__device__ __forceinline__ _Float16 pref_w_cast(float w, float sw) { return static_cast<_Float16>(w * sw + 0.0f); }
+__device__ __forceinline__ void pref_w_err_step(float w, float sw, float back, float& ff) {
+    const float e = fp16_input_error(w, w * sw, back);
+    ff = fmaf(e, e, ff);
+}
+__device__ __forceinline__ float pref_w_err_join(float ff) {
+    for (int off = 32; off > 0; off >>= 1) ff += __shfl_xor(ff, off, 64);
+    return ff;
+}
+// a row's contribution to meta[3] from its joined sum of squared input errors
+__device__ __forceinline__ float pref_w_row_err(float ff) { return sqrtf(ff) * 1.0001f; }
+
 // From a row's max |x|, sum x^2 and sum e^2 (e = fp16_input_error of its elements under the scale pow2_scale_for(max);
 // fp32 sums, any order; ee < 0: not measured, the worst case 2^-11 |x| is assumed): the power-of-two scale s_x of its
 // fp16 copy, inv = 1 / (s_x s_w) and margin = 2 eps_b.  eps_b bounds |approximate latent - exact fp32 chain| for every

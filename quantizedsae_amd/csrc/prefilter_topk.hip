@@ -63,19 +63,10 @@ pref_w_stats_kernel(const float* __restrict__ W, const float* __restrict__ bias,
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= H) return;
     float mx = 0.f, ss = 0.f;
-    for (int d = lane; d < D; d += 64) {
-        const float w = W[static_cast<int64_t>(row) * D + d];
-        const float a = fabsf(w);
-        mx = (a > mx || a != a) ? a : mx;       // NaN propagates (a != a)
-        ss = fmaf(w, w, ss);
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        const float o = __shfl_xor(mx, off, 64);
-        mx = (o > mx || o != o) ? o : mx;
-        ss += __shfl_xor(ss, off, 64);
-    }
+    for (int d = lane; d < D; d += 64) pref_w_stat_step(W[static_cast<int64_t>(row) * D + d], mx, ss);
+    pref_w_stat_join(mx, ss);
     if (lane == 0) {
-        const float nrm = sqrtf(ss) * 1.000001f;
+        const float nrm = pref_w_row_norm(ss);
         // non-negative floats (and NaN, which has the largest bit pattern) order like their bit patterns
         atomicMax(&meta[1], __float_as_uint(nrm));
         atomicMax(&meta[3], __float_as_uint(mx));
@@ -88,7 +79,7 @@ pref_w_cast_kernel(const float* __restrict__ W, long long n, float* __restrict__
     const float sw = pow2_scale_for(meta[3]);
     const long long gid = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (gid == 0) meta[0] = sw;
-    if (gid < n) Wq[gid] = static_cast<_Float16>(W[gid] * sw);       // exact scaling, one RNE rounding
+    if (gid < n) Wq[gid] = pref_w_cast(W[gid], sw);
 }
 
 // one wave per hidden unit: distance between the row and its fp16 copy as the matrix core reads it
@@ -100,13 +91,9 @@ pref_w_err_kernel(const float* __restrict__ W, int H, int D, const float* __rest
     if (!(sw > 0.f)) return;                                        // non-finite weights: every row is flagged anyway
     const float back = 1.0f / sw;
     float ff = 0.f;
-    for (int d = lane; d < D; d += 64) {
-        const float w = W[static_cast<int64_t>(row) * D + d];
-        const float e = fp16_input_error(w, w * sw, back);
-        ff = fmaf(e, e, ff);
-    }
-    for (int off = 32; off > 0; off >>= 1) ff += __shfl_xor(ff, off, 64);
-    if (lane == 0) atomicMax(out, __float_as_uint(sqrtf(ff) * 1.0001f));
+    for (int d = lane; d < D; d += 64) pref_w_err_step(W[static_cast<int64_t>(row) * D + d], sw, back, ff);
+    ff = pref_w_err_join(ff);
+    if (lane == 0) atomicMax(out, __float_as_uint(pref_w_row_err(ff)));
 }
 
 // one wave per activation row: fp16 copy scaled by a per-row power of two, 1/(sx*sw), margin = 2*eps_b.

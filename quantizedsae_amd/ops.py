@@ -2073,3 +2073,64 @@ def train_mask_update(w: torch.Tensor, mask: torch.Tensor, a: Optional[torch.Ten
     lib = _lib.load()
     ws = _train_ws(lib.qsae_train_mask_workspace_bytes(D, H), w.device)
     check(lib.qsae_train_mask_update(_p(w), _p(mask), _p(a), _p(delta), D, H, int(n), _p(ws), ws.numel(), _stream()))
+
+
+# ---- optimizer: the Adam step (csrc/optim.hip; quantizedsae_amd.optim.Adam is the user) -----------------------------------------
+def _adam_operands(who: str, names, tensors) -> None:
+    first = tensors[0]
+    for name, t in zip(names, tensors):
+        _dev(t, f"{who}: {name}", torch.float32)
+        if not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be contiguous (p, m and v are updated in place)")
+        if t.shape != first.shape or t.device != first.device:
+            raise ValueError(f"{who}: {name} is {tuple(t.shape)} on {t.device}, {names[0]} is {tuple(first.shape)} "
+                             f"on {first.device}")
+
+
+@_on_tensor_device
+def adam_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, one_minus_b1: float, b2: float,
+              one_minus_b2: float, bc2_sqrt: float, eps: float, step_size: float) -> None:
+    """One Adam step on p, m, v IN PLACE from the gradient g (all fp32, contiguous, the same shape; a view that starts off a
+    16-byte boundary is fine).  The scalars are Python floats, each rounded to fp32 once here; see qsae_adam_step."""
+    _adam_operands("adam_step", ("p", "g", "m", "v"), (p, g, m, v))
+    check(_lib.load().qsae_adam_step(_p(p), _p(g), _p(m), _p(v), p.numel(), one_minus_b1, b2, one_minus_b2, bc2_sqrt, eps,
+                                     step_size, _stream()))
+
+
+@_on_tensor_device
+def adam_step_prefilter(W: torch.Tensor, gW: torch.Tensor, mW: torch.Tensor, vW: torch.Tensor,
+                        bias: Optional[torch.Tensor], gb: Optional[torch.Tensor], mb: Optional[torch.Tensor],
+                        vb: Optional[torch.Tensor], one_minus_b1: float, b2: float, one_minus_b2: float, bc2_sqrt: float,
+                        eps: float, step_size: float, Wq: Optional[torch.Tensor] = None,
+                        meta: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """adam_step on the encoder weight W [H, D] and (all four given, or all four None) its bias [H], IN PLACE; -> (Wq, meta),
+    bit-identical to prefilter_pack_w(W, bias) of the updated values.  ``Wq`` (fp16 [H, D]) / ``meta`` (fp32 [4]): buffers
+    to write into instead of new ones.  See qsae_adam_step_prefilter."""
+    who = "adam_step_prefilter"
+    _adam_operands(who, ("W", "gW", "mW", "vW"), (W, gW, mW, vW))
+    if W.dim() != 2 or W.numel() == 0:
+        raise ValueError(f"{who}: W is {tuple(W.shape)}, expected [H >= 1, D >= 1]")
+    H, D = W.shape
+    quad = (bias, gb, mb, vb)
+    if any(t is None for t in quad) and not all(t is None for t in quad):
+        raise ValueError(f"{who}: bias, gb, mb and vb are given together or not at all")
+    if bias is not None:
+        _adam_operands(who, ("bias", "gb", "mb", "vb"), quad)
+        if tuple(bias.shape) != (H,) or bias.device != W.device:
+            raise ValueError(f"{who}: bias is {tuple(bias.shape)} on {bias.device}, W is {tuple(W.shape)} on {W.device}")
+    if W.data_ptr() % 16 != 0:
+        raise ValueError(f"{who}: W must be 16-byte aligned (the prefilter entry points ask for that too)")
+    if Wq is None:
+        Wq = torch.empty((H, D), dtype=torch.float16, device=W.device)
+    if meta is None:
+        meta = torch.empty((4,), dtype=torch.float32, device=W.device)
+    _dev(Wq, f"{who}: Wq", torch.float16)
+    _dev(meta, f"{who}: meta", torch.float32)
+    if tuple(Wq.shape) != (H, D) or tuple(meta.shape) != (4,) or not Wq.is_contiguous() or not meta.is_contiguous() \
+            or Wq.device != W.device or meta.device != W.device or Wq.data_ptr() % 16 != 0:
+        raise ValueError(f"{who}: Wq must be a contiguous 16-byte aligned fp16 [{H}, {D}] and meta a contiguous fp32 [4] on "
+                         f"{W.device}")
+    check(_lib.load().qsae_adam_step_prefilter(_p(W), _p(gW), _p(mW), _p(vW), _p(bias), _p(gb), _p(mb), _p(vb), H, D,
+                                               one_minus_b1, b2, one_minus_b2, bc2_sqrt, eps, step_size, _p(Wq), _p(meta),
+                                               _stream()))
+    return Wq, meta

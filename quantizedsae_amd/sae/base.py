@@ -90,6 +90,14 @@ class PackedCache:
         self._key = self._sig(tensors)
         self._value = value
 
+    def peek(self):
+        """The held value, current or stale, or None: for a caller that is about to replace it through put() and wants
+        to write into its buffers (quantizedsae_amd.optim.Adam)."""
+        return self._value
+
+    def is_current(self, tensors) -> bool:
+        return self._key is not None and self._key == self._sig(tensors)
+
     def clear(self):
         self._key = None
         self._value = None

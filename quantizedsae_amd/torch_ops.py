@@ -761,6 +761,33 @@ def _(W, want_table):
     return _f32((W.shape[1] if want_table else 0, W.shape[0]), W)
 
 
+# ---- optimizer: in-place dispatcher ops, so that the version counters of what they write move and every PackedCache keyed
+# on a stepped parameter rebuilds by itself ------------------------------------------------------------------------------------
+@_op("adam_step", mutates=("p", "m", "v"))
+def _adam_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, one_minus_b1: float, b2: float, one_minus_b2: float,
+               bc2_sqrt: float, eps: float, step_size: float) -> None:
+    _ops.adam_step(p, g, m, v, one_minus_b1, b2, one_minus_b2, bc2_sqrt, eps, step_size)
+
+
+@_adam_step.register_fake
+def _(p, g, m, v, one_minus_b1, b2, one_minus_b2, bc2_sqrt, eps, step_size):
+    return None
+
+
+@_op("adam_step_prefilter", mutates=("W", "mW", "vW", "bias", "mb", "vb", "Wq", "meta"))
+def _adam_step_prefilter(W: Tensor, gW: Tensor, mW: Tensor, vW: Tensor, bias: Optional[Tensor], gb: Optional[Tensor],
+                         mb: Optional[Tensor], vb: Optional[Tensor], one_minus_b1: float, b2: float, one_minus_b2: float,
+                         bc2_sqrt: float, eps: float, step_size: float, Wq: Tensor, meta: Tensor) -> None:
+    """Wq fp16 [H, D] and meta fp32 [4] receive the prefilter state of the updated W / bias"""
+    _ops.adam_step_prefilter(W, gW, mW, vW, bias, gb, mb, vb, one_minus_b1, b2, one_minus_b2, bc2_sqrt, eps, step_size,
+                             Wq, meta)
+
+
+@_adam_step_prefilter.register_fake
+def _(W, gW, mW, vW, bias, gb, mb, vb, one_minus_b1, b2, one_minus_b2, bc2_sqrt, eps, step_size, Wq, meta):
+    return None
+
+
 Q = torch.ops.qsae
 
 
@@ -1244,3 +1271,20 @@ train_ternary_dpre = _ops.train_ternary_dpre
 train_ternary_dweight = _ops.train_ternary_dweight
 train_mask_init = _ops.train_mask_init
 train_mask_update = _ops.train_mask_update
+
+
+# ---- optimizer (quantizedsae_amd.optim.Adam) ------------------------------------------------------------------------------------
+def adam_step(p, g, m, v, one_minus_b1, b2, one_minus_b2, bc2_sqrt, eps, step_size):
+    Q.adam_step(p, g, m, v, float(one_minus_b1), float(b2), float(one_minus_b2), float(bc2_sqrt), float(eps), float(step_size))
+
+
+def adam_step_prefilter(W, gW, mW, vW, bias, gb, mb, vb, one_minus_b1, b2, one_minus_b2, bc2_sqrt, eps, step_size,
+                        Wq=None, meta=None):
+    """-> (Wq, meta); ``Wq`` / ``meta`` given: written in place and returned"""
+    if Wq is None:
+        Wq = torch.empty(W.shape, dtype=torch.float16, device=W.device)
+    if meta is None:
+        meta = torch.empty((4,), dtype=torch.float32, device=W.device)
+    Q.adam_step_prefilter(W, gW, mW, vW, bias, gb, mb, vb, float(one_minus_b1), float(b2), float(one_minus_b2),
+                          float(bc2_sqrt), float(eps), float(step_size), Wq, meta)
+    return Wq, meta
