@@ -862,6 +862,27 @@ int qsae_train_mask_init(float* w, float* mask, int D, int H, int64_t n_inactive
 int qsae_train_mask_update(float* w, float* mask, const float* a, const float* delta, int D, int H, int64_t n,
                            void* workspace, size_t workspace_bytes, qsae_stream_t stream);
 
+/* -- BinaryLatentSAE training: the gradient of pre = x W_e^T + b_e, z = (sigmoid(pre) >= 0.5), recon = z W_d^T + b_d under
+ *    the straight-through estimator decode(latent + (binary - latent).detach()) (sae/binary_latent.py:19-27; the bl_sae of
+ *    training/trainer.py).  w_dec is decoder.weight [D][H] as nn.Linear keeps it; no transposed copy is made.  The encoder
+ *    gradients come from dpre through qsae_train_gemm_tn / qsae_train_col_sum, the decoder bias from qsae_train_col_sum.
+ *    All three take H a multiple of 32, B >= 1 and B * H below 2^31; every argument is checked before any HIP call.  No float
+ *    atomics anywhere: bitwise reproducible. ------------------------------------------------------------------------- */
+/* One pass over pre [B][H] (contiguous, 16-byte aligned): latent[r][h] = pre[r][h] >= cutoff ? 1 : 0 -- the bits of
+ * qsae_threshold_ge; NaN gives 0 -- and zbits[r][h / 32] bit h % 32 the same predicate (zbits [B][H / 32], contiguous).
+ * latent may be NULL (bits only).  Not the cutoff of qsae_train_pre_bits, which is the > 0.5 of the q_sae paths. */
+int qsae_blatent_binarize(const float* pre, int B, int H, float cutoff, float* latent, uint32_t* zbits, qsae_stream_t stream);
+/* pre [B][H] (contiguous) holds the encoder pre-activation on entry and dpre on return:
+ *   dpre[r][h] = <g_recon[r], w_dec[:, h]> p (1 - p),  p = sigmoid(pre[r][h])
+ * on the fp32 matrix pipe (k = d ascending).  g_recon [B][D] is read K-contiguous, w_dec [D][H] in its own layout through
+ * the K-slow loader.  D a multiple of 4 up to 4096; g_recon and w_dec 16-byte aligned. */
+int qsae_train_blatent_dpre(const float* g_recon, const float* w_dec, int B, int D, int H, float* pre, qsae_stream_t stream);
+/* dweight[d][h] = sum over rows r with z bit h set of g_recon[r][d], r ascending: the TN contraction of qsae_train_gemm_tn
+ * with the H-side operand expanded from zbits [B][words_ld] (K = B, the last K slice zero-filled), stored straight into the
+ * [D][H] layout of decoder.weight.  D a multiple of 4 up to 4096; g_recon 16-byte aligned; words_ld >= H / 32. */
+int qsae_train_blatent_dweight(const float* g_recon, const uint32_t* zbits, int64_t words_ld, int B, int D, int H,
+                               float* dweight, qsae_stream_t stream);
+
 /* -- Optimizer: the Adam step in one pass.  Per element, every line one IEEE fp32 operation, no
  *    contraction -- the op sequence of torch's single-tensor Adam with amsgrad, maximize and weight decay off:
  *        d = g - m;       m' = m + d * one_minus_b1

@@ -164,6 +164,9 @@ SIGNATURES = {
     "qsae_train_ternary_rows": (_i, [_vp, _i, _i, _vp, _vp]),
     "qsae_train_ternary_dpre": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "qsae_train_ternary_dweight": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "qsae_blatent_binarize": (_i, [_vp, _i, _i, _f, _vp, _vp, _vp]),
+    "qsae_train_blatent_dpre": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "qsae_train_blatent_dweight": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp]),
     "qsae_train_mask_workspace_bytes": (_sz, [_i, _i]),
     "qsae_train_mask_init": (_i, [_vp, _vp, _i, _i, _i64, _vp, _sz, _vp]),
     "qsae_train_mask_update": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _sz, _vp]),

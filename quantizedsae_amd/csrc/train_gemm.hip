@@ -6,6 +6,7 @@
 //   dpre[r][h] = dz[r][h] p (1 - p),  p = sigmoid(pre[r][h])                       epilogue of the same kernel, in place
 //   dW_enc[h][d] = sum_r dpre[r][h] x[r][d]                                        TN: K = B is the SLOW axis of both
 //   dSum[h][d]   = sum_r z[r][h] G_i[r][d]     (dense activations)                 TN, A expanded from the z bits
+// The TernarySparseAutoencoder and BinaryLatentSAE backwards (further down) are other pairings of the same loaders.
 //
 // The TN operands are staged by loaders that read 16-byte chunks ACROSS the output rows for a fixed k and write them
 // transposed into the LDS image of gemm_mfma_f32.h, so the MFMA loop -- and with it the fmaf chain in ascending r -- is the
@@ -297,6 +298,58 @@ ternary_dpre_const_kernel(const float* __restrict__ gh, const float* __restrict_
         dpre[i] = (gh && h[i] > 0.0f) ? gh[i] : 0.0f;
 }
 
+// BinaryLatentSAE: pre[row][col] <- acc p (1 - p), p = sigmoid(pre[row][col]) -- EpiDpre without a level scale or a group term
+// (the binary latent itself is not differentiable in the reference, so no gradient arrives beside the reconstruction's).
+template <int BM, int BN>
+struct EpiBlatentDpre : EpiTile<BM, BN> {
+    using T = EpiTile<BM, BN>;
+    static constexpr int MT = T::MT, NT = T::NT;
+    struct Args {
+        float* pre;            // [M][ld]
+        int64_t ld;
+    };
+    __device__ __forceinline__ void init(const Args&, f32x16 (&acc)[MT][NT], const TileCtx&) { T::fill(acc, 0.0f); }
+    __device__ __forceinline__ void finish(const Args& a, f32x16 (&acc)[MT][NT], const TileCtx& c) {
+        T::for_each_row(c, [=, &acc](int mt, int r, int row) {
+            float* prow = a.pre + static_cast<int64_t>(row) * a.ld;
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                const int col = T::col(c, nt);
+                if (col >= c.N) continue;
+                const float p = soft_bit_prob(prow[col]);
+                prow[col] = acc[mt][nt][r] * (p * (1.0f - p));
+            }
+        });
+    }
+};
+
+// latent[i] = pre[i] >= cutoff ? 1 : 0 (nullable) and its bits, one word per 8 lanes: a lane compares 4 consecutive units, the
+// 8 nibbles of a word meet through three xor shuffles.  H % 32 == 0, so a word never straddles two rows.
+__global__ void __launch_bounds__(256)
+blatent_binarize_kernel(const float* __restrict__ pre, long long total4, float cutoff, float* __restrict__ latent,
+                        uint32_t* __restrict__ zbits) {
+    const int lane = threadIdx.x & 63;
+    const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
+    for (long long base = static_cast<long long>(blockIdx.x) * blockDim.x + (threadIdx.x - lane); base < total4; base += stride) {
+        const long long i = base + lane;
+        const bool ok = i < total4;
+        uint32_t word = 0;
+        if (ok) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(pre + 4 * i);
+            const bool b0 = v[0] >= cutoff, b1 = v[1] >= cutoff, b2 = v[2] >= cutoff, b3 = v[3] >= cutoff;
+            if (latent)
+                *reinterpret_cast<f32x4*>(latent + 4 * i) = f32x4{b0 ? 1.0f : 0.0f, b1 ? 1.0f : 0.0f, b2 ? 1.0f : 0.0f, b3 ? 1.0f : 0.0f};
+            word = ((b0 ? 1u : 0u) | (b1 ? 2u : 0u) | (b2 ? 4u : 0u) | (b3 ? 8u : 0u)) << (4 * (lane & 7));
+        }
+        word |= __shfl_xor(word, 1, 64);                   // every lane of the wave takes part
+        word |= __shfl_xor(word, 2, 64);
+        word |= __shfl_xor(word, 4, 64);
+        if (ok && (lane & 7) == 0) zbits[i >> 3] = word;
+    }
+}
+
+inline bool blatent_shape_ok(int B, int H) { return H > 0 && H % 32 == 0 && static_cast<long long>(B) * H < (1LL << 31); }
+
 struct TrainLevels {
     int n;
     int begin[kTnMaxLevels], size[kTnMaxLevels];
@@ -448,4 +501,58 @@ extern "C" int qsae_train_ternary_dweight(const float* g_recon, const float* h, 
     using Epi = EpiStoreMasked<128, 128>;
     return run_tn<LA, LA, Epi>(typename LA::Args{g_recon, D, D}, typename LA::Args{h, H, H}, typename Epi::Args{dweight, mask, H},
                                D, H, B, as_stream(stream));
+}
+
+// ---- BinaryLatentSAE training (reference: sae/binary_latent.py:19-27 under loss.backward(); the bl_sae of training/trainer.py).
+// The latent is dense (about half of the bits are set), so the contractions are encoder-sized.  decoder.weight [D][H] is read
+// in its own layout by both: as the K-slow operand of dpre (K = D) and as the store layout of dweight. ---------------------
+extern "C" int qsae_blatent_binarize(const float* pre, int B, int H, float cutoff, float* latent, uint32_t* zbits,
+                                     qsae_stream_t stream) {
+    QSAE_CHECK_ARG(B >= 1 && H > 0, "B >= 1, H > 0 required");
+    QSAE_CHECK_SUPPORTED(blatent_shape_ok(B, H), "H a multiple of 32, B * H below 2^31");
+    QSAE_CHECK_ARG(pre && zbits, "pre and zbits required");
+    QSAE_CHECK_ARG(aligned16(pre) && (!latent || aligned16(latent)), "pre and latent must be 16-byte aligned");
+    const long long total4 = static_cast<long long>(B) * (H / 4);
+    long long blocks = (total4 + 255) / 256;
+    if (blocks > 16384) blocks = 16384;
+    hipLaunchKernelGGL(blatent_binarize_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, as_stream(stream), pre, total4,
+                       cutoff, latent, zbits);
+    QSAE_LAUNCH_CHECK();
+    return QSAE_OK;
+}
+
+extern "C" int qsae_train_blatent_dpre(const float* g_recon, const float* w_dec, int B, int D, int H, float* pre,
+                                       qsae_stream_t stream) {
+    QSAE_CHECK_ARG(B >= 1 && D > 0 && H > 0, "B >= 1, D > 0, H > 0 required");
+    QSAE_CHECK_SUPPORTED(tn_shape_ok(D) && blatent_shape_ok(B, H),
+                         "D a multiple of 4, at most 4096; H a multiple of 32; B * H below 2^31");
+    QSAE_CHECK_ARG(g_recon && w_dec && pre, "null pointer");
+    QSAE_CHECK_ARG(aligned16(g_recon) && aligned16(w_dec), "g_recon and w_dec must be 16-byte aligned");
+    // R = g_recon [B][D], K-contiguous; Cm = decoder.weight as it lies, element (h, k = d) at w_dec[d H + h]: the K-slow loader
+    using LB = LoaderTN<128, 32>;
+    using Epi = EpiBlatentDpre<128, 128>;
+    const typename LB::Args lb{w_dec, H, H};
+    const typename Epi::Args ea{pre, H};
+    const int sweep = pick_sweep<128, 128>(B, H, D);
+    hipStream_t s = as_stream(stream);
+    if (D % 32 == 0) {
+        using LA = LoaderF32<128, 32, false>;
+        return launch_gemm<LA, LB, Epi, 128, 128, 32>(typename LA::Args{g_recon, D, B}, lb, ea, B, H, D, sweep, s);
+    }
+    using LA = LoaderF32<128, 32, true>;
+    return launch_gemm<LA, LB, Epi, 128, 128, 32>(typename LA::Args{g_recon, D, B}, lb, ea, B, H, D, sweep, s);
+}
+
+extern "C" int qsae_train_blatent_dweight(const float* g_recon, const uint32_t* zbits, int64_t words_ld, int B, int D, int H,
+                                          float* dweight, qsae_stream_t stream) {
+    QSAE_CHECK_ARG(B >= 1 && D > 0 && H > 0, "B >= 1, D > 0, H > 0 required");
+    QSAE_CHECK_SUPPORTED(tn_shape_ok(D) && blatent_shape_ok(B, H),
+                         "D a multiple of 4, at most 4096; H a multiple of 32; B * H below 2^31");
+    QSAE_CHECK_ARG(g_recon && zbits && dweight && words_ld >= H / 32, "null pointer or words_ld < H / 32");
+    QSAE_CHECK_ARG(aligned16(g_recon), "g_recon must be 16-byte aligned");
+    using LA = LoaderTN<128, 32>;
+    using LB = LoaderTNBits<128, 32>;
+    using Epi = EpiStore<128, 128>;
+    return run_tn<LA, LB, Epi>(typename LA::Args{g_recon, D, D}, typename LB::Args{zbits, words_ld, H, 0},
+                               typename Epi::Args{dweight, H}, D, H, B, as_stream(stream));
 }

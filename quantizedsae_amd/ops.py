@@ -2033,6 +2033,64 @@ def train_ternary_dweight(g_recon: torch.Tensor, h: torch.Tensor, mask: torch.Te
     return out
 
 
+# ---- BinaryLatentSAE training -------------------------------------------------------------------------------------------
+def train_blatent_supported(D: int, H: int) -> bool:
+    return 0 < D <= TRAIN_MAX_D and D % 4 == 0 and H > 0 and H % 32 == 0
+
+
+_BLATENT_LIMITS = f"D a multiple of 4 up to {TRAIN_MAX_D}, H a multiple of 32, B >= 1 and B * H below 2^31"
+
+
+@_on_tensor_device
+def blatent_binarize(pre: torch.Tensor, cutoff: float, want_latent: bool = True):
+    """pre [B, H] -> (latent fp32 [B, H] = (pre >= cutoff) or None, zbits int32 [B, H / 32]) in one pass; see
+    qsae_blatent_binarize."""
+    _dev(pre, "pre", torch.float32)
+    if pre.dim() != 2 or not pre.is_contiguous() or pre.shape[0] < 1 or pre.shape[1] < 1 or pre.shape[1] % 32 \
+            or pre.numel() >= 2 ** 31:
+        raise ValueError(f"blatent_binarize: pre must be a contiguous [B, H] tensor with H a multiple of 32, B >= 1 and "
+                         f"B * H below 2^31, got {tuple(pre.shape)}")
+    B, H = pre.shape
+    latent = torch.empty_like(pre) if want_latent else None
+    zbits = torch.empty((B, H // 32), dtype=torch.int32, device=pre.device)
+    check(_lib.load().qsae_blatent_binarize(_p(pre), B, H, float(cutoff), _p(latent), _p(zbits), _stream()))
+    return latent, zbits
+
+
+@_on_tensor_device
+def train_blatent_dpre(pre: torch.Tensor, g_recon: torch.Tensor, w_dec: torch.Tensor) -> torch.Tensor:
+    """The pre-activation [B, H] (contiguous fp32) becomes dpre IN PLACE and is returned; w_dec is decoder.weight [D, H] as it
+    lies; see qsae_train_blatent_dpre."""
+    _dev(pre, "pre", torch.float32)
+    if pre.dim() != 2 or not pre.is_contiguous():
+        raise ValueError("train_blatent_dpre: pre must be a contiguous [B, H] tensor (it is updated in place)")
+    B, H = pre.shape
+    G, w_dec = _f32c(g_recon, "g_recon"), _f32c(w_dec, "w_dec")
+    D = w_dec.shape[0]
+    if not train_blatent_supported(D, H) or B < 1 or B * H >= 2 ** 31:
+        raise ValueError(f"train_blatent_dpre: {_BLATENT_LIMITS} (got B = {B}, D = {D}, H = {H})")
+    if tuple(w_dec.shape) != (D, H) or tuple(G.shape) != (B, D):
+        raise ValueError("train_blatent_dpre: inconsistent shapes")
+    check(_lib.load().qsae_train_blatent_dpre(_p(G), _p(w_dec), B, D, H, _p(pre), _stream()))
+    return pre
+
+
+@_on_tensor_device
+def train_blatent_dweight(g_recon: torch.Tensor, zbits: torch.Tensor, H: int) -> torch.Tensor:
+    """-> g_recon^T z [D, H] in the layout of decoder.weight, z expanded from zbits [B, H / 32]; see
+    qsae_train_blatent_dweight."""
+    _dev(zbits, "zbits", torch.int32)
+    G = _f32c(g_recon, "g_recon")
+    B, D = G.shape
+    if not train_blatent_supported(D, H) or B < 1 or B * H >= 2 ** 31:
+        raise ValueError(f"train_blatent_dweight: {_BLATENT_LIMITS} (got B = {B}, D = {D}, H = {H})")
+    if zbits.dim() != 2 or zbits.shape[0] != B or zbits.stride(1) != 1 or zbits.shape[1] * 32 < H:
+        raise ValueError("train_blatent_dweight: inconsistent shapes")
+    out = torch.empty((D, H), dtype=torch.float32, device=G.device)
+    check(_lib.load().qsae_train_blatent_dweight(_p(G), _p(zbits), zbits.stride(0), B, D, H, _p(out), _stream()))
+    return out
+
+
 def _mask_operands(w: torch.Tensor, mask: torch.Tensor, what: str):
     for t, name in ((w, "weight"), (mask, "mask")):
         _dev(t, name, torch.float32)

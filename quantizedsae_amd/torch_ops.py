@@ -1273,6 +1273,14 @@ train_mask_init = _ops.train_mask_init
 train_mask_update = _ops.train_mask_update
 
 
+# ---- BinaryLatentSAE training: called from an autograd.Function only (dpre updates the saved pre-activation in place through
+# its pointer), never traced -- plain functions over ops.py ------------------------------------------------------------------
+train_blatent_supported = _ops.train_blatent_supported
+blatent_binarize = _ops.blatent_binarize
+train_blatent_dpre = _ops.train_blatent_dpre
+train_blatent_dweight = _ops.train_blatent_dweight
+
+
 # ---- optimizer (quantizedsae_amd.optim.Adam) ------------------------------------------------------------------------------------
 def adam_step(p, g, m, v, one_minus_b1, b2, one_minus_b2, bc2_sqrt, eps, step_size):
     Q.adam_step(p, g, m, v, float(one_minus_b1), float(b2), float(one_minus_b2), float(bc2_sqrt), float(eps), float(step_size))
