@@ -902,6 +902,47 @@ int qsae_adam_step_prefilter(float* W, const float* gW, float* mW, float* vW, fl
                              float* vb, int H, int D, float one_minus_b1, float b2, float one_minus_b2, float bc2_sqrt,
                              float eps, float step_size, void* Wq, float* meta, qsae_stream_t stream);
 
+/* -- Trainer: what the epoch loop does around forward_train (training/trainer.py:73-173).  src is a
+ *    chunk of hidden states [n_rows][D], contiguous, dtype 0 = fp32, 1 = fp16, 2 = bf16 (the codes of
+ *    qsae_dataset_moments_add).  Invalid arguments are answered before any HIP call; no float atomics: the same bits on
+ *    every run. --------------------------------------------------------------------------------------------------------- */
+/* bits uint32 [ceil(n_rows / 32)], every word written once: bit r % 32 of word r / 32 is set where row r holds a NaN (tested
+ * on the stored bits; inf does not count), the bits past n_rows are 0.  One pass over the chunk, 16-byte loads when src is
+ * 16-byte aligned and a row is a whole number of 16-byte pieces.  Replaces `torch.isnan(batch).any()` per step
+ * (trainer.py:84): built once per chunk, read once per chunk.  n_rows == 0: QSAE_OK without a launch, whatever the pointers.
+ * Errors: QSAE_ERR_INVALID_ARG (n_rows < 0, D < 1, null or misaligned pointers), QSAE_ERR_UNSUPPORTED (unknown dtype,
+ * n_rows > 32 * (2^31 - 1)). */
+int qsae_rows_nan_bitmap(const void* src, int dtype, int64_t n_rows, int D, uint32_t* bits, qsae_stream_t stream);
+/* out[b][:] = float(src[idx[b]][:]) for b < B: idx int64 [B] and out fp32 [B][D] on the device.  The widening is exact, so
+ * out has the bits of the reference's `.float()` (data/dataset.py:32) for every value that is not a NaN; fp32 rows are
+ * copied, a bf16 NaN keeps sign and payload, an fp16 NaN keeps them when it is quiet (the hardware conversion quiets a
+ * signalling one; torch's CPU `.float()` maps every fp16 NaN to one pattern of its own).  Batches with a NaN are skipped by
+ * the loop, so no such value reaches a model.  An index outside [0, n_rows)
+ * is never dereferenced: its row is written as zeros and bit 0 of *flag (uint32, device, zeroed by the caller) is set
+ * through an integer atomic.  16-byte loads and stores when src and out are 16-byte aligned and a source row is a whole
+ * number of 16-byte pieces (D % 4 == 0 for fp32, D % 8 == 0 for the 16-bit types), element by element otherwise.
+ * B == 0: QSAE_OK without a launch, whatever the pointers.  src may be NULL only when n_rows == 0. */
+int qsae_gather_rows(const void* src, int dtype, int64_t n_rows, int D, const int64_t* idx, int B, float* out, uint32_t* flag,
+                     qsae_stream_t stream);
+/* The reconstruction losses of n <= 8 levels and their gradients in one pass (the per-type recipes of trainer.py:88-173).
+ * x, every recon_ptrs[i] and every grads_ptrs[i] are fp32 [B][D], contiguous; recon_ptrs / grads_ptrs are HOST arrays of n
+ * device pointers.  mode 0: the target of every level is t_i = x.  mode 1 (rq_sae): t_0 = x, t_{i+1} = fl(fl(t_i - r_i) * 2),
+ * the arithmetic of qsae_residual_update.  With N = B D and s = fp32(2 coef / N) formed in double:
+ *   grads_ptrs[i][e] = fl(fl(r_i[e] - t_i[e]) * s)
+ *   losses[i] (fp32, device) = fp32((coef * S_i) / N), both operations in fp64, S_i = the fp64 sum of fp32(fl(r_i[e] - t_i[e])^2)
+ * Order of S_i: workgroup b owns the elements [4096 b, 4096 (b + 1)) in 4 slabs of 1024; thread t of 256 adds the elements
+ * 4 t .. 4 t + 3 of slab 0, then of slab 1, ...; the 64 lane sums of a wave are joined by a butterfly (xor 32, 16, ..., 1),
+ * the 4 wave sums added in ascending order; then thread t of one workgroup per level adds the workgroup sums t, t + 256, ...
+ * in ascending order and the 256 thread sums are joined the same way.  x and every r_i are read once; nothing of size
+ * [B][D] is written other than the gradients.  16-byte loads and stores when all 2 n + 1 pointers are 16-byte aligned,
+ * scalar ones otherwise: the same bits.  n == 0 or B == 0: QSAE_OK without a launch, nothing written.
+ * Errors: QSAE_ERR_INVALID_ARG (negative n or B, D < 1, null or misaligned pointers), QSAE_ERR_UNSUPPORTED (n > 8, unknown
+ * mode, B D above 4096 * (2^31 - 1)), QSAE_ERR_WORKSPACE.  workspace: 8-byte aligned,
+ * qsae_trainer_loss_workspace_bytes(n, B, D) = n * ceil(B D / 4096) * 8 rounded up to 256 (0 for an invalid shape). */
+size_t qsae_trainer_loss_workspace_bytes(int n, int B, int D);
+int qsae_trainer_loss(const float* x, const float* const* recon_ptrs, int n, int B, int D, int mode, double coef,
+                      float* const* grads_ptrs, float* losses, void* workspace, size_t workspace_bytes, qsae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

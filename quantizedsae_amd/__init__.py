@@ -18,3 +18,5 @@ from .sae import (  # noqa: F401
 )
 from .inference import SAE_REGISTRY, SAEWrapper, available_saes, load_sae  # noqa: F401
 from . import optim  # noqa: F401  (optim.Adam: the optimizer step in HIP)
+from . import training  # noqa: F401  (training.Trainer: the reference's epoch loop on the GPU)
+from .training import Trainer  # noqa: F401

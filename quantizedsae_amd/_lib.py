@@ -172,6 +172,10 @@ SIGNATURES = {
     "qsae_train_mask_update": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _sz, _vp]),
     "qsae_adam_step": (_i, [_vp, _vp, _vp, _vp, C.c_longlong, _f, _f, _f, _f, _f, _f, _vp]),
     "qsae_adam_step_prefilter": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp]),
+    "qsae_rows_nan_bitmap": (_i, [_vp, _i, _i64, _i, _vp, _vp]),
+    "qsae_gather_rows": (_i, [_vp, _i, _i64, _i, _vp, _i, _vp, _vp, _vp]),
+    "qsae_trainer_loss_workspace_bytes": (_sz, [_i, _i, _i]),
+    "qsae_trainer_loss": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_double, _vp, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -2192,3 +2192,89 @@ def adam_step_prefilter(W: torch.Tensor, gW: torch.Tensor, mW: torch.Tensor, vW:
                                                one_minus_b1, b2, one_minus_b2, bc2_sqrt, eps, step_size, _p(Wq), _p(meta),
                                                _stream()))
     return Wq, meta
+
+
+# ---- trainer: batch supply and loss (csrc/trainer.hip; quantizedsae_amd.training is the user) ------------------------------------
+TRAINER_LOSS_MAX_LEVELS = 8
+
+
+def _chunk_rows(src: torch.Tensor, who: str):
+    """src: a chunk of hidden states, [..., D] contiguous in fp32 / fp16 / bf16 -> (rows, D)."""
+    _dev(src, f"{who}: src")
+    if src.dtype not in MOMENTS_DTYPES:
+        raise TypeError(f"{who}: src: expected fp32, fp16 or bf16, got {src.dtype}")
+    if src.dim() < 2 or src.shape[-1] < 1 or not src.is_contiguous():
+        raise ValueError(f"{who}: src must be contiguous [..., D >= 1], got {tuple(src.shape)} with strides {src.stride()}")
+    D = src.shape[-1]
+    return src.numel() // D, D
+
+
+@_on_tensor_device
+def rows_nan_bitmap(src: torch.Tensor) -> torch.Tensor:
+    """-> int32 [ceil(rows / 32)] on the device: bit r % 32 of word r // 32 is set where row r of src [..., D] (fp32, fp16 or
+    bf16; the leading dimensions are flattened) holds a NaN; inf does not count.  See qsae_rows_nan_bitmap."""
+    rows, D = _chunk_rows(src, "rows_nan_bitmap")
+    bits = torch.empty(((rows + 31) // 32,), dtype=torch.int32, device=src.device)
+    check(_lib.load().qsae_rows_nan_bitmap(_p(src), MOMENTS_DTYPES[src.dtype], rows, D, _p(bits), _stream()))
+    return bits
+
+
+@_on_tensor_device
+def gather_rows(src: torch.Tensor, idx: torch.Tensor, flag: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> fp32 [B, D]: out[b] = src[idx[b]].float() over the rows of src [..., D] (leading dimensions flattened), idx int64 [B]
+    on the device.  An index outside the chunk gives a row of zeros and sets bit 0 of ``flag`` (int32 [1] on the device,
+    zeroed by the caller); nothing is read back here.  See qsae_gather_rows."""
+    rows, D = _chunk_rows(src, "gather_rows")
+    _dev(idx, "gather_rows: idx", torch.int64)
+    _dev(flag, "gather_rows: flag", torch.int32)
+    if idx.dim() != 1 or not idx.is_contiguous() or flag.numel() != 1 or idx.device != src.device or flag.device != src.device:
+        raise ValueError(f"gather_rows: idx must be a contiguous int64 [B] and flag an int32 [1] on {src.device}, got "
+                         f"{tuple(idx.shape)} on {idx.device} and {tuple(flag.shape)} on {flag.device}")
+    B = idx.shape[0]
+    if out is None:
+        out = torch.empty((B, D), dtype=torch.float32, device=src.device)
+    else:
+        _dev(out, "gather_rows: out", torch.float32)
+        if tuple(out.shape) != (B, D) or not out.is_contiguous() or out.device != src.device:
+            raise ValueError(f"gather_rows: out must be a contiguous fp32 [{B}, {D}] on {src.device}")
+    check(_lib.load().qsae_gather_rows(_p(src), MOMENTS_DTYPES[src.dtype], rows, D, _p(idx), B, _p(out), _p(flag), _stream()))
+    return out
+
+
+@_on_tensor_device
+def trainer_loss(x: torch.Tensor, recons, mode: int, coef: float, grads: Optional[torch.Tensor] = None):
+    """-> (losses fp32 [n], grads fp32 [n, B, D]), both on the device: losses[i] = coef * mse(recons[i], t_i) and grads[i] its
+    gradient at recons[i], t_i = x (mode 0) or the detached doubled residual chain of rq_sae (mode 1), in one pass over x and
+    the n <= 8 reconstructions (fp32 [B, D], contiguous; views that start off a 16-byte boundary are fine).  ``grads``: a
+    buffer to write into instead of a new one.  See qsae_trainer_loss."""
+    who = "trainer_loss"
+    _dev(x, f"{who}: x", torch.float32)
+    if x.dim() != 2 or not x.is_contiguous() or x.shape[1] < 1:
+        raise ValueError(f"{who}: x must be a contiguous fp32 [B, D >= 1], got {tuple(x.shape)} with strides {x.stride()}")
+    B, D = x.shape
+    recons = list(recons)
+    n = len(recons)
+    if not 1 <= n <= TRAINER_LOSS_MAX_LEVELS:
+        raise ValueError(f"{who}: takes 1 to {TRAINER_LOSS_MAX_LEVELS} reconstructions, got {n}")
+    if mode not in (0, 1):
+        raise ValueError(f"{who}: mode must be 0 (every level against x) or 1 (the doubled residual chain), got {mode!r}")
+    for i, r in enumerate(recons):
+        _dev(r, f"{who}: recons[{i}]", torch.float32)
+        if r.shape != x.shape or not r.is_contiguous() or r.device != x.device:
+            raise ValueError(f"{who}: recons[{i}] is {tuple(r.shape)} on {r.device} (strides {r.stride()}), x is a contiguous "
+                             f"{tuple(x.shape)} on {x.device}")
+    if grads is None:
+        grads = torch.empty((n, B, D), dtype=torch.float32, device=x.device)
+    else:
+        _dev(grads, f"{who}: grads", torch.float32)
+        if tuple(grads.shape) != (n, B, D) or not grads.is_contiguous() or grads.device != x.device:
+            raise ValueError(f"{who}: grads must be a contiguous fp32 [{n}, {B}, {D}] on {x.device}")
+    losses = torch.empty((n,), dtype=torch.float32, device=x.device)
+    if B == 0:
+        return losses.fill_(float("nan")), grads             # the mean over nothing, as F.mse_loss reports it
+    lib = _lib.load()
+    ws = _workspace(x.device, max(int(lib.qsae_trainer_loss_workspace_bytes(n, B, D)), 16))
+    rp = (C.c_void_p * n)(*[r.data_ptr() for r in recons])
+    gp = (C.c_void_p * n)(*[grads.data_ptr() + i * B * D * 4 for i in range(n)])
+    check(lib.qsae_trainer_loss(_p(x), rp, n, B, D, int(mode), float(coef), gp, _p(losses), _p(ws), ws.numel(), _stream()))
+    return losses, grads

@@ -788,6 +788,40 @@ def _(W, gW, mW, vW, bias, gb, mb, vb, one_minus_b1, b2, one_minus_b2, bc2_sqrt,
     return None
 
 
+# ---- trainer: batch supply and loss (csrc/trainer.hip) -------------------------------------------------------------------
+@_op("rows_nan_bitmap")
+def _rows_nan_bitmap(src: Tensor) -> Tensor:
+    """-> int32 [ceil(rows / 32)]: the rows of src [..., D] that hold a NaN, one bit each"""
+    return _ops.rows_nan_bitmap(src)
+
+
+@_rows_nan_bitmap.register_fake
+def _(src):
+    return _i32(((src.numel() // src.shape[-1] + 31) // 32,), src)
+
+
+@_op("gather_rows", mutates=("flag",))
+def _gather_rows(src: Tensor, idx: Tensor, flag: Tensor) -> Tensor:
+    """-> fp32 [B, D] = src[idx].float(); flag int32 [1] gets bit 0 where an index is outside the chunk"""
+    return _ops.gather_rows(src, idx, flag)
+
+
+@_gather_rows.register_fake
+def _(src, idx, flag):
+    return _f32((idx.shape[0], src.shape[-1]), src)
+
+
+@_op("trainer_loss", mutates=("grads",))
+def _trainer_loss(x: Tensor, recons: List[Tensor], mode: int, coef: float, grads: Tensor) -> Tensor:
+    """-> losses fp32 [n]; grads fp32 [n, B, D] receives the gradient of every level's loss at its reconstruction"""
+    return _ops.trainer_loss(x, recons, mode, coef, grads)[0]
+
+
+@_trainer_loss.register_fake
+def _(x, recons, mode, coef, grads):
+    return _f32((len(recons),), x)
+
+
 Q = torch.ops.qsae
 
 
@@ -1296,3 +1330,19 @@ def adam_step_prefilter(W, gW, mW, vW, bias, gb, mb, vb, one_minus_b1, b2, one_m
     Q.adam_step_prefilter(W, gW, mW, vW, bias, gb, mb, vb, float(one_minus_b1), float(b2), float(one_minus_b2),
                           float(bc2_sqrt), float(eps), float(step_size), Wq, meta)
     return Wq, meta
+
+
+def rows_nan_bitmap(src):
+    return Q.rows_nan_bitmap(src)
+
+
+def gather_rows(src, idx, flag):
+    return Q.gather_rows(src, idx, flag)
+
+
+def trainer_loss(x, recons, mode, coef, grads=None):
+    """-> (losses fp32 [n], grads fp32 [n, B, D])"""
+    recons = list(recons)
+    if grads is None:
+        grads = torch.empty((len(recons),) + tuple(x.shape), dtype=torch.float32, device=x.device)
+    return Q.trainer_loss(x, recons, int(mode), float(coef), grads), grads

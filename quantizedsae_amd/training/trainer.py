@@ -1,0 +1,244 @@
+"""``Trainer``: the reference's epoch loop (training/trainer.py:18-261) on the GPU.
+
+The constructor arguments, ``one_epoch`` and ``train`` are the reference's; the pieces of a step are this package's:
+``ShuffledChunk`` supplies the DataLoader's batches from a device-resident chunk, ``model.forward_train`` carries the HIP
+backward, ``trainer_loss`` the per-type loss, ``optim.Adam`` the step.  What differs from the reference, on purpose:
+
+* ``bl_sae`` has no branch in the reference's loop, which never steps it; here it trains with ``mse`` + Adam, the recipe
+  of tests/golden/train_blatent_loop.npz.
+* ``t_sae`` without ``rigL`` raises ``ValueError`` at construction: the reference dies at its first step on
+  ``update_mask(None, 0.7)`` (``None * float``).  An unknown ``sae_type`` raises ``ValueError`` as well (the reference goes
+  on without a model).
+* The chunk files are taken in sorted order; the reference takes them in ``os.listdir`` order, which the file system
+  decides.
+* ``wandb`` is imported only when it is installed and ``no_log`` is false.  Otherwise ``log_fn`` -- or, without one, the
+  reference's ``print`` lines (its ``no_log`` formats; the ``bl_sae`` line is ``Loss=`` alone, the reference's fallback line
+  names a sparsity loss that type does not have) -- receives the same metric dictionaries.  Metrics are computed on logging steps only
+  (``batch_idx % log_every == 0``); no other step reads anything back or builds a [B, H] tensor for them.
+* ``model=`` hands in the model instead of building the reference's.  The reference builds
+  ``BinarySAE(input_dim, hidden_dim, n_bits)``, where ``n_bits`` lands in ``gamma`` and the decoder keeps its default of 8
+  bits; that call is kept.
+"""
+from __future__ import annotations
+
+import importlib.util
+import math
+import os
+import time
+from typing import Callable, Optional
+
+import torch
+
+from .. import optim
+from .. import torch_ops as ops
+from ..sae import (BaselineSparseAutoencoder, BinarySAE, QuantizedMatryoshkaSAE, ResidualQuantizedSAE,
+                   TernarySparseAutoencoder)
+from ..sae.binary_latent import BinaryLatentSAE
+from .batches import ShuffledChunk
+from .loss import SAE_TYPES, trainer_loss
+
+__all__ = ["Trainer", "model_path_for"]
+
+CHUNK_PREFIX, CHUNK_SUFFIX = "the_pile_hidden_states_L3_", ".pt"
+_BITS_IN_NAME = ("b_sae", "q_sae", "rq_sae")
+
+
+def model_path_for(save_dir: str, sae_type: str, config: dict, rigL: bool) -> str:
+    """The reference's checkpoint name (training/trainer.py:58) under ``save_dir``."""
+    name = (sae_type + "_" + str(config["hidden_dim"]) + ("_rigL" if rigL else "")
+            + (str(config["n_bits"]) + "_bits" if sae_type in _BITS_IN_NAME else "") + ".pth")
+    return os.path.join(save_dir, name)
+
+
+def _build_model(sae_type: str, config: dict) -> torch.nn.Module:
+    D, H = config["input_dim"], config["hidden_dim"]
+    if sae_type == "t_sae":
+        return TernarySparseAutoencoder(D, H)
+    if sae_type == "bl_sae":
+        return BinaryLatentSAE(D, H)
+    if sae_type == "b_sae":
+        return BinarySAE(D, H, config["n_bits"])              # positional, as in the reference: n_bits lands in gamma
+    if sae_type == "q_sae":
+        return QuantizedMatryoshkaSAE(D, H, config["top_k"], config["gamma"], config["n_bits"])
+    if sae_type == "rq_sae":
+        return ResidualQuantizedSAE(D, H, config["top_k"], config["gamma"], config["n_bits"])
+    return BaselineSparseAutoencoder(D, H)
+
+
+class Trainer:
+    def __init__(self, config, sae_type, rigL=False, no_log=False, proj_name=None, *, model: Optional[torch.nn.Module] = None,
+                 dataset_dir: str = "dataset/", save_dir: str = "SAEs/", log_fn: Optional[Callable[[dict], None]] = None,
+                 log_every: int = 100):
+        if sae_type not in SAE_TYPES:
+            raise ValueError(f"unknown sae_type {sae_type!r}; expected one of {', '.join(SAE_TYPES)}")
+        if sae_type == "t_sae" and not rigL:
+            raise ValueError("t_sae trains with rigL=True only: its step calls decoder.update_mask(f_decay, 0.7), and f_decay "
+                             "is set by the rigL schedule (the reference fails on None * float at the first step)")
+        if int(log_every) < 1:
+            raise ValueError(f"log_every = {log_every}")
+        self.config = config
+        self.sae_type = sae_type
+        self.device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        self.model = (model if model is not None else _build_model(sae_type, config)).to(self.device)
+        if sae_type == "b_sae":
+            self.scale_factor = torch.pow(2, torch.arange(self.config["n_bits"])).to(self.device)
+            self.scale_factor = self.scale_factor / self.scale_factor.sum().float()
+        self.epoch = 0
+        self.trained_batches = []                             # per one_epoch call: the batch_idx of every batch trained on
+        self.dataset_dir, self.save_dir = dataset_dir, save_dir
+        self.chunk_files = sorted(f for f in os.listdir(dataset_dir) if f.startswith(CHUNK_PREFIX) and f.endswith(CHUNK_SUFFIX))
+
+        # rigL settings:
+        self.rigL = rigL
+        self.connection_fraction_to_update = 0.3
+        self.f_decay = None
+
+        self.model_path = model_path_for(save_dir, sae_type, config, rigL)
+
+        self.no_log = no_log
+        self.log_fn = log_fn
+        self.log_every = int(log_every)
+        self._wandb = None
+        if not self.no_log and log_fn is None and importlib.util.find_spec("wandb") is not None:
+            import wandb
+            self._wandb = wandb
+            wandb.init(project=proj_name, config=config)
+            wandb.watch(self.model, log="all", log_freq=256)
+
+    # ---- one step ------------------------------------------------------------------------------------------------
+    def _forward(self, batch, want_latent: bool):
+        if self.sae_type in ("b_sae", "baseline_sae"):
+            return self.model.forward_train(batch, dense_latent=want_latent)
+        return self.model.forward_train(batch)
+
+    def _step(self, optimizer, batch, log_step: bool):
+        """forward, loss, backward and the type's step sequence (training/trainer.py:88-173) -> (outputs, losses)"""
+        st, model = self.sae_type, self.model
+        outputs = self._forward(batch, log_step)
+        optimizer.zero_grad(set_to_none=True)
+        losses = trainer_loss(st, outputs, batch, self.config)
+        if st == "q_sae":
+            model.decoder.apply_secant_grad()
+        elif st == "rq_sae":
+            model.apply_secant_grad()
+        elif st == "t_sae":
+            model.decoder.mask_grad()
+        optimizer.step()
+        if st == "t_sae":
+            model.decoder.update_mask(self.f_decay, 0.7)
+        elif st == "baseline_sae":
+            model.normalize_decoder_weights()
+        return outputs, losses
+
+    # ---- metrics (logging steps only) --------------------------------------------------------------------------------------
+    def _plane_magnitudes(self):
+        """mag_MSB, mag_LSB: decoder.weight[:, n-1::n].abs().mean() and [:, 0::n] for n = config["n_bits"], from the
+        per-bit-plane sums of |logit| that ops.quantization_error yields."""
+        dec, n = self.model.decoder, int(self.config["n_bits"])
+        N = dec.n_bits
+        if N % n != 0:                                         # the stride does not follow the planes: slice as the reference does
+            w = dec.weight.detach()
+            return w[:, n - 1::n].abs().mean().item(), w[:, 0::n].abs().mean().item()
+        H = dec.weight.shape[0]
+        D = dec.weight.shape[1] // N
+        result, _ = ops.quantization_error(dec.weight.detach(), D, N, float(dec.quantization_step), 0.0)
+        planes = result[16:16 + N].tolist()
+        per = H * D * (N // n)
+        return sum(planes[n - 1::n]) / per, sum(planes[0::n]) / per
+
+    def _metrics(self, outputs, losses) -> dict:
+        st, cfg = self.sae_type, self.config
+        lv = losses.tolist()
+        if st == "b_sae":
+            latent, _, pol = outputs
+            pol = pol.item()
+            msb, lsb = self._plane_magnitudes()
+            return {"loss": lv[0] + cfg["polarize_lambda"] * pol, "recon_loss": lv[0], "polarize_loss": pol,
+                    "activated_neurons": torch.mean(latent.sum(dim=-1)).item(), "mag_MSB": msb, "mag_LSB": lsb}
+        if st in ("q_sae", "rq_sae"):
+            n = cfg["n_bits"]
+            l0 = [g.item() for g in outputs[0]]
+            lam = cfg["sparsity_lambda"]
+            if st == "q_sae":
+                d = {f"recon_loss_group_{i}": lv[i] for i in range(n)}
+                d["recon_loss_total"] = sum(lv)
+                sparsity = sum(l0) * lam
+            else:
+                d = {f"recon_loss_group_{i}": lv[i] / 4 ** i for i in range(n)}
+                sparsity = sum(l0[i] * lam * w for i, w in enumerate((1.0, 2.5, 4.0, 8.0)[:len(l0)]))
+            d.update({f"L0 of latent_group_{i}": l0[i] for i in range(n)})
+            d["sparsity loss"] = sparsity
+            return d
+        return {"loss": lv[0]}
+
+    def _print_line(self, batch_idx: int, m: dict) -> str:
+        """The reference's print line of a logging step under no_log (training/trainer.py:213-230), from the metrics"""
+        st, n = self.sae_type, self.config["n_bits"]
+        if st == "b_sae":
+            return (f"Batch {batch_idx}: Loss={m['loss']:.4f}, recon_loss={m['recon_loss']:.4f}, "
+                    f"polarize_loss={m['polarize_loss']:.4f}, activated_neurons={m['activated_neurons']:.4f}, "
+                    f"mag_MSB={m['mag_MSB']:.4f}, mag_LSB={m['mag_LSB']:.4f}")
+        if st in ("q_sae", "rq_sae"):
+            scale = 4 if st == "rq_sae" else 1                 # the rq_sae line shows group i divided by 4^i, loss_total does not
+            loss_total = sum(m[f"recon_loss_group_{i}"] * scale ** i for i in range(n)) + m["sparsity loss"]
+            recon = ", ".join(f"recon_loss_group_{i}={m[f'recon_loss_group_{i}']:.4f}" for i in range(n))
+            l0 = ", ".join(f"L0_of_latent_group_{i}={m[f'L0 of latent_group_{i}']:.4f}" for i in range(n))
+            return f"Batch {batch_idx}: {recon}, recon_loss_total={loss_total:.4f}, {l0}"
+        return f"Batch {batch_idx}: Loss={m['loss']:.4f}"
+
+    def _log(self, batch_idx: int, metrics: dict) -> None:
+        if self.log_fn is not None:
+            self.log_fn(metrics)
+        elif self._wandb is not None:
+            self._wandb.log(metrics)
+        else:
+            print(self._print_line(batch_idx, metrics))
+
+    # ---- the reference's interface -----------------------------------------------------------------------------------------
+    def one_epoch(self, dataset, dead_neuron_threshold=0.2, no_log=False, rigL=False, f_decay=None):
+        """One pass over a chunk: ``dataset`` is a ``ShuffledChunk``, a ``HiddenStatesTorchDataset``, a chunk file or the
+        chunk tensor.  A fresh Adam per call, as in the reference.  The remaining arguments are the reference's and, as
+        there, not read."""
+        if self.device.type != "cuda":
+            raise RuntimeError("Trainer.one_epoch: quantizedsae_amd runs on MI355X only (no CPU fallback exists)")
+        chunk = dataset if isinstance(dataset, ShuffledChunk) else ShuffledChunk(dataset, self.config["batch_size"], self.device)
+        optimizer = optim.Adam(self.model.parameters(), lr=self.config["lr"], model=self.model)
+        self.trained_batches.append([])
+        told = 0                                               # skipped batches announced so far, in batch order
+
+        def announce(up_to):
+            nonlocal told
+            skipped = chunk.last_plan.skipped
+            while told < len(skipped) and (up_to is None or skipped[told] < up_to):
+                print(f"Batch {skipped[told]} contains NaN values before forward pass!")
+                told += 1
+        for batch_idx, batch in chunk.epoch():
+            announce(batch_idx)
+            self.trained_batches[-1].append(batch_idx)
+            log_step = batch_idx % self.log_every == 0
+            outputs, losses = self._step(optimizer, batch, log_step)
+            if log_step:
+                self._log(batch_idx, self._metrics(outputs, losses))
+        announce(None)
+        chunk.check()
+        return self.model
+
+    def train(self):
+        total_start = time.perf_counter()
+        for epoch, f in enumerate(self.chunk_files):
+            if epoch > 100:
+                break
+            print(f"Training on {f}:")
+            self.epoch = epoch
+            if self.rigL:
+                self.f_decay = self.connection_fraction_to_update / 2 * (1 + math.cos(epoch * math.pi / len(self.chunk_files)))
+                self.model.decoder.update_mask(self.f_decay, 0.7)
+            self.one_epoch(os.path.join(self.dataset_dir, f), dead_neuron_threshold=0.2, no_log=self.no_log, rigL=self.rigL,
+                           f_decay=self.f_decay)
+        if self._wandb is not None:
+            self._wandb.finish()
+        os.makedirs(os.path.dirname(self.model_path) or ".", exist_ok=True)
+        torch.save(self.model.state_dict(), self.model_path)
+        print(f"Training completed. Model been saved to {self.model_path}.")
+        total_time = time.perf_counter() - total_start
+        print(f"Total training time: {total_time:.2f} seconds")
