@@ -943,6 +943,32 @@ size_t qsae_trainer_loss_workspace_bytes(int n, int B, int D);
 int qsae_trainer_loss(const float* x, const float* const* recon_ptrs, int n, int B, int D, int mode, double coef,
                       float* const* grads_ptrs, float* losses, void* workspace, size_t workspace_bytes, qsae_stream_t stream);
 
+/* -- Watch: the distributions of T tensors in one call (what `wandb.watch(model, log="all")` logs of every parameter and
+ *    gradient).  ptrs and counts are HOST arrays of T device pointers and element counts (fp32,
+ *    contiguous, any sizes, 4-byte aligned; a tensor off its 16-byte boundary is read with scalar loads and gives the same
+ *    bits).  result (device, 8-byte aligned) holds T blocks of QSAE_TENSOR_STATS_HEAD + bins 8-byte words:
+ *      0 lo, 1 hi   the minimum and maximum of the finite elements as fp64 (exact images of the fp32 values; a zero is +0.0)
+ *      2 mean, 3 m2 fp64 over the finite elements: S / n_finite and the sum of (x - mean)^2 (std = sqrt(m2 / (n_finite - 1)))
+ *      4 n_finite, 5 n_nonfinite, 6 n_zero (+-0.0), 7 zero   int64
+ *      8 ..         counts int64 [bins]: torch.histc(finite elements, bins, lo, hi) as the CPU computes it in fp32,
+ *                   q = ((x - lo) * float(bins)) / (hi - lo), bin = int(q) with bin == bins folded into bins - 1.  lo == hi:
+ *                   the range is widened as torch does (lo - 1 and hi + 1, or the neighbouring floats where those round
+ *                   back), so everything lands in bin bins / 2 for |lo| < 2^24.  hi - lo overflows: all counts 0, as in torch.
+ *    A tensor with no element or no finite element has n_finite = 0, zero counts and zeros in words 0 .. 3.
+ *    Two streaming passes and two joins; fp64 sums in a fixed order (per-thread chains in ascending index over chunks of
+ *    8192 elements, a butterfly, chunk partials in ascending order), counts through integer atomics, no float atomics: the
+ *    same bits on every run.  Nothing is read back.
+ *    T == 0 or every count 0: QSAE_OK with nothing launched and nothing written.
+ *    Errors, all before any launch: QSAE_ERR_INVALID_ARG (T < 0, a negative count, a null or misaligned tensor pointer with
+ *    a non-zero count, bins outside 1 .. 256, null or misaligned result), QSAE_ERR_UNSUPPORTED (dtype other than 0 = fp32,
+ *    T > 65536, a tensor above 2^40 elements, more than 2^30 chunks in all), QSAE_ERR_WORKSPACE.  workspace: 8-byte aligned,
+ *    qsae_tensor_stats_workspace_bytes(counts, T) = 32 bytes per chunk and 24 per tensor, in seven arrays of 256-byte
+ *    pieces (0 where there is nothing to do or the counts are not taken). ------------------------------------------------------------------------ */
+#define QSAE_TENSOR_STATS_HEAD 8
+size_t qsae_tensor_stats_workspace_bytes(const int64_t* counts, int T);
+int qsae_tensor_stats(const void* const* ptrs, const int64_t* counts, int T, int dtype, int bins, void* result,
+                      void* workspace, size_t workspace_bytes, qsae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -176,6 +176,8 @@ SIGNATURES = {
     "qsae_gather_rows": (_i, [_vp, _i, _i64, _i, _vp, _i, _vp, _vp, _vp]),
     "qsae_trainer_loss_workspace_bytes": (_sz, [_i, _i, _i]),
     "qsae_trainer_loss": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_double, _vp, _vp, _vp, _sz, _vp]),
+    "qsae_tensor_stats_workspace_bytes": (_sz, [_vp, _i]),
+    "qsae_tensor_stats": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -2278,3 +2278,40 @@ def trainer_loss(x: torch.Tensor, recons, mode: int, coef: float, grads: Optiona
     gp = (C.c_void_p * n)(*[grads.data_ptr() + i * B * D * 4 for i in range(n)])
     check(lib.qsae_trainer_loss(_p(x), rp, n, B, D, int(mode), float(coef), gp, _p(losses), _p(ws), ws.numel(), _stream()))
     return losses, grads
+
+
+# ---- watch: the distributions of a list of tensors (csrc/watch.hip; quantizedsae_amd.training.watch is the user) ---------------
+TENSOR_STATS_HEAD = 8
+TENSOR_STATS_MAX_BINS = 256
+
+
+def tensor_stats(tensors, bins: int = 64) -> torch.Tensor:
+    """-> int64 [T, 8 + bins] on the device, one row per tensor of ``tensors`` (fp32, contiguous, any shapes and sizes, views
+    that start off a 16-byte boundary included): words 0 .. 3 are the fp64 bits of lo, hi, mean and the sum of squared
+    deviations over the finite elements, words 4 .. 6 n_finite, n_nonfinite and n_zero, words 8 .. the counts of
+    ``torch.histc(finite elements, bins, lo, hi)`` as the CPU computes them.  One call for the whole list, nothing read back.
+    See qsae_tensor_stats; ``quantizedsae_amd.training.tensor_stats`` gives the parsed form."""
+    who = "tensor_stats"
+    tensors = list(tensors)
+    bins = int(bins)
+    if not 1 <= bins <= TENSOR_STATS_MAX_BINS:
+        raise ValueError(f"{who}: bins must be in 1 .. {TENSOR_STATS_MAX_BINS}, got {bins}")
+    for i, t in enumerate(tensors):
+        _dev(t, f"{who}: tensors[{i}]")
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{who}: tensors[{i}] must be a contiguous fp32 tensor, got {t.dtype} {tuple(t.shape)} with strides "
+                             f"{t.stride()} (no silent copy is made)")
+        if t.device != tensors[0].device:
+            raise ValueError(f"{who}: tensors[{i}] is on {t.device}, tensors[0] on {tensors[0].device}")
+    T = len(tensors)
+    device = tensors[0].device if T else torch.device("cuda", torch.cuda.current_device())
+    with torch.cuda.device(device):
+        result = torch.zeros((T, TENSOR_STATS_HEAD + bins), dtype=torch.int64, device=device)
+        if sum(t.numel() for t in tensors) == 0:
+            return result
+        lib = _lib.load()
+        counts = (C.c_int64 * T)(*[t.numel() for t in tensors])
+        ptrs = (C.c_void_p * T)(*[t.data_ptr() if t.numel() else 0 for t in tensors])
+        ws = _workspace(device, max(int(lib.qsae_tensor_stats_workspace_bytes(counts, T)), 16))
+        check(lib.qsae_tensor_stats(ptrs, counts, T, 0, bins, _p(result), _p(ws), ws.numel(), _stream()))
+    return result

@@ -822,6 +822,19 @@ def _(x, recons, mode, coef, grads):
     return _f32((len(recons),), x)
 
 
+# ---- watch: the distributions of a list of tensors (csrc/watch.hip) ------------------------------------------------------
+@_op("tensor_stats")
+def _tensor_stats(tensors: List[Tensor], bins: int) -> Tensor:
+    """-> int64 [T, 8 + bins]: lo, hi, mean, m2, the counts and the histogram of every tensor of the list"""
+    return _ops.tensor_stats(tensors, bins)
+
+
+@_tensor_stats.register_fake
+def _(tensors, bins):
+    device = tensors[0].device if len(tensors) else torch.device("cuda")
+    return torch.empty((len(tensors), 8 + bins), dtype=torch.int64, device=device)
+
+
 Q = torch.ops.qsae
 
 
@@ -1346,3 +1359,11 @@ def trainer_loss(x, recons, mode, coef, grads=None):
     if grads is None:
         grads = torch.empty((len(recons),) + tuple(x.shape), dtype=torch.float32, device=x.device)
     return Q.trainer_loss(x, recons, int(mode), float(coef), grads), grads
+
+
+def tensor_stats(tensors, bins=64):
+    """-> int64 [T, 8 + bins] on the device"""
+    tensors = list(tensors)
+    if not tensors:                                           # no tensor to dispatch on
+        return _ops.tensor_stats(tensors, int(bins))
+    return Q.tensor_stats(tensors, int(bins))

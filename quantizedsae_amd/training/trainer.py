@@ -15,6 +15,11 @@ backward, ``trainer_loss`` the per-type loss, ``optim.Adam`` the step.  What dif
   reference's ``print`` lines (its ``no_log`` formats; the ``bl_sae`` line is ``Loss=`` alone, the reference's fallback line
   names a sparsity loss that type does not have) -- receives the same metric dictionaries.  Metrics are computed on logging steps only
   (``batch_idx % log_every == 0``); no other step reads anything back or builds a [B, H] tensor for them.
+* ``watch="all" | "parameters" | "gradients"`` with ``watch_freq`` (default 256, wandb's ``log_freq`` in the reference) gives
+  the other half of what the reference logs: the histograms of ``wandb.watch`` for every parameter and gradient, from one
+  kernel call (``ModelWatch``, csrc/watch.hip) on the steps with ``batch_idx % watch_freq == 0``.  They go to ``log_fn`` as
+  ``TensorStats`` under wandb's keys (merged into the metrics of a step that is also a logging step), to wandb as
+  ``wandb.Histogram``, and under ``no_log`` to one printed line per tensor.  The default ``None`` changes nothing.
 * ``model=`` hands in the model instead of building the reference's.  The reference builds
   ``BinarySAE(input_dim, hidden_dim, n_bits)``, where ``n_bits`` lands in ``gamma`` and the decoder keeps its default of 8
   bits; that call is kept.
@@ -36,6 +41,7 @@ from ..sae import (BaselineSparseAutoencoder, BinarySAE, QuantizedMatryoshkaSAE,
 from ..sae.binary_latent import BinaryLatentSAE
 from .batches import ShuffledChunk
 from .loss import SAE_TYPES, trainer_loss
+from .watch import WATCH_MODES, ModelWatch, watch_line
 
 __all__ = ["Trainer", "model_path_for"]
 
@@ -68,7 +74,7 @@ def _build_model(sae_type: str, config: dict) -> torch.nn.Module:
 class Trainer:
     def __init__(self, config, sae_type, rigL=False, no_log=False, proj_name=None, *, model: Optional[torch.nn.Module] = None,
                  dataset_dir: str = "dataset/", save_dir: str = "SAEs/", log_fn: Optional[Callable[[dict], None]] = None,
-                 log_every: int = 100):
+                 log_every: int = 100, watch: Optional[str] = None, watch_freq: int = 256):
         if sae_type not in SAE_TYPES:
             raise ValueError(f"unknown sae_type {sae_type!r}; expected one of {', '.join(SAE_TYPES)}")
         if sae_type == "t_sae" and not rigL:
@@ -76,6 +82,10 @@ class Trainer:
                              "is set by the rigL schedule (the reference fails on None * float at the first step)")
         if int(log_every) < 1:
             raise ValueError(f"log_every = {log_every}")
+        if watch is not None and watch not in WATCH_MODES:
+            raise ValueError(f"watch = {watch!r}; expected None or one of {', '.join(WATCH_MODES)}")
+        if int(watch_freq) < 1:
+            raise ValueError(f"watch_freq = {watch_freq}")
         self.config = config
         self.sae_type = sae_type
         self.device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
@@ -104,6 +114,9 @@ class Trainer:
             self._wandb = wandb
             wandb.init(project=proj_name, config=config)
             wandb.watch(self.model, log="all", log_freq=256)
+        self.watch_freq = int(watch_freq)
+        self._watch = ModelWatch(self.model, log=watch) if watch is not None else None
+        self._watch_due, self._watched = False, None          # this step collects / what it collected
 
     # ---- one step ------------------------------------------------------------------------------------------------
     def _forward(self, batch, want_latent: bool):
@@ -112,11 +125,15 @@ class Trainer:
         return self.model.forward_train(batch)
 
     def _step(self, optimizer, batch, log_step: bool):
-        """forward, loss, backward and the type's step sequence (training/trainer.py:88-173) -> (outputs, losses)"""
+        """forward, loss, backward and the type's step sequence (training/trainer.py:88-173) -> (outputs, losses).
+        On a watch step (``self._watch_due``, set by one_epoch) the distributions are collected into ``self._watched`` right
+        after the backward, where wandb's hooks see the tensors: the parameters as the forward used them, the gradients as
+        autograd left them (before apply_secant_grad / mask_grad and the optimizer step)."""
         st, model = self.sae_type, self.model
         outputs = self._forward(batch, log_step)
         optimizer.zero_grad(set_to_none=True)
         losses = trainer_loss(st, outputs, batch, self.config)
+        self._watched = self._watch.collect() if self._watch_due else None
         if st == "q_sae":
             model.decoder.apply_secant_grad()
         elif st == "rq_sae":
@@ -186,13 +203,21 @@ class Trainer:
             return f"Batch {batch_idx}: {recon}, recon_loss_total={loss_total:.4f}, {l0}"
         return f"Batch {batch_idx}: Loss={m['loss']:.4f}"
 
-    def _log(self, batch_idx: int, metrics: dict) -> None:
+    def _log(self, batch_idx: int, metrics: Optional[dict], watched: Optional[dict] = None) -> None:
+        """metrics: the scalars of a logging step or None; watched: the distributions of a watch step or None.  A step that
+        is both hands log_fn (or wandb) one dictionary."""
         if self.log_fn is not None:
-            self.log_fn(metrics)
+            self.log_fn({**(metrics or {}), **(watched or {})})
         elif self._wandb is not None:
-            self._wandb.log(metrics)
+            hists = {k: self._wandb.Histogram(np_histogram=s.np_histogram()) for k, s in (watched or {}).items()}
+            self._wandb.log({**(metrics or {}), **hists})
         else:
-            print(self._print_line(batch_idx, metrics))
+            if metrics is not None:
+                print(self._print_line(batch_idx, metrics))
+            if watched is not None:
+                print(f"Batch {batch_idx}: watch")
+                for key, s in watched.items():
+                    print(watch_line(key, s))
 
     # ---- the reference's interface -----------------------------------------------------------------------------------------
     def one_epoch(self, dataset, dead_neuron_threshold=0.2, no_log=False, rigL=False, f_decay=None):
@@ -216,9 +241,11 @@ class Trainer:
             announce(batch_idx)
             self.trained_batches[-1].append(batch_idx)
             log_step = batch_idx % self.log_every == 0
+            watch_step = self._watch is not None and batch_idx % self.watch_freq == 0
+            self._watch_due = watch_step
             outputs, losses = self._step(optimizer, batch, log_step)
-            if log_step:
-                self._log(batch_idx, self._metrics(outputs, losses))
+            if log_step or watch_step:
+                self._log(batch_idx, self._metrics(outputs, losses) if log_step else None, self._watched)
         announce(None)
         chunk.check()
         return self.model
