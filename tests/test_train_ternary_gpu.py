@@ -1,6 +1,7 @@
 """TernarySparseAutoencoder.forward_train, its HIP backward (csrc/train_gemm.hip, csrc/train.hip) and the RigL mask kernels
-(csrc/train_mask.hip) on the MI355X: the reference's own gradients and masks, forward parity with forward(), the full size
-against the fp64 table and against the exact mask restatement, determinism, missing incoming gradients, refusals, cache
+(csrc/train_mask.hip) on the MI355X: the reference's own gradients and masks, forward parity with forward(), the three
+backward kernels on their own at the tile edges against fp64, the full size against the fp64 table and against the exact mask
+restatement, determinism, missing incoming gradients, refusals, cache
 invalidation and the reference trainer's t_sae loop."""
 import sys
 from pathlib import Path
@@ -10,7 +11,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from quantizedsae_amd import TernarySparseAutoencoder, synthetic as S
+from quantizedsae_amd import TernarySparseAutoencoder, ops, synthetic as S
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 import train_ternary_util as U  # noqa: E402
@@ -122,6 +123,74 @@ def test_missing_incoming_gradients():
     F.mse_loss(recon, x).backward()
     assert lin.weight.grad is None and lin.bias.grad is None
     assert U.max_rel_err(dec.weight.grad, want["decoder.weight"]) <= TOL
+
+
+# ---- tile edges of each backward kernel on its own ---------------------------------------------------------------------------
+def edge_seed(B, D, H):
+    return 781 + B + D + H
+
+
+@pytest.mark.parametrize("H", [4, 132, 1060])
+@pytest.mark.parametrize("D", [4, 36, 132])
+@pytest.mark.parametrize("B", [1, 24, 257])
+def test_kernels_at_tile_edges_against_fp64(B, D, H):
+    """train_ternary_rows, train_ternary_dweight and train_ternary_dpre as plain ops calls: B = 1, a partial second tile in every
+    dimension (257 = 2 x 128 + 1 rows, D = 132, H = 1060), a K tail in both contractions (D = 36 and 132 against the 32-wide
+    slice of dpre, B = 24 and 257 against that of dweight), D = 4 and H = 4.  Measured on an MI355X (max |err| / max |g| over
+    the 27 shapes): see DESIGN.md section 4.13."""
+    seed = edge_seed(B, D, H)
+    sd = S.ternary_sae_params(seed, D, H)
+    x = torch.from_numpy(S.activations(seed, B, D)).to(DEV)
+    G = torch.from_numpy(S.normal(seed, (B, D), stream=11)).to(DEV)
+    gh = torch.from_numpy(S.normal(seed, (B, H), stream=12)).to(DEV)
+    # the ternary image, exactly, with the cutoff row of test_kernels_gpu.py::test_ternary_pack_and_decode
+    w_np = sd["decoder.weight"].copy()
+    row = np.array([0.5, -0.5, 0.49999997, -0.49999997, 0.0, -0.0, np.nan], dtype=np.float32)
+    w_np.reshape(-1)[:row.size] = row
+    w = torch.from_numpy(w_np).to(DEV)
+    t_rows = ops.train_ternary_rows(w)
+    w_cpu = torch.from_numpy(w_np)
+    want_rows = (torch.sign(w_cpu) * (w_cpu.abs() >= U.THRESHOLD).float()).t()            # sae/ternary.py:47-49; torch.sign(nan) = 0
+    assert tuple(t_rows.shape) == (H, D) and torch.equal(t_rows.cpu(), want_rows)          # by value: -1 * 0 = -0.0 equals 0.0
+    assert want_rows.t().reshape(-1)[:row.size].tolist() == [1.0, -1.0, 0.0, 0.0, 0.0, 0.0, 0.0]
+    assert bool(((t_rows == 0) | (t_rows.abs() == 1)).all())
+    # the rest runs on the model's own dictionary (no nan in a contraction operand)
+    t_rows = ops.train_ternary_rows(torch.from_numpy(sd["decoder.weight"]).to(DEV))
+    T64 = t_rows.double()                                                                 # [H, D], exact
+    h = ops.encode_dense(x, torch.from_numpy(sd["encoder.0.weight"]).to(DEV), torch.from_numpy(sd["encoder.0.bias"]).to(DEV),
+                         ops.ACT_RELU)
+    pos = h > 0
+    frac = float(pos.float().mean())
+    if B * H >= 96:
+        assert 0.2 <= frac <= 0.8, frac                       # a condition on the inputs: the gate is exercised both ways
+    # dweight: the loaders and chain of train_gemm_tn, the mask on the store
+    plain = ops.train_gemm_tn(G, h)
+    assert tuple(plain.shape) == (D, H)
+    ones = torch.ones((D, H), device=DEV)
+    assert torch.equal(bits(ops.train_ternary_dweight(G, h, ones)), bits(plain))
+    mask = torch.from_numpy((S.uniform01(seed, D * H, stream=13) < 0.3).astype(np.float32).reshape(D, H)).to(DEV)
+    dw = ops.train_ternary_dweight(G, h, mask)
+    assert torch.equal(bits(dw), bits(plain * mask))
+    assert bool((bits(dw)[mask == 0] & 0x7FFFFFFF == 0).all())
+    full64 = G.double().t() @ h.double()
+    errs = {"dweight": U.max_rel_err(plain, full64), "dweight masked": U.max_rel_err(dw, full64 * mask.double())}
+    # dpre: the four null combinations, on the h the kernel reads
+    for with_G in (True, False):
+        for with_gh in (True, False):
+            dpre = ops.train_ternary_dpre(h, G if with_G else None, gh if with_gh else None, t_rows)
+            want = torch.zeros((B, H), dtype=torch.float64, device=DEV)
+            if with_G:
+                want = want + G.double() @ T64.t()
+            if with_gh:
+                want = want + gh.double()
+            want = want * pos
+            assert tuple(dpre.shape) == (B, H) and bool((dpre[~pos] == 0).all())
+            if not with_G and not with_gh:
+                assert not bool(dpre.any())
+            errs[f"dpre G {int(with_G)} gh {int(with_gh)}"] = U.max_rel_err(dpre, want)
+    print(f"B {B} D {D} H {H} active {frac:.3f}:", " ".join(f"{k}: {e:.3g}" for k, e in errs.items()))
+    for k, e in errs.items():
+        assert e <= TOL, f"B {B} D {D} H {H} {k}: max |err| / max |g| = {e:.3g}"
 
 
 # ---- full size ---------------------------------------------------------------------------------------------------------------
