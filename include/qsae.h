@@ -969,6 +969,61 @@ size_t qsae_tensor_stats_workspace_bytes(const int64_t* counts, int T);
 int qsae_tensor_stats(const void* const* ptrs, const int64_t* counts, int T, int dtype, int bins, void* result,
                       void* workspace, size_t workspace_bytes, qsae_stream_t stream);
 
+/* -- Activity: which units of the dictionary are alive while a model trains.  The reference's
+ *    one_epoch takes a dead_neuron_threshold that nothing reads and a `latents` list it never fills (training/trainer.py:66-78).
+ *    State per tracker, on the device, 8-byte aligned, zeroed by the caller before the first call:
+ *      fired int64 [H]  rows in which the unit was active, over the run
+ *      last  int64 [H]  the stamp of the last batch in which it was active, 0 = never
+ *      base  int64 [H]  fired as of the previous summary
+ *    "Active" is the reference's activation mask (scripts/analysis/dynamic_analysis.py:30-73), as in qsae_activation_counts*.
+ *    A batch carries a stamp >= 1 (the caller's clock after the batch: rows seen so far); every unit active in at least one
+ *    of its rows gets last[u] = max(last[u], stamp), so a stamp out of order never lowers it, and fired[u] += its active rows.
+ *    Both go through 64-bit integer atomics (atomicAdd / atomicMax), which do not depend on order: the same bits on every
+ *    run.  fired[u] and last[u] of a unit that is active in no row of the batch are not written.  No float atomics.
+ *    B == 0: QSAE_OK with nothing launched and no device needed.  Errors, all before any launch: QSAE_ERR_INVALID_ARG (null or
+ *    misaligned pointers, B < 0, k < 1, nbits < 1, H <= 0, stamp < 1, ld < H, words_ld < nbits / 32, index == NULL with
+ *    nbits > H), QSAE_ERR_UNSUPPORTED (nbits % 32 != 0, B * k >= 2^31). ----------------------------------------------------- */
+/* Compact form of the top-k models: entry (b, idx[b][j]) is active iff val[b][j] > 0 (NaN, 0.0 and -0.0 are not; val == NULL:
+ * every entry).  Indices outside [0, H) are dropped; a unit listed twice in one row counts twice in fired, as in
+ * qsae_activation_counts.  One pass over the B k entries counts and stamps. */
+int qsae_activity_add_compact(const int32_t* idx, const float* val, int B, int k, int H, int64_t stamp, int64_t* fired,
+                              int64_t* last, qsae_stream_t stream);
+/* Packed bits of the threshold models: zbits uint32 [B][words_ld], bit j of word w = packed position 32 w + j (the layout of
+ * qsae_activation_counts_bits, whose column popcounts this repeats).  index int32 [nbits] (device) maps a packed position to
+ * its unit, -1 = pad slot: ignored, its bits need not be zero; values >= H are dropped; index == NULL: identity, requires
+ * nbits <= H.  Two positions that map to one unit are the caller's duty, as in qsae_coactivation_bits. */
+int qsae_activity_add_bits(const uint32_t* zbits, int64_t words_ld, int B, int nbits, const int32_t* index, int H, int64_t stamp,
+                           int64_t* fired, int64_t* last, qsae_stream_t stream);
+/* Dense latent fp32 [B][ld] (the ternary model's h): active iff latent > 0 (NaN no, +inf yes, positive denormals yes).
+ * Rows are read coalesced (16 bytes per lane when latent is 16-byte aligned and ld % 4 == 0, scalar loads otherwise: the
+ * same counts); a thread counts its columns over the rows of its workgroup and only non-zero counts reach memory. */
+int qsae_activity_add_dense(const float* latent, int64_t ld, int B, int H, int64_t stamp, int64_t* fired, int64_t* last,
+                            qsae_stream_t stream);
+/* The summary of a tracker at `clock` (>= 0: the rows added so far) with a window of `window` >= 1 rows:
+ *   dead    clock - last[u] >= window (a unit that never fired becomes dead once clock >= window; before that nothing is)
+ *   never   last[u] == 0
+ *   silent  fired[u] == base[u]: nothing since the previous summary;  interval count c = fired[u] - base[u] (base <= fired is
+ *           the caller's duty; base == NULL reads as zeros)
+ *   octave  bit length of c: bin 0 holds c == 0, bin b holds 2^(b-1) <= c < 2^b, bins above 33 are folded into 33
+ * result (device, 8-byte aligned) receives (1 + n_seg) blocks of QSAE_ACTIVITY_HEAD + QSAE_ACTIVITY_BINS int64: block 0 over
+ * all units, block s over segment s - 1 of seg_sizes (HOST array of n_seg <= QSAE_ACTIVITY_MAX_SEGMENTS sizes >= 0 that add
+ * up to H: consecutive slices of the units; NULL or n_seg == 0: block 0 alone).  Head words: 0 units, 1 never, 2 dead,
+ * 3 silent, 4 the sum of the interval counts, 5 the sum of fired, 6 the largest interval count, 7 zero; then the octave bins.
+ * advance != 0 writes base[u] = fired[u], in the thread that read both.  dead_out int32 [H] (NULL: no list) receives the dead
+ * units in ascending order in [0, result[2]); the rest is left untouched.  The list is placed by prefix counts, never by an
+ * atomic cursor: the same bits on every run (the rule of qsae_token_lists_*).  Nothing is read back.
+ * Errors, all before any launch: QSAE_ERR_INVALID_ARG (H <= 0, clock < 0, window < 1, null or misaligned fired / last /
+ * result, misaligned base / dead_out, n_seg outside 0 .. 16, n_seg > 0 without seg_sizes, a negative size, sizes that do not
+ * add up to H), QSAE_ERR_WORKSPACE.  workspace: 8-byte aligned, qsae_activity_summary_workspace_bytes(H) = 4 bytes per chunk
+ * of 1024 units rounded up to 256 (0 for H <= 0); it need not be zeroed. */
+#define QSAE_ACTIVITY_HEAD 8
+#define QSAE_ACTIVITY_BINS 34
+#define QSAE_ACTIVITY_MAX_SEGMENTS 16
+size_t qsae_activity_summary_workspace_bytes(int H);
+int qsae_activity_summary(const int64_t* fired, int64_t* base, const int64_t* last, int H, int64_t clock, int64_t window,
+                          const int32_t* seg_sizes, int n_seg, int advance, int64_t* result, int32_t* dead_out, void* workspace,
+                          size_t workspace_bytes, qsae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

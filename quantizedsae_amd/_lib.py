@@ -178,6 +178,11 @@ SIGNATURES = {
     "qsae_trainer_loss": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_double, _vp, _vp, _vp, _sz, _vp]),
     "qsae_tensor_stats_workspace_bytes": (_sz, [_vp, _i]),
     "qsae_tensor_stats": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "qsae_activity_add_compact": (_i, [_vp, _vp, _i, _i, _i, _i64, _vp, _vp, _vp]),
+    "qsae_activity_add_bits": (_i, [_vp, _i64, _i, _i, _vp, _i, _i64, _vp, _vp, _vp]),
+    "qsae_activity_add_dense": (_i, [_vp, _i64, _i, _i, _i64, _vp, _vp, _vp]),
+    "qsae_activity_summary_workspace_bytes": (_sz, [_i]),
+    "qsae_activity_summary": (_i, [_vp, _vp, _vp, _i, _i64, _i64, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
 }
 
 

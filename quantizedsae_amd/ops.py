@@ -2315,3 +2315,118 @@ def tensor_stats(tensors, bins: int = 64) -> torch.Tensor:
         ws = _workspace(device, max(int(lib.qsae_tensor_stats_workspace_bytes(counts, T)), 16))
         check(lib.qsae_tensor_stats(ptrs, counts, T, 0, bins, _p(result), _p(ws), ws.numel(), _stream()))
     return result
+
+
+# ---- activity: per-unit firing counts of a model in training (csrc/activity.hip; quantizedsae_amd.training.activity is the user) ----
+ACTIVITY_HEAD = 8
+ACTIVITY_BINS = 34
+ACTIVITY_MAX_SEGMENTS = 16
+
+
+def _activity_state(who: str, **state) -> int:
+    """fired / last / base: contiguous int64 [H] on one device -> H"""
+    H = dev = None
+    for name, t in state.items():
+        if t is None:
+            continue
+        _dev(t, f"{who}: {name}", torch.int64)
+        if t.dim() != 1 or not t.is_contiguous() or t.numel() < 1:
+            raise ValueError(f"{who}: {name} must be a contiguous int64 [H >= 1], got {tuple(t.shape)} with strides {t.stride()}")
+        if H is None:
+            H, dev = t.numel(), t.device
+        elif t.numel() != H or t.device != dev:
+            raise ValueError(f"{who}: {name} is [{t.numel()}] on {t.device}, expected [{H}] on {dev}")
+    return H
+
+
+def _activity_stamp(who: str, stamp) -> int:
+    stamp = int(stamp)
+    if stamp < 1:
+        raise ValueError(f"{who}: stamp must be >= 1, got {stamp}")
+    return stamp
+
+
+@_on_tensor_device
+def activity_add_compact(idx: torch.Tensor, val: Optional[torch.Tensor], stamp: int, fired: torch.Tensor,
+                         last: torch.Tensor) -> None:
+    """fired[h] += the rows whose entry h is active (val > 0; every listed entry when val is None) and
+    last[h] = max(last[h], stamp) for those units, in one pass over idx int32 [B, k].  fired / last int64 [H].  See
+    qsae_activity_add_compact."""
+    who = "activity_add_compact"
+    _dev(idx, f"{who}: idx", torch.int32)
+    if idx.dim() != 2:
+        raise ValueError(f"{who}: idx must be [B, k], got {tuple(idx.shape)}")
+    B, k = idx.shape
+    if val is not None:
+        _dev(val, f"{who}: val", torch.float32)
+        if val.shape != idx.shape:
+            raise ValueError(f"{who}: val is {tuple(val.shape)}, idx {tuple(idx.shape)}")
+        val = val.contiguous()
+    H = _activity_state(who, fired=fired, last=last)
+    check(_lib.load().qsae_activity_add_compact(_p(idx.contiguous()), _p(val), B, k, H, _activity_stamp(who, stamp), _p(fired),
+                                                _p(last), _stream()))
+
+
+@_on_tensor_device
+def activity_add_bits(zbits: torch.Tensor, index: Optional[torch.Tensor], stamp: int, fired: torch.Tensor,
+                      last: torch.Tensor) -> None:
+    """The same from packed bits: zbits int32 [B, words] (a column slice of a wider tensor is fine), ``index`` (int32 / int64
+    [32 * words]) maps a packed position to its unit, -1 = pad slot; None = identity (32 * words <= H).  An int32 contiguous
+    ``index`` is passed through as it is.  See qsae_activity_add_bits."""
+    who = "activity_add_bits"
+    _dev(zbits, f"{who}: zbits", torch.int32)
+    if zbits.dim() != 2:
+        raise ValueError(f"{who}: zbits must be [B, words], got {tuple(zbits.shape)}")
+    B, words = zbits.shape
+    if zbits.stride(1) != 1:
+        zbits = zbits.contiguous()
+    index = _packed_index_arg(index, 32 * words)
+    H = _activity_state(who, fired=fired, last=last)
+    check(_lib.load().qsae_activity_add_bits(_p(zbits), zbits.stride(0) if B else words, B, 32 * words, _p(index), H,
+                                             _activity_stamp(who, stamp), _p(fired), _p(last), _stream()))
+
+
+@_on_tensor_device
+def activity_add_dense(latent: torch.Tensor, stamp: int, fired: torch.Tensor, last: torch.Tensor) -> None:
+    """The same from a dense latent fp32 [B, H] with unit column stride (a row stride above H is fine): active = latent > 0.
+    See qsae_activity_add_dense."""
+    who = "activity_add_dense"
+    _dev(latent, f"{who}: latent", torch.float32)
+    H = _activity_state(who, fired=fired, last=last)
+    if latent.dim() != 2 or latent.shape[1] != H:
+        raise ValueError(f"{who}: latent must be [B, {H}], got {tuple(latent.shape)}")
+    if latent.stride(1) != 1:
+        latent = latent.contiguous()
+    B = latent.shape[0]
+    check(_lib.load().qsae_activity_add_dense(_p(latent), latent.stride(0) if B else H, B, H, _activity_stamp(who, stamp),
+                                              _p(fired), _p(last), _stream()))
+
+
+@_on_tensor_device
+def activity_summary(fired: torch.Tensor, base: Optional[torch.Tensor], last: torch.Tensor, clock: int, window: int,
+                     seg_sizes=(), advance: bool = True, dead_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> int64 [1 + n_seg, 8 + 34] on the device: per block (all units, then the consecutive segments of ``seg_sizes``) the
+    words units, never, dead, silent, sum of interval counts, sum of fired, largest interval count, 0, and the 34 octave bins
+    of the interval counts fired - base.  ``advance`` writes base = fired; ``dead_out`` (int32 [H]) receives the dead units
+    in ascending order in its first ``result[0, 2]`` entries.  Nothing is read back.  See qsae_activity_summary."""
+    who = "activity_summary"
+    H = _activity_state(who, fired=fired, last=last, base=base)
+    seg_sizes = [int(s) for s in seg_sizes]
+    if len(seg_sizes) > ACTIVITY_MAX_SEGMENTS:
+        raise ValueError(f"{who}: at most {ACTIVITY_MAX_SEGMENTS} segments, got {len(seg_sizes)}")
+    if seg_sizes and (min(seg_sizes) < 0 or sum(seg_sizes) != H):
+        raise ValueError(f"{who}: the segment sizes {seg_sizes} must be >= 0 and add up to H = {H}")
+    clock, window = int(clock), int(window)
+    if clock < 0 or window < 1:
+        raise ValueError(f"{who}: clock must be >= 0 and window >= 1, got clock = {clock}, window = {window}")
+    if dead_out is not None:
+        _dev(dead_out, f"{who}: dead_out", torch.int32)
+        if dead_out.dim() != 1 or dead_out.numel() != H or not dead_out.is_contiguous() or dead_out.device != fired.device:
+            raise ValueError(f"{who}: dead_out must be a contiguous int32 [{H}] on {fired.device}")
+    lib = _lib.load()
+    result = torch.empty((1 + len(seg_sizes), ACTIVITY_HEAD + ACTIVITY_BINS), dtype=torch.int64, device=fired.device)
+    ws = _workspace(fired.device, max(int(lib.qsae_activity_summary_workspace_bytes(H)), 16))
+    sizes = (C.c_int32 * len(seg_sizes))(*seg_sizes) if seg_sizes else None
+    check(lib.qsae_activity_summary(_p(fired), _p(base), _p(last), H, clock, window, sizes, len(seg_sizes), int(bool(advance)),
+                                    _p(result), _p(dead_out), _p(ws), ws.numel(), _stream()))
+    return result

@@ -10,6 +10,10 @@ from .topk import SubmittedForward, TopKCore, sparse_backward
 
 
 class BaselineSparseAutoencoder(ops.GraphForwardMixin, TopKCore, nn.Module):
+    #: a ``training.FeatureActivity`` or None: when set, ``forward_train`` (never ``forward``) adds every batch's active units
+    #: to it from the tensors it already holds; outputs and gradients are the same bits either way
+    activity = None
+
     def __init__(self, input_dim, hidden_dim):
         super().__init__()
         self.encoder = HipEncoder(nn.Linear(input_dim, hidden_dim))   # no ReLU in the reference either
@@ -157,6 +161,8 @@ class _BaselineTrainStep(torch.autograd.Function):
     def forward(ctx, model, dense_latent, x, W_enc, b_enc, W_dec, b_dec):
         xf = as_f32c(x.detach())
         idx, val, latent, recon = model._run(xf, dense_latent)
+        if model.activity is not None:
+            model.activity.add_compact(idx, val)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(xf, idx, val, model._table())
         ctx.model = model

@@ -155,6 +155,9 @@ class BinarySAE(ops.GraphForwardMixin, TopKCore, SparseAutoencoder):
     def top_k(self) -> int:
         return int(self.hidden_dim * self.k)
 
+    #: a ``training.FeatureActivity`` or None: when set, ``forward_train`` (never ``forward``) adds every batch's active units
+    #: to it from the tensors it already holds; outputs and gradients are the same bits either way
+    activity = None
     #: "auto" | "fused" | "inplace" | "prefilter".  fused: exact-fp32 encoder+top-k without a dense
     #: latent in HBM (the dense [B,H] return value is zero-filled inside the sweep); inplace: dense
     #: contraction, top-k masks it in place; prefilter: an fp16 MFMA pass with a rigorous error bound
@@ -309,6 +312,8 @@ class _BinaryTrainStep(torch.autograd.Function):
         table, pol = ops.binary_soft_table_polarize(logits.detach(), dec.out_features, dec.n_bits)
         xf = as_f32c(x.detach())
         idx, val, latent, recon = model._run(xf, dense_latent, soft_table=table)
+        if model.activity is not None:
+            model.activity.add_compact(idx, val)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(xf, idx, val, table)
         ctx.model = model

@@ -18,6 +18,10 @@ class BinaryLatentSAE(SparseAutoencoder):
     ``latent + (binary - latent).detach()``, which is the binary latent up to one rounding (<= 6e-8); here the
     decoder contracts the binary latent itself."""
 
+    #: a ``training.FeatureActivity`` or None: when set, ``forward_train`` (never ``forward``) adds every batch's active units
+    #: to it from the tensors it already holds; outputs and gradients are the same bits either way
+    activity = None
+
     def __init__(self, input_dim, hidden_dim):
         super().__init__(input_dim, hidden_dim)
         self.encoder = HipEncoder(nn.Linear(input_dim, hidden_dim), nn.Sigmoid())
@@ -73,6 +77,8 @@ class _BinaryLatentTrainStep(torch.autograd.Function):
         xf = as_f32c(x.detach())
         pre = ops.encode_dense(xf, W_enc.detach(), b_enc.detach(), ops.ACT_NONE)
         binary_latent, zbits = ops.blatent_binarize(pre, _GE_HALF_CUTOFF)
+        if model.activity is not None:
+            model.activity.add_bits(zbits)
         recon = ops.encode_dense(binary_latent, W_dec.detach(), b_dec.detach(), ops.ACT_NONE)
         ctx.mark_non_differentiable(binary_latent)
         ctx.set_materialize_grads(False)

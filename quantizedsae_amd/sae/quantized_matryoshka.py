@@ -253,6 +253,9 @@ class QuantizedMatryoshkaSAE(ops.GraphForwardMixin, SparseAutoencoder):
     #: candidate lists, i.e. more than ~8 % of the units fire), then band (dense where the shape is not covered) for this model.
     bits_path = "auto"
     _PREFILTER_MIN_ROWS = 2048
+    #: a ``training.FeatureActivity`` or None: when set, ``forward_train`` (never ``forward``) adds every batch's active units
+    #: to it from the tensors it already holds; outputs and gradients are the same bits either way
+    activity = None
 
     def resolved_bits_path(self, batch_rows: int) -> str:
         path = self.bits_path
@@ -418,6 +421,8 @@ class _MatryoshkaTrainStep(torch.autograd.Function):
         if path == "auto":
             path = "lists" if (frac < model.LISTS_MAX_ACTIVE_FRACTION and ops.train_bits_csr_supported(B, st["H"])) else "dense"
         tp = dec.train_pack()
+        if model.activity is not None:
+            model.activity.add_bits(zbits, tp["index"])      # the map analysis._stage_bits uses, as int32
         dec._train_ctx = {"zbits": zbits, "scale": st["scale"], "index": tp["index"], "rows": B,
                           "versions": (dec.weight._version, dec.weight_mirror._version)}
         ctx.set_materialize_grads(False)

@@ -14,6 +14,10 @@ class ResidualQuantizedSAE(ops.GraphForwardMixin, SparseAutoencoder):
     """``forward(x) -> (latent_groups, reconstruction_levels)``: stage i encodes the residual left
     by stage i-1, ``residual = (residual - recon) * 2``; only stage 0 has a decoder bias."""
 
+    #: a ``training.FeatureActivity`` or None: when set, ``forward_train`` (never ``forward``) hands stage i the segment of its
+    #: units for the call and advances the clock once per batch; outputs and gradients are the same bits either way
+    activity = None
+
     def __init__(self, input_dim, hidden_dim, top_k, abs_range=4, n_bits=8):
         super().__init__(input_dim, hidden_dim)
         self.n_bits = n_bits
@@ -56,6 +60,8 @@ class ResidualQuantizedSAE(ops.GraphForwardMixin, SparseAutoencoder):
         residual = require_device_input(x, "x")
         if residual.dtype != torch.float32:
             residual = residual.float()
+        if self.activity is not None:
+            return self._forward_train_tracked(residual, self.activity)
         groups, levels = [], []
         for sae in self.saes:
             g, recs = sae.forward_train(residual)
@@ -63,6 +69,29 @@ class ResidualQuantizedSAE(ops.GraphForwardMixin, SparseAutoencoder):
             levels.append(recs[-1])
             with torch.no_grad():
                 residual = ops.residual_update(residual.detach(), recs[-1].detach(), 2.0)    # (residual - reconstruction) * 2
+        return groups, levels
+
+    def _forward_train_tracked(self, residual, activity):
+        """forward_train with ``self.activity`` set: the same chain, stage i feeding ``activity.segment(offset_i, h_i)`` --
+        the stages sit side by side in the tracker -- for the duration of the call; whatever the stage had as ``activity`` is
+        put back, and the clock advances once, by the batch's rows."""
+        groups, levels, offset = [], [], 0
+        for sae, h in zip(self.saes, self.sae_hidden_dims):
+            had = sae.__dict__.get("activity", self)           # self: the stage has no attribute of its own
+            sae.activity = activity.segment(offset, h)
+            try:
+                g, recs = sae.forward_train(residual)
+            finally:
+                if had is self:
+                    del sae.activity
+                else:
+                    sae.activity = had
+            offset += h
+            groups.append(g[-1])
+            levels.append(recs[-1])
+            with torch.no_grad():
+                residual = ops.residual_update(residual.detach(), recs[-1].detach(), 2.0)    # (residual - reconstruction) * 2
+        activity.advance(residual.shape[0])
         return groups, levels
 
     def apply_secant_grad(self):

@@ -150,6 +150,10 @@ class STEWeights(nn.Module):
 class TernarySparseAutoencoder(ops.GraphForwardMixin, nn.Module):
     """``forward(x) -> (h [B,H], recon [B,D])``; no top-k in forward (sae/ternary.py:116-122)."""
 
+    #: a ``training.FeatureActivity`` or None: when set, ``forward_train`` (never ``forward``) adds every batch's active units
+    #: to it from the tensors it already holds; outputs and gradients are the same bits either way
+    activity = None
+
     def __init__(self, input_dim, hidden_dim):
         super().__init__()
         self.encoder = HipEncoder(nn.Linear(input_dim, hidden_dim), nn.ReLU())
@@ -213,6 +217,8 @@ class _TernaryTrainStep(torch.autograd.Function):
         xf = as_f32c(x.detach())
         h = model.encoder(xf)
         recon = dec(h)
+        if model.activity is not None:
+            model.activity.add_dense(h)
         dec.activation_mean = ops.train_col_sum(h).div_(h.shape[0])
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(xf, h, dec.ternary_rows(), dec.mask)

@@ -835,6 +835,49 @@ def _(tensors, bins):
     return torch.empty((len(tensors), 8 + bins), dtype=torch.int64, device=device)
 
 
+# ---- activity: per-unit firing counts of a model in training (csrc/activity.hip) ----------------------------------------------
+@_op("activity_add_compact", mutates=("fired", "last"))
+def _activity_add_compact(idx: Tensor, val: Optional[Tensor], stamp: int, fired: Tensor, last: Tensor) -> None:
+    _ops.activity_add_compact(idx, val, stamp, fired, last)
+
+
+@_activity_add_compact.register_fake
+def _(idx, val, stamp, fired, last):
+    return None
+
+
+@_op("activity_add_bits", mutates=("fired", "last"))
+def _activity_add_bits(zbits: Tensor, index: Optional[Tensor], stamp: int, fired: Tensor, last: Tensor) -> None:
+    _ops.activity_add_bits(zbits, index, stamp, fired, last)
+
+
+@_activity_add_bits.register_fake
+def _(zbits, index, stamp, fired, last):
+    return None
+
+
+@_op("activity_add_dense", mutates=("fired", "last"))
+def _activity_add_dense(latent: Tensor, stamp: int, fired: Tensor, last: Tensor) -> None:
+    _ops.activity_add_dense(latent, stamp, fired, last)
+
+
+@_activity_add_dense.register_fake
+def _(latent, stamp, fired, last):
+    return None
+
+
+@_op("activity_summary", mutates=("base", "dead_out"))
+def _activity_summary(fired: Tensor, base: Optional[Tensor], last: Tensor, clock: int, window: int, seg_sizes: List[int],
+                      advance: bool, dead_out: Optional[Tensor]) -> Tensor:
+    """-> int64 [1 + n_seg, 8 + 34]: the head words and octave bins of all units and of every segment"""
+    return _ops.activity_summary(fired, base, last, clock, window, seg_sizes, advance, dead_out)
+
+
+@_activity_summary.register_fake
+def _(fired, base, last, clock, window, seg_sizes, advance, dead_out):
+    return torch.empty((1 + len(seg_sizes), 8 + 34), dtype=torch.int64, device=fired.device)
+
+
 Q = torch.ops.qsae
 
 
@@ -1367,3 +1410,20 @@ def tensor_stats(tensors, bins=64):
     if not tensors:                                           # no tensor to dispatch on
         return _ops.tensor_stats(tensors, int(bins))
     return Q.tensor_stats(tensors, int(bins))
+
+
+def activity_add_compact(idx, val, stamp, fired, last):
+    Q.activity_add_compact(idx, val, int(stamp), fired, last)
+
+
+def activity_add_bits(zbits, index, stamp, fired, last):
+    Q.activity_add_bits(zbits, index, int(stamp), fired, last)
+
+
+def activity_add_dense(latent, stamp, fired, last):
+    Q.activity_add_dense(latent, int(stamp), fired, last)
+
+
+def activity_summary(fired, base, last, clock, window, seg_sizes=(), advance=True, dead_out=None):
+    """-> int64 [1 + n_seg, 8 + 34] on the device"""
+    return Q.activity_summary(fired, base, last, int(clock), int(window), [int(s) for s in seg_sizes], bool(advance), dead_out)

@@ -20,6 +20,13 @@ backward, ``trainer_loss`` the per-type loss, ``optim.Adam`` the step.  What dif
   kernel call (``ModelWatch``, csrc/watch.hip) on the steps with ``batch_idx % watch_freq == 0``.  They go to ``log_fn`` as
   ``TensorStats`` under wandb's keys (merged into the metrics of a step that is also a logging step), to wandb as
   ``wandb.Histogram``, and under ``no_log`` to one printed line per tensor.  The default ``None`` changes nothing.
+* ``activity_window=W`` (rows; default ``None`` changes nothing) keeps per-feature firing counts on the GPU while the run
+  trains (``FeatureActivity``, csrc/activity.hip): ``model.activity`` is set, every ``forward_train`` adds its batch from the
+  tensors it already holds, and on logging steps -- the only steps that read anything back -- the metrics gain
+  ``dead_features`` (not fired within the last W rows), ``dead_fraction``, ``never_fired``, ``silent_features`` (not fired since
+  the previous logging step), ``mean_l0`` over that interval, ``count_octaves`` (34 bins of the interval's firing counts) and,
+  for ``q_sae`` / ``rq_sae``, ``dead_features_level_{i}``; under ``no_log`` a second printed line follows the reference's.  The
+  tracker lives as long as the Trainer, across ``one_epoch`` calls.  ``dead_neuron_threshold`` stays unread, as in the reference.
 * ``model=`` hands in the model instead of building the reference's.  The reference builds
   ``BinarySAE(input_dim, hidden_dim, n_bits)``, where ``n_bits`` lands in ``gamma`` and the decoder keeps its default of 8
   bits; that call is kept.
@@ -41,6 +48,7 @@ from ..sae import (BaselineSparseAutoencoder, BinarySAE, QuantizedMatryoshkaSAE,
 from ..sae.binary_latent import BinaryLatentSAE
 from .batches import ShuffledChunk
 from .loss import SAE_TYPES, trainer_loss
+from .activity import FeatureActivity, activity_line
 from .watch import WATCH_MODES, ModelWatch, watch_line
 
 __all__ = ["Trainer", "model_path_for"]
@@ -74,7 +82,8 @@ def _build_model(sae_type: str, config: dict) -> torch.nn.Module:
 class Trainer:
     def __init__(self, config, sae_type, rigL=False, no_log=False, proj_name=None, *, model: Optional[torch.nn.Module] = None,
                  dataset_dir: str = "dataset/", save_dir: str = "SAEs/", log_fn: Optional[Callable[[dict], None]] = None,
-                 log_every: int = 100, watch: Optional[str] = None, watch_freq: int = 256):
+                 log_every: int = 100, watch: Optional[str] = None, watch_freq: int = 256,
+                 activity_window: Optional[int] = None):
         if sae_type not in SAE_TYPES:
             raise ValueError(f"unknown sae_type {sae_type!r}; expected one of {', '.join(SAE_TYPES)}")
         if sae_type == "t_sae" and not rigL:
@@ -86,6 +95,8 @@ class Trainer:
             raise ValueError(f"watch = {watch!r}; expected None or one of {', '.join(WATCH_MODES)}")
         if int(watch_freq) < 1:
             raise ValueError(f"watch_freq = {watch_freq}")
+        if activity_window is not None and int(activity_window) < 1:
+            raise ValueError(f"activity_window = {activity_window}; expected None or a number of rows >= 1")
         self.config = config
         self.sae_type = sae_type
         self.device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
@@ -117,6 +128,10 @@ class Trainer:
         self.watch_freq = int(watch_freq)
         self._watch = ModelWatch(self.model, log=watch) if watch is not None else None
         self._watch_due, self._watched = False, None          # this step collects / what it collected
+        self.activity_window = int(activity_window) if activity_window is not None else None
+        self.activity = None
+        if self.activity_window is not None:
+            self.activity = self.model.activity = FeatureActivity.for_model(self.model)
 
     # ---- one step ------------------------------------------------------------------------------------------------
     def _forward(self, batch, want_latent: bool):
@@ -188,6 +203,14 @@ class Trainer:
             return d
         return {"loss": lv[0]}
 
+    def _activity_metrics(self, summary) -> dict:
+        """What a logging step adds with ``activity_window``: the summary that ends the interval since the previous one"""
+        d = {"dead_features": summary.dead, "dead_fraction": summary.dead_fraction, "never_fired": summary.never,
+             "silent_features": summary.silent, "mean_l0": summary.mean_l0, "count_octaves": list(summary.octaves)}
+        if self.sae_type in ("q_sae", "rq_sae"):
+            d.update({f"dead_features_level_{i}": lv.dead for i, lv in enumerate(summary.levels)})
+        return d
+
     def _print_line(self, batch_idx: int, m: dict) -> str:
         """The reference's print line of a logging step under no_log (training/trainer.py:213-230), from the metrics"""
         st, n = self.sae_type, self.config["n_bits"]
@@ -203,9 +226,12 @@ class Trainer:
             return f"Batch {batch_idx}: {recon}, recon_loss_total={loss_total:.4f}, {l0}"
         return f"Batch {batch_idx}: Loss={m['loss']:.4f}"
 
-    def _log(self, batch_idx: int, metrics: Optional[dict], watched: Optional[dict] = None) -> None:
-        """metrics: the scalars of a logging step or None; watched: the distributions of a watch step or None.  A step that
-        is both hands log_fn (or wandb) one dictionary."""
+    def _log(self, batch_idx: int, metrics: Optional[dict], watched: Optional[dict] = None, activity=None) -> None:
+        """metrics: the scalars of a logging step or None; watched: the distributions of a watch step or None; activity: the
+        ActivitySummary of a logging step with ``activity_window`` or None.  A step that is several of these hands log_fn (or
+        wandb) one dictionary."""
+        if activity is not None:
+            metrics = {**(metrics or {}), **self._activity_metrics(activity)}
         if self.log_fn is not None:
             self.log_fn({**(metrics or {}), **(watched or {})})
         elif self._wandb is not None:
@@ -214,6 +240,8 @@ class Trainer:
         else:
             if metrics is not None:
                 print(self._print_line(batch_idx, metrics))
+            if activity is not None:
+                print(activity_line(activity))
             if watched is not None:
                 print(f"Batch {batch_idx}: watch")
                 for key, s in watched.items():
@@ -245,7 +273,8 @@ class Trainer:
             self._watch_due = watch_step
             outputs, losses = self._step(optimizer, batch, log_step)
             if log_step or watch_step:
-                self._log(batch_idx, self._metrics(outputs, losses) if log_step else None, self._watched)
+                summary = self.activity.summary(self.activity_window) if (log_step and self.activity is not None) else None
+                self._log(batch_idx, self._metrics(outputs, losses) if log_step else None, self._watched, summary)
         announce(None)
         chunk.check()
         return self.model
