@@ -1024,6 +1024,64 @@ int qsae_activity_summary(const int64_t* fired, int64_t* base, const int64_t* la
                           const int32_t* seg_sizes, int n_seg, int advance, int64_t* result, int32_t* dead_out, void* workspace,
                           size_t workspace_bytes, qsae_stream_t stream);
 
+/* -- Resampling: revive the dead units of a top-k dictionary from the rows it reconstructs worst,
+ *    the consumer of qsae_activity_summary's dead list.  Five steps, each an entry point, chained on the device with no
+ *    host read: row weights, the draw, the statistics of the alive units, and one of two writes.  Every floating-point sum
+ *    is an fp64 sum in a fixed order (csrc/resample.hip states the two orders, tests/resample_util.py mirrors them); counts
+ *    go through 64-bit integer atomicAdd, the owner of a row through 32-bit integer atomicMin: the same bits on every run.
+ *    No float atomics.  D: a multiple of 4 up to QSAE_RESAMPLE_MAX_D (QSAE_ERR_UNSUPPORTED otherwise).  All argument
+ *    errors are raised before any launch. ----------------------------------------------------------------------------------- */
+#define QSAE_RESAMPLE_MAX_D 4096
+/* int64 words of a report: 0 dead (n), 1 revived, 2 duplicate (the row has an earlier owner), 3 degenerate (the row equals
+ * the decoder bias, or its norm is not finite), 4 no_weight (the total weight is 0 or not finite), 5 entries of the dead
+ * list or of rows that were out of range or out of order and therefore skipped, 6 and 7 zero. */
+#define QSAE_RESAMPLE_REPORT_WORDS 8
+/* w[r] = e_r e_r with e_r = sum over d of (x[r][d] - recon[r][d])^2: the difference is one fp32 subtraction, widened
+ * exactly, squared and summed in fp64; w[r] = 0 where e_r is not finite.  x fp32 [N][ldx], recon fp32 [N][ldr], w fp64 [N].
+ * N == 0: QSAE_OK with nothing launched. */
+int qsae_resample_row_weights(const float* x, int64_t ldx, const float* recon, int64_t ldr, int N, int D, double* w,
+                              qsae_stream_t stream);
+/* The draw: cdf = the inclusive fixed-order prefix sum of w (non-negative, finite: the caller's duty), total = cdf[N - 1].
+ * Dead unit j takes t_j = u[j] total (u fp64 [n] in [0, 1)) and r_j = the smallest r with cdf[r] > t_j, by binary search
+ * (a u outside [0, 1) or a NaN: the row at which the cdf reaches the total); a row of weight 0 is never drawn.  The
+ * first drawer of a row (lowest j) owns it.  rows int32 [n]: r_j for the owner, -2 for a later drawer of the same row, -1
+ * when total is 0 or not finite.  report (QSAE_RESAMPLE_REPORT_WORDS int64) is zeroed and receives words 0, 2 and 4.
+ * n == 0: QSAE_OK with nothing launched and nothing written.  workspace: 8-byte aligned, need not be zeroed,
+ * qsae_resample_draw_workspace_bytes(N) = 8 N, 8 per chunk of 1024 rows and 4 N bytes, each rounded up to 256 (0 for N <= 0).
+ * Errors: QSAE_ERR_INVALID_ARG (N < 1, n < 0, null or misaligned pointers), QSAE_ERR_WORKSPACE. */
+size_t qsae_resample_draw_workspace_bytes(int N);
+int qsae_resample_draw(const double* w, int N, const double* u, int n, int32_t* rows, int64_t* report, void* workspace,
+                       size_t workspace_bytes, qsae_stream_t stream);
+/* stats[0] = enc_norm_mean: the mean over the alive units (those not in the ascending list dead int32 [n]; every unit when
+ * none is alive) of sqrt(sum over d of W_enc[h][d]^2); stats[1] = logit_mean: the mean of |logits[h][c]| over the same rows
+ * of logits fp32 [H][D n_bits] (NULL: stats[1] = 0, n_bits and unit_abs are not looked at).  unit_norm / unit_abs fp64 [H]
+ * receive the per-unit root and sum.  Errors: QSAE_ERR_INVALID_ARG (H or D <= 0, n outside 0 .. H, n_bits outside 1 .. 8,
+ * null or misaligned pointers, logits without unit_abs). */
+int qsae_resample_alive_stats(const float* W_enc, int H, int D, const float* logits, int n_bits, const int32_t* dead, int n,
+                              double* unit_norm, double* unit_abs, double* stats, qsae_stream_t stream);
+/* The write, one workgroup per dead unit j with h = dead[j] and r = rows[j] >= 0 (negative: nothing is done):
+ *   v_d = x[r][d] - dec_bias[d] (fp32), s = sum v_d^2 (fp64), nrm = sqrt(s); s == 0 or not finite: the unit is left untouched
+ *   and counted as degenerate;  W_enc[h][d] = fp32(fp64(v_d) c) with c = (encoder_scale stats[0]) / nrm;  b_enc[h] = 0;
+ *   table form (BaselineSparseAutoencoder, dec fp32 [D][H]): dec[d][h] = fp32(fp64(v_d) / nrm);
+ *   binary form (BinarySAE, dec fp32 [H][D n_bits], bit b of dimension d at column d n_bits + b, LSB first, MSB negative):
+ *     q_d = clamp(rint(fp64(v_d) (max(qmax, 1) / fp64(max_d |v_d|))), -2^(n_bits-1), qmax), qmax = 2^(n_bits-1) - 1; the logit
+ *     is +L where bit b of q_d & (2^n_bits - 1) is set and -L elsewhere, L = fp32(logit_scale) when has_logit_scale, else
+ *     fp32(stats[1]).
+ * The Adam moments m_* / v_* (shapes of W_enc, b_enc, dec; each may be NULL) are set to 0 at exactly the written positions;
+ * last (int64 [H], may be NULL) receives last[h] = rows_seen.  report gains words 1, 3 and 5.  An entry with dead[j] outside
+ * [0, H), dead[j] <= dead[j - 1] or rows[j] >= N is skipped and counted in word 5, never written through.
+ * n == 0: QSAE_OK with nothing launched.  Errors: QSAE_ERR_INVALID_ARG (n < 0, n > H, N < 1, H or D <= 0, ldx < D,
+ * rows_seen < 0, n_bits outside 1 .. 8, null or misaligned pointers), QSAE_ERR_UNSUPPORTED (D, n > 65536). */
+int qsae_resample_write_table(const int32_t* dead, const int32_t* rows, int n, const float* x, int64_t ldx, int N, int D, int H,
+                              const float* dec_bias, const double* stats, double encoder_scale, float* W_enc, float* b_enc,
+                              float* dec, float* m_We, float* v_We, float* m_be, float* v_be, float* m_dec, float* v_dec,
+                              int64_t* last, int64_t rows_seen, int64_t* report, qsae_stream_t stream);
+int qsae_resample_write_binary(const int32_t* dead, const int32_t* rows, int n, const float* x, int64_t ldx, int N, int D, int H,
+                               int n_bits, const float* dec_bias, const double* stats, double encoder_scale, int has_logit_scale,
+                               double logit_scale, float* W_enc, float* b_enc, float* dec, float* m_We, float* v_We, float* m_be,
+                               float* v_be, float* m_dec, float* v_dec, int64_t* last, int64_t rows_seen, int64_t* report,
+                               qsae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -183,6 +183,14 @@ SIGNATURES = {
     "qsae_activity_add_dense": (_i, [_vp, _i64, _i, _i, _i64, _vp, _vp, _vp]),
     "qsae_activity_summary_workspace_bytes": (_sz, [_i]),
     "qsae_activity_summary": (_i, [_vp, _vp, _vp, _i, _i64, _i64, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "qsae_resample_row_weights": (_i, [_vp, _i64, _vp, _i64, _i, _i, _vp, _vp]),
+    "qsae_resample_draw_workspace_bytes": (_sz, [_i]),
+    "qsae_resample_draw": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "qsae_resample_alive_stats": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "qsae_resample_write_table": (_i, [_vp, _vp, _i, _vp, _i64, _i, _i, _i, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       _vp, _vp, _vp, _i64, _vp, _vp]),
+    "qsae_resample_write_binary": (_i, [_vp, _vp, _i, _vp, _i64, _i, _i, _i, _i, _vp, _vp, C.c_double, _i, C.c_double, _vp, _vp, _vp,
+                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
 }
 
 

@@ -21,7 +21,7 @@ OBJDIR = PKG / "lib" / "obj"
 
 SOURCES = ["encode.hip", "topk.hip", "binary.hip", "dense_dec.hip", "encode_topk.hip", "prefilter_topk.hip", "encode_bits.hip",
            "encode_emu.hip", "misc.hip", "analysis.hip", "coactivation_bits.hip", "coactivation_partners.hip", "token_overlap.hip", "token_lists.hip", "dictionary.hip", "dictionary_neighbors.hip", "dictionary_neighbors_f32.hip", "kmeans.hip", "top_examples.hip", "evaluation.hip", "train.hip", "train_gemm.hip",
-           "train_mask.hip", "optim.hip", "trainer.hip", "watch.hip", "activity.hip"]
+           "train_mask.hip", "optim.hip", "trainer.hip", "watch.hip", "activity.hip", "resample.hip"]
 HEADERS = sorted(p.name for p in (Path(__file__).resolve().parent / "csrc").glob("*.h"))   # every header: all sources rebuild
 ARCH = "gfx950"
 FLAGS = ["-O3", f"--offload-arch={ARCH}", "-ffp-contract=off", "-fPIC", "-std=c++17", "-Wall",

@@ -2430,3 +2430,193 @@ def activity_summary(fired: torch.Tensor, base: Optional[torch.Tensor], last: to
     check(lib.qsae_activity_summary(_p(fired), _p(base), _p(last), H, clock, window, sizes, len(seg_sizes), int(bool(advance)),
                                     _p(result), _p(dead_out), _p(ws), ws.numel(), _stream()))
     return result
+
+
+# ---- resampling: revive dead units from high-loss rows (csrc/resample.hip; quantizedsae_amd.training.resample is the user) ----
+RESAMPLE_MAX_D = 4096
+RESAMPLE_REPORT_WORDS = 8
+
+
+def resample_supported(D: int) -> bool:
+    """The resampling kernels take input_dim a multiple of 4 up to 4096"""
+    return 4 <= D <= RESAMPLE_MAX_D and D % 4 == 0
+
+
+def _resample_rows(who: str, name: str, t: torch.Tensor, D: Optional[int] = None) -> torch.Tensor:
+    """fp32 [N, D] with unit column stride (a row stride above D is read in place)"""
+    _dev(t, f"{who}: {name}", torch.float32)
+    if t.dim() != 2 or (D is not None and t.shape[1] != D):
+        raise ValueError(f"{who}: {name} must be fp32 [N, {D if D is not None else 'D'}], got {tuple(t.shape)}")
+    if not resample_supported(t.shape[1]):
+        raise ValueError(f"{who}: the kernels take D a multiple of 4 up to {RESAMPLE_MAX_D}, got {t.shape[1]}")
+    return t if t.stride(1) == 1 and t.stride(0) >= t.shape[1] else t.contiguous()
+
+
+def _resample_vec(who: str, name: str, t: torch.Tensor, dtype, n: Optional[int] = None) -> int:
+    _dev(t, f"{who}: {name}", dtype)
+    if t.dim() != 1 or not t.is_contiguous() or (n is not None and t.numel() != n):
+        raise ValueError(f"{who}: {name} must be a contiguous {dtype} [{n if n is not None else 'n'}], got {tuple(t.shape)} "
+                         f"with strides {t.stride()}")
+    return t.numel()
+
+
+@_on_tensor_device
+def resample_row_weights(x: torch.Tensor, recon: torch.Tensor) -> torch.Tensor:
+    """-> w fp64 [N]: the squared loss of every row, w_r = (sum_d (x[r,d] - recon[r,d])^2)^2 in a fixed order, 0 where the sum
+    is not finite.  See qsae_resample_row_weights."""
+    who = "resample_row_weights"
+    x = _resample_rows(who, "x", x)
+    N, D = x.shape
+    recon = _resample_rows(who, "recon", recon, D)
+    if recon.shape[0] != N or recon.device != x.device:
+        raise ValueError(f"{who}: recon is {tuple(recon.shape)} on {recon.device}, x {tuple(x.shape)} on {x.device}")
+    w = torch.empty((N,), dtype=torch.float64, device=x.device)
+    check(_lib.load().qsae_resample_row_weights(_p(x), x.stride(0) if N else D, _p(recon), recon.stride(0) if N else D, N, D,
+                                                _p(w), _stream()))
+    return w
+
+
+@_on_tensor_device
+def resample_draw(w: torch.Tensor, u: torch.Tensor):
+    """-> (rows int32 [n], report int64 [8]): one row per dead unit with probability proportional to w (fp64 [N]) from the
+    uniforms u (fp64 [n] in [0, 1)); rows[j] = -1 when the total weight is 0 or not finite, -2 when an earlier unit drew the
+    same row.  See qsae_resample_draw."""
+    who = "resample_draw"
+    N = _resample_vec(who, "w", w, torch.float64)
+    n = _resample_vec(who, "u", u, torch.float64)
+    if N < 1:
+        raise ValueError(f"{who}: w must hold at least one row")
+    if u.device != w.device:
+        raise ValueError(f"{who}: u is on {u.device}, w on {w.device}")
+    rows = torch.empty((n,), dtype=torch.int32, device=w.device)
+    report = torch.zeros((RESAMPLE_REPORT_WORDS,), dtype=torch.int64, device=w.device)
+    if n == 0:
+        return rows, report
+    lib = _lib.load()
+    ws = _workspace(w.device, max(int(lib.qsae_resample_draw_workspace_bytes(N)), 16))
+    check(lib.qsae_resample_draw(_p(w), N, _p(u), n, _p(rows), _p(report), _p(ws), ws.numel(), _stream()))
+    return rows, report
+
+
+def _resample_weights(who: str, W_enc: torch.Tensor):
+    _dev(W_enc, f"{who}: W_enc", torch.float32)
+    if W_enc.dim() != 2 or not W_enc.is_contiguous():
+        raise ValueError(f"{who}: W_enc must be a contiguous fp32 [H, D], got {tuple(W_enc.shape)} with strides {W_enc.stride()} "
+                         "(it is written in place: no copy is made)")
+    H, D = W_enc.shape
+    if not resample_supported(D):
+        raise ValueError(f"{who}: the kernels take D a multiple of 4 up to {RESAMPLE_MAX_D}, got {D}")
+    return H, D
+
+
+def _resample_bits(who: str, n_bits) -> int:
+    n_bits = int(n_bits)
+    if not 1 <= n_bits <= 8:
+        raise ValueError(f"{who}: n_bits must be 1 .. 8, got {n_bits}")
+    return n_bits
+
+
+def _resample_same(who: str, name: str, t: Optional[torch.Tensor], like: torch.Tensor, dtype=torch.float32) -> None:
+    """an operand written in place (or a moment of one): the dtype, shape and device of ``like``, contiguous; None passes"""
+    if t is None:
+        return
+    _dev(t, f"{who}: {name}", dtype)
+    if tuple(t.shape) != tuple(like.shape) or not t.is_contiguous() or t.device != like.device:
+        raise ValueError(f"{who}: {name} must be a contiguous {dtype} {tuple(like.shape)} on {like.device}, got {tuple(t.shape)} "
+                         f"with strides {t.stride()} on {t.device}")
+
+
+@_on_tensor_device
+def resample_alive_stats(W_enc: torch.Tensor, logits: Optional[torch.Tensor], dead: torch.Tensor, n_bits: int = 8) -> torch.Tensor:
+    """-> stats fp64 [2]: the mean encoder-row norm of the units not in ``dead`` (int32 [n], ascending) and, with ``logits``
+    (fp32 [H, D n_bits]), the mean |logit| of the same rows (0.0 without); over every unit when none is alive.  See
+    qsae_resample_alive_stats."""
+    who = "resample_alive_stats"
+    H, D = _resample_weights(who, W_enc)
+    n = _resample_vec(who, "dead", dead, torch.int32)
+    if n > H:
+        raise ValueError(f"{who}: {n} dead units of {H}")
+    unit_abs = None
+    if logits is not None:
+        n_bits = _resample_bits(who, n_bits)
+        _dev(logits, f"{who}: logits", torch.float32)
+        if tuple(logits.shape) != (H, D * n_bits) or not logits.is_contiguous():
+            raise ValueError(f"{who}: logits must be a contiguous fp32 [{H}, {D * n_bits}], got {tuple(logits.shape)}")
+        unit_abs = torch.empty((H,), dtype=torch.float64, device=W_enc.device)
+    unit_norm = torch.empty((H,), dtype=torch.float64, device=W_enc.device)
+    stats = torch.empty((2,), dtype=torch.float64, device=W_enc.device)
+    check(_lib.load().qsae_resample_alive_stats(_p(W_enc), H, D, _p(logits), int(n_bits) if logits is not None else 0,
+                                                _p(dead) if n else C.c_void_p(0), n, _p(unit_norm), _p(unit_abs), _p(stats),
+                                                _stream()))
+    return stats
+
+
+def _resample_write_args(who, dead, rows, x, dec_bias, stats, W_enc, b_enc, dec, dec_shape, moments, last, rows_seen, report):
+    H, D = _resample_weights(who, W_enc)
+    n = _resample_vec(who, "dead", dead, torch.int32)
+    _resample_vec(who, "rows", rows, torch.int32, n)
+    if n > H:
+        raise ValueError(f"{who}: {n} dead units of {H}")
+    x = _resample_rows(who, "x", x, D)
+    if x.shape[0] < 1:
+        raise ValueError(f"{who}: x holds no row")
+    _resample_vec(who, "dec_bias", dec_bias, torch.float32, D)
+    _resample_vec(who, "stats", stats, torch.float64, 2)
+    _resample_vec(who, "b_enc", b_enc, torch.float32, H)
+    _resample_vec(who, "report", report, torch.int64, RESAMPLE_REPORT_WORDS)
+    _dev(dec, f"{who}: dec", torch.float32)
+    if tuple(dec.shape) != dec_shape(H, D) or not dec.is_contiguous():
+        raise ValueError(f"{who}: dec must be a contiguous fp32 {dec_shape(H, D)}, got {tuple(dec.shape)}")
+    moments = list(moments) if moments is not None else [None] * 6
+    if len(moments) != 6:
+        raise ValueError(f"{who}: moments must be (m_We, v_We, m_be, v_be, m_dec, v_dec), each a tensor or None")
+    for name, t, like in zip(("m_We", "v_We", "m_be", "v_be", "m_dec", "v_dec"), moments, (W_enc, W_enc, b_enc, b_enc, dec, dec)):
+        _resample_same(who, name, t, like)
+    if last is not None:
+        _resample_vec(who, "last", last, torch.int64, H)
+    rows_seen = int(rows_seen)
+    if rows_seen < 0:
+        raise ValueError(f"{who}: rows_seen = {rows_seen}")
+    for name, t in (("dead", dead), ("rows", rows), ("x", x), ("dec_bias", dec_bias), ("stats", stats), ("b_enc", b_enc),
+                    ("dec", dec), ("report", report), ("last", last)):
+        if t is not None and t.device != W_enc.device:
+            raise ValueError(f"{who}: {name} is on {t.device}, W_enc on {W_enc.device}")
+    return n, x, H, D, moments, rows_seen
+
+
+@_on_tensor_device
+def resample_write_table(W_enc: torch.Tensor, b_enc: torch.Tensor, dec: torch.Tensor, dead: torch.Tensor, rows: torch.Tensor,
+                         x: torch.Tensor, dec_bias: torch.Tensor, stats: torch.Tensor, report: torch.Tensor, moments=None,
+                         last: Optional[torch.Tensor] = None, rows_seen: int = 0, encoder_scale: float = 0.2) -> None:
+    """Point every dead unit that owns a row at it, in place: W_enc [H, D] row, b_enc [H] entry and column h of ``dec``
+    [D, H] (the nn.Linear layout of BaselineSparseAutoencoder.decoder.weight); ``moments`` = (m_We, v_We, m_be, v_be, m_dec,
+    v_dec), each a tensor or None, are zeroed at the written positions; ``last`` [H] receives rows_seen.  ``report`` (from
+    resample_draw) gains the revived and degenerate counts.  See qsae_resample_write_table."""
+    who = "resample_write_table"
+    n, x, H, D, moments, rows_seen = _resample_write_args(who, dead, rows, x, dec_bias, stats, W_enc, b_enc, dec,
+                                                           lambda H, D: (D, H), moments, last, rows_seen, report)
+    if n == 0:
+        return
+    check(_lib.load().qsae_resample_write_table(_p(dead), _p(rows), n, _p(x), x.stride(0), x.shape[0], D, H, _p(dec_bias),
+                                                _p(stats), float(encoder_scale), _p(W_enc), _p(b_enc), _p(dec),
+                                                *[_p(m) for m in moments], _p(last), rows_seen, _p(report), _stream()))
+
+
+@_on_tensor_device
+def resample_write_binary(W_enc: torch.Tensor, b_enc: torch.Tensor, dec: torch.Tensor, dead: torch.Tensor, rows: torch.Tensor,
+                          x: torch.Tensor, dec_bias: torch.Tensor, stats: torch.Tensor, report: torch.Tensor, n_bits: int,
+                          moments=None, last: Optional[torch.Tensor] = None, rows_seen: int = 0, encoder_scale: float = 0.2,
+                          logit_scale: Optional[float] = None) -> None:
+    """The same for BinarySAE: ``dec`` is the logit matrix [H, D n_bits]; row h receives +-L per bit of the row's direction
+    quantized to n_bits two's-complement integers, L = logit_scale or, when None, stats[1] (the alive rows' mean |logit|).
+    See qsae_resample_write_binary."""
+    who = "resample_write_binary"
+    n_bits = _resample_bits(who, n_bits)
+    n, x, H, D, moments, rows_seen = _resample_write_args(who, dead, rows, x, dec_bias, stats, W_enc, b_enc, dec,
+                                                           lambda H, D: (H, D * n_bits), moments, last, rows_seen, report)
+    if n == 0:
+        return
+    check(_lib.load().qsae_resample_write_binary(_p(dead), _p(rows), n, _p(x), x.stride(0), x.shape[0], D, H, n_bits,
+                                                 _p(dec_bias), _p(stats), float(encoder_scale), int(logit_scale is not None),
+                                                 float(logit_scale) if logit_scale is not None else 0.0, _p(W_enc), _p(b_enc),
+                                                 _p(dec), *[_p(m) for m in moments], _p(last), rows_seen, _p(report), _stream()))

@@ -878,6 +878,74 @@ def _(fired, base, last, clock, window, seg_sizes, advance, dead_out):
     return torch.empty((1 + len(seg_sizes), 8 + 34), dtype=torch.int64, device=fired.device)
 
 
+# ---- resampling: revive dead units from high-loss rows (csrc/resample.hip) ---------------------------------------------------
+@_op("resample_row_weights")
+def _resample_row_weights(x: Tensor, recon: Tensor) -> Tensor:
+    """-> fp64 [N]: the squared loss of every row"""
+    return _ops.resample_row_weights(x, recon)
+
+
+@_resample_row_weights.register_fake
+def _(x, recon):
+    return torch.empty((x.shape[0],), dtype=torch.float64, device=x.device)
+
+
+@_op("resample_draw")
+def _resample_draw(w: Tensor, u: Tensor) -> Tuple[Tensor, Tensor]:
+    """-> (rows int32 [n], report int64 [8])"""
+    return _ops.resample_draw(w, u)
+
+
+@_resample_draw.register_fake
+def _(w, u):
+    return (torch.empty((u.shape[0],), dtype=torch.int32, device=w.device),
+            torch.empty((_ops.RESAMPLE_REPORT_WORDS,), dtype=torch.int64, device=w.device))
+
+
+@_op("resample_alive_stats")
+def _resample_alive_stats(W_enc: Tensor, logits: Optional[Tensor], dead: Tensor, n_bits: int) -> Tensor:
+    """-> fp64 [2]: enc_norm_mean, logit_mean"""
+    return _ops.resample_alive_stats(W_enc, logits, dead, n_bits)
+
+
+@_resample_alive_stats.register_fake
+def _(W_enc, logits, dead, n_bits):
+    return torch.empty((2,), dtype=torch.float64, device=W_enc.device)
+
+
+_RESAMPLE_WRITTEN = ("W_enc", "b_enc", "dec", "report", "m_We", "v_We", "m_be", "v_be", "m_dec", "v_dec", "last")
+
+
+@_op("resample_write_table", mutates=_RESAMPLE_WRITTEN)
+def _resample_write_table(W_enc: Tensor, b_enc: Tensor, dec: Tensor, dead: Tensor, rows: Tensor, x: Tensor, dec_bias: Tensor,
+                          stats: Tensor, report: Tensor, m_We: Optional[Tensor], v_We: Optional[Tensor], m_be: Optional[Tensor],
+                          v_be: Optional[Tensor], m_dec: Optional[Tensor], v_dec: Optional[Tensor], last: Optional[Tensor],
+                          rows_seen: int, encoder_scale: float) -> None:
+    _ops.resample_write_table(W_enc, b_enc, dec, dead, rows, x, dec_bias, stats, report, (m_We, v_We, m_be, v_be, m_dec, v_dec),
+                              last, rows_seen, encoder_scale)
+
+
+@_resample_write_table.register_fake
+def _(W_enc, b_enc, dec, dead, rows, x, dec_bias, stats, report, m_We, v_We, m_be, v_be, m_dec, v_dec, last, rows_seen,
+      encoder_scale):
+    return None
+
+
+@_op("resample_write_binary", mutates=_RESAMPLE_WRITTEN)
+def _resample_write_binary(W_enc: Tensor, b_enc: Tensor, dec: Tensor, dead: Tensor, rows: Tensor, x: Tensor, dec_bias: Tensor,
+                           stats: Tensor, report: Tensor, n_bits: int, m_We: Optional[Tensor], v_We: Optional[Tensor],
+                           m_be: Optional[Tensor], v_be: Optional[Tensor], m_dec: Optional[Tensor], v_dec: Optional[Tensor],
+                           last: Optional[Tensor], rows_seen: int, encoder_scale: float, logit_scale: Optional[float]) -> None:
+    _ops.resample_write_binary(W_enc, b_enc, dec, dead, rows, x, dec_bias, stats, report, n_bits,
+                               (m_We, v_We, m_be, v_be, m_dec, v_dec), last, rows_seen, encoder_scale, logit_scale)
+
+
+@_resample_write_binary.register_fake
+def _(W_enc, b_enc, dec, dead, rows, x, dec_bias, stats, report, n_bits, m_We, v_We, m_be, v_be, m_dec, v_dec, last, rows_seen,
+      encoder_scale, logit_scale):
+    return None
+
+
 Q = torch.ops.qsae
 
 
@@ -1427,3 +1495,37 @@ def activity_add_dense(latent, stamp, fired, last):
 def activity_summary(fired, base, last, clock, window, seg_sizes=(), advance=True, dead_out=None):
     """-> int64 [1 + n_seg, 8 + 34] on the device"""
     return Q.activity_summary(fired, base, last, int(clock), int(window), [int(s) for s in seg_sizes], bool(advance), dead_out)
+
+
+def resample_row_weights(x, recon):
+    """-> fp64 [N]"""
+    return Q.resample_row_weights(x, recon)
+
+
+def resample_draw(w, u):
+    """-> (rows int32 [n], report int64 [8])"""
+    return Q.resample_draw(w, u)
+
+
+def resample_alive_stats(W_enc, logits, dead, n_bits=8):
+    """-> fp64 [2]"""
+    return Q.resample_alive_stats(W_enc, logits, dead, int(n_bits))
+
+
+def _moments(moments):
+    moments = tuple(moments) if moments is not None else (None,) * 6
+    if len(moments) != 6:
+        raise ValueError("moments must be (m_We, v_We, m_be, v_be, m_dec, v_dec), each a tensor or None")
+    return moments
+
+
+def resample_write_table(W_enc, b_enc, dec, dead, rows, x, dec_bias, stats, report, moments=None, last=None, rows_seen=0,
+                         encoder_scale=0.2):
+    Q.resample_write_table(W_enc, b_enc, dec, dead, rows, x, dec_bias, stats, report, *_moments(moments), last, int(rows_seen),
+                           float(encoder_scale))
+
+
+def resample_write_binary(W_enc, b_enc, dec, dead, rows, x, dec_bias, stats, report, n_bits, moments=None, last=None, rows_seen=0,
+                          encoder_scale=0.2, logit_scale=None):
+    Q.resample_write_binary(W_enc, b_enc, dec, dead, rows, x, dec_bias, stats, report, int(n_bits), *_moments(moments), last,
+                            int(rows_seen), float(encoder_scale), None if logit_scale is None else float(logit_scale))

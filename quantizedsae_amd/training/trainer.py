@@ -27,6 +27,13 @@ backward, ``trainer_loss`` the per-type loss, ``optim.Adam`` the step.  What dif
   the previous logging step), ``mean_l0`` over that interval, ``count_octaves`` (34 bins of the interval's firing counts) and,
   for ``q_sae`` / ``rq_sae``, ``dead_features_level_{i}``; under ``no_log`` a second printed line follows the reference's.  The
   tracker lives as long as the Trainer, across ``one_epoch`` calls.  ``dead_neuron_threshold`` stays unread, as in the reference.
+* ``resample_every=R`` (batches; ``baseline_sae`` and ``b_sae`` with ``activity_window`` only; default ``None`` changes
+  nothing) revives dead units (``resample_dead``, csrc/resample.hip): on the steps with ``batch_idx % R == 0``, after the
+  type's step sequence, the dead list of ``summary(activity_window, dead_list=True, advance=False)`` is rewritten from the
+  batch just trained on, with the epoch's optimizer.  The uniforms come from a generator of the Trainer's own, seeded with
+  ``resample_seed``; the default generator, and with it the loader's order, is not touched.  ``resample_scale`` is the
+  encoder scale.  The report joins that step's metrics (``resampled_features``, ``resample_duplicates``, ...; one printed
+  line under ``no_log``); these steps read the summary and the report back, no other step reads anything more than before.
 * ``model=`` hands in the model instead of building the reference's.  The reference builds
   ``BinarySAE(input_dim, hidden_dim, n_bits)``, where ``n_bits`` lands in ``gamma`` and the decoder keeps its default of 8
   bits; that call is kept.
@@ -49,6 +56,7 @@ from ..sae.binary_latent import BinaryLatentSAE
 from .batches import ShuffledChunk
 from .loss import SAE_TYPES, trainer_loss
 from .activity import FeatureActivity, activity_line
+from .resample import ResampleReport, resample_dead, resample_line
 from .watch import WATCH_MODES, ModelWatch, watch_line
 
 __all__ = ["Trainer", "model_path_for"]
@@ -83,7 +91,8 @@ class Trainer:
     def __init__(self, config, sae_type, rigL=False, no_log=False, proj_name=None, *, model: Optional[torch.nn.Module] = None,
                  dataset_dir: str = "dataset/", save_dir: str = "SAEs/", log_fn: Optional[Callable[[dict], None]] = None,
                  log_every: int = 100, watch: Optional[str] = None, watch_freq: int = 256,
-                 activity_window: Optional[int] = None):
+                 activity_window: Optional[int] = None, resample_every: Optional[int] = None, resample_seed: int = 0,
+                 resample_scale: float = 0.2):
         if sae_type not in SAE_TYPES:
             raise ValueError(f"unknown sae_type {sae_type!r}; expected one of {', '.join(SAE_TYPES)}")
         if sae_type == "t_sae" and not rigL:
@@ -97,6 +106,14 @@ class Trainer:
             raise ValueError(f"watch_freq = {watch_freq}")
         if activity_window is not None and int(activity_window) < 1:
             raise ValueError(f"activity_window = {activity_window}; expected None or a number of rows >= 1")
+        if resample_every is not None:
+            if int(resample_every) < 1:
+                raise ValueError(f"resample_every = {resample_every}; expected None or a number of batches >= 1")
+            if activity_window is None:
+                raise ValueError("resample_every needs activity_window: the dead list comes from the activity tracker")
+            if sae_type not in ("baseline_sae", "b_sae"):
+                raise ValueError(f"resample_every: resampling is built for baseline_sae and b_sae, the two top-k models; got "
+                                 f"{sae_type!r}")
         self.config = config
         self.sae_type = sae_type
         self.device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
@@ -132,6 +149,9 @@ class Trainer:
         self.activity = None
         if self.activity_window is not None:
             self.activity = self.model.activity = FeatureActivity.for_model(self.model)
+        self.resample_every = int(resample_every) if resample_every is not None else None
+        self.resample_scale, self._resample_seed = float(resample_scale), int(resample_seed)
+        self._resample_rng = None                             # made on the first resampling step, on the model's device
 
     # ---- one step ------------------------------------------------------------------------------------------------
     def _forward(self, batch, want_latent: bool):
@@ -226,12 +246,27 @@ class Trainer:
             return f"Batch {batch_idx}: {recon}, recon_loss_total={loss_total:.4f}, {l0}"
         return f"Batch {batch_idx}: Loss={m['loss']:.4f}"
 
-    def _log(self, batch_idx: int, metrics: Optional[dict], watched: Optional[dict] = None, activity=None) -> None:
+    def _resample(self, optimizer, batch):
+        """A resampling step: the dead units of the tracker, rewritten from the batch just trained on -> the report (all
+        zeros, with nothing launched, when no unit is dead)"""
+        summary = self.activity.summary(self.activity_window, dead_list=True, advance=False)
+        if summary.dead == 0:
+            return ResampleReport()
+        if self._resample_rng is None:
+            self._resample_rng = torch.Generator(device=self.device)
+            self._resample_rng.manual_seed(self._resample_seed)
+        return resample_dead(self.model, summary.dead_indices, batch, optimizer=optimizer, activity=self.activity,
+                             generator=self._resample_rng, encoder_scale=self.resample_scale)
+
+    def _log(self, batch_idx: int, metrics: Optional[dict], watched: Optional[dict] = None, activity=None, resampled=None) -> None:
         """metrics: the scalars of a logging step or None; watched: the distributions of a watch step or None; activity: the
-        ActivitySummary of a logging step with ``activity_window`` or None.  A step that is several of these hands log_fn (or
-        wandb) one dictionary."""
+        ActivitySummary of a logging step with ``activity_window`` or None; resampled: the ResampleReport of a resampling
+        step or None.  A step that is several of these hands log_fn (or wandb) one dictionary."""
         if activity is not None:
             metrics = {**(metrics or {}), **self._activity_metrics(activity)}
+        printing = self.log_fn is None and self._wandb is None
+        if resampled is not None and not printing:
+            metrics = {**(metrics or {}), **resampled.metrics()}
         if self.log_fn is not None:
             self.log_fn({**(metrics or {}), **(watched or {})})
         elif self._wandb is not None:
@@ -242,6 +277,8 @@ class Trainer:
                 print(self._print_line(batch_idx, metrics))
             if activity is not None:
                 print(activity_line(activity))
+            if resampled is not None:
+                print(f"Batch {batch_idx}:" + resample_line(resampled))
             if watched is not None:
                 print(f"Batch {batch_idx}: watch")
                 for key, s in watched.items():
@@ -272,9 +309,12 @@ class Trainer:
             watch_step = self._watch is not None and batch_idx % self.watch_freq == 0
             self._watch_due = watch_step
             outputs, losses = self._step(optimizer, batch, log_step)
-            if log_step or watch_step:
+            resampled = None
+            if self.resample_every is not None and batch_idx % self.resample_every == 0:
+                resampled = self._resample(optimizer, batch)
+            if log_step or watch_step or resampled is not None:
                 summary = self.activity.summary(self.activity_window) if (log_step and self.activity is not None) else None
-                self._log(batch_idx, self._metrics(outputs, losses) if log_step else None, self._watched, summary)
+                self._log(batch_idx, self._metrics(outputs, losses) if log_step else None, self._watched, summary, resampled)
         announce(None)
         chunk.check()
         return self.model
