@@ -193,6 +193,15 @@ SIGNATURES = {
                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
 }
 
+# name -> (restype, argtypes) of the qsaex_* entry points of include/qsae_ext.h (csrc/auxk.hip): the same library, bound next
+# to SIGNATURES; they move into that table when qsae.h takes them in.  Must list every symbol declared in qsae_ext.h.
+EXT_SIGNATURES = {
+    "qsaex_encode_topk_units_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "qsaex_encode_topk_units": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "qsaex_auxk_loss_workspace_bytes": (_sz, [_i, _i]),
+    "qsaex_auxk_loss": (_i, [_vp, _vp, _vp, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _sz, _vp]),
+}
+
 
 class QsaeError(RuntimeError):
     """A libqsae_hip call returned a non-zero status."""
@@ -212,7 +221,7 @@ def _open(path: Path) -> C.CDLL:
             f"{path} is missing: build it with `python -m quantizedsae_amd.build` "
             "(hipcc --offload-arch=gfx950).  quantizedsae_amd has no CPU / eager fallback.")
     lib = C.CDLL(str(path))
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here means the library is stale
         fn.restype = res
         fn.argtypes = args

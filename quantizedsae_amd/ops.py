@@ -2620,3 +2620,69 @@ def resample_write_binary(W_enc: torch.Tensor, b_enc: torch.Tensor, dec: torch.T
                                                  _p(dec_bias), _p(stats), float(encoder_scale), int(logit_scale is not None),
                                                  float(logit_scale) if logit_scale is not None else 0.0, _p(W_enc), _p(b_enc),
                                                  _p(dec), *[_p(m) for m in moments], _p(last), rows_seen, _p(report), _stream()))
+
+
+# ---- AuxK: the dead units' own top-k and the normalised auxiliary loss (csrc/auxk.hip, include/qsae_ext.h) -----------------
+ENCODE_TOPK_UNITS_MAX_K = 64
+
+
+@_on_tensor_device
+def encode_topk_units(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], units: torch.Tensor, k: int):
+    """-> (idx int32 [B, k] of unit ids, val fp32 [B, k]): the k largest encoder pre-activations of every row among the units
+    listed in ``units`` (int32 [n], ascending, distinct, on the device), ordered by value descending, then unit ascending.  W's
+    rows are read in place: no gathered copy, no [B, n] tensor.  See qsaex_encode_topk_units."""
+    who = "encode_topk_units"
+    x, W = _f32c(x, "x"), _f32c(W, "W")
+    _dev(units, f"{who}: units", torch.int32)
+    if x.dim() != 2 or W.dim() != 2 or units.dim() != 1 or x.shape[1] != W.shape[1]:
+        raise ValueError(f"{who}: x is {tuple(x.shape)}, W {tuple(W.shape)}, units {tuple(units.shape)}; expected [B, D], [H, D], [n]")
+    units = units.contiguous()
+    B, D = x.shape
+    H, n = W.shape[0], units.shape[0]
+    k = int(k)
+    if not 1 <= k <= ENCODE_TOPK_UNITS_MAX_K:
+        raise ValueError(f"{who}: k = {k} is outside 1 .. {ENCODE_TOPK_UNITS_MAX_K}, the width of the kernel's lists")
+    if k > n:
+        raise ValueError(f"{who}: k = {k} exceeds the {n} listed units")
+    if D % 4 != 0:
+        raise ValueError(f"{who}: D = {D} must be a multiple of 4")
+    b = _f32c(bias, "bias") if bias is not None else None
+    if b is not None and tuple(b.shape) != (H,):
+        raise ValueError(f"{who}: bias is {tuple(b.shape)}, expected [{H}]")
+    idx = torch.empty((B, k), dtype=torch.int32, device=x.device)
+    val = torch.empty((B, k), dtype=torch.float32, device=x.device)
+    if B == 0:
+        return idx, val
+    lib = _lib.load()
+    ws = _workspace(x.device, int(lib.qsaex_encode_topk_units_workspace_bytes(B, D, n, k)))
+    check(lib.qsaex_encode_topk_units(_p(x), D, _p(W), D, _p(b), B, D, H, _p(units), n, k, _p(idx), _p(val), _p(ws), ws.numel(),
+                                      _stream()))
+    return idx, val
+
+
+@_on_tensor_device
+def auxk_loss(x: torch.Tensor, recon: torch.Tensor, aux: torch.Tensor, coef: float, sums: Optional[torch.Tensor] = None):
+    """-> (loss fp32 0-d, grad fp32 [B, D]), both on the device: loss = coef * |aux - e|^2 / |e - mean_rows(e)|^2 with
+    e = x - recon, and its gradient at ``aux`` (the only operand that has one); 0 and zeros when the denominator is 0.
+    x, recon, aux: fp32 [B, D], contiguous (views that start off a 16-byte boundary are fine).  ``sums``: an fp64 [2] device
+    tensor that receives (numerator, denominator).  Fixed summation order, nothing read back.  See qsaex_auxk_loss."""
+    who = "auxk_loss"
+    for name, t in (("x", x), ("recon", recon), ("aux", aux)):
+        _dev(t, f"{who}: {name}", torch.float32)
+        if t.dim() != 2 or t.shape != x.shape or not t.is_contiguous() or t.device != x.device or t.shape[1] < 1:
+            raise ValueError(f"{who}: {name} is {tuple(t.shape)} on {t.device} (strides {t.stride()}); expected contiguous fp32 "
+                             f"[B, D >= 1] tensors of one shape on one device")
+    if sums is not None:
+        _dev(sums, f"{who}: sums", torch.float64)
+        if tuple(sums.shape) != (2,) or not sums.is_contiguous() or sums.device != x.device:
+            raise ValueError(f"{who}: sums must be a contiguous fp64 [2] on {x.device}")
+    B, D = x.shape
+    loss = torch.zeros((), dtype=torch.float32, device=x.device)
+    grad = torch.empty((B, D), dtype=torch.float32, device=x.device)
+    if B == 0:
+        return loss, grad
+    lib = _lib.load()
+    ws = _workspace(x.device, int(lib.qsaex_auxk_loss_workspace_bytes(B, D)))
+    check(lib.qsaex_auxk_loss(_p(x), _p(recon), _p(aux), B, D, float(coef), _p(loss), _p(grad), _p(sums), _p(ws), ws.numel(),
+                              _stream()))
+    return loss, grad

@@ -97,6 +97,14 @@ class BaselineSparseAutoencoder(ops.GraphForwardMixin, TopKCore, nn.Module):
         latent, recon = _BaselineTrainStep.apply(self, bool(dense_latent), x, lin.weight, lin.bias, dec.weight, dec.bias)
         return (latent if dense_latent else None), recon
 
+    def _aux_decoder(self):
+        """-> (decoder.weight, its transpose [H, D], 1.0) for forward_aux"""
+        return self.decoder.weight, self._table(), 1.0
+
+    def _aux_unit_grad(self, offsets, entries, val, gv, x, g_recon, want_encoder: bool, want_decoder: bool):
+        return ops.train_table_unit_grad(offsets, entries, val, gv, x, g_recon, want_encoder=want_encoder,
+                                         want_decoder=want_decoder)
+
     def forward_compact(self, x):
         """(idx, val, reconstruction) without the dense latent; same path selection as forward()."""
         with torch.no_grad():

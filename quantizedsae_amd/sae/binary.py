@@ -149,6 +149,8 @@ class BinarySAE(ops.GraphForwardMixin, TopKCore, SparseAutoencoder):
         self.encoder = HipEncoder(lin)
         self.decoder = binary_decoder(hidden_dim, input_dim, gamma=gamma, n_bits=self.n_bits)
         self._init_topk()
+        #: the soft table of the last forward_train, keyed on the logits' version: forward_aux decodes from it
+        self._train_cache = PackedCache()
         ops.module_handle(self)
 
     @property
@@ -185,6 +187,7 @@ class BinarySAE(ops.GraphForwardMixin, TopKCore, SparseAutoencoder):
         """Forget every derived copy of the weights (packed dictionary, fp16 / K-interleaved encoder copies); see
         binary_decoder.invalidate_packed."""
         self.decoder.invalidate_packed()
+        self._train_cache.clear()
         self._clear_encoder_copies()
 
     def _check_limits(self, path: str, rows: int) -> None:
@@ -280,6 +283,19 @@ class BinarySAE(ops.GraphForwardMixin, TopKCore, SparseAutoencoder):
         latent, recon, pol = _BinaryTrainStep.apply(self, bool(dense_latent), x, lin.weight, lin.bias, dec.weight, dec.bias)
         return (latent if dense_latent else None), recon, pol
 
+    def _aux_decoder(self):
+        """-> (logits, soft table [H, D], step) for forward_aux: the table the step's forward_train built while the logits
+        have not changed since (no second [H, D n_bits] pass per step), a fresh one when forward_aux is called on its own."""
+        dec = self.decoder
+        st = self._train_cache.get((dec.weight,), lambda: {
+            "table": ops.binary_soft_table(dec.weight.detach(), dec.out_features, dec.n_bits)})
+        return dec.weight, st["table"], dec.quantization_step
+
+    def _aux_unit_grad(self, offsets, entries, val, gv, x, g_recon, want_encoder: bool, want_decoder: bool):
+        dec = self.decoder
+        return ops.train_unit_grad(offsets, entries, val, gv, x, g_recon, dec.weight.detach(), dec.n_bits,
+                                   dec.quantization_step, None, want_encoder=want_encoder, want_logits=want_decoder)
+
     # -- two batches in flight --------------------------------------------------------------------------------
     def forward_submit(self, x, slot: int = 0, want_dense: bool = True):
         """Queue one forward without waiting for the GPU anywhere: returns a handle whose ``result()`` gives
@@ -310,6 +326,7 @@ class _BinaryTrainStep(torch.autograd.Function):
     def forward(ctx, model, dense_latent, x, W_enc, b_enc, logits, b_dec):
         dec = model.decoder
         table, pol = ops.binary_soft_table_polarize(logits.detach(), dec.out_features, dec.n_bits)
+        model._train_cache.put((dec.weight,), {"table": table})
         xf = as_f32c(x.detach())
         idx, val, latent, recon = model._run(xf, dense_latent, soft_table=table)
         if model.activity is not None:

@@ -6,11 +6,13 @@ from __future__ import annotations
 import torch
 
 from .. import torch_ops as ops          # torch.ops.qsae.* (dispatcher ops over the C ABI)
-from .base import PackedCache, as_f32c
+from .base import PackedCache, as_f32c, require_device_input
 
 # forward-in-one-call entry points by the kind of decoder description (see ops._decode_prefilter_args)
 _FORWARD_PREFILTER = {"packed": ops.binary_forward_prefilter, "table": ops.table_forward_prefilter}
 _FORWARD_PREFILTER_SUBMIT = {"packed": ops.binary_forward_prefilter_submit, "table": ops.table_forward_prefilter_submit}
+#: widest top-k of forward_aux: the list width of the subset top-k kernel (qsaex_encode_topk_units)
+AUX_MAX_K = ops.ENCODE_TOPK_UNITS_MAX_K
 
 
 class TopKCore:
@@ -81,6 +83,70 @@ class TopKCore:
         """The two-call form of _forward_prefilter: -> ops.PendingForward (nothing in here waits for the GPU)."""
         return _FORWARD_PREFILTER_SUBMIT[decoder[0]](*enc, k, *decoder[1:], dec_bias, want_dense=want_dense, slot=slot,
                                                      owner=self._qsae_handle)
+
+    # -- AuxK: the listed (dead) units reconstruct on their own ---------------------------------------------------------
+    def forward_aux(self, x, units, k_aux: int):
+        """The auxiliary reconstruction ``[B, D]`` of AuxK (Gao et al. 2024), with a ``grad_fn``: every row's top-``k_aux``
+        pre-activations among the units listed in ``units`` (int32, ascending, distinct, on the device -- the tracker's
+        ``dead_indices``), decoded through the model's training table without the decoder bias.  The backward is
+        ``sparse_backward`` on that selection: encoder weight and bias and the decoder weight (logits) of the selected units get
+        a gradient; ``x``, the decoder bias and the selection get none, and there is no polarize term.  ``model.activity`` is
+        not fed: an auxiliary selection is not a firing.  An empty ``units`` gives zeros without a ``grad_fn`` and launches no
+        kernel of the library."""
+        x = require_device_input(x, "x")
+        lin = self.encoder.linear
+        H, D = lin.weight.shape
+        who = f"{type(self).__name__}.forward_aux"
+        if x.dim() != 2 or x.shape[1] != D:
+            raise ValueError(f"x is {tuple(x.shape)}, expected [batch, {D}]")
+        if not isinstance(units, torch.Tensor) or units.dtype != torch.int32 or units.dim() != 1:
+            raise ValueError(f"{who}: units must be a 1-D int32 tensor of unit ids")
+        if not units.is_cuda:
+            raise RuntimeError(f"units is on {units.device}: quantizedsae_amd computes on MI355X only and has no CPU fallback; "
+                               "move the model and the batch to a ROCm device")
+        k_aux, n = int(k_aux), units.shape[0]
+        if k_aux < 1:
+            raise ValueError(f"{who}: k_aux = {k_aux}; expected a number >= 1")
+        if k_aux > AUX_MAX_K:
+            raise ValueError(f"{who}: k_aux = {k_aux} exceeds the subset top-k kernel's limit of {AUX_MAX_K}")
+        if n == 0:
+            return torch.zeros((x.shape[0], D), dtype=torch.float32, device=x.device)
+        if k_aux > n:
+            raise ValueError(f"{who}: k_aux = {k_aux} exceeds the {n} listed units")
+        if not ops.train_supported(D, k_aux):
+            raise ValueError(f"{who}: the gradient kernels take input_dim a multiple of 4 up to 4096 (got {D})")
+        return _AuxStep.apply(self, units, k_aux, x, lin.weight, lin.bias, self._aux_decoder()[0])
+
+
+class _AuxStep(torch.autograd.Function):
+    """forward_aux and its gradient.  The model supplies ``_aux_decoder() -> (decoder parameter, table [H, D], step)`` and
+    ``_aux_unit_grad(offsets, entries, val, gv, x, g_recon, want_encoder, want_decoder)``, its unit-gradient kernel without
+    a polarize term."""
+
+    @staticmethod
+    def forward(ctx, model, units, k_aux, x, W_enc, b_enc, dec_param):
+        _, table, step = model._aux_decoder()
+        xf = as_f32c(x.detach())
+        idx, val = ops.encode_topk_units(xf, W_enc.detach(), b_enc.detach(), units, k_aux)
+        recon = ops.decode_table_sparse(idx, val, table, step, None)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(xf, idx, val, table)
+        ctx.model, ctx.step, ctx.x_dtype = model, step, x.dtype
+        return recon
+
+    @staticmethod
+    def backward(ctx, g_recon):
+        xf, idx, val, table = ctx.saved_tensors
+        model = ctx.model
+        need_W, need_b, need_dec = ctx.needs_input_grad[4:7]
+        if g_recon is None or not (need_W or need_b or need_dec):
+            return (None,) * 7
+
+        def unit_grad(offsets, entries, gv):
+            return model._aux_unit_grad(offsets, entries, val, gv, xf, g_recon, need_W or need_b, need_dec)
+        grads = sparse_backward(idx, table, ctx.step, g_recon, None, model.encoder.linear.weight, None,
+                                (False, need_W, need_b, need_dec, False), ctx.x_dtype, unit_grad)
+        return (None, None, None) + grads[:4]
 
 
 class SubmittedForward:

@@ -946,6 +946,28 @@ def _(W_enc, b_enc, dec, dead, rows, x, dec_bias, stats, report, n_bits, m_We, v
     return None
 
 
+@_op("encode_topk_units")
+def _encode_topk_units(x: Tensor, W: Tensor, bias: Optional[Tensor], units: Tensor, k: int) -> Tuple[Tensor, Tensor]:
+    """-> (idx int32 [B, k] of unit ids, val fp32 [B, k]): the top-k of the listed units' pre-activations"""
+    return _ops.encode_topk_units(x, W, bias, units, k)
+
+
+@_encode_topk_units.register_fake
+def _(x, W, bias, units, k):
+    return _i32((x.shape[0], k), x), _f32((x.shape[0], k), x)
+
+
+@_op("auxk_loss")
+def _auxk_loss(x: Tensor, recon: Tensor, aux: Tensor, coef: float) -> Tuple[Tensor, Tensor]:
+    """-> (loss fp32 0-d, grad fp32 [B, D]): the normalised auxiliary loss and its gradient at aux"""
+    return _ops.auxk_loss(x, recon, aux, coef)
+
+
+@_auxk_loss.register_fake
+def _(x, recon, aux, coef):
+    return _f32((), x), _f32(x.shape, x)
+
+
 Q = torch.ops.qsae
 
 
@@ -1529,3 +1551,16 @@ def resample_write_binary(W_enc, b_enc, dec, dead, rows, x, dec_bias, stats, rep
                           encoder_scale=0.2, logit_scale=None):
     Q.resample_write_binary(W_enc, b_enc, dec, dead, rows, x, dec_bias, stats, report, int(n_bits), *_moments(moments), last,
                             int(rows_seen), float(encoder_scale), None if logit_scale is None else float(logit_scale))
+
+
+ENCODE_TOPK_UNITS_MAX_K = _ops.ENCODE_TOPK_UNITS_MAX_K
+
+
+def encode_topk_units(x, W, bias, units, k):
+    """-> (idx int32 [B, k], val fp32 [B, k])"""
+    return Q.encode_topk_units(x, W, bias, units, int(k))
+
+
+def auxk_loss(x, recon, aux, coef):
+    """-> (loss fp32 0-d, grad fp32 [B, D])"""
+    return Q.auxk_loss(x, recon, aux, float(coef))

@@ -34,6 +34,14 @@ backward, ``trainer_loss`` the per-type loss, ``optim.Adam`` the step.  What dif
   ``resample_seed``; the default generator, and with it the loader's order, is not touched.  ``resample_scale`` is the
   encoder scale.  The report joins that step's metrics (``resampled_features``, ``resample_duplicates``, ...; one printed
   line under ``no_log``); these steps read the summary and the report back, no other step reads anything more than before.
+* ``aux_k=K`` (``baseline_sae`` and ``b_sae`` with ``activity_window`` only; default ``None`` changes nothing) adds the AuxK
+  loss of the top-k SAEs (``aux_k_loss``, csrc/auxk.hip): after the type's loss and its backward, the dead units of the
+  tracker reconstruct the residual through their own top-K (K <= 64, clamped to the number of dead units) and
+  ``aux_coef`` times the normalised error is backpropagated into the same ``.grad`` before the optimizer step.  The dead list
+  is ``summary(activity_window, dead_list=True, advance=False).dead_indices``, taken every ``aux_refresh`` steps (default
+  ``log_every``): a refresh is that summary's one host copy, between two refreshes nothing more is read back than before,
+  and a list that has gone stale in between is fine.  Logging steps gain ``aux_loss`` and ``aux_units``.  Works together with
+  ``resample_every``.
 * ``model=`` hands in the model instead of building the reference's.  The reference builds
   ``BinarySAE(input_dim, hidden_dim, n_bits)``, where ``n_bits`` lands in ``gamma`` and the decoder keeps its default of 8
   bits; that call is kept.
@@ -56,6 +64,7 @@ from ..sae.binary_latent import BinaryLatentSAE
 from .batches import ShuffledChunk
 from .loss import SAE_TYPES, trainer_loss
 from .activity import FeatureActivity, activity_line
+from .auxk import AUX_MAX_K, aux_k_loss
 from .resample import ResampleReport, resample_dead, resample_line
 from .watch import WATCH_MODES, ModelWatch, watch_line
 
@@ -92,7 +101,8 @@ class Trainer:
                  dataset_dir: str = "dataset/", save_dir: str = "SAEs/", log_fn: Optional[Callable[[dict], None]] = None,
                  log_every: int = 100, watch: Optional[str] = None, watch_freq: int = 256,
                  activity_window: Optional[int] = None, resample_every: Optional[int] = None, resample_seed: int = 0,
-                 resample_scale: float = 0.2):
+                 resample_scale: float = 0.2, aux_k: Optional[int] = None, aux_coef: float = 1 / 32,
+                 aux_refresh: Optional[int] = None):
         if sae_type not in SAE_TYPES:
             raise ValueError(f"unknown sae_type {sae_type!r}; expected one of {', '.join(SAE_TYPES)}")
         if sae_type == "t_sae" and not rigL:
@@ -114,6 +124,17 @@ class Trainer:
             if sae_type not in ("baseline_sae", "b_sae"):
                 raise ValueError(f"resample_every: resampling is built for baseline_sae and b_sae, the two top-k models; got "
                                  f"{sae_type!r}")
+        if aux_k is not None:
+            if not 1 <= int(aux_k) <= AUX_MAX_K:
+                raise ValueError(f"aux_k = {aux_k}; expected None or a number of units from 1 to {AUX_MAX_K}, the subset top-k "
+                                 "kernel's limit")
+            if activity_window is None:
+                raise ValueError("aux_k needs activity_window: the dead list comes from the activity tracker")
+            if sae_type not in ("baseline_sae", "b_sae"):
+                raise ValueError(f"aux_k: the auxiliary loss is built for baseline_sae and b_sae, the two top-k models; got "
+                                 f"{sae_type!r}")
+            if aux_refresh is not None and int(aux_refresh) < 1:
+                raise ValueError(f"aux_refresh = {aux_refresh}; expected None or a number of batches >= 1")
         self.config = config
         self.sae_type = sae_type
         self.device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
@@ -152,6 +173,10 @@ class Trainer:
         self.resample_every = int(resample_every) if resample_every is not None else None
         self.resample_scale, self._resample_seed = float(resample_scale), int(resample_seed)
         self._resample_rng = None                             # made on the first resampling step, on the model's device
+        self.aux_k = int(aux_k) if aux_k is not None else None
+        self.aux_coef = float(aux_coef)
+        self.aux_refresh = int(aux_refresh) if aux_refresh is not None else self.log_every
+        self._aux_units, self._aux_steps, self._aux_loss = None, 0, None   # the dead list in use, steps taken with it, last loss
 
     # ---- one step ------------------------------------------------------------------------------------------------
     def _forward(self, batch, want_latent: bool):
@@ -168,6 +193,8 @@ class Trainer:
         outputs = self._forward(batch, log_step)
         optimizer.zero_grad(set_to_none=True)
         losses = trainer_loss(st, outputs, batch, self.config)
+        if self.aux_k is not None:
+            self._aux_backward(batch, outputs[1])
         self._watched = self._watch.collect() if self._watch_due else None
         if st == "q_sae":
             model.decoder.apply_secant_grad()
@@ -181,6 +208,17 @@ class Trainer:
         elif st == "baseline_sae":
             model.normalize_decoder_weights()
         return outputs, losses
+
+    def _aux_backward(self, batch, recon) -> None:
+        """The AuxK term of a step: its loss over the dead list in use, backpropagated into the ``.grad`` the type's loss
+        has just filled.  The list is refreshed every ``aux_refresh`` steps (the summary's one host copy)."""
+        if self._aux_steps % self.aux_refresh == 0:
+            self._aux_units = self.activity.summary(self.activity_window, dead_list=True, advance=False).dead_indices
+        self._aux_steps += 1
+        self._aux_loss = None
+        if self._aux_units.shape[0] > 0:
+            self._aux_loss = aux_k_loss(self.model, batch, recon, self._aux_units, self.aux_k, self.aux_coef)
+            self._aux_loss.backward()
 
     # ---- metrics (logging steps only) --------------------------------------------------------------------------------------
     def _plane_magnitudes(self):
@@ -222,6 +260,12 @@ class Trainer:
             d["sparsity loss"] = sparsity
             return d
         return {"loss": lv[0]}
+
+    def _aux_metrics(self) -> dict:
+        """What a logging step adds with ``aux_k``: the step's auxiliary loss (0.0 when no unit was dead) and the length of the
+        dead list it ran over"""
+        return {"aux_loss": self._aux_loss.item() if self._aux_loss is not None else 0.0,
+                "aux_units": int(self._aux_units.shape[0])}
 
     def _activity_metrics(self, summary) -> dict:
         """What a logging step adds with ``activity_window``: the summary that ends the interval since the previous one"""
@@ -314,7 +358,10 @@ class Trainer:
                 resampled = self._resample(optimizer, batch)
             if log_step or watch_step or resampled is not None:
                 summary = self.activity.summary(self.activity_window) if (log_step and self.activity is not None) else None
-                self._log(batch_idx, self._metrics(outputs, losses) if log_step else None, self._watched, summary, resampled)
+                metrics = self._metrics(outputs, losses) if log_step else None
+                if log_step and self.aux_k is not None:
+                    metrics.update(self._aux_metrics())
+                self._log(batch_idx, metrics, self._watched, summary, resampled)
         announce(None)
         chunk.check()
         return self.model
