@@ -202,6 +202,17 @@ EXT_SIGNATURES = {
     "qsaex_auxk_loss": (_i, [_vp, _vp, _vp, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
+# name -> (restype, argtypes) of the qsaec_* entry points of include/qsae_curve.h (csrc/sparsity_curve.hip): a table of its
+# own for the same reason.  Must list every symbol declared in qsae_curve.h.
+CURVE_SIGNATURES = {
+    "qsaec_prefix_errors_binary_workspace_bytes": (_sz, [_i, _i, _i]),
+    "qsaec_prefix_errors_binary": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp,
+                                        _sz, _vp]),
+    "qsaec_prefix_errors_table_workspace_bytes": (_sz, [_i, _i, _i]),
+    "qsaec_prefix_errors_table": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _f, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz,
+                                       _vp]),
+}
+
 
 class QsaeError(RuntimeError):
     """A libqsae_hip call returned a non-zero status."""
@@ -221,7 +232,7 @@ def _open(path: Path) -> C.CDLL:
             f"{path} is missing: build it with `python -m quantizedsae_amd.build` "
             "(hipcc --offload-arch=gfx950).  quantizedsae_amd has no CPU / eager fallback.")
     lib = C.CDLL(str(path))
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(CURVE_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here means the library is stale
         fn.restype = res
         fn.argtypes = args

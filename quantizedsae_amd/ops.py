@@ -2686,3 +2686,82 @@ def auxk_loss(x: torch.Tensor, recon: torch.Tensor, aux: torch.Tensor, coef: flo
     check(lib.qsaex_auxk_loss(_p(x), _p(recon), _p(aux), B, D, float(coef), _p(loss), _p(grad), _p(sums), _p(ws), ws.numel(),
                               _stream()))
     return loss, grad
+
+
+# ---- sparsity-fidelity curve (include/qsae_curve.h) ---------------------------------------------------------------------
+PREFIX_ERRORS_MAX_K = 256
+PREFIX_ERRORS_MAX_POINTS = 16
+PREFIX_ERRORS_MAX_D = 4096
+
+
+@_on_tensor_device
+def prefix_errors(x: torch.Tensor, idx: torch.Tensor, val: torch.Tensor, ks, decoder, dec_bias: Optional[torch.Tensor],
+                  group_rows: int, sums: torch.Tensor, counts: torch.Tensor, recon_out: Optional[torch.Tensor] = None) -> None:
+    """sums fp64 [len(ks)] += the squared reconstruction error of the rows of x [B, D] at every k' of ``ks`` (ascending,
+    distinct, 0 <= k' <= K), each decoded from the first k' entries of the rank-ordered lists idx int32 / val fp32 [B, K];
+    counts int64 [2] += (rows kept, rows skipped), groups of ``group_rows`` rows holding a NaN being skipped as in
+    dataset_moments_add.  ``decoder`` = ("packed", packed uint8 [H, row_bytes], n_bits, step) or ("table", fp32 [H, D],
+    scale).  recon_out: fp32 [len(ks), B, D] that receives every point's reconstruction, or None.  Each point is bit for bit
+    the sparse decoder's result on the truncated lists.  See qsaec_prefix_errors_binary / _table."""
+    who = "prefix_errors"
+    _dev(x, f"{who}: x", torch.float32)
+    _dev(idx, f"{who}: idx", torch.int32)
+    _dev(val, f"{who}: val", torch.float32)
+    if x.dim() != 2 or idx.dim() != 2 or idx.shape != val.shape or idx.shape[0] != x.shape[0]:
+        raise ValueError(f"{who}: x is {tuple(x.shape)}, idx {tuple(idx.shape)}, val {tuple(val.shape)}; expected [B, D], [B, K], [B, K]")
+    for name, t in (("x", x), ("idx", idx), ("val", val)):
+        if not t.is_contiguous() or t.device != x.device:
+            raise ValueError(f"{who}: {name} must be contiguous and on {x.device}")
+    B, D = x.shape
+    K = idx.shape[1]
+    ks = [int(k) for k in ks]
+    n_ks = len(ks)
+    if not 1 <= n_ks <= PREFIX_ERRORS_MAX_POINTS:
+        raise ValueError(f"{who}: {n_ks} points; 1 .. {PREFIX_ERRORS_MAX_POINTS} are supported")
+    if K > PREFIX_ERRORS_MAX_K:
+        raise ValueError(f"{who}: K = {K} exceeds {PREFIX_ERRORS_MAX_K}")
+    if ks[0] < 0 or ks[-1] > K or any(b <= a for a, b in zip(ks, ks[1:])):
+        raise ValueError(f"{who}: ks = {ks} must be ascending and distinct within 0 .. K = {K}")
+    if D < 4 or D % 4 != 0 or D > PREFIX_ERRORS_MAX_D:
+        raise ValueError(f"{who}: D = {D} must be a positive multiple of 4 up to {PREFIX_ERRORS_MAX_D}")
+    group_rows = int(group_rows)
+    if group_rows < 1:
+        raise ValueError(f"{who}: group_rows must be >= 1, got {group_rows}")
+    _dev(sums, f"{who}: sums", torch.float64)
+    _dev(counts, f"{who}: counts", torch.int64)
+    if tuple(sums.shape) != (n_ks,) or tuple(counts.shape) != (2,) or not sums.is_contiguous() or not counts.is_contiguous() \
+            or sums.device != x.device or counts.device != x.device:
+        raise ValueError(f"{who}: state: expected contiguous sums fp64 [{n_ks}] and counts int64 [2] on {x.device}")
+    if recon_out is not None:
+        _dev(recon_out, f"{who}: recon_out", torch.float32)
+        if tuple(recon_out.shape) != (n_ks, B, D) or not recon_out.is_contiguous() or recon_out.device != x.device:
+            raise ValueError(f"{who}: recon_out must be a contiguous fp32 [{n_ks}, {B}, {D}] on {x.device}")
+    db = _f32c(dec_bias, "dec_bias") if dec_bias is not None else None
+    if db is not None and tuple(db.shape) != (D,):
+        raise ValueError(f"{who}: dec_bias is {tuple(db.shape)}, expected [{D}]")
+    lib = _lib.load()
+    if decoder[0] == "packed":
+        dict_t = _dev(decoder[1], f"{who}: packed", torch.uint8)
+        n_bits = int(decoder[2])
+        if not 1 <= n_bits <= 8:
+            raise ValueError(f"{who}: n_bits = {n_bits} is outside 1 .. 8")
+        if dict_t.dim() != 2 or dict_t.shape[1] != binary_row_bytes(D, n_bits) or not dict_t.is_contiguous():
+            raise ValueError(f"{who}: packed is {tuple(dict_t.shape)}, expected contiguous [H, {binary_row_bytes(D, n_bits)}]")
+        fn, size = lib.qsaec_prefix_errors_binary, lib.qsaec_prefix_errors_binary_workspace_bytes
+        dargs = (_p(dict_t), dict_t.shape[0], D, n_bits, float(decoder[3]))
+    elif decoder[0] == "table":
+        dict_t = _f32c(decoder[1], "table")
+        if dict_t.dim() != 2 or dict_t.shape[1] != D:
+            raise ValueError(f"{who}: table is {tuple(dict_t.shape)}, expected [H, {D}]")
+        fn, size = lib.qsaec_prefix_errors_table, lib.qsaec_prefix_errors_table_workspace_bytes
+        dargs = (_p(dict_t), dict_t.shape[0], D, float(decoder[2]))
+    else:
+        raise ValueError(f"{who}: decoder must be ('packed', packed, n_bits, step) or ('table', table, scale)")
+    if dict_t.device != x.device:
+        raise ValueError(f"{who}: the dictionary must be on {x.device}")
+    if B == 0:
+        return
+    ws = _workspace(x.device, max(int(size(B, n_ks, group_rows)), 16))
+    karr = (C.c_int * n_ks)(*ks)                              # the one host array: read before the call returns
+    check(fn(_p(x), _p(idx), _p(val), B, K, *dargs, _p(db), C.cast(karr, C.c_void_p), n_ks, group_rows, _p(sums), _p(counts), _p(recon_out), _p(ws),
+             ws.numel(), _stream()))

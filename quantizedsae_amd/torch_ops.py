@@ -968,6 +968,21 @@ def _(x, recon, aux, coef):
     return _f32((), x), _f32(x.shape, x)
 
 
+@_op("prefix_errors", mutates=("sums", "counts", "recon_out"))
+def _prefix_errors(x: Tensor, idx: Tensor, val: Tensor, ks: List[int], dictionary: Tensor, n_bits: int, mult: float,
+                   dec_bias: Optional[Tensor], group_rows: int, sums: Tensor, counts: Tensor,
+                   recon_out: Optional[Tensor]) -> None:
+    """sums [len(ks)], counts [2] += the squared error at every k' of ks from one top-K list; n_bits > 0: ``dictionary`` is the
+    packed n-bit one and mult its step, n_bits == 0: an fp32 table and its scale"""
+    decoder = ("packed", dictionary, n_bits, mult) if n_bits > 0 else ("table", dictionary, mult)
+    _ops.prefix_errors(x, idx, val, ks, decoder, dec_bias, group_rows, sums, counts, recon_out)
+
+
+@_prefix_errors.register_fake
+def _(x, idx, val, ks, dictionary, n_bits, mult, dec_bias, group_rows, sums, counts, recon_out):
+    return None
+
+
 Q = torch.ops.qsae
 
 
@@ -1564,3 +1579,16 @@ def encode_topk_units(x, W, bias, units, k):
 def auxk_loss(x, recon, aux, coef):
     """-> (loss fp32 0-d, grad fp32 [B, D])"""
     return Q.auxk_loss(x, recon, aux, float(coef))
+
+
+def prefix_errors(x, idx, val, ks, decoder, dec_bias, group_rows, sums, counts, recon_out=None):
+    """decoder = ("packed", packed, n_bits, step) or ("table", table, scale), as for the forward-in-one-call ops"""
+    if decoder[0] == "packed":
+        dictionary, n_bits, mult = decoder[1], int(decoder[2]), float(decoder[3])
+        if n_bits < 1:
+            raise ValueError(f"prefix_errors: n_bits = {n_bits} is outside 1 .. 8")
+    elif decoder[0] == "table":
+        dictionary, n_bits, mult = decoder[1], 0, float(decoder[2])
+    else:
+        raise ValueError("prefix_errors: decoder must be ('packed', packed, n_bits, step) or ('table', table, scale)")
+    Q.prefix_errors(x, idx, val, [int(k) for k in ks], dictionary, n_bits, mult, dec_bias, int(group_rows), sums, counts, recon_out)
