@@ -213,6 +213,20 @@ CURVE_SIGNATURES = {
                                        _vp]),
 }
 
+# name -> (restype, argtypes) of the qsaen_* entry points of include/qsae_nested.h (csrc/nested.hip): the nested-dictionary
+# objective of the top-k SAEs, a table of its own for the same reason.  Must list every symbol declared in qsae_nested.h.
+NESTED_SIGNATURES = {
+    "qsaen_decode_nested_binary": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp, _i, _vp, _vp]),
+    "qsaen_decode_nested_table": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _f, _vp, _vp, _i, _vp, _vp]),
+    "qsaen_row_grad_nested": (_i, [_vp, _i, _i, _vp, _i, _i, _f, _vp, _vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "qsaen_train_unit_grad_nested_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "qsaen_train_unit_grad_nested": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _f, _vp, _vp, _vp,
+                                          _vp, _vp, _sz, _vp]),
+    "qsaen_train_table_unit_grad_nested_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "qsaen_train_table_unit_grad_nested": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp,
+                                                _sz, _vp]),
+}
+
 
 class QsaeError(RuntimeError):
     """A libqsae_hip call returned a non-zero status."""
@@ -232,7 +246,8 @@ def _open(path: Path) -> C.CDLL:
             f"{path} is missing: build it with `python -m quantizedsae_amd.build` "
             "(hipcc --offload-arch=gfx950).  quantizedsae_amd has no CPU / eager fallback.")
     lib = C.CDLL(str(path))
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(CURVE_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(CURVE_SIGNATURES.items()) \
+            + list(NESTED_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here means the library is stale
         fn.restype = res
         fn.argtypes = args

@@ -1,0 +1,411 @@
+// nested.hip -- the nested-dictionary (Matryoshka) objective of the top-k SAEs (include/qsae_nested.h): one reconstruction per
+// dictionary prefix from ONE walk over a row's list, and the gradient of a loss that sums over the prefixes.
+//
+// Forward.  The sparse decoders sum a row's entries as one fmaf chain in ascending unit index (decode_row.h), so the
+// reconstruction from the units below a bound is a prefix of that chain.  One wave per activation row sorts the k pairs by unit
+// id in LDS (ids outside the dictionary are dropped there), counts the entries below every bound -- wave-uniform numbers -- and
+// runs the chain ONCE per column group: when the walk reaches the count of a level, the accumulator is scaled, biased and stored
+// as that level's row, and the chain goes on from the same registers.  Every dictionary row is gathered once, whatever the number
+// of levels; no accumulator is indexed at run time.  The list reaches the lanes through LDS broadcasts, not through v_readlane,
+// so a lane that owns no column may leave the walk (the hazard of decode_row_sorted_wide does not arise).
+//
+// Backward.  The gradient that reaches the dictionary row of unit h is the sum of the level gradients from level(h) on:
+// G[l] = g[l] + G[l + 1].  nested_row_kernel writes these suffix sums for its row and then is train_row_kernel (train.hip) with
+// g_recon = G[level(h)] per entry; a lane reads back only the columns it wrote itself.  The unit sums are the kernels of
+// train.hip with the same lookup (unit_levels.h).
+#include "common.h"
+#include "csr_lists.h"
+#include "unit_levels.h"
+#include "../../include/qsae_nested.h"
+
+namespace qsae {
+
+constexpr int kNestedWaves = 4;           // activation rows of a workgroup
+constexpr int kNestedMaxK = QSAEN_MAX_K;
+constexpr int kNestedDropped = -1;        // "this id is outside the dictionary"
+static_assert(kMaxLevels == QSAEN_MAX_LEVELS, "unit_levels.h and qsae_nested.h name the same limit");
+
+typedef float nd_f32x4 __attribute__((ext_vector_type(4)));
+
+struct NestedDict {
+    const uint32_t* packed;   // [H][row_dwords] n-bit fields (qsae_pack_binary), or
+    const float* table;       // [H][D] fp32, 16-byte aligned
+    int row_dwords, n, D;
+    float mult;               // packed: step; table: scale
+};
+
+// MODE 0: fp32 table, a lane owns 4 columns; 1, 2, 4, 8: the field width of the packed dictionary, a lane owns one dword of the
+// packed row = 32 / MODE columns.
+template <int MODE> constexpr int kNestedCols = MODE == 0 ? 4 : 32 / MODE;
+template <int MODE> constexpr int kNestedInFlight = MODE == 0 ? 4 : 8;      // dictionary rows in flight per lane
+template <int MODE> struct NestedRaw { uint32_t w; };
+template <> struct NestedRaw<0> { nd_f32x4 w; };
+
+template <int MODE>
+__device__ __forceinline__ NestedRaw<MODE> nested_load(const NestedDict& d, int h, int c) {
+    NestedRaw<MODE> r;
+    if constexpr (MODE == 0) r.w = *reinterpret_cast<const nd_f32x4*>(d.table + static_cast<long long>(h) * d.D + 4 * c);
+    else r.w = d.packed[static_cast<long long>(h) * d.row_dwords + c];
+    return r;
+}
+
+template <int MODE>
+__device__ __forceinline__ void nested_take(float (&acc)[kNestedCols<MODE>], float a, const NestedRaw<MODE>& r, int n) {
+#pragma unroll
+    for (int f = 0; f < kNestedCols<MODE>; ++f) {
+        if constexpr (MODE == 0) acc[f] = fmaf(a, r.w[f], acc[f]);
+        else acc[f] = fmaf(a, static_cast<float>(sbfe_i32(static_cast<int>(r.w), f * MODE, n)), acc[f]);
+    }
+}
+
+// recon [lv.n][B][D]
+template <int MODE>
+__global__ void __launch_bounds__(64 * kNestedWaves)
+nested_decode_kernel(const int32_t* __restrict__ idx, const float* __restrict__ val, int B, int k, int H, NestedDict d,
+                     const float* __restrict__ bias, UnitLevels lv, float* __restrict__ recon) {
+    __shared__ int s_idx[kNestedWaves][kNestedMaxK];      // the kept entries, ascending unit id
+    __shared__ float s_val[kNestedWaves][kNestedMaxK];
+    __shared__ int t_idx[kNestedWaves][kNestedMaxK];      // list order; kNestedDropped for an id outside [0, H)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long row = static_cast<long long>(blockIdx.x) * kNestedWaves + wave;
+    const bool active = row < B;
+    const long long off = row * k;
+    if (active) {
+        for (int j = lane; j < k; j += 64) {
+            const int h = idx[off + j];
+            t_idx[wave][j] = (h >= 0 && h < H) ? h : kNestedDropped;
+        }
+    }
+    __syncthreads();
+    // Every lane ranks its (up to 4) entries in ONE pass over the list: rank = kept entries with a smaller (id, position).
+    // The same pass counts the kept entries below every bound; every lane sees the whole list, so the counts are wave-uniform.
+    int cnt[kMaxLevels];
+#pragma unroll
+    for (int l = 0; l < kMaxLevels; ++l) cnt[l] = 0;
+    if (active) {
+        constexpr int Q = kNestedMaxK / 64;
+        int mine[Q], rank[Q];
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            const int j = lane + 64 * q;
+            mine[q] = j < k ? t_idx[wave][j] : kNestedDropped;
+            rank[q] = 0;
+        }
+#pragma unroll 4
+        for (int i = 0; i < k; ++i) {
+            const int o = t_idx[wave][i];
+            const bool kept = o != kNestedDropped;
+#pragma unroll
+            for (int l = 0; l < kMaxLevels; ++l) cnt[l] += (kept && l < lv.n && o < lv.bounds[l]) ? 1 : 0;
+#pragma unroll
+            for (int q = 0; q < Q; ++q) rank[q] += (kept && (o < mine[q] || (o == mine[q] && i < lane + 64 * q))) ? 1 : 0;
+        }
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            if (mine[q] != kNestedDropped) {
+                s_idx[wave][rank[q]] = mine[q];
+                s_val[wave][rank[q]] = val[off + lane + 64 * q];
+            }
+        }
+#pragma unroll
+        for (int l = 0; l < kMaxLevels; ++l) cnt[l] = __builtin_amdgcn_readfirstlane(cnt[l]);
+    }
+    __syncthreads();
+    if (!active) return;
+
+    constexpr int F = kNestedCols<MODE>, U = kNestedInFlight<MODE>;
+    const int D = d.D;
+    const int groups = MODE == 0 ? D / 4 : d.row_dwords;   // column groups of a row: one per lane and round
+    const bool mul = MODE != 0 || d.mult != 1.0f;         // the table decode skips `* 1`, the packed one never does
+    const long long level_stride = static_cast<long long>(B) * D;
+    for (int c = lane; c < groups; c += 64) {
+        float acc[F], bv[F];
+#pragma unroll
+        for (int f = 0; f < F; ++f) {
+            acc[f] = 0.0f;
+            const int col = c * F + f;
+            bv[f] = (bias && col < D) ? bias[col] : 0.0f;
+        }
+        float* out = recon + row * D + c * F;
+        int e = 0;
+#pragma unroll
+        for (int l = 0; l < kMaxLevels; ++l) {
+            if (l < lv.n) {                                // wave-uniform, like the counts
+                const int end = cnt[l];
+                for (; e + U <= end; e += U) {            // a chunk's loads are issued before the first is consumed
+                    NestedRaw<MODE> raw[U];
+                    float a[U];
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        raw[u] = nested_load<MODE>(d, s_idx[wave][e + u], c);
+                        a[u] = s_val[wave][e + u];
+                    }
+#pragma unroll
+                    for (int u = 0; u < U; ++u) nested_take<MODE>(acc, a[u], raw[u], d.n);
+                }
+                for (; e < end; ++e) nested_take<MODE>(acc, s_val[wave][e], nested_load<MODE>(d, s_idx[wave][e], c), d.n);
+                // the snapshot of level l: rounded multiply, then rounded add (binary.py:38); the chain goes on from acc
+                float* o = out + l * level_stride;
+                if constexpr (MODE == 0) {
+                    nd_f32x4 v;
+#pragma unroll
+                    for (int f = 0; f < 4; ++f) {
+                        const float r = mul ? d.mult * acc[f] : acc[f];
+                        v[f] = r + bv[f];
+                    }
+                    *reinterpret_cast<nd_f32x4*>(o) = v;
+                } else {
+#pragma unroll
+                    for (int f = 0; f < F; ++f) {
+                        const float r = d.mult * acc[f];
+                        if (c * F + f < D) o[f] = r + bv[f];
+                    }
+                }
+            }
+        }
+    }
+}
+
+// ---- row kernel: the suffix sums G, then gv and dx as train_row_kernel computes them --------------------------------------
+struct LevelGrads { const float* p[kMaxLevels]; };          // g[l] [B][D] or nullptr
+
+__device__ __forceinline__ nd_f32x4 nd_ld4(const float* p) { return *reinterpret_cast<const nd_f32x4*>(p); }
+__device__ __forceinline__ void nd_st4(float* p, nd_f32x4 v) { *reinterpret_cast<nd_f32x4*>(p) = v; }
+
+// One wave per row, four rows per workgroup; lane l owns columns 4 (l + 64 i) .. + 3 in every phase, so the G it reads in the
+// dot products is the G it stored.  G is read and written through the same pointer: no __restrict__ on it.
+__global__ void __launch_bounds__(64 * kNestedWaves)
+nested_row_kernel(const int32_t* __restrict__ idx, int B, int k, int H, int D, const float* __restrict__ table, float step,
+                  LevelGrads gl, UnitLevels lv, const float* __restrict__ gL, long long gl_ld, const float* __restrict__ Wenc,
+                  float* G, float* __restrict__ gv, float* __restrict__ dx) {
+    __shared__ int s_h[kNestedWaves][kNestedMaxK];
+    __shared__ int s_l[kNestedWaves][kNestedMaxK];
+    __shared__ float s_g[kNestedWaves][kNestedMaxK];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r = blockIdx.x * kNestedWaves + wave;
+    const bool active = r < B;
+    const int D4 = D / 4;
+    if (active) {
+        for (int j = lane; j < k; j += 64) {
+            const int h = clamp_unit(idx[static_cast<long long>(r) * k + j], H);
+            s_h[wave][j] = h;
+            s_l[wave][j] = unit_level(lv, h);
+        }
+        for (int c = lane; c < D4; c += 64) {
+            nd_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            bool have = false;
+#pragma unroll
+            for (int l = kMaxLevels - 1; l >= 0; --l) {
+                if (l < lv.n) {
+                    const float* g = gl.p[l];
+                    if (g) {                               // an absent level is skipped, not added as zero
+                        const nd_f32x4 v = nd_ld4(g + static_cast<long long>(r) * D + 4 * c);
+                        acc = have ? v + acc : v;
+                        have = true;
+                    }
+                    nd_st4(G + (static_cast<long long>(l) * B + r) * D + 4 * c, acc);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (active) {
+        for (int j0 = 0; j0 < k; j0 += 4) {
+            float part[4] = {0.f, 0.f, 0.f, 0.f};
+            int hh[4];
+            const float* g[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int j = min(j0 + u, k - 1);
+                hh[u] = s_h[wave][j];
+                g[u] = G + (static_cast<long long>(s_l[wave][j]) * B + r) * D;
+            }
+            for (int c = lane; c < D4; c += 64) {
+                nd_f32x4 a[4], t[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    a[u] = nd_ld4(g[u] + 4 * c);
+                    t[u] = nd_ld4(table + static_cast<long long>(hh[u]) * D + 4 * c);
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) part[u] = fmaf(a[u][e], t[u][e], part[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                for (int off = 32; off > 0; off >>= 1) part[u] += __shfl_xor(part[u], off, 64);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int j = j0 + u;
+                if (j < k) {
+                    float v = step * part[u];
+                    if (gL) v = gL[static_cast<long long>(r) * gl_ld + s_h[wave][j]] + v;
+                    if (lane == 0) {
+                        gv[static_cast<long long>(r) * k + j] = v;
+                        s_g[wave][j] = v;
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (active && dx) {
+        for (int c = lane; c < D4; c += 64) {
+            nd_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            for (int j = 0; j < k; ++j) {
+                const nd_f32x4 w = nd_ld4(Wenc + static_cast<long long>(s_h[wave][j]) * D + 4 * c);
+                const float a = s_g[wave][j];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[e] = fmaf(a, w[e], acc[e]);
+            }
+            nd_st4(dx + static_cast<long long>(r) * D + 4 * c, acc);
+        }
+    }
+}
+
+// ---- the checks every entry point shares, in the order the header states ---------------------------------------------------
+inline bool nested_misaligned(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+
+// limits (from the sizes alone), then the host array bounds -> lv
+static int nested_limits(const char* who, int B, int k, int H, int D, bool packed, int n_bits, const int* bounds, int n_levels,
+                         UnitLevels* lv) {
+    if (B < 0 || H < 1) return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: B >= 0 and H >= 1 required", who);
+    if (n_levels < 1 || n_levels > kMaxLevels) return fail(QSAE_ERR_UNSUPPORTED, "%s: unsupported: 1 <= n_levels <= 8", who);
+    if (k < 0 || k > kNestedMaxK) return fail(QSAE_ERR_UNSUPPORTED, "%s: unsupported: 0 <= k <= 256", who);
+    if (D < 4 || D % 4 != 0 || D > QSAEN_MAX_D) return fail(QSAE_ERR_UNSUPPORTED, "%s: unsupported: D a positive multiple of 4 up to 4096", who);
+    if (packed && (n_bits < 1 || n_bits > 8)) return fail(QSAE_ERR_UNSUPPORTED, "%s: unsupported: 1 <= n_bits <= 8", who);
+    if (static_cast<long long>(B) * k >= (1LL << 31)) return fail(QSAE_ERR_UNSUPPORTED, "%s: unsupported: B * k < 2^31", who);
+    if (!bounds) return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: bounds is null", who);
+    lv->stride = static_cast<long long>(B) * D;
+    lv->n = n_levels;
+    for (int i = 0; i < kMaxLevels; ++i) lv->bounds[i] = i < n_levels ? bounds[i] : 0;
+    for (int i = 0; i < n_levels; ++i)
+        if (bounds[i] <= (i > 0 ? bounds[i - 1] : 0))
+            return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: 0 < bounds[0] < ... < bounds[n_levels - 1] == H required", who);
+    if (bounds[n_levels - 1] != H)
+        return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: 0 < bounds[0] < ... < bounds[n_levels - 1] == H required", who);
+    return QSAE_OK;
+}
+
+static int decode_nested(const char* who, const int32_t* idx, const float* val, int B, int k, NestedDict d, int H,
+                         const float* bias, const int* bounds, int n_levels, float* recon, qsae_stream_t stream) {
+    const bool packed = d.table == nullptr && d.n != 0;
+    UnitLevels lv;
+    if (const int rc = nested_limits(who, B, k, H, d.D, packed, d.n, bounds, n_levels, &lv); rc != QSAE_OK) return rc;
+    if (B == 0) return QSAE_OK;
+    if (!recon || (k > 0 && (!idx || !val)) || (!d.packed && !d.table))
+        return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: null pointer", who);
+    if (nested_misaligned(idx, 4) || nested_misaligned(val, 4) || nested_misaligned(bias, 4) || nested_misaligned(recon, 16) ||
+        nested_misaligned(d.packed, 4) || nested_misaligned(d.table, 16))
+        return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: a pointer is not aligned as the header asks", who);
+    hipStream_t s = as_stream(stream);
+    const dim3 grid(static_cast<unsigned>((static_cast<long long>(B) + kNestedWaves - 1) / kNestedWaves)), block(64 * kNestedWaves);
+    switch (packed ? field_width(d.n) : 0) {
+        case 0: hipLaunchKernelGGL(nested_decode_kernel<0>, grid, block, 0, s, idx, val, B, k, H, d, bias, lv, recon); break;
+        case 1: hipLaunchKernelGGL(nested_decode_kernel<1>, grid, block, 0, s, idx, val, B, k, H, d, bias, lv, recon); break;
+        case 2: hipLaunchKernelGGL(nested_decode_kernel<2>, grid, block, 0, s, idx, val, B, k, H, d, bias, lv, recon); break;
+        case 4: hipLaunchKernelGGL(nested_decode_kernel<4>, grid, block, 0, s, idx, val, B, k, H, d, bias, lv, recon); break;
+        default: hipLaunchKernelGGL(nested_decode_kernel<8>, grid, block, 0, s, idx, val, B, k, H, d, bias, lv, recon); break;
+    }
+    QSAE_LAUNCH_CHECK();
+    return QSAE_OK;
+}
+
+}  // namespace qsae
+
+using namespace qsae;
+
+extern "C" int qsaen_decode_nested_binary(const int32_t* idx, const float* val, int B, int k, const uint8_t* packed, int H, int D,
+                                          int n_bits, float step, const float* dec_bias, const int* bounds, int n_levels,
+                                          float* recon, qsae_stream_t stream) {
+    const bool bits_ok = n_bits >= 1 && n_bits <= 8;
+    // n == 0 marks the table form, so a refused n_bits travels as -1
+    const NestedDict d{reinterpret_cast<const uint32_t*>(packed), nullptr,
+                       (bits_ok && D > 0 && D <= QSAEN_MAX_D) ? (D * field_width(n_bits) + 31) / 32 : 0,    // qsae_binary_row_bytes / 4
+                       bits_ok ? n_bits : -1, D, step};
+    return decode_nested(__func__, idx, val, B, k, d, H, dec_bias, bounds, n_levels, recon, stream);
+}
+
+extern "C" int qsaen_decode_nested_table(const int32_t* idx, const float* val, int B, int k, const float* table, int H, int D,
+                                         float scale, const float* dec_bias, const int* bounds, int n_levels, float* recon,
+                                         qsae_stream_t stream) {
+    const NestedDict d{nullptr, table, 0, 0, D, scale};
+    return decode_nested(__func__, idx, val, B, k, d, H, dec_bias, bounds, n_levels, recon, stream);
+}
+
+extern "C" int qsaen_row_grad_nested(const int32_t* idx, int B, int k, const float* table, int H, int D, float step,
+                                     const float* const* g_levels, const int* bounds, int n_levels, const float* g_latent,
+                                     int64_t g_latent_ld, const float* W_enc, float* G, float* gv, float* dx,
+                                     qsae_stream_t stream) {
+    UnitLevels lv;
+    if (const int rc = nested_limits(__func__, B, k, H, D, false, 0, bounds, n_levels, &lv); rc != QSAE_OK) return rc;
+    QSAE_CHECK_ARG(g_levels != nullptr, "g_levels is null");
+    LevelGrads gl;
+    for (int l = 0; l < kMaxLevels; ++l) gl.p[l] = l < n_levels ? g_levels[l] : nullptr;
+    if (B == 0) return QSAE_OK;
+    QSAE_CHECK_ARG(table && G && (k == 0 || (idx && gv)), "null pointer");
+    QSAE_CHECK_ARG(!dx || W_enc, "dx needs W_enc");
+    bool g_ok = true;
+    for (int l = 0; l < kMaxLevels; ++l) g_ok = g_ok && aligned16(gl.p[l]);
+    QSAE_CHECK_ARG(g_ok && aligned16(table) && aligned16(G) && (!dx || (aligned16(dx) && aligned16(W_enc))),
+                   "table, g_levels, G, W_enc and dx must be 16-byte aligned");
+    QSAE_CHECK_ARG(!nested_misaligned(idx, 4) && !nested_misaligned(gv, 4) && !nested_misaligned(g_latent, 4),
+                   "idx, gv and g_latent must be 4-byte aligned");
+    QSAE_CHECK_ARG(!g_latent || g_latent_ld >= 0, "g_latent_ld >= 0 required");
+    hipLaunchKernelGGL(nested_row_kernel, dim3((B + kNestedWaves - 1) / kNestedWaves), dim3(64 * kNestedWaves), 0,
+                       as_stream(stream), idx, B, k, H, D, table, step, gl, lv, g_latent, static_cast<long long>(g_latent_ld),
+                       W_enc, G, gv, dx);
+    QSAE_LAUNCH_CHECK();
+    return QSAE_OK;
+}
+
+extern "C" size_t qsaen_train_unit_grad_nested_workspace_bytes(int B, int k, int H, int D) {
+    if (k > kNestedMaxK || static_cast<long long>(B) * k >= (1LL << 31)) return 0;
+    return qsae_train_unit_grad_workspace_bytes(B, k, H, D);
+}
+
+extern "C" size_t qsaen_train_table_unit_grad_nested_workspace_bytes(int B, int k, int H, int D) {
+    return qsae_train_table_unit_grad_workspace_bytes(B, k, H, D);
+}
+
+extern "C" int qsaen_train_unit_grad_nested(const int32_t* offsets, const int32_t* entries, const float* val, const float* gv,
+                                            int B, int k, const float* x, const float* G, const int* bounds, int n_levels,
+                                            const float* logits, int H, int D, int n_bits, float step, const float* g_polarize,
+                                            float* dW_enc, float* db_enc, float* dlogits, void* workspace,
+                                            size_t workspace_bytes, qsae_stream_t stream) {
+    UnitLevels lv;
+    if (const int rc = nested_limits(__func__, B, k, H, D, true, n_bits, bounds, n_levels, &lv); rc != QSAE_OK) return rc;
+    const long long Bk = static_cast<long long>(B) * k;
+    QSAE_CHECK_ARG(offsets != nullptr, "null pointer");
+    QSAE_CHECK_ARG(Bk == 0 || (entries && val && gv && x), "null pointer");
+    QSAE_CHECK_ARG(!dlogits || logits, "dlogits needs logits");
+    QSAE_CHECK_ARG((!x || aligned16(x)) && aligned16(G) && (!dW_enc || aligned16(dW_enc)) &&
+                   (!dlogits || (aligned16(dlogits) && aligned16(logits))),
+                   "x, G, logits, dW_enc and dlogits must be 16-byte aligned");
+    if (!workspace || workspace_bytes < qsaen_train_unit_grad_nested_workspace_bytes(B, k, H, D))
+        return fail(QSAE_ERR_WORKSPACE, "%s: workspace missing or smaller than the sizer's bytes", __func__);
+    QSAE_HIP(train_unit_grad_levels(offsets, entries, val, gv, B, k, x, G, lv, logits, H, D, n_bits, step, g_polarize, dW_enc,
+                                    db_enc, dlogits, workspace, as_stream(stream)));
+    return QSAE_OK;
+}
+
+extern "C" int qsaen_train_table_unit_grad_nested(const int32_t* offsets, const int32_t* entries, const float* val,
+                                                  const float* gv, int B, int k, const float* x, const float* G,
+                                                  const int* bounds, int n_levels, int H, int D, float* dW_enc, float* db_enc,
+                                                  float* dW_dec, int64_t dW_dec_ld, void* workspace, size_t workspace_bytes,
+                                                  qsae_stream_t stream) {
+    UnitLevels lv;
+    if (const int rc = nested_limits(__func__, B, k, H, D, false, 0, bounds, n_levels, &lv); rc != QSAE_OK) return rc;
+    const long long Bk = static_cast<long long>(B) * k;
+    QSAE_CHECK_ARG(offsets != nullptr, "null pointer");
+    QSAE_CHECK_ARG(Bk == 0 || (entries && val && gv && x), "null pointer");
+    QSAE_CHECK_ARG(!dW_dec || dW_dec_ld >= H, "dW_dec_ld >= H required");
+    QSAE_CHECK_ARG((!x || aligned16(x)) && aligned16(G) && (!dW_enc || aligned16(dW_enc)),
+                   "x, G and dW_enc must be 16-byte aligned");
+    if (!workspace || workspace_bytes < qsaen_train_table_unit_grad_nested_workspace_bytes(B, k, H, D))
+        return fail(QSAE_ERR_WORKSPACE, "%s: workspace missing or smaller than the sizer's bytes", __func__);
+    QSAE_HIP(train_table_unit_grad_levels(offsets, entries, val, gv, B, k, x, G, lv, H, D, dW_enc, db_enc, dW_dec,
+                                          static_cast<long long>(dW_dec_ld), workspace, as_stream(stream)));
+    return QSAE_OK;
+}

@@ -20,6 +20,7 @@
 // integer ORs that mark (unit, row) pairs in the CSR build, whose result does not depend on their order.
 #include "common.h"
 #include "csr_lists.h"
+#include "unit_levels.h"
 
 namespace qsae {
 
@@ -195,6 +196,7 @@ struct UnitArgs {
     float* slab;            // [slab_rows][slab_ld]: partials of the chunks of split lists
     int slab_rows, slab_ld;
     float* dT;              // TABLE instantiation: [H][D] = sum v gR (the decoder.weight gradient, transposed) or nullptr
+    UnitLevels lv;          // lv.n > 0: gR is [lv.n][B][D] and unit h reads level unit_level(lv, h) of it (qsae_nested.h)
 };
 
 // dlogit row h from s_dint[D] (dInt, step applied); the whole workgroup calls it
@@ -253,13 +255,15 @@ unit_chunk_kernel(UnitArgs a) {
     const int row = 2 * (a.chunk_off[h] - h) + c;          // slab row of a split list's chunk (< slab_rows, see host)
     const bool split = nch > 1;
     float* srow = (split && row < a.slab_rows) ? a.slab + static_cast<long long>(row) * a.slab_ld : nullptr;
+    // the gradient tensor of this unit (workgroup-uniform): a.gR itself unless the call names levels
+    const float* gR = (a.gR && a.lv.n > 0) ? a.gR + unit_level(a.lv, h) * a.lv.stride : a.gR;
     for (int c4 = threadIdx.x; c4 < D4; c4 += blockDim.x) {
         tr_f32x4 w = {0.f, 0.f, 0.f, 0.f}, s = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
         for (int i = 0; i < len; ++i) {
             const long long ro = static_cast<long long>(s_r[i]) * D + 4 * c4;
             if (a.x) w = fma4(s_gv[i], ld4(a.x + ro), w);
-            if (a.gR) s = fma4(s_v[i], ld4(a.gR + ro), s);
+            if (gR) s = fma4(s_v[i], ld4(gR + ro), s);
         }
         if (!split) {
             if (a.dW) st4(a.dW + static_cast<long long>(h) * D + 4 * c4, w);
@@ -909,6 +913,69 @@ extern "C" int qsae_train_table_unit_grad(const int32_t* offsets, const int32_t*
     }
     return QSAE_OK;
 }
+
+// The two unit-gradient calls above with one gradient tensor per dictionary prefix (unit_levels.h; the checks are the
+// caller's, csrc/nested.hip): the same kernels, the same workspace layout, g_recon = G[level(h)] for unit h.
+namespace qsae {
+static UnitArgs unit_args_levels(const int32_t* offsets, const int32_t* entries, const float* val, const float* gv, int B, int k,
+                                 const float* x, const float* G, const UnitLevels& lv, int H, int D) {
+    const long long Bk = static_cast<long long>(B) * k;
+    UnitArgs a{};
+    a.offsets = offsets;
+    a.entries = entries;
+    a.val = val;
+    a.gv = gv;
+    a.Bk = Bk;
+    a.k = k > 0 ? k : 1;
+    a.H = H;
+    a.D = D;
+    a.x = x;
+    a.gR = Bk > 0 ? G : nullptr;
+    a.lv = lv;
+    return a;
+}
+
+hipError_t train_unit_grad_levels(const int32_t* offsets, const int32_t* entries, const float* val, const float* gv, int B, int k,
+                                  const float* x, const float* G, const UnitLevels& lv, const float* logits, int H, int D,
+                                  int n_bits, float step, const float* g_polarize, float* dW_enc, float* db_enc, float* dlogits,
+                                  void* workspace, hipStream_t s) {
+    UnitArgs a = unit_args_levels(offsets, entries, val, gv, B, k, x, G, lv, H, D);
+    a.n = n_bits;
+    a.logits = logits;
+    a.step = step;
+    a.gP = g_polarize;
+    a.pol_count = static_cast<double>(H) * D * n_bits;
+    a.dW = dW_enc;
+    a.db = db_enc;
+    a.dlogit = dlogits;
+    return launch_unit_sums<false>(a, a.Bk, static_cast<char*>(workspace), unit_layout(a.Bk, H, D), s);
+}
+
+hipError_t train_table_unit_grad_levels(const int32_t* offsets, const int32_t* entries, const float* val, const float* gv, int B,
+                                        int k, const float* x, const float* G, const UnitLevels& lv, int H, int D, float* dW_enc,
+                                        float* db_enc, float* dW_dec, long long dW_dec_ld, void* workspace, hipStream_t s) {
+    UnitArgs a = unit_args_levels(offsets, entries, val, gv, B, k, x, G, lv, H, D);
+    const UnitLayout L = unit_layout(a.Bk, H, D);
+    char* ws = static_cast<char*>(workspace);
+    float* dT = (dW_dec && a.gR) ? reinterpret_cast<float*>(ws + L.total) : nullptr;
+    if (dW_enc || db_enc || dT) {
+        a.n = 1;
+        a.step = 1.0f;
+        a.pol_count = 1.0;
+        a.dW = dW_enc;
+        a.db = db_enc;
+        a.dT = dT;
+        if (hipError_t e = launch_unit_sums<true>(a, a.Bk, ws, L, s); e != hipSuccess) return e;
+    }
+    if (dW_dec) {
+        const int vec = (dW_dec_ld % 4 == 0 && aligned16(dW_dec)) ? 1 : 0;
+        const dim3 grid((H + kTrTile - 1) / kTrTile, (D + kTrTile * kTrTilesD - 1) / (kTrTile * kTrTilesD));
+        hipLaunchKernelGGL(transpose_rows_kernel<false>, grid, dim3(256), 0, s, dT, H, D, dW_dec, dW_dec_ld, vec);
+        return hipGetLastError();
+    }
+    return hipSuccess;
+}
+}  // namespace qsae
 
 extern "C" int qsae_normalize_columns_table(float* W, int D, int H, float* table, qsae_stream_t stream) {
     QSAE_CHECK_ARG(D >= 1 && H >= 1, "D >= 1 and H >= 1 required");

@@ -28,6 +28,7 @@ from .evaluation import (  # noqa: F401,E402
     quantization_error,
 )
 from .sparsity_curve import SparsityCurve, default_ks, sparsity_curve  # noqa: F401,E402
+from .nested import nested_errors  # noqa: F401,E402
 from .summary import (  # noqa: F401,E402
     average_coactivating_features,
     count_below_threshold,

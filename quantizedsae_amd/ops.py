@@ -2765,3 +2765,200 @@ def prefix_errors(x: torch.Tensor, idx: torch.Tensor, val: torch.Tensor, ks, dec
     karr = (C.c_int * n_ks)(*ks)                              # the one host array: read before the call returns
     check(fn(_p(x), _p(idx), _p(val), B, K, *dargs, _p(db), C.cast(karr, C.c_void_p), n_ks, group_rows, _p(sums), _p(counts), _p(recon_out), _p(ws),
              ws.numel(), _stream()))
+
+
+# ---- nested-dictionary (Matryoshka) objective of the top-k SAEs (include/qsae_nested.h, csrc/nested.hip) --------------------
+NESTED_MAX_LEVELS = 8
+
+
+def nested_bounds(bounds, H: int, who: str = "nested_bounds"):
+    """``bounds`` as a list of ints after the checks of qsae_nested.h: 1 .. 8 levels, 0 < bounds[0] < ... < bounds[-1] == H."""
+    try:
+        out = [int(b) for b in bounds]
+    except TypeError:
+        raise ValueError(f"{who}: bounds must be a sequence of ints, got {bounds!r}") from None
+    if any(isinstance(b, bool) or int(b) != b for b in bounds):
+        raise ValueError(f"{who}: bounds must be whole numbers, got {list(bounds)!r}")
+    if not 1 <= len(out) <= NESTED_MAX_LEVELS:
+        raise ValueError(f"{who}: {len(out)} levels; 1 .. {NESTED_MAX_LEVELS} are supported")
+    if out[0] < 1 or any(b <= a for a, b in zip(out, out[1:])) or out[-1] != int(H):
+        raise ValueError(f"{who}: bounds = {out} must be ascending and distinct, start above 0 and end at hidden_dim = {int(H)}")
+    return out
+
+
+def _bounds_arg(bounds):
+    return C.cast((C.c_int * len(bounds))(*bounds), C.c_void_p)      # a host array: read before the call returns
+
+
+def _nested_lists(who: str, idx, val):
+    _dev(idx, f"{who}: idx", torch.int32)
+    _dev(val, f"{who}: val", torch.float32)
+    if idx.dim() != 2 or idx.shape != val.shape or val.device != idx.device:
+        raise ValueError(f"{who}: idx is {tuple(idx.shape)}, val {tuple(val.shape)}; expected two [B, k] tensors on one device")
+    if idx.shape[1] > TRAIN_MAX_K:
+        raise ValueError(f"{who}: k = {idx.shape[1]} exceeds {TRAIN_MAX_K}")
+    return idx.contiguous(), val.contiguous()
+
+
+def _nested_D(who: str, D: int) -> None:
+    if D < 4 or D % 4 != 0 or D > TRAIN_MAX_D:
+        raise ValueError(f"{who}: D = {D} must be a positive multiple of 4 up to {TRAIN_MAX_D}")
+
+
+@_on_tensor_device
+def decode_nested_binary(idx, val, packed, D: int, n_bits: int, step: float, bias, bounds) -> torch.Tensor:
+    """-> fp32 [L, B, D]: level l is decode_binary_sparse on the lists without the entries of units >= bounds[l], bit for bit,
+    all levels from one walk over each row's list; see qsaen_decode_nested_binary."""
+    who = "decode_nested_binary"
+    idx, val = _nested_lists(who, idx, val)
+    _dev(packed, f"{who}: packed", torch.uint8)
+    D, n_bits = int(D), int(n_bits)
+    _nested_D(who, D)
+    if not 1 <= n_bits <= 8:
+        raise ValueError(f"{who}: n_bits = {n_bits} is outside 1 .. 8")
+    if packed.dim() != 2 or packed.shape[1] != binary_row_bytes(D, n_bits) or not packed.is_contiguous() or packed.device != idx.device:
+        raise ValueError(f"{who}: packed is {tuple(packed.shape)}, expected contiguous [H, {binary_row_bytes(D, n_bits)}] on {idx.device}")
+    H = packed.shape[0]
+    bounds = nested_bounds(bounds, H, who)
+    b = _f32c(bias, "bias") if bias is not None else None
+    if b is not None and tuple(b.shape) != (D,):
+        raise ValueError(f"{who}: bias is {tuple(b.shape)}, expected [{D}]")
+    B, k = idx.shape
+    recon = torch.empty((len(bounds), B, D), dtype=torch.float32, device=idx.device)
+    check(_lib.load().qsaen_decode_nested_binary(_p(idx), _p(val), B, k, _p(packed), H, D, n_bits, float(step), _p(b),
+                                                 _bounds_arg(bounds), len(bounds), _p(recon), _stream()))
+    return recon
+
+
+@_on_tensor_device
+def decode_nested_table(idx, val, table: torch.Tensor, scale: float, bias, bounds) -> torch.Tensor:
+    """-> fp32 [L, B, D]: level l is decode_table_sparse on the lists without the entries of units >= bounds[l], bit for bit;
+    see qsaen_decode_nested_table."""
+    who = "decode_nested_table"
+    idx, val = _nested_lists(who, idx, val)
+    table = _f32c(table, "table")
+    if table.dim() != 2 or table.device != idx.device:
+        raise ValueError(f"{who}: table is {tuple(table.shape)} on {table.device}, expected [H, D] on {idx.device}")
+    H, D = table.shape
+    _nested_D(who, D)
+    bounds = nested_bounds(bounds, H, who)
+    b = _f32c(bias, "bias") if bias is not None else None
+    if b is not None and tuple(b.shape) != (D,):
+        raise ValueError(f"{who}: bias is {tuple(b.shape)}, expected [{D}]")
+    B, k = idx.shape
+    recon = torch.empty((len(bounds), B, D), dtype=torch.float32, device=idx.device)
+    check(_lib.load().qsaen_decode_nested_table(_p(idx), _p(val), B, k, _p(table), H, D, float(scale), _p(b),
+                                                _bounds_arg(bounds), len(bounds), _p(recon), _stream()))
+    return recon
+
+
+@_on_tensor_device
+def train_row_grad_nested(idx: torch.Tensor, table: torch.Tensor, step: float, g_levels, bounds,
+                          g_latent: Optional[torch.Tensor], W_enc: Optional[torch.Tensor], want_dx: bool = False):
+    """-> (G fp32 [L, B, D], gv fp32 [B, k], dx fp32 [B, D] or None).  ``g_levels``: L gradients [B, D], None for a level the
+    loss does not read.  G holds their suffix sums; gv and dx are train_row_grad's with g_recon = G[level(unit)] per entry.  See
+    qsaen_row_grad_nested."""
+    who = "train_row_grad_nested"
+    _dev(idx, f"{who}: idx", torch.int32)
+    idx = idx.contiguous()
+    table = _f32c(table, "table")
+    B, k = idx.shape
+    H, D = table.shape
+    _check_train_shape(D, k)
+    bounds = nested_bounds(bounds, H, who)
+    g_levels = list(g_levels)
+    if len(g_levels) != len(bounds):
+        raise ValueError(f"{who}: {len(g_levels)} level gradients for {len(bounds)} levels")
+    gs = []
+    for l, g in enumerate(g_levels):
+        if g is not None:
+            g = _f32c(g, f"g_levels[{l}]")
+            if tuple(g.shape) != (B, D) or g.device != idx.device:
+                raise ValueError(f"{who}: g_levels[{l}] is {tuple(g.shape)} on {g.device}, expected [{B}, {D}] on {idx.device}")
+        gs.append(g)
+    gL, gl_ld = _latent_grad(g_latent, B, H)
+    W = _f32c(W_enc, "W_enc") if want_dx else None
+    if W is not None and tuple(W.shape) != (H, D):
+        raise ValueError(f"W_enc is {tuple(W.shape)}, expected [{H}, {D}]")
+    G = torch.empty((len(bounds), B, D), dtype=torch.float32, device=idx.device)
+    gv = torch.empty((B, k), dtype=torch.float32, device=idx.device)
+    dx = torch.empty((B, D), dtype=torch.float32, device=idx.device) if want_dx else None
+    garr = (C.c_void_p * len(gs))(*[0 if g is None else g.data_ptr() for g in gs])     # host array of device pointers
+    check(_lib.load().qsaen_row_grad_nested(_p(idx), B, k, _p(table), H, D, float(step), C.cast(garr, C.c_void_p),
+                                            _bounds_arg(bounds), len(bounds), _p(gL), int(gl_ld), _p(W), _p(G), _p(gv), _p(dx),
+                                            _stream()))
+    return G, gv, dx
+
+
+def _nested_G(who: str, G, L: int, B: int, D: int):
+    if G is None:
+        return None
+    _dev(G, f"{who}: G", torch.float32)
+    if tuple(G.shape) != (L, B, D) or not G.is_contiguous():
+        raise ValueError(f"{who}: G is {tuple(G.shape)} (strides {G.stride()}), expected contiguous [{L}, {B}, {D}]")
+    return G
+
+
+@_on_tensor_device
+def train_unit_grad_nested(offsets: torch.Tensor, entries: torch.Tensor, val: torch.Tensor, gv: torch.Tensor, x: torch.Tensor,
+                           G: Optional[torch.Tensor], bounds, logits: torch.Tensor, n_bits: int, step: float,
+                           g_polarize: Optional[torch.Tensor], want_encoder: bool = True, want_logits: bool = True):
+    """train_unit_grad with g_recon = G[level(h)] for unit h (G fp32 [L, B, D] from train_row_grad_nested, or None);
+    see qsaen_train_unit_grad_nested."""
+    who = "train_unit_grad_nested"
+    _dev(offsets, "offsets", torch.int32)
+    _dev(entries, "entries", torch.int32)
+    val, gv, x, logits = _f32c(val, "val"), _f32c(gv, "gv"), _f32c(x, "x"), _f32c(logits, "logits")
+    B, k = val.shape
+    D = x.shape[1]
+    H = offsets.shape[0] - 1
+    _check_train_shape(D, k)
+    if tuple(logits.shape) != (H, D * n_bits) or tuple(x.shape) != (B, D) or tuple(gv.shape) != (B, k) \
+            or entries.numel() != B * k:
+        raise ValueError(f"{who}: inconsistent shapes")
+    bounds = nested_bounds(bounds, H, who)
+    G = _nested_G(who, G, len(bounds), B, D)
+    gP = _f32c(g_polarize.reshape(()), "g_polarize") if g_polarize is not None else None
+    dev = x.device
+    dW = torch.empty((H, D), dtype=torch.float32, device=dev) if want_encoder else None
+    db = torch.empty((H,), dtype=torch.float32, device=dev) if want_encoder else None
+    dl = torch.empty((H, D * n_bits), dtype=torch.float32, device=dev) if want_logits else None
+    lib = _lib.load()
+    ws = _train_ws(lib.qsaen_train_unit_grad_nested_workspace_bytes(B, k, H, D), dev)
+    check(lib.qsaen_train_unit_grad_nested(_p(offsets.contiguous()), _p(entries.contiguous()), _p(val), _p(gv), B, k, _p(x),
+                                           _p(G), _bounds_arg(bounds), len(bounds), _p(logits), H, D, int(n_bits), float(step),
+                                           _p(gP), _p(dW), _p(db), _p(dl), _p(ws), ws.numel(), _stream()))
+    return dW, db, dl
+
+
+@_on_tensor_device
+def train_table_unit_grad_nested(offsets: torch.Tensor, entries: torch.Tensor, val: torch.Tensor, gv: torch.Tensor,
+                                 x: torch.Tensor, G: Optional[torch.Tensor], bounds, want_encoder: bool = True,
+                                 want_decoder: bool = True):
+    """train_table_unit_grad with g_recon = G[level(h)] for unit h; see qsaen_train_table_unit_grad_nested."""
+    who = "train_table_unit_grad_nested"
+    _dev(offsets, "offsets", torch.int32)
+    _dev(entries, "entries", torch.int32)
+    val, gv, x = _f32c(val, "val"), _f32c(gv, "gv"), _f32c(x, "x")
+    if val.dim() != 2 or x.dim() != 2 or offsets.dim() != 1:
+        raise ValueError(f"{who}: val and x must be 2-D, offsets 1-D")
+    B, k = val.shape
+    D = x.shape[1]
+    H = offsets.shape[0] - 1
+    _check_train_shape(D, k)
+    if H < 1 or tuple(x.shape) != (B, D) or tuple(gv.shape) != (B, k) or entries.numel() != B * k:
+        raise ValueError(f"{who}: inconsistent shapes")
+    if B * k >= 2 ** 31:
+        raise ValueError(f"{who}: B * k = {B * k} is not below 2^31")
+    bounds = nested_bounds(bounds, H, who)
+    G = _nested_G(who, G, len(bounds), B, D)
+    dev = x.device
+    dW = torch.empty((H, D), dtype=torch.float32, device=dev) if want_encoder else None
+    db = torch.empty((H,), dtype=torch.float32, device=dev) if want_encoder else None
+    dWd = torch.empty((D, H), dtype=torch.float32, device=dev) if want_decoder else None
+    lib = _lib.load()
+    ws = _train_ws(lib.qsaen_train_table_unit_grad_nested_workspace_bytes(B, k, H, D), dev)
+    check(lib.qsaen_train_table_unit_grad_nested(_p(offsets.contiguous()), _p(entries.contiguous()), _p(val), _p(gv), B, k,
+                                                 _p(x), _p(G), _bounds_arg(bounds), len(bounds), H, D, _p(dW), _p(db), _p(dWd),
+                                                 H, _p(ws), ws.numel(), _stream()))
+    return dW, db, dWd

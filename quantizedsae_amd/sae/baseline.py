@@ -105,6 +105,37 @@ class BaselineSparseAutoencoder(ops.GraphForwardMixin, TopKCore, nn.Module):
         return ops.train_table_unit_grad(offsets, entries, val, gv, x, g_recon, want_encoder=want_encoder,
                                          want_decoder=want_decoder)
 
+    # -- nested dictionaries ----------------------------------------------------------------------------------------
+    def forward_train_nested(self, x, bounds, *, dense_latent: bool = True):
+        """``forward_train`` with one reconstruction per dictionary prefix: ``(h_sparse [B,H] or None, (recon_0, ...,
+        recon_{L-1}))``, where ``recon_l`` [B,D] decodes the selected units below ``bounds[l]`` (ascending, the last one
+        ``hidden_dim``) and ``recon_{L-1}`` is ``forward_train``'s reconstruction bit for bit.  The levels are the rows of one
+        [L,B,D] tensor; see BinarySAE.forward_train_nested."""
+        H, D = self.encoder.linear.weight.shape
+        if not ops.train_supported(D, self.topk) or self.topk < 1:
+            raise ValueError(f"BaselineSparseAutoencoder.forward_train_nested: the gradient kernels take input_dim a multiple of "
+                             f"4 up to 4096 and 1 <= topk <= 256 (got input_dim = {D}, topk = {self.topk})")
+        if isinstance(x, torch.Tensor) and x.dim() == 2 and x.shape[0] * self.topk >= 2 ** 31:
+            raise ValueError(f"BaselineSparseAutoencoder.forward_train_nested: batch * topk = {x.shape[0] * self.topk} is not "
+                             "below 2^31")
+        return self._forward_train_nested(x, bounds, dense_latent, self.decoder.weight, self.decoder.bias)[:2]
+
+    def _nested_select(self, x, want_dense: bool):
+        """-> (idx, val, dense latent or None): the selection of _run() without its decode"""
+        self._check_limits(x.shape[0])
+        return self._select(x, self.topk, self.resolved_latent_path(x.shape[0]), want_dense)
+
+    def _nested_decoder(self):
+        """-> (decoder description, decoder bias) of forward_nested: what forward() decodes from"""
+        return ("table", self._table(), 1.0), self.decoder.bias.detach()
+
+    def _nested_train_decoder(self):
+        return self._table(), 1.0, None
+
+    def _nested_unit_grad(self, offsets, entries, val, gv, x, G, bounds, g_extra, want_encoder: bool, want_decoder: bool):
+        return ops.train_table_unit_grad_nested(offsets, entries, val, gv, x, G, bounds, want_encoder=want_encoder,
+                                                want_decoder=want_decoder)
+
     def forward_compact(self, x):
         """(idx, val, reconstruction) without the dense latent; same path selection as forward()."""
         with torch.no_grad():

@@ -296,6 +296,43 @@ class BinarySAE(ops.GraphForwardMixin, TopKCore, SparseAutoencoder):
         return ops.train_unit_grad(offsets, entries, val, gv, x, g_recon, dec.weight.detach(), dec.n_bits,
                                    dec.quantization_step, None, want_encoder=want_encoder, want_logits=want_decoder)
 
+    # -- nested dictionaries ----------------------------------------------------------------------------------------
+    def forward_train_nested(self, x, bounds, *, dense_latent: bool = True):
+        """``forward_train`` with one reconstruction per dictionary prefix: ``(sparse_latent [B,H] or None, (recon_0, ...,
+        recon_{L-1}), polarize_loss [])``, where ``recon_l`` [B,D] decodes the selected units below ``bounds[l]`` (ascending,
+        the last one ``hidden_dim``) through the soft table and ``recon_{L-1}`` is ``forward_train``'s reconstruction bit for
+        bit.  The levels are the rows of one [L,B,D] tensor, written by one walk over each row's list; the backward
+        (csrc/nested.hip, csrc/train.hip) fills the same ``.grad`` as ``forward_train``'s from the gradients of all levels.
+        Same selection path and bits as ``forward_train``; ``model.activity`` is fed once."""
+        if not ops.train_supported(self.input_dim, self.top_k):
+            raise ValueError(f"BinarySAE.forward_train_nested: the gradient kernels take input_dim a multiple of 4 up to 4096 "
+                             f"and top-k <= 256 (got input_dim = {self.input_dim}, top-k = {self.top_k})")
+        return self._forward_train_nested(x, bounds, dense_latent, self.decoder.weight, self.decoder.bias)
+
+    def _nested_select(self, x, want_dense: bool):
+        """-> (idx, val, dense latent or None): the selection of _run() without its decode"""
+        if self.top_k == 0:
+            return self._zero_k(x, want_dense)[:3]
+        path = self.resolved_latent_path(x.shape[0])
+        self._check_limits(path, x.shape[0])
+        return self._select(x, self.top_k, path, want_dense)
+
+    def _nested_decoder(self):
+        """-> (decoder description, decoder bias) of forward_nested: what forward() decodes from"""
+        return self._fused_decoder(self.decoder.resolved_decode_mode() == "hard"), self.decoder.bias.detach()
+
+    def _nested_train_decoder(self):
+        """-> (soft table [H, D], step, polarize loss): built once per step and left for forward_aux, as forward_train does"""
+        dec = self.decoder
+        table, pol = ops.binary_soft_table_polarize(dec.weight.detach(), dec.out_features, dec.n_bits)
+        self._train_cache.put((dec.weight,), {"table": table})
+        return table, dec.quantization_step, pol
+
+    def _nested_unit_grad(self, offsets, entries, val, gv, x, G, bounds, g_pol, want_encoder: bool, want_decoder: bool):
+        dec = self.decoder
+        return ops.train_unit_grad_nested(offsets, entries, val, gv, x, G, bounds, dec.weight.detach(), dec.n_bits,
+                                          dec.quantization_step, g_pol, want_encoder=want_encoder, want_logits=want_decoder)
+
     # -- two batches in flight --------------------------------------------------------------------------------
     def forward_submit(self, x, slot: int = 0, want_dense: bool = True):
         """Queue one forward without waiting for the GPU anywhere: returns a handle whose ``result()`` gives

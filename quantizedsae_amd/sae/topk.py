@@ -118,6 +118,89 @@ class TopKCore:
         return _AuxStep.apply(self, units, k_aux, x, lin.weight, lin.bias, self._aux_decoder()[0])
 
 
+    # -- nested dictionaries (Matryoshka): one reconstruction per dictionary prefix ----------------------------------------
+    @staticmethod
+    def default_nested_bounds(H: int, levels: int = 4):
+        """``[H >> (levels - 1), ..., H >> 1, H]``: the prefixes ``[H/8, H/4, H/2, H]`` the levels of the matryoshka classes
+        are read in."""
+        H, levels = int(H), int(levels)
+        if not 1 <= levels <= ops.NESTED_MAX_LEVELS:
+            raise ValueError(f"default_nested_bounds: levels = {levels}; 1 .. {ops.NESTED_MAX_LEVELS} are supported")
+        return ops.nested_bounds([H >> (levels - 1 - l) for l in range(levels)], H, "default_nested_bounds")
+
+    def _nested_input(self, x, bounds, who: str):
+        x = require_device_input(x, "x")
+        H, D = self.encoder.linear.weight.shape
+        if x.dim() != 2 or x.shape[1] != D:
+            raise ValueError(f"x is {tuple(x.shape)}, expected [batch, {D}]")
+        return x, ops.nested_bounds(bounds, H, f"{type(self).__name__}.{who}")
+
+    def forward_nested(self, x, bounds):
+        """``(idx int32 [B,k], val fp32 [B,k], levels fp32 [L,B,D])`` without a ``grad_fn``: the selection of ``forward()`` and,
+        for every ``bounds[l]`` (ascending, the last one ``hidden_dim``), the reconstruction from the selected units below it,
+        decoded from what ``forward()`` decodes from.  All levels come from one walk over each row's list
+        (csrc/nested.hip); the last level is ``forward()``'s reconstruction bit for bit."""
+        with torch.no_grad():
+            x, bounds = self._nested_input(x, bounds, "forward_nested")
+            idx, val, _ = self._nested_select(as_f32c(x), False)
+            decoder, dec_bias = self._nested_decoder()
+            if decoder[0] == "packed":
+                D = self.encoder.linear.weight.shape[1]
+                return idx, val, ops.decode_nested_binary(idx, val, decoder[1], D, decoder[2], decoder[3], dec_bias, bounds)
+            return idx, val, ops.decode_nested_table(idx, val, decoder[1], decoder[2], dec_bias, bounds)
+
+    def _forward_train_nested(self, x, bounds, dense_latent: bool, dec_param, dec_bias):
+        """-> (latent or None, tuple of L level views [B, D] of one [L, B, D] tensor, what _nested_train_decoder adds)"""
+        x, bounds = self._nested_input(x, bounds, "forward_train_nested")
+        lin = self.encoder.linear
+        latent, levels, extra = _NestedTrainStep.apply(self, bool(dense_latent), tuple(bounds), x, lin.weight, lin.bias,
+                                                       dec_param, dec_bias)
+        return (latent if dense_latent else None), tuple(levels[l] for l in range(len(bounds))), extra
+
+
+class _NestedTrainStep(torch.autograd.Function):
+    """forward_train_nested and its gradient.  The model supplies ``_nested_train_decoder() -> (table [H, D], step, extra
+    output or None)``, ``_nested_select(x, want_dense) -> (idx, val, latent)`` and ``_nested_unit_grad(offsets, entries, val, gv,
+    x, G, bounds, g_extra, want_encoder, want_decoder)``.  The levels are the rows of ONE output tensor, so a loss over them
+    sends one gradient [L, B, D] back; its suffix sums G[l] = g[l] + G[l + 1] are what reaches the dictionary rows of level l
+    (include/qsae_nested.h)."""
+
+    @staticmethod
+    def forward(ctx, model, dense_latent, bounds, x, W_enc, b_enc, dec_param, b_dec):
+        table, step, extra = model._nested_train_decoder()
+        xf = as_f32c(x.detach())
+        idx, val, latent = model._nested_select(xf, dense_latent)
+        levels = ops.decode_nested_table(idx, val, table, step, b_dec.detach(), bounds)
+        if model.activity is not None:
+            model.activity.add_compact(idx, val)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(xf, idx, val, table)
+        ctx.model, ctx.step, ctx.bounds, ctx.x_dtype = model, step, bounds, x.dtype
+        return latent, levels, extra
+
+    @staticmethod
+    def backward(ctx, g_latent, g_levels, g_extra):
+        xf, idx, val, table = ctx.saved_tensors
+        model, bounds = ctx.model, ctx.bounds
+        need_x, need_W, need_b, need_dec, need_bd = ctx.needs_input_grad[3:8]
+        want_units = need_W or need_b or need_dec
+        dx = dW = db = ddec = dbd = None
+        if (need_x or want_units or need_bd) and not (g_latent is None and g_levels is None and g_extra is None):
+            g_list = [None] * len(bounds) if g_levels is None else [g_levels[l] for l in range(len(bounds))]
+            G, gv, dx = ops.train_row_grad_nested(idx, table, ctx.step, g_list, bounds, g_latent,
+                                                  model.encoder.linear.weight.detach(), want_dx=need_x)
+            if want_units:
+                offsets, entries = ops.train_csr(idx, table.shape[0])
+                dW, db, ddec = model._nested_unit_grad(offsets, entries, val, gv, xf, G, bounds, g_extra, need_W or need_b,
+                                                       need_dec)
+            if need_bd:
+                dbd = ops.train_col_sum(G[0])                  # every level adds the bias: its gradient is the whole sum
+            if dx is not None and dx.dtype != ctx.x_dtype:
+                dx = dx.to(ctx.x_dtype)
+        return (None, None, None, dx if need_x else None, dW if need_W else None, db if need_b else None,
+                ddec if need_dec else None, dbd if need_bd else None)
+
+
 class _AuxStep(torch.autograd.Function):
     """forward_aux and its gradient.  The model supplies ``_aux_decoder() -> (decoder parameter, table [H, D], step)`` and
     ``_aux_unit_grad(offsets, entries, val, gv, x, g_recon, want_encoder, want_decoder)``, its unit-gradient kernel without

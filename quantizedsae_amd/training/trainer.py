@@ -42,6 +42,12 @@ backward, ``trainer_loss`` the per-type loss, ``optim.Adam`` the step.  What dif
   ``log_every``): a refresh is that summary's one host copy, between two refreshes nothing more is read back than before,
   and a list that has gone stale in between is fine.  Logging steps gain ``aux_loss`` and ``aux_units``.  Works together with
   ``resample_every``.
+* ``nested_bounds="default" | [b_0, ..., b_{L-1}]`` (``baseline_sae`` and ``b_sae`` only; default ``None`` changes nothing) trains
+  with the nested-dictionary objective (``nested_loss``, csrc/nested.hip): ``model.forward_train_nested`` gives one
+  reconstruction per dictionary prefix ``[0, b_l)`` and the type's reconstruction term is summed over them; ``"default"`` is
+  ``default_nested_bounds(hidden_dim)`` = ``[H/8, H/4, H/2, H]``.  Logging steps gain ``recon_loss_level_{l}``; ``loss`` and
+  ``recon_loss`` are the sums.  The last level is the model's reconstruction, so ``aux_k``, ``resample_every`` and
+  ``activity_window`` work as before.
 * ``model=`` hands in the model instead of building the reference's.  The reference builds
   ``BinarySAE(input_dim, hidden_dim, n_bits)``, where ``n_bits`` lands in ``gamma`` and the decoder keeps its default of 8
   bits; that call is kept.
@@ -65,6 +71,7 @@ from .batches import ShuffledChunk
 from .loss import SAE_TYPES, trainer_loss
 from .activity import FeatureActivity, activity_line
 from .auxk import AUX_MAX_K, aux_k_loss
+from .nested import NESTED_TYPES, default_nested_bounds, nested_loss
 from .resample import ResampleReport, resample_dead, resample_line
 from .watch import WATCH_MODES, ModelWatch, watch_line
 
@@ -102,7 +109,7 @@ class Trainer:
                  log_every: int = 100, watch: Optional[str] = None, watch_freq: int = 256,
                  activity_window: Optional[int] = None, resample_every: Optional[int] = None, resample_seed: int = 0,
                  resample_scale: float = 0.2, aux_k: Optional[int] = None, aux_coef: float = 1 / 32,
-                 aux_refresh: Optional[int] = None):
+                 aux_refresh: Optional[int] = None, nested_bounds=None):
         if sae_type not in SAE_TYPES:
             raise ValueError(f"unknown sae_type {sae_type!r}; expected one of {', '.join(SAE_TYPES)}")
         if sae_type == "t_sae" and not rigL:
@@ -135,6 +142,9 @@ class Trainer:
                                  f"{sae_type!r}")
             if aux_refresh is not None and int(aux_refresh) < 1:
                 raise ValueError(f"aux_refresh = {aux_refresh}; expected None or a number of batches >= 1")
+        if nested_bounds is not None and sae_type not in NESTED_TYPES:
+            raise ValueError(f"nested_bounds: the nested objective is built for baseline_sae and b_sae, the two top-k models; "
+                             f"got {sae_type!r}")
         self.config = config
         self.sae_type = sae_type
         self.device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
@@ -177,9 +187,19 @@ class Trainer:
         self.aux_coef = float(aux_coef)
         self.aux_refresh = int(aux_refresh) if aux_refresh is not None else self.log_every
         self._aux_units, self._aux_steps, self._aux_loss = None, 0, None   # the dead list in use, steps taken with it, last loss
+        self.nested_bounds = None
+        if nested_bounds is not None:
+            H = self.model.encoder.linear.weight.shape[0]
+            if isinstance(nested_bounds, str):
+                if nested_bounds != "default":
+                    raise ValueError(f"nested_bounds = {nested_bounds!r}; expected None, 'default' or a list of bounds")
+                nested_bounds = default_nested_bounds(H)
+            self.nested_bounds = ops.nested_bounds(nested_bounds, H, "Trainer: nested_bounds")
 
     # ---- one step ------------------------------------------------------------------------------------------------
     def _forward(self, batch, want_latent: bool):
+        if self.nested_bounds is not None:
+            return self.model.forward_train_nested(batch, self.nested_bounds, dense_latent=want_latent)
         if self.sae_type in ("b_sae", "baseline_sae"):
             return self.model.forward_train(batch, dense_latent=want_latent)
         return self.model.forward_train(batch)
@@ -192,9 +212,12 @@ class Trainer:
         st, model = self.sae_type, self.model
         outputs = self._forward(batch, log_step)
         optimizer.zero_grad(set_to_none=True)
-        losses = trainer_loss(st, outputs, batch, self.config)
-        if self.aux_k is not None:
-            self._aux_backward(batch, outputs[1])
+        if self.nested_bounds is not None:
+            losses = nested_loss(st, outputs, batch, self.config)
+        else:
+            losses = trainer_loss(st, outputs, batch, self.config)
+        if self.aux_k is not None:                             # (nested: the last level is the model's reconstruction)
+            self._aux_backward(batch, outputs[1] if self.nested_bounds is None else outputs[1][-1])
         self._watched = self._watch.collect() if self._watch_due else None
         if st == "q_sae":
             model.decoder.apply_secant_grad()
@@ -239,12 +262,16 @@ class Trainer:
     def _metrics(self, outputs, losses) -> dict:
         st, cfg = self.sae_type, self.config
         lv = losses.tolist()
+        levels = {}
+        if self.nested_bounds is not None:                     # the objective is the sum over the levels
+            levels = {f"recon_loss_level_{i}": v for i, v in enumerate(lv)}
+            lv = [sum(lv)]
         if st == "b_sae":
             latent, _, pol = outputs
             pol = pol.item()
             msb, lsb = self._plane_magnitudes()
             return {"loss": lv[0] + cfg["polarize_lambda"] * pol, "recon_loss": lv[0], "polarize_loss": pol,
-                    "activated_neurons": torch.mean(latent.sum(dim=-1)).item(), "mag_MSB": msb, "mag_LSB": lsb}
+                    "activated_neurons": torch.mean(latent.sum(dim=-1)).item(), "mag_MSB": msb, "mag_LSB": lsb, **levels}
         if st in ("q_sae", "rq_sae"):
             n = cfg["n_bits"]
             l0 = [g.item() for g in outputs[0]]
@@ -259,7 +286,7 @@ class Trainer:
             d.update({f"L0 of latent_group_{i}": l0[i] for i in range(n)})
             d["sparsity loss"] = sparsity
             return d
-        return {"loss": lv[0]}
+        return {"loss": lv[0], **levels}
 
     def _aux_metrics(self) -> dict:
         """What a logging step adds with ``aux_k``: the step's auxiliary loss (0.0 when no unit was dead) and the length of the
