@@ -227,6 +227,21 @@ NESTED_SIGNATURES = {
                                                 _sz, _vp]),
 }
 
+# name -> (restype, argtypes) of the qsaeb_* entry points of include/qsae_batch.h (csrc/batch_topk.hip, batch_topk_decode.hip):
+# BatchTopK -- the batch-wide selection, the threshold selection and the ragged row operations -- a table of its own for the
+# same reason.  Must list every symbol declared in qsae_batch.h.
+BATCH_SIGNATURES = {
+    "qsaeb_batch_select_workspace_bytes": (_sz, [_i, _i]),
+    "qsaeb_batch_select": (_i, [_vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _f, _vp, _sz, _vp]),
+    "qsaeb_threshold_select_workspace_bytes": (_sz, [_i, _i]),
+    "qsaeb_threshold_select": (_i, [_vp, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "qsaeb_decode_ragged_binary": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "qsaeb_decode_ragged_table": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _f, _vp, _vp, _vp]),
+    "qsaeb_row_grad_ragged": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _f, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "qsaeb_csr_ragged_workspace_bytes": (_sz, [_i, _i, _i]),
+    "qsaeb_csr_ragged": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+}
+
 
 class QsaeError(RuntimeError):
     """A libqsae_hip call returned a non-zero status."""
@@ -247,7 +262,7 @@ def _open(path: Path) -> C.CDLL:
             "(hipcc --offload-arch=gfx950).  quantizedsae_amd has no CPU / eager fallback.")
     lib = C.CDLL(str(path))
     for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(CURVE_SIGNATURES.items()) \
-            + list(NESTED_SIGNATURES.items()):
+            + list(NESTED_SIGNATURES.items()) + list(BATCH_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here means the library is stale
         fn.restype = res
         fn.argtypes = args

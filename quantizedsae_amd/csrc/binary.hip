@@ -96,41 +96,7 @@ soft_table_kernel(const float* __restrict__ logits, int H, int D, int n, float* 
 // One wave per activation row; 4 rows per workgroup.  The k (idx,val) pairs are sorted by idx
 // in LDS (rank counting) so that the fmaf chain runs in ascending feature index exactly like the
 // oracle; then each lane owns one dword of the packed row (32/fw output dims) per sweep.
-constexpr int kDecWaves = 4;
-constexpr int kDecMaxK = 256;
-
-struct DecShared {
-    int idx[kDecWaves][kDecMaxK];
-    float val[kDecWaves][kDecMaxK];
-};
-
-// All threads of the workgroup call this (it contains workgroup barriers); waves whose row is
-// out of range pass active = false and only take part in the barriers.
-__device__ __forceinline__ void sort_pairs_by_index(bool active, const int32_t* __restrict__ idx,
-                                                    const float* __restrict__ val, int k, int H, int lane,
-                                                    int* s_idx, float* s_val, int* t_idx) {
-    if (active) {
-        for (int j = lane; j < k; j += 64) {
-            int h = idx[j];
-            h = h < 0 ? 0 : (h >= H ? H - 1 : h);   // never index outside the dictionary
-            t_idx[j] = h;
-        }
-    }
-    __syncthreads();
-    if (active) {
-        for (int j = lane; j < k; j += 64) {
-            const int mine = t_idx[j];
-            int rank = 0;
-            for (int i = 0; i < k; ++i) {
-                const int o = t_idx[i];
-                rank += (o < mine || (o == mine && i < j)) ? 1 : 0;
-            }
-            s_idx[rank] = mine;
-            s_val[rank] = val[j];
-        }
-    }
-    __syncthreads();
-}
+// (kDecWaves, DecShared and sort_pairs_by_index are in decode_row.h, shared with the ragged decode of batch_topk.hip.)
 
 // rows != nullptr: row b of this launch is activation row rows[b] (the flagged rows of the prefilter pipeline)
 template <int FW>

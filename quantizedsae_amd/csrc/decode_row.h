@@ -272,4 +272,42 @@ __device__ __forceinline__ void decode_row_sorted_any(const int* s_idx, const fl
     }
 }
 
+// ---- the list of one row, sorted by unit id: shared by the sparse decode kernels (binary.hip) and the ragged ones
+// (batch_topk.hip), which sort the first counts[r] entries of a row ---------------------------------------------------------
+constexpr int kDecWaves = 4;
+constexpr int kDecMaxK = 256;
+
+struct DecShared {
+    int idx[kDecWaves][kDecMaxK];
+    float val[kDecWaves][kDecMaxK];
+};
+
+// All threads of the workgroup call this (it contains workgroup barriers); waves whose row is
+// out of range pass active = false and only take part in the barriers.
+__device__ __forceinline__ void sort_pairs_by_index(bool active, const int32_t* __restrict__ idx,
+                                                    const float* __restrict__ val, int k, int H, int lane,
+                                                    int* s_idx, float* s_val, int* t_idx) {
+    if (active) {
+        for (int j = lane; j < k; j += 64) {
+            int h = idx[j];
+            h = h < 0 ? 0 : (h >= H ? H - 1 : h);   // never index outside the dictionary
+            t_idx[j] = h;
+        }
+    }
+    __syncthreads();
+    if (active) {
+        for (int j = lane; j < k; j += 64) {
+            const int mine = t_idx[j];
+            int rank = 0;
+            for (int i = 0; i < k; ++i) {
+                const int o = t_idx[i];
+                rank += (o < mine || (o == mine && i < j)) ? 1 : 0;
+            }
+            s_idx[rank] = mine;
+            s_val[rank] = val[j];
+        }
+    }
+    __syncthreads();
+}
+
 }  // namespace qsae

@@ -20,26 +20,15 @@
 // integer ORs that mark (unit, row) pairs in the CSR build, whose result does not depend on their order.
 #include "common.h"
 #include "csr_lists.h"
+#include "train_row.h"
 #include "unit_levels.h"
 
 namespace qsae {
 
 constexpr int kTrainChunk = 256;        // entries of a unit list one workgroup sums; longer lists are split
 constexpr int kTrainMaxD = 4096;
-constexpr int kTrainMaxK = 256;
 constexpr int kColRows = 256;           // rows per partial of the column sum
 constexpr size_t kTrainAlign = 256;
-
-typedef float tr_f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ tr_f32x4 ld4(const float* p) { return *reinterpret_cast<const tr_f32x4*>(p); }
-__device__ __forceinline__ void st4(float* p, tr_f32x4 v) { *reinterpret_cast<tr_f32x4*>(p) = v; }
-__device__ __forceinline__ tr_f32x4 fma4(float a, tr_f32x4 w, tr_f32x4 acc) {
-    tr_f32x4 r;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) r[e] = fmaf(a, w[e], acc[e]);
-    return r;
-}
 
 __host__ __device__ inline int list_chunks(int len) { return len <= kTrainChunk ? 1 : (len + kTrainChunk - 1) / kTrainChunk; }
 
@@ -111,68 +100,13 @@ csr_fill_kernel(const int32_t* __restrict__ idx, long long Bk, int k, int H, int
 }
 
 // ---- row kernel: gv and dx --------------------------------------------------------------------------------------------
-// One wave per row, four rows per workgroup.  Lane l owns columns 4 (l + 64 i) .. + 3; each dot product is the lane's
-// chain over its columns, then a butterfly (every lane of the wave takes part in every shuffle, whatever D is).
-constexpr int kRowWaves = 4;
-
+// One wave per row, four rows per workgroup; the body is train_row.h (shared with the ragged rows of batch_topk.hip).
 __global__ void __launch_bounds__(64 * kRowWaves)
 train_row_kernel(const int32_t* __restrict__ idx, int B, int k, int H, int D, const float* __restrict__ table, float step,
                  const float* __restrict__ gR, const float* __restrict__ gL, long long gl_ld,
                  const float* __restrict__ Wenc, float* __restrict__ gv, float* __restrict__ dx) {
-    __shared__ int s_h[kRowWaves][kTrainMaxK];
-    __shared__ float s_g[kRowWaves][kTrainMaxK];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = blockIdx.x * kRowWaves + wave;
-    const bool active = r < B;
-    const int D4 = D / 4;
-    if (active)
-        for (int j = lane; j < k; j += 64) s_h[wave][j] = clamp_unit(idx[static_cast<long long>(r) * k + j], H);
-    __syncthreads();
-    if (active) {
-        const float* g = gR ? gR + static_cast<long long>(r) * D : nullptr;
-        for (int j0 = 0; j0 < k; j0 += 4) {
-            float part[4] = {0.f, 0.f, 0.f, 0.f};
-            if (g) {
-                int hh[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) hh[u] = s_h[wave][min(j0 + u, k - 1)];
-                for (int c = lane; c < D4; c += 64) {
-                    const tr_f32x4 a = ld4(g + 4 * c);
-                    tr_f32x4 t[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) t[u] = ld4(table + static_cast<long long>(hh[u]) * D + 4 * c);
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) part[u] = fmaf(a[e], t[u][e], part[u]);
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    for (int off = 32; off > 0; off >>= 1) part[u] += __shfl_xor(part[u], off, 64);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int j = j0 + u;
-                if (j < k) {
-                    float val = g ? step * part[u] : 0.0f;
-                    if (gL) val = gL[static_cast<long long>(r) * gl_ld + s_h[wave][j]] + val;
-                    if (lane == 0) {
-                        gv[static_cast<long long>(r) * k + j] = val;
-                        s_g[wave][j] = val;
-                    }
-                }
-            }
-        }
-    }
-    __syncthreads();
-    if (active && dx) {
-        for (int c = lane; c < D4; c += 64) {
-            tr_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            for (int j = 0; j < k; ++j)
-                acc = fma4(s_g[wave][j], ld4(Wenc + static_cast<long long>(s_h[wave][j]) * D + 4 * c), acc);
-            st4(dx + static_cast<long long>(r) * D + 4 * c, acc);
-        }
-    }
+    const int r = blockIdx.x * kRowWaves + (threadIdx.x >> 6);
+    train_row_body(r < B, r, idx, k, k, H, D, table, step, gR, gL, gl_ld, Wenc, gv, dx);
 }
 
 // ---- unit kernels: dW_enc, db_enc, dInt and the logit-gradient row ---------------------------------------------------

@@ -91,15 +91,7 @@ class SparsityCurve:
         return ("table", m._table(), 1.0), m.decoder.bias.detach()
 
     def _path(self, rows: int, K: int) -> str:
-        m = self.model
-        path = m.resolved_latent_path(rows)
-        if path == "prefilter" and not T.prefilter_supported(rows, self.input_dim, self.hidden_dim, K):
-            path = "fused"
-        if not T.encode_topk_supported(max(rows, 1), self.input_dim, self.hidden_dim, K) or \
-                (path == "inplace" and self.hidden_dim > 32768):
-            raise ValueError(f"SparsityCurve: no top-k path takes input_dim = {self.input_dim}, hidden_dim = {self.hidden_dim}, "
-                             f"k = {K} at a batch of {rows} rows")
-        return path
+        return self.model._select_path(rows, K, "SparsityCurve")
 
     def add(self, x: torch.Tensor, recon_out: Optional[torch.Tensor] = None) -> None:
         """Add the rows of ``x`` [rows, input_dim] (on the device).  ``recon_out``: an fp32 [len(ks), rows, input_dim] tensor

@@ -2962,3 +2962,182 @@ def train_table_unit_grad_nested(offsets: torch.Tensor, entries: torch.Tensor, v
                                                  _p(x), _p(G), _bounds_arg(bounds), len(bounds), H, D, _p(dW), _p(db), _p(dWd),
                                                  H, _p(ws), ws.numel(), _stream()))
     return dW, db, dWd
+
+
+# ---- BatchTopK of the top-k SAEs (include/qsae_batch.h, csrc/batch_topk.hip, csrc/batch_topk_decode.hip) -------------------
+BATCH_TOPK_MAX_K = 256
+BATCH_TOPK_REPORT_WORDS = 4       # selected, saturated rows, empty rows, bits of the smallest selected value
+
+
+def _batch_vals(who: str, val):
+    _dev(val, f"{who}: val", torch.float32)
+    if val.dim() != 2 or val.shape[1] < 1:
+        raise ValueError(f"{who}: val is {tuple(val.shape)}, expected [B, K] with K >= 1")
+    if val.shape[1] > BATCH_TOPK_MAX_K:
+        raise ValueError(f"{who}: the cap K = {val.shape[1]} exceeds {BATCH_TOPK_MAX_K}")
+    if val.shape[0] * val.shape[1] >= 2 ** 31:
+        raise ValueError(f"{who}: B * K = {val.shape[0] * val.shape[1]} is not below 2^31")
+    return val.contiguous()
+
+
+def _batch_lists(who: str, idx, val, counts):
+    _dev(idx, f"{who}: idx", torch.int32)
+    _dev(counts, f"{who}: counts", torch.int32)
+    if val is not None:
+        val = _batch_vals(who, val)
+        if idx.shape != val.shape or idx.device != val.device:
+            raise ValueError(f"{who}: idx is {tuple(idx.shape)}, val {tuple(val.shape)}; expected two [B, K] tensors on one device")
+    if idx.dim() != 2 or not 1 <= idx.shape[1] <= BATCH_TOPK_MAX_K:
+        raise ValueError(f"{who}: idx is {tuple(idx.shape)}, expected [B, K] with 1 <= K <= {BATCH_TOPK_MAX_K}")
+    if tuple(counts.shape) != (idx.shape[0],) or counts.device != idx.device:
+        raise ValueError(f"{who}: counts is {tuple(counts.shape)} on {counts.device}, expected [{idx.shape[0]}] on {idx.device}")
+    return idx.contiguous(), val, counts.contiguous()
+
+
+def _batch_state(who: str, theta, batches, device):
+    if (theta is None) != (batches is None):
+        raise ValueError(f"{who}: theta and batches go together")
+    if theta is None:
+        return
+    _dev(theta, f"{who}: theta", torch.float32)
+    _dev(batches, f"{who}: batches", torch.int64)
+    if theta.numel() != 1 or batches.numel() != 1 or theta.device != device or batches.device != device:
+        raise ValueError(f"{who}: theta and batches are one element each on {device}")
+
+
+@_on_tensor_device
+def batch_select(val: torch.Tensor, n_select: int, want_val: bool = True, theta: Optional[torch.Tensor] = None,
+                 batches: Optional[torch.Tensor] = None, lr: float = 0.01):
+    """The n_select largest entries of the whole batch of top-K lists ``val`` [B, K] (ties to the lowest row, then position)
+    -> (counts int32 [B], val_sel fp32 [B, K] or None, report int64 [4]); updates the threshold state (theta fp32, batches
+    int64, one element each, in place) when given.  No host read.  See qsaeb_batch_select."""
+    who = "batch_select"
+    val = _batch_vals(who, val)
+    B, K = val.shape
+    n_select = int(n_select)
+    if not 0 <= n_select <= B * K:
+        raise ValueError(f"{who}: n_select = {n_select} is outside 0 .. B * K = {B * K}")
+    _batch_state(who, theta, batches, val.device)
+    counts = torch.empty((B,), dtype=torch.int32, device=val.device)
+    val_sel = torch.empty_like(val) if want_val else None
+    report = torch.zeros((BATCH_TOPK_REPORT_WORDS,), dtype=torch.int64, device=val.device)
+    lib = _lib.load()
+    ws = _train_ws(lib.qsaeb_batch_select_workspace_bytes(B, K), val.device)
+    check(lib.qsaeb_batch_select(_p(val), B, K, n_select, _p(counts), _p(val_sel), _p(report), _p(theta), _p(batches), float(lr),
+                                 _p(ws), ws.numel(), _stream()))
+    return counts, val_sel, report
+
+
+@_on_tensor_device
+def threshold_select(val: torch.Tensor, theta, want_val: bool = True):
+    """counts[r] = the longest prefix of row r of ``val`` [B, K] with val >= theta (a float compare; ``theta``: a one-element
+    fp32 device tensor, read on the device, or a number) -> (counts, val_sel or None, report) as batch_select.  See
+    qsaeb_threshold_select."""
+    who = "threshold_select"
+    val = _batch_vals(who, val)
+    B, K = val.shape
+    if isinstance(theta, torch.Tensor):
+        _dev(theta, f"{who}: theta", torch.float32)
+        if theta.numel() != 1 or theta.device != val.device:
+            raise ValueError(f"{who}: theta is one element on {val.device}")
+        t_dev, t_host = theta, 0.0
+    else:
+        t_dev, t_host = None, float(theta)
+    counts = torch.empty((B,), dtype=torch.int32, device=val.device)
+    val_sel = torch.empty_like(val) if want_val else None
+    report = torch.zeros((BATCH_TOPK_REPORT_WORDS,), dtype=torch.int64, device=val.device)
+    lib = _lib.load()
+    ws = _train_ws(lib.qsaeb_threshold_select_workspace_bytes(B, K), val.device)
+    check(lib.qsaeb_threshold_select(_p(val), B, K, _p(t_dev), t_host, _p(counts), _p(val_sel), _p(report), _p(ws), ws.numel(),
+                                     _stream()))
+    return counts, val_sel, report
+
+
+@_on_tensor_device
+def decode_ragged_binary(idx, val, counts, packed, D: int, n_bits: int, step: float, bias=None) -> torch.Tensor:
+    """-> fp32 [B, D]: row r is decode_binary_sparse on the first counts[r] entries of its list, bit for bit; an entry behind
+    the prefix is not read.  See qsaeb_decode_ragged_binary."""
+    who = "decode_ragged_binary"
+    idx, val, counts = _batch_lists(who, idx, val, counts)
+    _dev(packed, f"{who}: packed", torch.uint8)
+    D, n_bits = int(D), int(n_bits)
+    _nested_D(who, D)
+    if not 1 <= n_bits <= 8:
+        raise ValueError(f"{who}: n_bits = {n_bits} is outside 1 .. 8")
+    if packed.dim() != 2 or packed.shape[1] != binary_row_bytes(D, n_bits) or not packed.is_contiguous() or packed.device != idx.device:
+        raise ValueError(f"{who}: packed is {tuple(packed.shape)}, expected contiguous [H, {binary_row_bytes(D, n_bits)}] on {idx.device}")
+    H = packed.shape[0]
+    b = _f32c(bias, "bias") if bias is not None else None
+    if b is not None and tuple(b.shape) != (D,):
+        raise ValueError(f"{who}: bias is {tuple(b.shape)}, expected [{D}]")
+    B, K = idx.shape
+    recon = torch.empty((B, D), dtype=torch.float32, device=idx.device)
+    check(_lib.load().qsaeb_decode_ragged_binary(_p(idx), _p(val), _p(counts), B, K, _p(packed), H, D, n_bits, float(step), _p(b),
+                                                 _p(recon), _stream()))
+    return recon
+
+
+@_on_tensor_device
+def decode_ragged_table(idx, val, counts, table: torch.Tensor, scale: float = 1.0, bias=None) -> torch.Tensor:
+    """-> fp32 [B, D]: row r is decode_table_sparse on the first counts[r] entries of its list, bit for bit.  See
+    qsaeb_decode_ragged_table."""
+    who = "decode_ragged_table"
+    idx, val, counts = _batch_lists(who, idx, val, counts)
+    table = _f32c(table, "table")
+    if table.dim() != 2 or table.device != idx.device:
+        raise ValueError(f"{who}: table is {tuple(table.shape)} on {table.device}, expected [H, D] on {idx.device}")
+    H, D = table.shape
+    _nested_D(who, D)
+    b = _f32c(bias, "bias") if bias is not None else None
+    if b is not None and tuple(b.shape) != (D,):
+        raise ValueError(f"{who}: bias is {tuple(b.shape)}, expected [{D}]")
+    B, K = idx.shape
+    recon = torch.empty((B, D), dtype=torch.float32, device=idx.device)
+    check(_lib.load().qsaeb_decode_ragged_table(_p(idx), _p(val), _p(counts), B, K, _p(table), H, D, float(scale), _p(b),
+                                                _p(recon), _stream()))
+    return recon
+
+
+@_on_tensor_device
+def train_row_grad_ragged(idx: torch.Tensor, counts: torch.Tensor, table: torch.Tensor, step: float,
+                          g_recon: Optional[torch.Tensor], g_latent: Optional[torch.Tensor],
+                          W_enc: Optional[torch.Tensor] = None, want_dx: bool = False):
+    """-> (gv fp32 [B, K], dx fp32 [B, D] or None): train_row_grad on the first counts[r] entries of every row, bit for bit;
+    gv behind the prefix is +0.  See qsaeb_row_grad_ragged."""
+    who = "train_row_grad_ragged"
+    idx, _, counts = _batch_lists(who, idx, None, counts)
+    table = _f32c(table, "table")
+    B, K = idx.shape
+    H, D = table.shape
+    _nested_D(who, D)
+    gR = _f32c(g_recon, "g_recon") if g_recon is not None else None
+    if gR is not None and tuple(gR.shape) != (B, D):
+        raise ValueError(f"g_recon is {tuple(gR.shape)}, expected [{B}, {D}]")
+    gL, gl_ld = _latent_grad(g_latent, B, H)
+    W = _f32c(W_enc, "W_enc") if want_dx else None
+    if W is not None and tuple(W.shape) != (H, D):
+        raise ValueError(f"W_enc is {tuple(W.shape)}, expected [{H}, {D}]")
+    gv = torch.empty((B, K), dtype=torch.float32, device=idx.device)
+    dx = torch.empty((B, D), dtype=torch.float32, device=idx.device) if want_dx else None
+    check(_lib.load().qsaeb_row_grad_ragged(_p(idx), _p(counts), B, K, _p(table), H, D, float(step), _p(gR), _p(gL), int(gl_ld),
+                                            _p(W), _p(gv), _p(dx), _stream()))
+    return gv, dx
+
+
+@_on_tensor_device
+def train_csr_ragged(idx: torch.Tensor, counts: torch.Tensor, H: int):
+    """The first counts[r] entries of the lists [B, K] grouped by unit -> (offsets int32 [H + 1], entries int32 [B K], of which
+    the first offsets[H] are set and the rest are -1): what train_unit_grad / train_table_unit_grad take together with
+    [B, K] val_sel and gv.  See qsaeb_csr_ragged."""
+    who = "train_csr_ragged"
+    idx, _, counts = _batch_lists(who, idx, None, counts)
+    B, K = idx.shape
+    H = int(H)
+    if H < 1:
+        raise ValueError(f"{who}: H = {H} must be positive")
+    offsets = torch.empty((H + 1,), dtype=torch.int32, device=idx.device)
+    entries = torch.empty((B * K,), dtype=torch.int32, device=idx.device)
+    lib = _lib.load()
+    ws = _train_ws(lib.qsaeb_csr_ragged_workspace_bytes(B, K, H), idx.device)
+    check(lib.qsaeb_csr_ragged(_p(idx), _p(counts), B, K, H, _p(offsets), _p(entries), _p(ws), ws.numel(), _stream()))
+    return offsets, entries

@@ -105,6 +105,11 @@ class BaselineSparseAutoencoder(ops.GraphForwardMixin, TopKCore, nn.Module):
         return ops.train_table_unit_grad(offsets, entries, val, gv, x, g_recon, want_encoder=want_encoder,
                                          want_decoder=want_decoder)
 
+    def _batch_unit_grad(self, offsets, entries, val, gv, x, g_recon, g_extra, want_encoder: bool, want_decoder: bool):
+        """the unit sums of forward_train_batch_topk: forward_train's, over lists of stride cap"""
+        return ops.train_table_unit_grad(offsets, entries, val, gv, x, g_recon, want_encoder=want_encoder,
+                                         want_decoder=want_decoder)
+
     # -- nested dictionaries ----------------------------------------------------------------------------------------
     def forward_train_nested(self, x, bounds, *, dense_latent: bool = True):
         """``forward_train`` with one reconstruction per dictionary prefix: ``(h_sparse [B,H] or None, (recon_0, ...,

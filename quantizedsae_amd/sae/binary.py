@@ -296,6 +296,12 @@ class BinarySAE(ops.GraphForwardMixin, TopKCore, SparseAutoencoder):
         return ops.train_unit_grad(offsets, entries, val, gv, x, g_recon, dec.weight.detach(), dec.n_bits,
                                    dec.quantization_step, None, want_encoder=want_encoder, want_logits=want_decoder)
 
+    def _batch_unit_grad(self, offsets, entries, val, gv, x, g_recon, g_pol, want_encoder: bool, want_decoder: bool):
+        """the unit sums of forward_train_batch_topk: forward_train's, polarize term included, over lists of stride cap"""
+        dec = self.decoder
+        return ops.train_unit_grad(offsets, entries, val, gv, x, g_recon, dec.weight.detach(), dec.n_bits,
+                                   dec.quantization_step, g_pol, want_encoder=want_encoder, want_logits=want_decoder)
+
     # -- nested dictionaries ----------------------------------------------------------------------------------------
     def forward_train_nested(self, x, bounds, *, dense_latent: bool = True):
         """``forward_train`` with one reconstruction per dictionary prefix: ``(sparse_latent [B,H] or None, (recon_0, ...,

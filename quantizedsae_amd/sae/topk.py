@@ -70,6 +70,17 @@ class TopKCore:
         idx, val = ops.topk_rows(latent, k, zero_rest=True)          # latent * mask, in place
         return idx, val, latent
 
+    def _select_path(self, rows: int, K: int, who: str) -> str:
+        """The path ``_select`` takes for a list width K that is not the model's own top-k (the test-time k sweep, the cap of
+        BatchTopK): what ``resolved_latent_path`` gives for the batch, the fused path where the prefilter does not take K."""
+        H, D = (int(n) for n in self.encoder.linear.weight.shape)
+        path = self.resolved_latent_path(rows)
+        if path == "prefilter" and not ops.prefilter_supported(rows, D, H, K):
+            path = "fused"
+        if not ops.encode_topk_supported(max(rows, 1), D, H, K) or (path == "inplace" and H > 32768):
+            raise ValueError(f"{who}: no top-k path takes input_dim = {D}, hidden_dim = {H}, k = {K} at a batch of {rows} rows")
+        return path
+
     def _forward_prefilter(self, enc, k: int, decoder, dec_bias, want_dense: bool):
         """One call: candidate sweep, exact refinement, and every row's reconstruction as soon as the refinement kernel has
         ranked it.  ``enc`` = _prefilter_operands(x).  -> (idx, val, dense latent or None, reconstruction)"""
@@ -156,6 +167,130 @@ class TopKCore:
         latent, levels, extra = _NestedTrainStep.apply(self, bool(dense_latent), tuple(bounds), x, lin.weight, lin.bias,
                                                        dec_param, dec_bias)
         return (latent if dense_latent else None), tuple(levels[l] for l in range(len(bounds))), extra
+
+
+    # -- BatchTopK: the B k largest pre-activations of the batch, ragged rows ------------------------------------------------
+    def _batch_topk_input(self, x, who: str):
+        x = require_device_input(x, "x")
+        H, D = self.encoder.linear.weight.shape
+        if x.dim() != 2 or x.shape[1] != D:
+            raise ValueError(f"x is {tuple(x.shape)}, expected [batch, {D}]")
+        return x, f"{type(self).__name__}.{who}"
+
+    def _select_cap(self, xf, cap: int, who: str):
+        """-> (idx, val) [B, cap]: one selection at the list width ``cap`` through the model's own paths, no dense latent"""
+        idx, val, _ = self._select(xf, cap, self._select_path(xf.shape[0], cap, who), False)
+        return idx, val
+
+    def _decode_ragged(self, idx, val, counts, decoder, dec_bias):
+        if decoder[0] == "packed":
+            D = self.encoder.linear.weight.shape[1]
+            return ops.decode_ragged_binary(idx, val, counts, decoder[1], D, decoder[2], decoder[3], dec_bias)
+        return ops.decode_ragged_table(idx, val, counts, decoder[1], decoder[2], dec_bias)
+
+    def forward_batch_topk(self, x, ctl):
+        """``(idx int32 [B,K], val_sel fp32 [B,K], counts int32 [B], reconstruction [B,D])`` without a ``grad_fn``: the
+        ``B * ctl.k`` largest pre-activations of the whole batch (no ReLU in front, as in ``forward()``), selected from every
+        row's top-``K`` list with K = ``ctl.cap`` (``training.BatchTopK``).  Row r keeps the first ``counts[r]`` entries of
+        its list; ``val_sel`` is the list's values with +0 behind them, so ``(idx, val_sel)`` reads like any compact
+        selection.  Decoded from what ``forward()`` decodes from, ``counts[r]`` entries per row.  ``ctl.counts`` and
+        ``ctl.report`` are left on the device; the threshold state is not moved (``forward_train_batch_topk`` does that)."""
+        with torch.no_grad():
+            x, who = self._batch_topk_input(x, "forward_batch_topk")
+            xf = as_f32c(x)
+            idx, val = self._select_cap(xf, ctl.cap, who)
+            counts, val_sel, report = ops.batch_select(val, xf.shape[0] * ctl.k)
+            ctl.record(counts, report)
+            decoder, dec_bias = self._nested_decoder()
+            return idx, val_sel, counts, self._decode_ragged(idx, val_sel, counts, decoder, dec_bias)
+
+    def forward_threshold(self, x, ctl_or_theta, cap=None):
+        """Evaluation with the global threshold BatchTopK learned: ``(idx, val_sel, counts, reconstruction)`` as
+        ``forward_batch_topk``, where row r keeps every entry of its top-``cap`` list that is ``>=`` the threshold.
+        ``ctl_or_theta``: a ``training.BatchTopK`` (its threshold is read on the device, ``cap`` defaults to its cap) or a
+        number (``cap`` defaults to ``min(256, hidden_dim)``)."""
+        with torch.no_grad():
+            x, who = self._batch_topk_input(x, "forward_threshold")
+            xf = as_f32c(x)
+            H = int(self.encoder.linear.weight.shape[0])
+            if hasattr(ctl_or_theta, "theta") and hasattr(ctl_or_theta, "cap"):
+                theta = ctl_or_theta.state(xf.device)[0]
+                cap = ctl_or_theta.cap if cap is None else int(cap)
+            else:
+                theta, cap = float(ctl_or_theta), (min(ops.BATCH_TOPK_MAX_K, H) if cap is None else int(cap))
+            if not 1 <= cap <= min(ops.BATCH_TOPK_MAX_K, H):
+                raise ValueError(f"{who}: cap = {cap}; expected 1 .. {min(ops.BATCH_TOPK_MAX_K, H)}")
+            idx, val = self._select_cap(xf, cap, who)
+            counts, val_sel, report = ops.threshold_select(val, theta)
+            if hasattr(ctl_or_theta, "record"):
+                ctl_or_theta.record(counts, report)
+            decoder, dec_bias = self._nested_decoder()
+            return idx, val_sel, counts, self._decode_ragged(idx, val_sel, counts, decoder, dec_bias)
+
+    def forward_train_batch_topk(self, x, ctl, *, dense_latent: bool = True):
+        """The tuple of the model's ``forward_train`` with a ``grad_fn``, under the batch-wide selection of
+        ``forward_batch_topk``: the latent holds ``B * ctl.k`` entries in all, ``counts[r]`` of them in row r, and the
+        reconstruction decodes those through the model's training table.  Moves ``ctl``'s threshold state (on the device, in the
+        selection's kernel chain) and feeds ``model.activity`` with the selected entries only.  The backward walks the ragged
+        rows: ``train_row_grad_ragged`` -> ``train_csr_ragged`` -> the model's unit-gradient op -> ``train_col_sum``;
+        ``BinarySAE`` keeps its polarize term.  With ``ctl.cap == ctl.k`` every entry is selected and outputs and gradients
+        are ``forward_train``'s bit for bit."""
+        x, who = self._batch_topk_input(x, "forward_train_batch_topk")
+        lin = self.encoder.linear
+        D = lin.weight.shape[1]
+        if not ops.train_supported(D, ctl.cap):
+            raise ValueError(f"{who}: the gradient kernels take input_dim a multiple of 4 up to 4096 (got {D})")
+        if x.shape[0] * ctl.cap >= 2 ** 31:
+            raise ValueError(f"{who}: batch * cap = {x.shape[0] * ctl.cap} is not below 2^31")
+        dec_param, dec_bias = self.decoder.weight, self.decoder.bias
+        latent, recon, extra = _BatchTopKTrainStep.apply(self, ctl, bool(dense_latent), x, lin.weight, lin.bias, dec_param,
+                                                         dec_bias)
+        out = ((latent if dense_latent else None), recon)
+        return out if extra is None else out + (extra,)
+
+
+class _BatchTopKTrainStep(torch.autograd.Function):
+    """forward_train_batch_topk and its gradient.  The model supplies ``_nested_train_decoder() -> (table [H, D], step, extra
+    output or None)`` and ``_batch_unit_grad(offsets, entries, val, gv, x, g_recon, g_extra, want_encoder, want_decoder)``, its
+    unit-gradient kernel; the lists are [B, K] with stride K, of which row r uses the first counts[r] entries."""
+
+    @staticmethod
+    def forward(ctx, model, ctl, dense_latent, x, W_enc, b_enc, dec_param, b_dec):
+        table, step, extra = model._nested_train_decoder()
+        xf = as_f32c(x.detach())
+        idx, val = model._select_cap(xf, ctl.cap, f"{type(model).__name__}.forward_train_batch_topk")
+        theta, batches = ctl.state(xf.device)
+        counts, val_sel, report = ops.batch_select(val, xf.shape[0] * ctl.k, True, theta, batches, ctl.threshold_lr)
+        ctl.record(counts, report)
+        recon = ops.decode_ragged_table(idx, val_sel, counts, table, step, b_dec.detach())
+        latent = ops.densify(idx, val_sel, table.shape[0]) if dense_latent else None
+        if model.activity is not None:
+            model.activity.add_compact(idx, val_sel)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(xf, idx, val_sel, counts, table)
+        ctx.model, ctx.step, ctx.x_dtype = model, step, x.dtype
+        return latent, recon, extra
+
+    @staticmethod
+    def backward(ctx, g_latent, g_recon, g_extra):
+        xf, idx, val_sel, counts, table = ctx.saved_tensors
+        model = ctx.model
+        need_x, need_W, need_b, need_dec, need_bd = ctx.needs_input_grad[3:8]
+        want_units = need_W or need_b or need_dec
+        dx = dW = db = ddec = dbd = None
+        if need_x or want_units:
+            gv, dx = ops.train_row_grad_ragged(idx, counts, table, ctx.step, g_recon, g_latent,
+                                               model.encoder.linear.weight.detach(), want_dx=need_x)
+            if want_units:
+                offsets, entries = ops.train_csr_ragged(idx, counts, table.shape[0])
+                dW, db, ddec = model._batch_unit_grad(offsets, entries, val_sel, gv, xf, g_recon, g_extra, need_W or need_b,
+                                                      need_dec)
+        if need_bd:
+            dbd = ops.train_col_sum(g_recon) if g_recon is not None else torch.zeros_like(model.decoder.bias)
+        if dx is not None and dx.dtype != ctx.x_dtype:
+            dx = dx.to(ctx.x_dtype)
+        return (None, None, None, dx if need_x else None, dW if need_W else None, db if need_b else None,
+                ddec if need_dec else None, dbd)
 
 
 class _NestedTrainStep(torch.autograd.Function):

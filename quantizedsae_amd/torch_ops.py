@@ -1057,6 +1057,81 @@ def _(offsets, entries, val, gv, x, G, bounds, want_encoder, want_decoder):
             _f32((D, H if want_decoder else 0), x))
 
 
+# ---- BatchTopK of the top-k SAEs (include/qsae_batch.h) --------------------------------------------------------------------
+@_op("batch_select", mutates=("theta", "batches"))
+def _batch_select(val: Tensor, n_select: int, want_val: bool, theta: Optional[Tensor], batches: Optional[Tensor],
+                  lr: float) -> Tuple[Tensor, Tensor, Tensor]:
+    """-> (counts int32 [B], val_sel fp32 [B, K] ([0, K] when not wanted), report int64 [4]); theta / batches in place"""
+    counts, val_sel, report = _ops.batch_select(val, n_select, want_val, theta, batches, lr)
+    return counts, (val_sel if val_sel is not None else _f32((0, val.shape[1]), val)), report
+
+
+@_batch_select.register_fake
+def _(val, n_select, want_val, theta, batches, lr):
+    B, K = val.shape
+    return _i32((B,), val), _f32((B if want_val else 0, K), val), torch.empty((4,), dtype=torch.int64, device=val.device)
+
+
+@_op("threshold_select")
+def _threshold_select(val: Tensor, theta_dev: Optional[Tensor], theta_host: float, want_val: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    """-> (counts, val_sel, report) as batch_select; theta is theta_dev (read on the device) or, without one, theta_host"""
+    counts, val_sel, report = _ops.threshold_select(val, theta_dev if theta_dev is not None else theta_host, want_val)
+    return counts, (val_sel if val_sel is not None else _f32((0, val.shape[1]), val)), report
+
+
+@_threshold_select.register_fake
+def _(val, theta_dev, theta_host, want_val):
+    B, K = val.shape
+    return _i32((B,), val), _f32((B if want_val else 0, K), val), torch.empty((4,), dtype=torch.int64, device=val.device)
+
+
+@_op("decode_ragged_binary")
+def _decode_ragged_binary(idx: Tensor, val: Tensor, counts: Tensor, packed: Tensor, D: int, n_bits: int, step: float,
+                          bias: Optional[Tensor]) -> Tensor:
+    """-> fp32 [B, D]: row r decodes the first counts[r] entries of its list from the packed n-bit dictionary"""
+    return _ops.decode_ragged_binary(idx, val, counts, packed, D, n_bits, step, bias)
+
+
+@_decode_ragged_binary.register_fake
+def _(idx, val, counts, packed, D, n_bits, step, bias):
+    return _f32((idx.shape[0], D), idx)
+
+
+@_op("decode_ragged_table")
+def _decode_ragged_table(idx: Tensor, val: Tensor, counts: Tensor, table: Tensor, scale: float, bias: Optional[Tensor]) -> Tensor:
+    """-> fp32 [B, D]: row r decodes the first counts[r] entries of its list from an fp32 [H, D] table"""
+    return _ops.decode_ragged_table(idx, val, counts, table, scale, bias)
+
+
+@_decode_ragged_table.register_fake
+def _(idx, val, counts, table, scale, bias):
+    return _f32((idx.shape[0], table.shape[1]), idx)
+
+
+@_op("train_row_grad_ragged")
+def _train_row_grad_ragged(idx: Tensor, counts: Tensor, table: Tensor, step: float, g_recon: Optional[Tensor],
+                           g_latent: Optional[Tensor], W_enc: Optional[Tensor], want_dx: bool) -> Tuple[Tensor, Tensor]:
+    """-> (gv [B, K], dx [B, D] ([0, D] when not wanted))"""
+    gv, dx = _ops.train_row_grad_ragged(idx, counts, table, step, g_recon, g_latent, W_enc, want_dx)
+    return gv, (dx if dx is not None else _f32((0, table.shape[1]), idx))
+
+
+@_train_row_grad_ragged.register_fake
+def _(idx, counts, table, step, g_recon, g_latent, W_enc, want_dx):
+    return _f32(tuple(idx.shape), idx), _f32((idx.shape[0] if want_dx else 0, table.shape[1]), idx)
+
+
+@_op("train_csr_ragged")
+def _train_csr_ragged(idx: Tensor, counts: Tensor, H: int) -> Tuple[Tensor, Tensor]:
+    """-> (offsets int32 [H + 1], entries int32 [B K])"""
+    return _ops.train_csr_ragged(idx, counts, H)
+
+
+@_train_csr_ragged.register_fake
+def _(idx, counts, H):
+    return _i32((H + 1,), idx), _i32((idx.shape[0] * idx.shape[1],), idx)
+
+
 Q = torch.ops.qsae
 
 
@@ -1700,3 +1775,37 @@ def train_table_unit_grad_nested(offsets, entries, val, gv, x, G, bounds, want_e
     dW, db, dWd = Q.train_table_unit_grad_nested(offsets, entries, val, gv, x, G, [int(b) for b in bounds], bool(want_encoder),
                                                  bool(want_decoder))
     return (dW if want_encoder else None), (db if want_encoder else None), (dWd if want_decoder else None)
+
+
+BATCH_TOPK_MAX_K = _ops.BATCH_TOPK_MAX_K
+
+
+def batch_select(val, n_select, want_val=True, theta=None, batches=None, lr=0.01):
+    """-> (counts int32 [B], val_sel fp32 [B, K] or None, report int64 [4])"""
+    counts, val_sel, report = Q.batch_select(val, int(n_select), bool(want_val), theta, batches, float(lr))
+    return counts, (val_sel if want_val else None), report
+
+
+def threshold_select(val, theta, want_val=True):
+    """theta: a one-element fp32 device tensor (read on the device) or a number"""
+    on_dev = isinstance(theta, Tensor)
+    counts, val_sel, report = Q.threshold_select(val, theta if on_dev else None, 0.0 if on_dev else float(theta), bool(want_val))
+    return counts, (val_sel if want_val else None), report
+
+
+def decode_ragged_binary(idx, val, counts, packed, D, n_bits, step, bias=None):
+    return Q.decode_ragged_binary(idx, val, counts, packed, int(D), int(n_bits), float(step), bias)
+
+
+def decode_ragged_table(idx, val, counts, table, scale=1.0, bias=None):
+    return Q.decode_ragged_table(idx, val, counts, table, float(scale), bias)
+
+
+def train_row_grad_ragged(idx, counts, table, step, g_recon, g_latent, W_enc=None, want_dx=False):
+    """-> (gv fp32 [B, K], dx fp32 [B, D] or None)"""
+    gv, dx = Q.train_row_grad_ragged(idx, counts, table, float(step), g_recon, g_latent, W_enc if want_dx else None, bool(want_dx))
+    return gv, (dx if want_dx else None)
+
+
+def train_csr_ragged(idx, counts, H):
+    return Q.train_csr_ragged(idx, counts, int(H))

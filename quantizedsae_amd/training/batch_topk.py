@@ -1,0 +1,91 @@
+"""BatchTopK for the two top-k models (Bussmann et al., "BatchTopK Sparse Autoencoders"; the selection their Matryoshka SAEs
+train with): keep the ``B * k`` largest pre-activations of the whole batch instead of k per row, so a row spends as many units
+as it needs, and at inference one global threshold learned during training.
+
+    ctl = BatchTopK(model, k=65)                              cap = min(256, hidden_dim, 4 k) list places per row
+    outputs = model.forward_train_batch_topk(batch, ctl)      the tuple of forward_train; moves ctl's threshold
+    idx, val, counts, recon = model.forward_threshold(x, ctl) evaluation: every entry at or above the threshold
+
+Every row's top-``cap`` list is rank ordered, so the batch-wide selection (ties to the lowest row, then list position) is a
+prefix of every row's list: the whole result is one count per row, and the decode and the backward walk ``counts[r]`` entries
+of row r (csrc/batch_topk.hip, csrc/batch_topk_decode.hip).  The selection is BatchTopK capped at ``cap`` per row; it equals
+the uncapped one whenever no row is saturated (``report[1] == 0``), because a unit outside a row's top-``cap`` can beat the
+threshold only if the row's ``cap``-th entry does too.
+
+The threshold state -- ``theta`` (fp32) and ``batches`` (int64) -- lives on the device and is moved by the selection's own
+kernel chain: with m the smallest selected value of a batch, ``theta <- m`` on the first update and
+``theta <- theta + lr * (m - theta)`` afterwards, when m > 0.  Nothing is read back unless ``threshold()`` or ``summary()`` is
+called.  The models' state-dict keys stay the reference's; the controller has a ``state_dict()`` of its own.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+
+from .. import torch_ops as ops
+from ..sae.topk import TopKCore
+
+__all__ = ["BatchTopK"]
+
+
+class BatchTopK:
+    def __init__(self, model, k: Optional[int] = None, cap: Optional[int] = None, threshold_lr: float = 0.01) -> None:
+        if not isinstance(model, TopKCore):
+            raise TypeError(f"BatchTopK: expected one of the two top-k models (BinarySAE, BaselineSparseAutoencoder), got "
+                            f"{type(model).__name__}: the sparsity of the other classes is not a k")
+        H = int(model.encoder.linear.weight.shape[0])
+        if k is None:
+            k = model.top_k if hasattr(model, "top_k") else model.topk
+        k, limit = int(k), min(ops.BATCH_TOPK_MAX_K, H)
+        if not 1 <= k <= limit:
+            raise ValueError(f"BatchTopK: k = {k}; expected 1 .. {limit} (the kernels' limit of {ops.BATCH_TOPK_MAX_K} and "
+                             f"hidden_dim = {H})")
+        cap = min(limit, 4 * k) if cap is None else int(cap)
+        if not k <= cap <= limit:
+            raise ValueError(f"BatchTopK: cap = {cap}; expected k = {k} .. {limit} list places per row")
+        threshold_lr = float(threshold_lr)
+        if not 0.0 <= threshold_lr <= 1.0:
+            raise ValueError(f"BatchTopK: threshold_lr = {threshold_lr}; expected a rate in [0, 1]")
+        self.model, self.k, self.cap, self.threshold_lr = model, k, cap, threshold_lr
+        device = model.encoder.linear.weight.device
+        #: the inference threshold and the number of batches that have moved it, on the device
+        self.theta = torch.zeros((), dtype=torch.float32, device=device)
+        self.batches = torch.zeros((), dtype=torch.int64, device=device)
+        #: counts int32 [B] and report int64 [4] (selected, saturated rows, empty rows, bits of the smallest selected value) of
+        #: the last selection, on the device
+        self.counts: Optional[torch.Tensor] = None
+        self.report: Optional[torch.Tensor] = None
+
+    def state(self, device):
+        """-> (theta, batches) on ``device`` (moved there once, when the model has moved since)"""
+        if self.theta.device != device:
+            self.theta, self.batches = self.theta.to(device), self.batches.to(device)
+        return self.theta, self.batches
+
+    def record(self, counts: torch.Tensor, report: torch.Tensor) -> None:
+        self.counts, self.report = counts, report
+
+    def threshold(self) -> float:
+        """The learned threshold (one host read)."""
+        return float(self.theta)
+
+    def summary(self) -> dict:
+        """The last selection's report and the threshold as numbers (one host copy of five words)."""
+        if self.report is None:
+            raise ValueError("BatchTopK: no selection has run yet")
+        both = torch.cat([self.report.to(torch.float64), self.theta.reshape(1).to(torch.float64)]).tolist()
+        return {"selected": int(both[0]), "saturated_rows": int(both[1]), "empty_rows": int(both[2]), "threshold": both[4]}
+
+    def state_dict(self) -> dict:
+        return {"theta": self.theta.detach().cpu().clone(), "batches": self.batches.detach().cpu().clone(), "k": self.k,
+                "cap": self.cap, "threshold_lr": self.threshold_lr}
+
+    def load_state_dict(self, state: dict) -> None:
+        if int(state["k"]) != self.k or int(state["cap"]) != self.cap:
+            raise ValueError(f"BatchTopK: the state was saved with k = {int(state['k'])}, cap = {int(state['cap'])}; this "
+                             f"controller has k = {self.k}, cap = {self.cap}")
+        device = self.theta.device
+        self.theta = torch.as_tensor(state["theta"], dtype=torch.float32).reshape(()).to(device).clone()
+        self.batches = torch.as_tensor(state["batches"], dtype=torch.int64).reshape(()).to(device).clone()
+        self.threshold_lr = float(state["threshold_lr"])

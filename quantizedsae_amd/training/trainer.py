@@ -48,6 +48,12 @@ backward, ``trainer_loss`` the per-type loss, ``optim.Adam`` the step.  What dif
   ``default_nested_bounds(hidden_dim)`` = ``[H/8, H/4, H/2, H]``.  Logging steps gain ``recon_loss_level_{l}``; ``loss`` and
   ``recon_loss`` are the sums.  The last level is the model's reconstruction, so ``aux_k``, ``resample_every`` and
   ``activity_window`` work as before.
+* ``batch_topk=True`` (``baseline_sae`` and ``b_sae`` only; default ``False`` changes nothing) trains with BatchTopK
+  (``BatchTopK``, csrc/batch_topk.hip): ``model.forward_train_batch_topk`` keeps the ``batch * k`` largest pre-activations of
+  the whole batch, at most ``batch_topk_cap`` (default ``min(256, hidden_dim, 4 k)``) per row, and learns the inference
+  threshold on the device.  Logging steps gain ``batch_topk/threshold``, ``batch_topk/saturated_rows`` and
+  ``batch_topk/empty_rows``; nothing is read back between them.  ``aux_k``, ``resample_every`` and ``activity_window`` work
+  as before; together with ``nested_bounds`` it raises (nested levels over ragged rows are not built).
 * ``model=`` hands in the model instead of building the reference's.  The reference builds
   ``BinarySAE(input_dim, hidden_dim, n_bits)``, where ``n_bits`` lands in ``gamma`` and the decoder keeps its default of 8
   bits; that call is kept.
@@ -71,6 +77,7 @@ from .batches import ShuffledChunk
 from .loss import SAE_TYPES, trainer_loss
 from .activity import FeatureActivity, activity_line
 from .auxk import AUX_MAX_K, aux_k_loss
+from .batch_topk import BatchTopK
 from .nested import NESTED_TYPES, default_nested_bounds, nested_loss
 from .resample import ResampleReport, resample_dead, resample_line
 from .watch import WATCH_MODES, ModelWatch, watch_line
@@ -109,7 +116,8 @@ class Trainer:
                  log_every: int = 100, watch: Optional[str] = None, watch_freq: int = 256,
                  activity_window: Optional[int] = None, resample_every: Optional[int] = None, resample_seed: int = 0,
                  resample_scale: float = 0.2, aux_k: Optional[int] = None, aux_coef: float = 1 / 32,
-                 aux_refresh: Optional[int] = None, nested_bounds=None):
+                 aux_refresh: Optional[int] = None, nested_bounds=None, batch_topk: bool = False,
+                 batch_topk_cap: Optional[int] = None):
         if sae_type not in SAE_TYPES:
             raise ValueError(f"unknown sae_type {sae_type!r}; expected one of {', '.join(SAE_TYPES)}")
         if sae_type == "t_sae" and not rigL:
@@ -145,6 +153,13 @@ class Trainer:
         if nested_bounds is not None and sae_type not in NESTED_TYPES:
             raise ValueError(f"nested_bounds: the nested objective is built for baseline_sae and b_sae, the two top-k models; "
                              f"got {sae_type!r}")
+        if batch_topk and sae_type not in NESTED_TYPES:
+            raise ValueError(f"batch_topk: the batch-wide selection is built for baseline_sae and b_sae, the two top-k models; "
+                             f"got {sae_type!r}")
+        if batch_topk and nested_bounds is not None:
+            raise ValueError("batch_topk together with nested_bounds: nested levels over ragged rows are not built yet")
+        if batch_topk_cap is not None and not batch_topk:
+            raise ValueError("batch_topk_cap needs batch_topk=True")
         self.config = config
         self.sae_type = sae_type
         self.device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
@@ -195,11 +210,15 @@ class Trainer:
                     raise ValueError(f"nested_bounds = {nested_bounds!r}; expected None, 'default' or a list of bounds")
                 nested_bounds = default_nested_bounds(H)
             self.nested_bounds = ops.nested_bounds(nested_bounds, H, "Trainer: nested_bounds")
+        #: the BatchTopK controller (k = the model's top-k), or None
+        self.batch_topk = BatchTopK(self.model, cap=batch_topk_cap) if batch_topk else None
 
     # ---- one step ------------------------------------------------------------------------------------------------
     def _forward(self, batch, want_latent: bool):
         if self.nested_bounds is not None:
             return self.model.forward_train_nested(batch, self.nested_bounds, dense_latent=want_latent)
+        if self.batch_topk is not None:
+            return self.model.forward_train_batch_topk(batch, self.batch_topk, dense_latent=want_latent)
         if self.sae_type in ("b_sae", "baseline_sae"):
             return self.model.forward_train(batch, dense_latent=want_latent)
         return self.model.forward_train(batch)
@@ -293,6 +312,13 @@ class Trainer:
         dead list it ran over"""
         return {"aux_loss": self._aux_loss.item() if self._aux_loss is not None else 0.0,
                 "aux_units": int(self._aux_units.shape[0])}
+
+    def _batch_topk_metrics(self) -> dict:
+        """What a logging step adds with ``batch_topk``: the threshold and the last selection's saturated and empty rows (one
+        host copy of five words; no other step reads them)"""
+        b = self.batch_topk.summary()
+        return {"batch_topk/threshold": b["threshold"], "batch_topk/saturated_rows": b["saturated_rows"],
+                "batch_topk/empty_rows": b["empty_rows"]}
 
     def _activity_metrics(self, summary) -> dict:
         """What a logging step adds with ``activity_window``: the summary that ends the interval since the previous one"""
@@ -388,6 +414,8 @@ class Trainer:
                 metrics = self._metrics(outputs, losses) if log_step else None
                 if log_step and self.aux_k is not None:
                     metrics.update(self._aux_metrics())
+                if log_step and self.batch_topk is not None:
+                    metrics.update(self._batch_topk_metrics())
                 self._log(batch_idx, metrics, self._watched, summary, resampled)
         announce(None)
         chunk.check()
