@@ -242,6 +242,15 @@ BATCH_SIGNATURES = {
     "qsaeb_csr_ragged": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
 }
 
+# name -> (restype, argtypes) of the qsaem_* entry points of include/qsae_nested_batch.h (csrc/nested_ragged.hip): the nested
+# levels over the ragged rows of BatchTopK, a table of its own for the same reason.  Must list every symbol declared in
+# qsae_nested_batch.h.
+NESTED_BATCH_SIGNATURES = {
+    "qsaem_decode_nested_ragged_binary": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp, _i, _vp, _vp, _vp]),
+    "qsaem_decode_nested_ragged_table": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _f, _vp, _vp, _i, _vp, _vp, _vp]),
+    "qsaem_row_grad_nested_ragged": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _f, _vp, _vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+}
+
 
 class QsaeError(RuntimeError):
     """A libqsae_hip call returned a non-zero status."""
@@ -262,7 +271,7 @@ def _open(path: Path) -> C.CDLL:
             "(hipcc --offload-arch=gfx950).  quantizedsae_amd has no CPU / eager fallback.")
     lib = C.CDLL(str(path))
     for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(CURVE_SIGNATURES.items()) \
-            + list(NESTED_SIGNATURES.items()) + list(BATCH_SIGNATURES.items()):
+            + list(NESTED_SIGNATURES.items()) + list(BATCH_SIGNATURES.items()) + list(NESTED_BATCH_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here means the library is stale
         fn.restype = res
         fn.argtypes = args

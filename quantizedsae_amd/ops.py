@@ -3141,3 +3141,94 @@ def train_csr_ragged(idx: torch.Tensor, counts: torch.Tensor, H: int):
     ws = _train_ws(lib.qsaeb_csr_ragged_workspace_bytes(B, K, H), idx.device)
     check(lib.qsaeb_csr_ragged(_p(idx), _p(counts), B, K, H, _p(offsets), _p(entries), _p(ws), ws.numel(), _stream()))
     return offsets, entries
+
+
+# ---- nested levels over the ragged rows of BatchTopK (include/qsae_nested_batch.h, csrc/nested_ragged.hip) ------------------
+def _nested_ragged_out(bounds, B: int, D: int, device):
+    recon = torch.empty((len(bounds), B, D), dtype=torch.float32, device=device)
+    below = torch.empty((len(bounds), B), dtype=torch.int32, device=device)
+    return recon, below
+
+
+@_on_tensor_device
+def decode_nested_ragged_binary(idx, val, counts, packed, D: int, n_bits: int, step: float, bias, bounds):
+    """-> (levels fp32 [L, B, D], counts_below int32 [L, B]): level l of row r is decode_nested_binary on the first counts[r]
+    entries of its list, bit for bit; counts_below[l, r] = its kept entries below bounds[l].  An entry behind the prefix is not
+    read.  See qsaem_decode_nested_ragged_binary."""
+    who = "decode_nested_ragged_binary"
+    idx, val, counts = _batch_lists(who, idx, val, counts)
+    _dev(packed, f"{who}: packed", torch.uint8)
+    D, n_bits = int(D), int(n_bits)
+    _nested_D(who, D)
+    if not 1 <= n_bits <= 8:
+        raise ValueError(f"{who}: n_bits = {n_bits} is outside 1 .. 8")
+    if packed.dim() != 2 or packed.shape[1] != binary_row_bytes(D, n_bits) or not packed.is_contiguous() or packed.device != idx.device:
+        raise ValueError(f"{who}: packed is {tuple(packed.shape)}, expected contiguous [H, {binary_row_bytes(D, n_bits)}] on {idx.device}")
+    H = packed.shape[0]
+    bounds = nested_bounds(bounds, H, who)
+    b = _f32c(bias, "bias") if bias is not None else None
+    if b is not None and tuple(b.shape) != (D,):
+        raise ValueError(f"{who}: bias is {tuple(b.shape)}, expected [{D}]")
+    B, K = idx.shape
+    recon, below = _nested_ragged_out(bounds, B, D, idx.device)
+    check(_lib.load().qsaem_decode_nested_ragged_binary(_p(idx), _p(val), _p(counts), B, K, _p(packed), H, D, n_bits, float(step),
+                                                        _p(b), _bounds_arg(bounds), len(bounds), _p(recon), _p(below), _stream()))
+    return recon, below
+
+
+@_on_tensor_device
+def decode_nested_ragged_table(idx, val, counts, table: torch.Tensor, scale: float, bias, bounds):
+    """-> (levels fp32 [L, B, D], counts_below int32 [L, B]): level l of row r is decode_nested_table on the first counts[r]
+    entries of its list, bit for bit.  See qsaem_decode_nested_ragged_table."""
+    who = "decode_nested_ragged_table"
+    idx, val, counts = _batch_lists(who, idx, val, counts)
+    table = _f32c(table, "table")
+    if table.dim() != 2 or table.device != idx.device:
+        raise ValueError(f"{who}: table is {tuple(table.shape)} on {table.device}, expected [H, D] on {idx.device}")
+    H, D = table.shape
+    _nested_D(who, D)
+    bounds = nested_bounds(bounds, H, who)
+    b = _f32c(bias, "bias") if bias is not None else None
+    if b is not None and tuple(b.shape) != (D,):
+        raise ValueError(f"{who}: bias is {tuple(b.shape)}, expected [{D}]")
+    B, K = idx.shape
+    recon, below = _nested_ragged_out(bounds, B, D, idx.device)
+    check(_lib.load().qsaem_decode_nested_ragged_table(_p(idx), _p(val), _p(counts), B, K, _p(table), H, D, float(scale), _p(b),
+                                                       _bounds_arg(bounds), len(bounds), _p(recon), _p(below), _stream()))
+    return recon, below
+
+
+@_on_tensor_device
+def train_row_grad_nested_ragged(idx: torch.Tensor, counts: torch.Tensor, table: torch.Tensor, step: float, g_levels, bounds,
+                                 g_latent: Optional[torch.Tensor], W_enc: Optional[torch.Tensor] = None, want_dx: bool = False):
+    """-> (G fp32 [L, B, D], gv fp32 [B, K], dx fp32 [B, D] or None): train_row_grad_nested on the first counts[r] entries of
+    every row, bit for bit; G is written for every row, gv behind the prefix is +0.  See qsaem_row_grad_nested_ragged."""
+    who = "train_row_grad_nested_ragged"
+    idx, _, counts = _batch_lists(who, idx, None, counts)
+    table = _f32c(table, "table")
+    B, K = idx.shape
+    H, D = table.shape
+    _nested_D(who, D)
+    bounds = nested_bounds(bounds, H, who)
+    g_levels = list(g_levels)
+    if len(g_levels) != len(bounds):
+        raise ValueError(f"{who}: {len(g_levels)} level gradients for {len(bounds)} levels")
+    gs = []
+    for l, g in enumerate(g_levels):
+        if g is not None:
+            g = _f32c(g, f"g_levels[{l}]")
+            if tuple(g.shape) != (B, D) or g.device != idx.device:
+                raise ValueError(f"{who}: g_levels[{l}] is {tuple(g.shape)} on {g.device}, expected [{B}, {D}] on {idx.device}")
+        gs.append(g)
+    gL, gl_ld = _latent_grad(g_latent, B, H)
+    W = _f32c(W_enc, "W_enc") if want_dx else None
+    if W is not None and tuple(W.shape) != (H, D):
+        raise ValueError(f"W_enc is {tuple(W.shape)}, expected [{H}, {D}]")
+    G = torch.empty((len(bounds), B, D), dtype=torch.float32, device=idx.device)
+    gv = torch.empty((B, K), dtype=torch.float32, device=idx.device)
+    dx = torch.empty((B, D), dtype=torch.float32, device=idx.device) if want_dx else None
+    garr = (C.c_void_p * len(gs))(*[0 if g is None else g.data_ptr() for g in gs])     # host array of device pointers
+    check(_lib.load().qsaem_row_grad_nested_ragged(_p(idx), _p(counts), B, K, _p(table), H, D, float(step),
+                                                   C.cast(garr, C.c_void_p), _bounds_arg(bounds), len(bounds), _p(gL), int(gl_ld),
+                                                   _p(W), _p(G), _p(gv), _p(dx), _stream()))
+    return G, gv, dx

@@ -211,21 +211,25 @@ class TopKCore:
         number (``cap`` defaults to ``min(256, hidden_dim)``)."""
         with torch.no_grad():
             x, who = self._batch_topk_input(x, "forward_threshold")
-            xf = as_f32c(x)
-            H = int(self.encoder.linear.weight.shape[0])
-            if hasattr(ctl_or_theta, "theta") and hasattr(ctl_or_theta, "cap"):
-                theta = ctl_or_theta.state(xf.device)[0]
-                cap = ctl_or_theta.cap if cap is None else int(cap)
-            else:
-                theta, cap = float(ctl_or_theta), (min(ops.BATCH_TOPK_MAX_K, H) if cap is None else int(cap))
-            if not 1 <= cap <= min(ops.BATCH_TOPK_MAX_K, H):
-                raise ValueError(f"{who}: cap = {cap}; expected 1 .. {min(ops.BATCH_TOPK_MAX_K, H)}")
-            idx, val = self._select_cap(xf, cap, who)
-            counts, val_sel, report = ops.threshold_select(val, theta)
+            idx, val_sel, counts, report = self._select_threshold(as_f32c(x), ctl_or_theta, cap, who)
             if hasattr(ctl_or_theta, "record"):
                 ctl_or_theta.record(counts, report)
             decoder, dec_bias = self._nested_decoder()
             return idx, val_sel, counts, self._decode_ragged(idx, val_sel, counts, decoder, dec_bias)
+
+    def _select_threshold(self, xf, ctl_or_theta, cap, who: str):
+        """-> (idx, val_sel, counts, report): every entry of the rows' top-``cap`` lists that is >= the threshold"""
+        H = int(self.encoder.linear.weight.shape[0])
+        if hasattr(ctl_or_theta, "theta") and hasattr(ctl_or_theta, "cap"):
+            theta = ctl_or_theta.state(xf.device)[0]
+            cap = ctl_or_theta.cap if cap is None else int(cap)
+        else:
+            theta, cap = float(ctl_or_theta), (min(ops.BATCH_TOPK_MAX_K, H) if cap is None else int(cap))
+        if not 1 <= cap <= min(ops.BATCH_TOPK_MAX_K, H):
+            raise ValueError(f"{who}: cap = {cap}; expected 1 .. {min(ops.BATCH_TOPK_MAX_K, H)}")
+        idx, val = self._select_cap(xf, cap, who)
+        counts, val_sel, report = ops.threshold_select(val, theta)
+        return idx, val_sel, counts, report
 
     def forward_train_batch_topk(self, x, ctl, *, dense_latent: bool = True):
         """The tuple of the model's ``forward_train`` with a ``grad_fn``, under the batch-wide selection of
@@ -247,6 +251,119 @@ class TopKCore:
                                                          dec_bias)
         out = ((latent if dense_latent else None), recon)
         return out if extra is None else out + (extra,)
+
+
+    # -- Matryoshka BatchTopK: nested levels over the ragged rows ------------------------------------------------------------
+    def _decode_nested_ragged(self, idx, val, counts, decoder, dec_bias, bounds):
+        """-> (levels [L, B, D], counts_below [L, B])"""
+        if decoder[0] == "packed":
+            D = self.encoder.linear.weight.shape[1]
+            return ops.decode_nested_ragged_binary(idx, val, counts, decoder[1], D, decoder[2], decoder[3], dec_bias, bounds)
+        return ops.decode_nested_ragged_table(idx, val, counts, decoder[1], decoder[2], dec_bias, bounds)
+
+    def forward_nested_batch_topk(self, x, ctl, bounds):
+        """``(idx int32 [B,K], val_sel fp32 [B,K], counts int32 [B], levels fp32 [L,B,D])`` without a ``grad_fn``: the selection
+        of ``forward_batch_topk`` and, for every ``bounds[l]`` (ascending, the last one ``hidden_dim``), the reconstruction from
+        the selected units below it, decoded from what ``forward()`` decodes from.  All levels come from one walk over the first
+        ``counts[r]`` entries of each row's list (csrc/nested_ragged.hip); an entry behind the prefix is never read; the last
+        level is ``forward_batch_topk``'s reconstruction.  ``ctl.counts`` and ``ctl.report`` are recorded as there, and
+        ``ctl.level_counts`` (int32 [L,B], on the device) holds every row's selected entries below each bound."""
+        with torch.no_grad():
+            x, who = self._batch_topk_input(x, "forward_nested_batch_topk")
+            bounds = ops.nested_bounds(bounds, self.encoder.linear.weight.shape[0], who)
+            xf = as_f32c(x)
+            idx, val = self._select_cap(xf, ctl.cap, who)
+            counts, val_sel, report = ops.batch_select(val, xf.shape[0] * ctl.k)
+            ctl.record(counts, report)
+            decoder, dec_bias = self._nested_decoder()
+            levels, ctl.level_counts = self._decode_nested_ragged(idx, val_sel, counts, decoder, dec_bias, bounds)
+            return idx, val_sel, counts, levels
+
+    def forward_nested_threshold(self, x, ctl_or_theta, bounds, cap=None):
+        """``forward_nested_batch_topk`` with the selection of ``forward_threshold``: row r keeps every entry of its top-``cap``
+        list that is ``>=`` the threshold (``ctl_or_theta``: a ``training.BatchTopK`` or a number, as there).  With a
+        ``BatchTopK``, ``counts``, ``report`` and ``level_counts`` are recorded on it."""
+        return self._nested_threshold(x, ctl_or_theta, bounds, cap)[:4]
+
+    def _nested_threshold(self, x, ctl_or_theta, bounds, cap):
+        """-> (idx, val_sel, counts, levels, counts_below [L, B]) of forward_nested_threshold"""
+        with torch.no_grad():
+            x, who = self._batch_topk_input(x, "forward_nested_threshold")
+            bounds = ops.nested_bounds(bounds, self.encoder.linear.weight.shape[0], who)
+            idx, val_sel, counts, report = self._select_threshold(as_f32c(x), ctl_or_theta, cap, who)
+            decoder, dec_bias = self._nested_decoder()
+            levels, below = self._decode_nested_ragged(idx, val_sel, counts, decoder, dec_bias, bounds)
+            if hasattr(ctl_or_theta, "record"):
+                ctl_or_theta.record(counts, report)
+                ctl_or_theta.level_counts = below
+            return idx, val_sel, counts, levels, below
+
+    def forward_train_nested_batch_topk(self, x, ctl, bounds, *, dense_latent: bool = True):
+        """The tuple of the model's ``forward_train_nested`` with a ``grad_fn`` -- ``training.nested_loss`` consumes it
+        unchanged -- under the batch-wide selection of ``forward_batch_topk``: the training recipe of the Matryoshka SAEs of
+        Bussmann et al.  ``recon_l`` decodes, through the model's training table, the selected units below ``bounds[l]`` from
+        the first ``counts[r]`` entries of every row.  Moves ``ctl``'s threshold state (on the device, in the selection's
+        kernel chain), records ``ctl.counts``, ``ctl.report`` and ``ctl.level_counts``, and feeds ``model.activity`` once, with
+        the selected entries only.  The backward walks the ragged rows: ``train_row_grad_nested_ragged`` ->
+        ``train_csr_ragged`` -> the model's nested unit-gradient op -> ``train_col_sum(G[0])``.  With ``ctl.cap == ctl.k`` it
+        is ``forward_train_nested`` bit for bit, with ``bounds = [hidden_dim]`` ``forward_train_batch_topk``."""
+        x, who = self._batch_topk_input(x, "forward_train_nested_batch_topk")
+        lin = self.encoder.linear
+        H, D = lin.weight.shape
+        bounds = ops.nested_bounds(bounds, H, who)
+        if not ops.train_supported(D, ctl.cap):
+            raise ValueError(f"{who}: the gradient kernels take input_dim a multiple of 4 up to 4096 (got {D})")
+        if x.shape[0] * ctl.cap >= 2 ** 31:
+            raise ValueError(f"{who}: batch * cap = {x.shape[0] * ctl.cap} is not below 2^31")
+        latent, levels, extra = _NestedBatchTopKTrainStep.apply(self, ctl, bool(dense_latent), tuple(bounds), x, lin.weight,
+                                                                lin.bias, self.decoder.weight, self.decoder.bias)
+        out = ((latent if dense_latent else None), tuple(levels[l] for l in range(len(bounds))))
+        return out if extra is None else out + (extra,)
+
+
+class _NestedBatchTopKTrainStep(torch.autograd.Function):
+    """forward_train_nested_batch_topk and its gradient: _BatchTopKTrainStep's selection and ragged lists ([B, K] with stride K,
+    row r uses the first counts[r] entries), _NestedTrainStep's levels (the rows of ONE output tensor, whose gradient's suffix
+    sums G reach the dictionary rows; include/qsae_nested_batch.h).  The model supplies what those two ask for."""
+
+    @staticmethod
+    def forward(ctx, model, ctl, dense_latent, bounds, x, W_enc, b_enc, dec_param, b_dec):
+        table, step, extra = model._nested_train_decoder()
+        xf = as_f32c(x.detach())
+        idx, val = model._select_cap(xf, ctl.cap, f"{type(model).__name__}.forward_train_nested_batch_topk")
+        theta, batches = ctl.state(xf.device)
+        counts, val_sel, report = ops.batch_select(val, xf.shape[0] * ctl.k, True, theta, batches, ctl.threshold_lr)
+        ctl.record(counts, report)
+        levels, ctl.level_counts = ops.decode_nested_ragged_table(idx, val_sel, counts, table, step, b_dec.detach(), bounds)
+        latent = ops.densify(idx, val_sel, table.shape[0]) if dense_latent else None
+        if model.activity is not None:
+            model.activity.add_compact(idx, val_sel)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(xf, idx, val_sel, counts, table)
+        ctx.model, ctx.step, ctx.bounds, ctx.x_dtype = model, step, bounds, x.dtype
+        return latent, levels, extra
+
+    @staticmethod
+    def backward(ctx, g_latent, g_levels, g_extra):
+        xf, idx, val_sel, counts, table = ctx.saved_tensors
+        model, bounds = ctx.model, ctx.bounds
+        need_x, need_W, need_b, need_dec, need_bd = ctx.needs_input_grad[4:9]
+        want_units = need_W or need_b or need_dec
+        dx = dW = db = ddec = dbd = None
+        if (need_x or want_units or need_bd) and not (g_latent is None and g_levels is None and g_extra is None):
+            g_list = [None] * len(bounds) if g_levels is None else [g_levels[l] for l in range(len(bounds))]
+            G, gv, dx = ops.train_row_grad_nested_ragged(idx, counts, table, ctx.step, g_list, bounds, g_latent,
+                                                         model.encoder.linear.weight.detach(), want_dx=need_x)
+            if want_units:
+                offsets, entries = ops.train_csr_ragged(idx, counts, table.shape[0])
+                dW, db, ddec = model._nested_unit_grad(offsets, entries, val_sel, gv, xf, G, bounds, g_extra, need_W or need_b,
+                                                       need_dec)
+            if need_bd:
+                dbd = ops.train_col_sum(G[0])                  # every level adds the bias: its gradient is the whole sum
+            if dx is not None and dx.dtype != ctx.x_dtype:
+                dx = dx.to(ctx.x_dtype)
+        return (None, None, None, None, dx if need_x else None, dW if need_W else None, db if need_b else None,
+                ddec if need_dec else None, dbd if need_bd else None)
 
 
 class _BatchTopKTrainStep(torch.autograd.Function):

@@ -1132,6 +1132,46 @@ def _(idx, counts, H):
     return _i32((H + 1,), idx), _i32((idx.shape[0] * idx.shape[1],), idx)
 
 
+# ---- nested levels over the ragged rows of BatchTopK (include/qsae_nested_batch.h) ------------------------------------------
+@_op("decode_nested_ragged_binary")
+def _decode_nested_ragged_binary(idx: Tensor, val: Tensor, counts: Tensor, packed: Tensor, D: int, n_bits: int, step: float,
+                                 bias: Optional[Tensor], bounds: List[int]) -> Tuple[Tensor, Tensor]:
+    """-> (levels fp32 [L, B, D], counts_below int32 [L, B]) from the first counts[r] entries of every row's list"""
+    return _ops.decode_nested_ragged_binary(idx, val, counts, packed, D, n_bits, step, bias, bounds)
+
+
+@_decode_nested_ragged_binary.register_fake
+def _(idx, val, counts, packed, D, n_bits, step, bias, bounds):
+    return _f32((len(bounds), idx.shape[0], D), idx), _i32((len(bounds), idx.shape[0]), idx)
+
+
+@_op("decode_nested_ragged_table")
+def _decode_nested_ragged_table(idx: Tensor, val: Tensor, counts: Tensor, table: Tensor, scale: float, bias: Optional[Tensor],
+                                bounds: List[int]) -> Tuple[Tensor, Tensor]:
+    """-> (levels fp32 [L, B, D], counts_below int32 [L, B]) from an fp32 [H, D] table"""
+    return _ops.decode_nested_ragged_table(idx, val, counts, table, scale, bias, bounds)
+
+
+@_decode_nested_ragged_table.register_fake
+def _(idx, val, counts, table, scale, bias, bounds):
+    return _f32((len(bounds), idx.shape[0], table.shape[1]), idx), _i32((len(bounds), idx.shape[0]), idx)
+
+
+@_op("train_row_grad_nested_ragged")
+def _train_row_grad_nested_ragged(idx: Tensor, counts: Tensor, table: Tensor, step: float, g_levels: List[Optional[Tensor]],
+                                  bounds: List[int], g_latent: Optional[Tensor], W_enc: Optional[Tensor],
+                                  want_dx: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    """-> (G [L, B, D], gv [B, K], dx [B, D] ([0, D] when not wanted))"""
+    G, gv, dx = _ops.train_row_grad_nested_ragged(idx, counts, table, step, g_levels, bounds, g_latent, W_enc, want_dx)
+    return G, gv, (dx if dx is not None else _f32((0, table.shape[1]), idx))
+
+
+@_train_row_grad_nested_ragged.register_fake
+def _(idx, counts, table, step, g_levels, bounds, g_latent, W_enc, want_dx):
+    B, D = idx.shape[0], table.shape[1]
+    return _f32((len(bounds), B, D), idx), _f32(tuple(idx.shape), idx), _f32((B if want_dx else 0, D), idx)
+
+
 Q = torch.ops.qsae
 
 
@@ -1809,3 +1849,20 @@ def train_row_grad_ragged(idx, counts, table, step, g_recon, g_latent, W_enc=Non
 
 def train_csr_ragged(idx, counts, H):
     return Q.train_csr_ragged(idx, counts, int(H))
+
+
+def decode_nested_ragged_binary(idx, val, counts, packed, D, n_bits, step, bias, bounds):
+    """-> (levels fp32 [L, B, D], counts_below int32 [L, B])"""
+    return Q.decode_nested_ragged_binary(idx, val, counts, packed, int(D), int(n_bits), float(step), bias, [int(b) for b in bounds])
+
+
+def decode_nested_ragged_table(idx, val, counts, table, scale, bias, bounds):
+    """-> (levels fp32 [L, B, D], counts_below int32 [L, B])"""
+    return Q.decode_nested_ragged_table(idx, val, counts, table, float(scale), bias, [int(b) for b in bounds])
+
+
+def train_row_grad_nested_ragged(idx, counts, table, step, g_levels, bounds, g_latent, W_enc=None, want_dx=False):
+    """-> (G fp32 [L, B, D], gv fp32 [B, K], dx fp32 [B, D] or None)"""
+    G, gv, dx = Q.train_row_grad_nested_ragged(idx, counts, table, float(step), list(g_levels), [int(b) for b in bounds], g_latent,
+                                               W_enc if want_dx else None, bool(want_dx))
+    return G, gv, (dx if want_dx else None)

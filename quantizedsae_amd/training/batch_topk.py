@@ -5,6 +5,8 @@ as it needs, and at inference one global threshold learned during training (DESI
     ctl = BatchTopK(model, k=65)                              cap = min(256, hidden_dim, 4 k) list places per row
     outputs = model.forward_train_batch_topk(batch, ctl)      the tuple of forward_train; moves ctl's threshold
     idx, val, counts, recon = model.forward_threshold(x, ctl) evaluation: every entry at or above the threshold
+    outputs = model.forward_train_nested_batch_topk(batch, ctl, bounds)    the same selection, one reconstruction per
+                                                              dictionary prefix (the tuple of forward_train_nested)
 
 Every row's top-``cap`` list is rank ordered, so the batch-wide selection (ties to the lowest row, then list position) is a
 prefix of every row's list: the whole result is one count per row, and the decode and the backward walk ``counts[r]`` entries
@@ -56,6 +58,9 @@ class BatchTopK:
         #: the last selection, on the device
         self.counts: Optional[torch.Tensor] = None
         self.report: Optional[torch.Tensor] = None
+        #: int32 [L, B]: every row's selected entries below each bound, left by the last nested selection
+        #: (forward_nested_batch_topk, forward_nested_threshold, forward_train_nested_batch_topk), on the device
+        self.level_counts: Optional[torch.Tensor] = None
 
     def state(self, device):
         """-> (theta, batches) on ``device`` (moved there once, when the model has moved since)"""

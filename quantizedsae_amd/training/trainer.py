@@ -53,7 +53,13 @@ backward, ``trainer_loss`` the per-type loss, ``optim.Adam`` the step.  What dif
   the whole batch, at most ``batch_topk_cap`` (default ``min(256, hidden_dim, 4 k)``) per row, and learns the inference
   threshold on the device.  Logging steps gain ``batch_topk/threshold``, ``batch_topk/saturated_rows`` and
   ``batch_topk/empty_rows``; nothing is read back between them.  ``aux_k``, ``resample_every`` and ``activity_window`` work
-  as before; together with ``nested_bounds`` it raises (nested levels over ragged rows are not built).
+  as before.  Together with ``nested_bounds`` it raises: that keyword means the per-row top-k of ``forward_train_nested``, and
+  the combination is asked for by name, with ``batch_topk_nested_bounds``.
+* ``batch_topk_nested_bounds="default" | [b_0, ..., b_{L-1}]`` (needs ``batch_topk=True``; default ``None`` changes nothing)
+  trains the Matryoshka SAE as Bussmann et al. do, with BatchTopK: ``model.forward_train_nested_batch_topk`` gives one
+  reconstruction per dictionary prefix from the batch-wide selection (csrc/nested_ragged.hip), the loss is ``nested_loss``,
+  and AuxK takes the last level.  Logging steps gain ``recon_loss_level_{l}`` and ``l0_level_{l}``, the mean number of selected
+  units below ``b_l`` per row (one small host copy; none on other steps), next to the ``batch_topk/*`` metrics.
 * ``model=`` hands in the model instead of building the reference's.  The reference builds
   ``BinarySAE(input_dim, hidden_dim, n_bits)``, where ``n_bits`` lands in ``gamma`` and the decoder keeps its default of 8
   bits; that call is kept.
@@ -117,7 +123,7 @@ class Trainer:
                  activity_window: Optional[int] = None, resample_every: Optional[int] = None, resample_seed: int = 0,
                  resample_scale: float = 0.2, aux_k: Optional[int] = None, aux_coef: float = 1 / 32,
                  aux_refresh: Optional[int] = None, nested_bounds=None, batch_topk: bool = False,
-                 batch_topk_cap: Optional[int] = None):
+                 batch_topk_cap: Optional[int] = None, batch_topk_nested_bounds=None):
         if sae_type not in SAE_TYPES:
             raise ValueError(f"unknown sae_type {sae_type!r}; expected one of {', '.join(SAE_TYPES)}")
         if sae_type == "t_sae" and not rigL:
@@ -157,7 +163,10 @@ class Trainer:
             raise ValueError(f"batch_topk: the batch-wide selection is built for baseline_sae and b_sae, the two top-k models; "
                              f"got {sae_type!r}")
         if batch_topk and nested_bounds is not None:
-            raise ValueError("batch_topk together with nested_bounds: nested levels over ragged rows are not built yet")
+            raise ValueError("batch_topk together with nested_bounds: nested_bounds selects k units per row; the nested levels "
+                             "of a batch-wide selection are asked for with batch_topk_nested_bounds")
+        if batch_topk_nested_bounds is not None and not batch_topk:
+            raise ValueError("batch_topk_nested_bounds needs batch_topk=True (nested_bounds is the keyword of the per-row top-k)")
         if batch_topk_cap is not None and not batch_topk:
             raise ValueError("batch_topk_cap needs batch_topk=True")
         self.config = config
@@ -202,19 +211,24 @@ class Trainer:
         self.aux_coef = float(aux_coef)
         self.aux_refresh = int(aux_refresh) if aux_refresh is not None else self.log_every
         self._aux_units, self._aux_steps, self._aux_loss = None, 0, None   # the dead list in use, steps taken with it, last loss
+        #: the bounds of the nested objective, from ``nested_bounds`` or (with BatchTopK) ``batch_topk_nested_bounds``, or None
         self.nested_bounds = None
-        if nested_bounds is not None:
-            H = self.model.encoder.linear.weight.shape[0]
-            if isinstance(nested_bounds, str):
-                if nested_bounds != "default":
-                    raise ValueError(f"nested_bounds = {nested_bounds!r}; expected None, 'default' or a list of bounds")
-                nested_bounds = default_nested_bounds(H)
-            self.nested_bounds = ops.nested_bounds(nested_bounds, H, "Trainer: nested_bounds")
+        for name, given in (("nested_bounds", nested_bounds), ("batch_topk_nested_bounds", batch_topk_nested_bounds)):
+            if given is not None:
+                H = self.model.encoder.linear.weight.shape[0]
+                if isinstance(given, str):
+                    if given != "default":
+                        raise ValueError(f"{name} = {given!r}; expected None, 'default' or a list of bounds")
+                    given = default_nested_bounds(H)
+                self.nested_bounds = ops.nested_bounds(given, H, f"Trainer: {name}")
         #: the BatchTopK controller (k = the model's top-k), or None
         self.batch_topk = BatchTopK(self.model, cap=batch_topk_cap) if batch_topk else None
 
     # ---- one step ------------------------------------------------------------------------------------------------
     def _forward(self, batch, want_latent: bool):
+        if self.nested_bounds is not None and self.batch_topk is not None:
+            return self.model.forward_train_nested_batch_topk(batch, self.batch_topk, self.nested_bounds,
+                                                              dense_latent=want_latent)
         if self.nested_bounds is not None:
             return self.model.forward_train_nested(batch, self.nested_bounds, dense_latent=want_latent)
         if self.batch_topk is not None:
@@ -317,8 +331,12 @@ class Trainer:
         """What a logging step adds with ``batch_topk``: the threshold and the last selection's saturated and empty rows (one
         host copy of five words; no other step reads them)"""
         b = self.batch_topk.summary()
-        return {"batch_topk/threshold": b["threshold"], "batch_topk/saturated_rows": b["saturated_rows"],
-                "batch_topk/empty_rows": b["empty_rows"]}
+        d = {"batch_topk/threshold": b["threshold"], "batch_topk/saturated_rows": b["saturated_rows"],
+             "batch_topk/empty_rows": b["empty_rows"]}
+        if self.nested_bounds is not None:                     # the mean selected units per row below every bound (one copy)
+            l0 = self.batch_topk.level_counts.to(torch.float64).mean(dim=1).tolist()
+            d.update({f"l0_level_{l}": v for l, v in enumerate(l0)})
+        return d
 
     def _activity_metrics(self, summary) -> dict:
         """What a logging step adds with ``activity_window``: the summary that ends the interval since the previous one"""
