@@ -251,6 +251,20 @@ NESTED_BATCH_SIGNATURES = {
     "qsaem_row_grad_nested_ragged": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _f, _vp, _vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# name -> (restype, argtypes) of the qsaek_* entry points of include/qsae_multik.h (csrc/multi_topk.hip): the Multi-TopK
+# objective of the top-k SAEs, a table of its own for the same reason.  Must list every symbol declared in qsae_multik.h.
+MULTIK_SIGNATURES = {
+    "qsaek_decode_multik_binary": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp, _i, _vp, _vp]),
+    "qsaek_decode_multik_table": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _f, _vp, _vp, _i, _vp, _vp]),
+    "qsaek_row_grad_multik": (_i, [_vp, _i, _i, _vp, _i, _i, _f, _vp, _vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "qsaek_train_unit_grad_multik_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "qsaek_train_unit_grad_multik": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _f, _vp, _vp, _vp,
+                                          _vp, _vp, _sz, _vp]),
+    "qsaek_train_table_unit_grad_multik_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "qsaek_train_table_unit_grad_multik": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp,
+                                                _sz, _vp]),
+}
+
 
 class QsaeError(RuntimeError):
     """A libqsae_hip call returned a non-zero status."""
@@ -271,7 +285,7 @@ def _open(path: Path) -> C.CDLL:
             "(hipcc --offload-arch=gfx950).  quantizedsae_amd has no CPU / eager fallback.")
     lib = C.CDLL(str(path))
     for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(CURVE_SIGNATURES.items()) \
-            + list(NESTED_SIGNATURES.items()) + list(BATCH_SIGNATURES.items()) + list(NESTED_BATCH_SIGNATURES.items()):
+            + list(NESTED_SIGNATURES.items()) + list(BATCH_SIGNATURES.items()) + list(NESTED_BATCH_SIGNATURES.items()) + list(MULTIK_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here means the library is stale
         fn.restype = res
         fn.argtypes = args

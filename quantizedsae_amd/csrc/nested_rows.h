@@ -173,6 +173,8 @@ __device__ __forceinline__ void nd_st4(float* p, nd_f32x4 v) { *reinterpret_cast
 // Row r: G for the whole row whatever `c` is; gv and dx over the first `c` entries of the list (idx, gv: rows `ld` entries
 // apart; the caller writes gv behind the prefix).  Lane l owns columns 4 (l + 64 i) .. + 3 in every phase, so the G it reads
 // in the dot products is the G it stored.  G is read and written through the same pointer: no __restrict__ on it.
+// BY_RANK (csrc/multi_topk.hip): lv.bounds are rank prefixes and entry j reads G[unit_level(lv, j)], not G[unit_level(lv, h)].
+template <bool BY_RANK = false>
 __device__ __forceinline__ void nested_row_body(bool active, int r, const int32_t* __restrict__ idx, int c, int ld, int B, int H,
                                                 int D, const float* __restrict__ table, float step, const LevelGrads& gl,
                                                 const UnitLevels& lv, const float* __restrict__ gL, long long gl_ld,
@@ -187,7 +189,7 @@ __device__ __forceinline__ void nested_row_body(bool active, int r, const int32_
         for (int j = lane; j < c; j += 64) {
             const int h = clamp_unit(idx[static_cast<long long>(r) * ld + j], H);
             s_h[wave][j] = h;
-            s_l[wave][j] = unit_level(lv, h);
+            s_l[wave][j] = unit_level(lv, BY_RANK ? j : h);
         }
         for (int q = lane; q < D4; q += 64) {
             nd_f32x4 acc = {0.f, 0.f, 0.f, 0.f};

@@ -130,7 +130,8 @@ struct UnitArgs {
     float* slab;            // [slab_rows][slab_ld]: partials of the chunks of split lists
     int slab_rows, slab_ld;
     float* dT;              // TABLE instantiation: [H][D] = sum v gR (the decoder.weight gradient, transposed) or nullptr
-    UnitLevels lv;          // lv.n > 0: gR is [lv.n][B][D] and unit h reads level unit_level(lv, h) of it (qsae_nested.h)
+    UnitLevels lv;          // lv.n > 0: gR is [lv.n][B][D] and unit h reads level unit_level(lv, h) of it (qsae_nested.h);
+                            // BY_RANK kernels: entry e reads level unit_level(lv, e % k), lv.bounds = ks (qsae_multik.h)
 };
 
 // dlogit row h from s_dint[D] (dInt, step applied); the whole workgroup calls it
@@ -159,12 +160,15 @@ __device__ __forceinline__ void unit_logit_row(const UnitArgs& a, int h, const f
 // One workgroup per chunk of a unit list (every unit has at least one chunk, empty lists included).  A unit with one
 // chunk is finished here; the chunks of a split list store their partials in the slab for unit_final_kernel.
 // TABLE = false: the BinarySAE epilogue (dInt -> LDS -> logit-gradient row); TABLE = true: the row of sums goes to dT as is.
-template <bool TABLE>
+// BY_RANK = false: the gradient row is looked up by unit (one tensor per workgroup); BY_RANK = true: by entry, from the rank
+// e % k of the entry in its row's list (Multi-TopK) -- the same sums in the same order, only the address of each term differs.
+template <bool TABLE, bool BY_RANK = false>
 __global__ void __launch_bounds__(256)
 unit_chunk_kernel(UnitArgs a) {
     extern __shared__ float s_dint[];                      // [D]
     __shared__ int s_r[kTrainChunk];
     __shared__ float s_v[kTrainChunk], s_gv[kTrainChunk];
+    __shared__ int s_p[BY_RANK ? kTrainChunk : 1];         // the point of every entry of the chunk
     const int g = blockIdx.x;
     if (g >= a.chunk_off[a.H]) return;                     // workgroup-uniform: the grid is an upper bound
     int lo = 0, hi = a.H - 1;                              // the unit: largest h with chunk_off[h] <= g
@@ -183,6 +187,7 @@ unit_chunk_kernel(UnitArgs a) {
         s_r[i] = static_cast<int>(e / a.k);
         s_v[i] = a.val[e];
         s_gv[i] = a.gv[e];
+        if constexpr (BY_RANK) s_p[i] = unit_level(a.lv, static_cast<int>(e % a.k));
     }
     __syncthreads();
     const int D = a.D, D4 = D / 4;
@@ -190,14 +195,18 @@ unit_chunk_kernel(UnitArgs a) {
     const bool split = nch > 1;
     float* srow = (split && row < a.slab_rows) ? a.slab + static_cast<long long>(row) * a.slab_ld : nullptr;
     // the gradient tensor of this unit (workgroup-uniform): a.gR itself unless the call names levels
-    const float* gR = (a.gR && a.lv.n > 0) ? a.gR + unit_level(a.lv, h) * a.lv.stride : a.gR;
+    const float* gR = (!BY_RANK && a.gR && a.lv.n > 0) ? a.gR + unit_level(a.lv, h) * a.lv.stride : a.gR;
     for (int c4 = threadIdx.x; c4 < D4; c4 += blockDim.x) {
         tr_f32x4 w = {0.f, 0.f, 0.f, 0.f}, s = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
         for (int i = 0; i < len; ++i) {
             const long long ro = static_cast<long long>(s_r[i]) * D + 4 * c4;
             if (a.x) w = fma4(s_gv[i], ld4(a.x + ro), w);
-            if (gR) s = fma4(s_v[i], ld4(gR + ro), s);
+            if constexpr (BY_RANK) {
+                if (gR) s = fma4(s_v[i], ld4(gR + s_p[i] * a.lv.stride + ro), s);
+            } else {
+                if (gR) s = fma4(s_v[i], ld4(gR + ro), s);
+            }
         }
         if (!split) {
             if (a.dW) st4(a.dW + static_cast<long long>(h) * D + 4 * c4, w);
@@ -600,7 +609,7 @@ inline bool train_shape_ok(int D) { return D > 0 && D % 4 == 0 && D <= kTrainMax
 // workspace, sums every chunk, and adds up the partials of the lists that were split.  The caller fills the lists, the
 // operands and the outputs of `a`; chunk_off and the slab come from the workspace (unit_layout) here.  TABLE: the
 // table epilogue (dT) instead of the logit epilogue, which stages dInt[D] in LDS.
-template <bool TABLE>
+template <bool TABLE, bool BY_RANK = false>
 hipError_t launch_unit_sums(UnitArgs a, long long n_entries, char* ws, const UnitLayout& L, hipStream_t s) {
     int* chunk_off = reinterpret_cast<int*>(ws + L.chunk_off);
     hipLaunchKernelGGL(scan_kernel<1>, dim3(1), dim3(1024), 0, s, a.offsets, a.H, chunk_off);
@@ -613,7 +622,7 @@ hipError_t launch_unit_sums(UnitArgs a, long long n_entries, char* ws, const Uni
     const int threads = D4 >= 256 ? 256 : ((D4 + 63) / 64) * 64;
     const size_t lds = TABLE ? 0 : static_cast<size_t>(a.D) * 4;
     const long long grid = static_cast<long long>(a.H) + (n_entries + kTrainChunk - 1) / kTrainChunk;   // >= number of chunks
-    hipLaunchKernelGGL(unit_chunk_kernel<TABLE>, dim3(static_cast<unsigned>(grid)), dim3(threads), lds, s, a);
+    hipLaunchKernelGGL((unit_chunk_kernel<TABLE, BY_RANK>), dim3(static_cast<unsigned>(grid)), dim3(threads), lds, s, a);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     if (n_entries > kTrainChunk)                           // otherwise no list can be split
         hipLaunchKernelGGL(unit_final_kernel<TABLE>, dim3(a.H), dim3(threads), lds, s, a);
@@ -849,7 +858,8 @@ extern "C" int qsae_train_table_unit_grad(const int32_t* offsets, const int32_t*
 }
 
 // The two unit-gradient calls above with one gradient tensor per dictionary prefix (unit_levels.h; the checks are the
-// caller's, csrc/nested.hip): the same kernels, the same workspace layout, g_recon = G[level(h)] for unit h.
+// caller's, csrc/nested.hip): the same kernels, the same workspace layout, g_recon = G[level(h)] for unit h -- or, with
+// by_rank (csrc/multi_topk.hip, lv.bounds = ks), g_recon = G[point(e % k)] for entry e.
 namespace qsae {
 static UnitArgs unit_args_levels(const int32_t* offsets, const int32_t* entries, const float* val, const float* gv, int B, int k,
                                  const float* x, const float* G, const UnitLevels& lv, int H, int D) {
@@ -869,10 +879,10 @@ static UnitArgs unit_args_levels(const int32_t* offsets, const int32_t* entries,
     return a;
 }
 
-hipError_t train_unit_grad_levels(const int32_t* offsets, const int32_t* entries, const float* val, const float* gv, int B, int k,
-                                  const float* x, const float* G, const UnitLevels& lv, const float* logits, int H, int D,
-                                  int n_bits, float step, const float* g_polarize, float* dW_enc, float* db_enc, float* dlogits,
-                                  void* workspace, hipStream_t s) {
+static hipError_t unit_grad_lookup(const int32_t* offsets, const int32_t* entries, const float* val, const float* gv, int B, int k,
+                                   const float* x, const float* G, const UnitLevels& lv, const float* logits, int H, int D,
+                                   int n_bits, float step, const float* g_polarize, float* dW_enc, float* db_enc, float* dlogits,
+                                   void* workspace, hipStream_t s, bool by_rank) {
     UnitArgs a = unit_args_levels(offsets, entries, val, gv, B, k, x, G, lv, H, D);
     a.n = n_bits;
     a.logits = logits;
@@ -882,12 +892,14 @@ hipError_t train_unit_grad_levels(const int32_t* offsets, const int32_t* entries
     a.dW = dW_enc;
     a.db = db_enc;
     a.dlogit = dlogits;
+    if (by_rank) return launch_unit_sums<false, true>(a, a.Bk, static_cast<char*>(workspace), unit_layout(a.Bk, H, D), s);
     return launch_unit_sums<false>(a, a.Bk, static_cast<char*>(workspace), unit_layout(a.Bk, H, D), s);
 }
 
-hipError_t train_table_unit_grad_levels(const int32_t* offsets, const int32_t* entries, const float* val, const float* gv, int B,
-                                        int k, const float* x, const float* G, const UnitLevels& lv, int H, int D, float* dW_enc,
-                                        float* db_enc, float* dW_dec, long long dW_dec_ld, void* workspace, hipStream_t s) {
+static hipError_t table_unit_grad_lookup(const int32_t* offsets, const int32_t* entries, const float* val, const float* gv, int B,
+                                         int k, const float* x, const float* G, const UnitLevels& lv, int H, int D, float* dW_enc,
+                                         float* db_enc, float* dW_dec, long long dW_dec_ld, void* workspace, hipStream_t s,
+                                         bool by_rank) {
     UnitArgs a = unit_args_levels(offsets, entries, val, gv, B, k, x, G, lv, H, D);
     const UnitLayout L = unit_layout(a.Bk, H, D);
     char* ws = static_cast<char*>(workspace);
@@ -899,7 +911,9 @@ hipError_t train_table_unit_grad_levels(const int32_t* offsets, const int32_t* e
         a.dW = dW_enc;
         a.db = db_enc;
         a.dT = dT;
-        if (hipError_t e = launch_unit_sums<true>(a, a.Bk, ws, L, s); e != hipSuccess) return e;
+        if (hipError_t e = by_rank ? launch_unit_sums<true, true>(a, a.Bk, ws, L, s) : launch_unit_sums<true>(a, a.Bk, ws, L, s);
+            e != hipSuccess)
+            return e;
     }
     if (dW_dec) {
         const int vec = (dW_dec_ld % 4 == 0 && aligned16(dW_dec)) ? 1 : 0;
@@ -908,6 +922,36 @@ hipError_t train_table_unit_grad_levels(const int32_t* offsets, const int32_t* e
         return hipGetLastError();
     }
     return hipSuccess;
+}
+
+hipError_t train_unit_grad_levels(const int32_t* offsets, const int32_t* entries, const float* val, const float* gv, int B, int k,
+                                  const float* x, const float* G, const UnitLevels& lv, const float* logits, int H, int D,
+                                  int n_bits, float step, const float* g_polarize, float* dW_enc, float* db_enc, float* dlogits,
+                                  void* workspace, hipStream_t s) {
+    return unit_grad_lookup(offsets, entries, val, gv, B, k, x, G, lv, logits, H, D, n_bits, step, g_polarize, dW_enc, db_enc,
+                            dlogits, workspace, s, false);
+}
+
+hipError_t train_table_unit_grad_levels(const int32_t* offsets, const int32_t* entries, const float* val, const float* gv, int B,
+                                        int k, const float* x, const float* G, const UnitLevels& lv, int H, int D, float* dW_enc,
+                                        float* db_enc, float* dW_dec, long long dW_dec_ld, void* workspace, hipStream_t s) {
+    return table_unit_grad_lookup(offsets, entries, val, gv, B, k, x, G, lv, H, D, dW_enc, db_enc, dW_dec, dW_dec_ld, workspace, s,
+                                  false);
+}
+
+hipError_t train_unit_grad_ranks(const int32_t* offsets, const int32_t* entries, const float* val, const float* gv, int B, int k,
+                                 const float* x, const float* G, const UnitLevels& pts, const float* logits, int H, int D,
+                                 int n_bits, float step, const float* g_polarize, float* dW_enc, float* db_enc, float* dlogits,
+                                 void* workspace, hipStream_t s) {
+    return unit_grad_lookup(offsets, entries, val, gv, B, k, x, G, pts, logits, H, D, n_bits, step, g_polarize, dW_enc, db_enc,
+                            dlogits, workspace, s, true);
+}
+
+hipError_t train_table_unit_grad_ranks(const int32_t* offsets, const int32_t* entries, const float* val, const float* gv, int B,
+                                       int k, const float* x, const float* G, const UnitLevels& pts, int H, int D, float* dW_enc,
+                                       float* db_enc, float* dW_dec, long long dW_dec_ld, void* workspace, hipStream_t s) {
+    return table_unit_grad_lookup(offsets, entries, val, gv, B, k, x, G, pts, H, D, dW_enc, db_enc, dW_dec, dW_dec_ld, workspace, s,
+                                  true);
 }
 }  // namespace qsae
 

@@ -34,4 +34,14 @@ hipError_t train_table_unit_grad_levels(const int32_t* offsets, const int32_t* e
                                         int k, const float* x, const float* G, const UnitLevels& lv, int H, int D, float* dW_enc,
                                         float* db_enc, float* dW_dec, long long dW_dec_ld, void* workspace, hipStream_t s);
 
+// The same with an entry-keyed lookup (include/qsae_multik.h): pts.bounds are the rank prefixes ks, and entry e of a list (the
+// flat index r k + j) reads g_recon = G[unit_level(pts, e % k)], the point of its rank, instead of the level of its unit.
+hipError_t train_unit_grad_ranks(const int32_t* offsets, const int32_t* entries, const float* val, const float* gv, int B, int k,
+                                 const float* x, const float* G, const UnitLevels& pts, const float* logits, int H, int D,
+                                 int n_bits, float step, const float* g_polarize, float* dW_enc, float* db_enc, float* dlogits,
+                                 void* workspace, hipStream_t s);
+hipError_t train_table_unit_grad_ranks(const int32_t* offsets, const int32_t* entries, const float* val, const float* gv, int B,
+                                       int k, const float* x, const float* G, const UnitLevels& pts, int H, int D, float* dW_enc,
+                                       float* db_enc, float* dW_dec, long long dW_dec_ld, void* workspace, hipStream_t s);
+
 }  // namespace qsae

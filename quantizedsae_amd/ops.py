@@ -2964,6 +2964,183 @@ def train_table_unit_grad_nested(offsets: torch.Tensor, entries: torch.Tensor, v
     return dW, db, dWd
 
 
+# ---- Multi-TopK objective of the top-k SAEs (include/qsae_multik.h, csrc/multi_topk.hip) ------------------------------------
+MULTIK_MAX_POINTS = 8
+
+
+def multik_points(ks, K: int, who: str = "multik_points"):
+    """``ks`` as a list of ints after the checks of qsae_multik.h: 1 .. 8 points, 0 < ks[0] < ... < ks[-1] == K <= 256."""
+    try:
+        out = [int(k) for k in ks]
+    except TypeError:
+        raise ValueError(f"{who}: ks must be a sequence of ints, got {ks!r}") from None
+    if any(isinstance(k, bool) or int(k) != k for k in ks):
+        raise ValueError(f"{who}: ks must be whole numbers, got {list(ks)!r}")
+    if not 1 <= len(out) <= MULTIK_MAX_POINTS:
+        raise ValueError(f"{who}: {len(out)} points; 1 .. {MULTIK_MAX_POINTS} are supported")
+    if not 1 <= int(K) <= TRAIN_MAX_K:
+        raise ValueError(f"{who}: the list width K = {int(K)} is outside 1 .. {TRAIN_MAX_K}")
+    if out[0] < 1 or any(b <= a for a, b in zip(out, out[1:])) or out[-1] != int(K):
+        raise ValueError(f"{who}: ks = {out} must be ascending and distinct, start above 0 and end at the list width K = {int(K)}")
+    return out
+
+
+@_on_tensor_device
+def decode_multik_binary(idx, val, packed, D: int, n_bits: int, step: float, bias, ks) -> torch.Tensor:
+    """-> fp32 [P, B, D]: point p is decode_binary_sparse on idx[:, :ks[p]], val[:, :ks[p]], bit for bit, every dictionary row
+    gathered once for up to four points; see qsaek_decode_multik_binary."""
+    who = "decode_multik_binary"
+    idx, val = _nested_lists(who, idx, val)
+    _dev(packed, f"{who}: packed", torch.uint8)
+    D, n_bits = int(D), int(n_bits)
+    _nested_D(who, D)
+    if not 1 <= n_bits <= 8:
+        raise ValueError(f"{who}: n_bits = {n_bits} is outside 1 .. 8")
+    if packed.dim() != 2 or packed.shape[1] != binary_row_bytes(D, n_bits) or not packed.is_contiguous() or packed.device != idx.device:
+        raise ValueError(f"{who}: packed is {tuple(packed.shape)}, expected contiguous [H, {binary_row_bytes(D, n_bits)}] on {idx.device}")
+    H = packed.shape[0]
+    B, K = idx.shape
+    ks = multik_points(ks, K, who)
+    b = _f32c(bias, "bias") if bias is not None else None
+    if b is not None and tuple(b.shape) != (D,):
+        raise ValueError(f"{who}: bias is {tuple(b.shape)}, expected [{D}]")
+    recon = torch.empty((len(ks), B, D), dtype=torch.float32, device=idx.device)
+    check(_lib.load().qsaek_decode_multik_binary(_p(idx), _p(val), B, K, _p(packed), H, D, n_bits, float(step), _p(b),
+                                                 _bounds_arg(ks), len(ks), _p(recon), _stream()))
+    return recon
+
+
+@_on_tensor_device
+def decode_multik_table(idx, val, table: torch.Tensor, scale: float, bias, ks) -> torch.Tensor:
+    """-> fp32 [P, B, D]: point p is decode_table_sparse on idx[:, :ks[p]], val[:, :ks[p]], bit for bit; see
+    qsaek_decode_multik_table."""
+    who = "decode_multik_table"
+    idx, val = _nested_lists(who, idx, val)
+    table = _f32c(table, "table")
+    if table.dim() != 2 or table.device != idx.device:
+        raise ValueError(f"{who}: table is {tuple(table.shape)} on {table.device}, expected [H, D] on {idx.device}")
+    H, D = table.shape
+    _nested_D(who, D)
+    B, K = idx.shape
+    ks = multik_points(ks, K, who)
+    b = _f32c(bias, "bias") if bias is not None else None
+    if b is not None and tuple(b.shape) != (D,):
+        raise ValueError(f"{who}: bias is {tuple(b.shape)}, expected [{D}]")
+    recon = torch.empty((len(ks), B, D), dtype=torch.float32, device=idx.device)
+    check(_lib.load().qsaek_decode_multik_table(_p(idx), _p(val), B, K, _p(table), H, D, float(scale), _p(b),
+                                                _bounds_arg(ks), len(ks), _p(recon), _stream()))
+    return recon
+
+
+@_on_tensor_device
+def train_row_grad_multik(idx: torch.Tensor, table: torch.Tensor, step: float, g_points, ks,
+                          g_latent: Optional[torch.Tensor], W_enc: Optional[torch.Tensor], want_dx: bool = False):
+    """-> (G fp32 [P, B, D], gv fp32 [B, K], dx fp32 [B, D] or None).  ``g_points``: P gradients [B, D], None for a point the
+    loss does not read.  G holds their suffix sums; gv and dx are train_row_grad's with g_recon = G[point(rank)] per entry.  See
+    qsaek_row_grad_multik."""
+    who = "train_row_grad_multik"
+    _dev(idx, f"{who}: idx", torch.int32)
+    if idx.dim() != 2:
+        raise ValueError(f"{who}: idx is {tuple(idx.shape)}, expected [B, K]")
+    idx = idx.contiguous()
+    table = _f32c(table, "table")
+    B, K = idx.shape
+    H, D = table.shape
+    _check_train_shape(D, K)
+    ks = multik_points(ks, K, who)
+    g_points = list(g_points)
+    if len(g_points) != len(ks):
+        raise ValueError(f"{who}: {len(g_points)} point gradients for {len(ks)} points")
+    gs = []
+    for p, g in enumerate(g_points):
+        if g is not None:
+            g = _f32c(g, f"g_points[{p}]")
+            if tuple(g.shape) != (B, D) or g.device != idx.device:
+                raise ValueError(f"{who}: g_points[{p}] is {tuple(g.shape)} on {g.device}, expected [{B}, {D}] on {idx.device}")
+        gs.append(g)
+    gL, gl_ld = _latent_grad(g_latent, B, H)
+    W = _f32c(W_enc, "W_enc") if want_dx else None
+    if W is not None and tuple(W.shape) != (H, D):
+        raise ValueError(f"W_enc is {tuple(W.shape)}, expected [{H}, {D}]")
+    G = torch.empty((len(ks), B, D), dtype=torch.float32, device=idx.device)
+    gv = torch.empty((B, K), dtype=torch.float32, device=idx.device)
+    dx = torch.empty((B, D), dtype=torch.float32, device=idx.device) if want_dx else None
+    garr = (C.c_void_p * len(gs))(*[0 if g is None else g.data_ptr() for g in gs])     # host array of device pointers
+    check(_lib.load().qsaek_row_grad_multik(_p(idx), B, K, _p(table), H, D, float(step), C.cast(garr, C.c_void_p),
+                                            _bounds_arg(ks), len(ks), _p(gL), int(gl_ld), _p(W), _p(G), _p(gv), _p(dx),
+                                            _stream()))
+    return G, gv, dx
+
+
+@_on_tensor_device
+def train_unit_grad_multik(offsets: torch.Tensor, entries: torch.Tensor, val: torch.Tensor, gv: torch.Tensor, x: torch.Tensor,
+                           G: Optional[torch.Tensor], ks, logits: torch.Tensor, n_bits: int, step: float,
+                           g_polarize: Optional[torch.Tensor], want_encoder: bool = True, want_logits: bool = True):
+    """train_unit_grad with g_recon = G[point(e % K)] for list entry e (G fp32 [P, B, D] from train_row_grad_multik, or None);
+    see qsaek_train_unit_grad_multik."""
+    who = "train_unit_grad_multik"
+    _dev(offsets, "offsets", torch.int32)
+    _dev(entries, "entries", torch.int32)
+    val, gv, x, logits = _f32c(val, "val"), _f32c(gv, "gv"), _f32c(x, "x"), _f32c(logits, "logits")
+    if val.dim() != 2 or x.dim() != 2 or offsets.dim() != 1:
+        raise ValueError(f"{who}: val and x must be 2-D, offsets 1-D")
+    B, K = val.shape
+    D = x.shape[1]
+    H = offsets.shape[0] - 1
+    _check_train_shape(D, K)
+    if H < 1 or tuple(logits.shape) != (H, D * n_bits) or tuple(x.shape) != (B, D) or tuple(gv.shape) != (B, K) \
+            or entries.numel() != B * K:
+        raise ValueError(f"{who}: inconsistent shapes")
+    if B * K >= 2 ** 31:
+        raise ValueError(f"{who}: B * K = {B * K} is not below 2^31")
+    ks = multik_points(ks, K, who)
+    G = _nested_G(who, G, len(ks), B, D)
+    gP = _f32c(g_polarize.reshape(()), "g_polarize") if g_polarize is not None else None
+    dev = x.device
+    dW = torch.empty((H, D), dtype=torch.float32, device=dev) if want_encoder else None
+    db = torch.empty((H,), dtype=torch.float32, device=dev) if want_encoder else None
+    dl = torch.empty((H, D * n_bits), dtype=torch.float32, device=dev) if want_logits else None
+    lib = _lib.load()
+    ws = _train_ws(lib.qsaek_train_unit_grad_multik_workspace_bytes(B, K, H, D), dev)
+    check(lib.qsaek_train_unit_grad_multik(_p(offsets.contiguous()), _p(entries.contiguous()), _p(val), _p(gv), B, K, _p(x),
+                                           _p(G), _bounds_arg(ks), len(ks), _p(logits), H, D, int(n_bits), float(step),
+                                           _p(gP), _p(dW), _p(db), _p(dl), _p(ws), ws.numel(), _stream()))
+    return dW, db, dl
+
+
+@_on_tensor_device
+def train_table_unit_grad_multik(offsets: torch.Tensor, entries: torch.Tensor, val: torch.Tensor, gv: torch.Tensor,
+                                 x: torch.Tensor, G: Optional[torch.Tensor], ks, want_encoder: bool = True,
+                                 want_decoder: bool = True):
+    """train_table_unit_grad with g_recon = G[point(e % K)] for list entry e; see qsaek_train_table_unit_grad_multik."""
+    who = "train_table_unit_grad_multik"
+    _dev(offsets, "offsets", torch.int32)
+    _dev(entries, "entries", torch.int32)
+    val, gv, x = _f32c(val, "val"), _f32c(gv, "gv"), _f32c(x, "x")
+    if val.dim() != 2 or x.dim() != 2 or offsets.dim() != 1:
+        raise ValueError(f"{who}: val and x must be 2-D, offsets 1-D")
+    B, K = val.shape
+    D = x.shape[1]
+    H = offsets.shape[0] - 1
+    _check_train_shape(D, K)
+    if H < 1 or tuple(x.shape) != (B, D) or tuple(gv.shape) != (B, K) or entries.numel() != B * K:
+        raise ValueError(f"{who}: inconsistent shapes")
+    if B * K >= 2 ** 31:
+        raise ValueError(f"{who}: B * K = {B * K} is not below 2^31")
+    ks = multik_points(ks, K, who)
+    G = _nested_G(who, G, len(ks), B, D)
+    dev = x.device
+    dW = torch.empty((H, D), dtype=torch.float32, device=dev) if want_encoder else None
+    db = torch.empty((H,), dtype=torch.float32, device=dev) if want_encoder else None
+    dWd = torch.empty((D, H), dtype=torch.float32, device=dev) if want_decoder else None
+    lib = _lib.load()
+    ws = _train_ws(lib.qsaek_train_table_unit_grad_multik_workspace_bytes(B, K, H, D), dev)
+    check(lib.qsaek_train_table_unit_grad_multik(_p(offsets.contiguous()), _p(entries.contiguous()), _p(val), _p(gv), B, K,
+                                                 _p(x), _p(G), _bounds_arg(ks), len(ks), H, D, _p(dW), _p(db), _p(dWd),
+                                                 H, _p(ws), ws.numel(), _stream()))
+    return dW, db, dWd
+
+
 # ---- BatchTopK of the top-k SAEs (include/qsae_batch.h, csrc/batch_topk.hip, csrc/batch_topk_decode.hip) -------------------
 BATCH_TOPK_MAX_K = 256
 BATCH_TOPK_REPORT_WORDS = 4       # selected, saturated rows, empty rows, bits of the smallest selected value

@@ -141,6 +141,10 @@ class BaselineSparseAutoencoder(ops.GraphForwardMixin, TopKCore, nn.Module):
         return ops.train_table_unit_grad_nested(offsets, entries, val, gv, x, G, bounds, want_encoder=want_encoder,
                                                 want_decoder=want_decoder)
 
+    def _multik_unit_grad(self, offsets, entries, val, gv, x, G, ks, g_extra, want_encoder: bool, want_decoder: bool):
+        return ops.train_table_unit_grad_multik(offsets, entries, val, gv, x, G, ks, want_encoder=want_encoder,
+                                                want_decoder=want_decoder)
+
     def forward_compact(self, x):
         """(idx, val, reconstruction) without the dense latent; same path selection as forward()."""
         with torch.no_grad():

@@ -339,6 +339,11 @@ class BinarySAE(ops.GraphForwardMixin, TopKCore, SparseAutoencoder):
         return ops.train_unit_grad_nested(offsets, entries, val, gv, x, G, bounds, dec.weight.detach(), dec.n_bits,
                                           dec.quantization_step, g_pol, want_encoder=want_encoder, want_logits=want_decoder)
 
+    def _multik_unit_grad(self, offsets, entries, val, gv, x, G, ks, g_pol, want_encoder: bool, want_decoder: bool):
+        dec = self.decoder
+        return ops.train_unit_grad_multik(offsets, entries, val, gv, x, G, ks, dec.weight.detach(), dec.n_bits,
+                                          dec.quantization_step, g_pol, want_encoder=want_encoder, want_logits=want_decoder)
+
     # -- two batches in flight --------------------------------------------------------------------------------
     def forward_submit(self, x, slot: int = 0, want_dense: bool = True):
         """Queue one forward without waiting for the GPU anywhere: returns a handle whose ``result()`` gives

@@ -169,6 +169,69 @@ class TopKCore:
         return (latent if dense_latent else None), tuple(levels[l] for l in range(len(bounds))), extra
 
 
+    # -- Multi-TopK (Gao et al. 2024): one reconstruction per rank prefix of one top-K list -------------------------------------
+    @staticmethod
+    def default_multi_topk(top_k: int, H: int):
+        """``[top_k, min(4 * top_k, 256, H)]``: the two points of ``L(k) + L(4k) / 8``, the wider one clipped to the longest
+        list of the kernels and to the dictionary; one point when the two coincide."""
+        top_k, H = int(top_k), int(H)
+        wide = min(4 * top_k, ops.MULTIK_MAX_K, H)
+        if top_k < 1 or top_k > wide:
+            raise ValueError(f"default_multi_topk: top_k = {top_k}; expected 1 .. {min(ops.MULTIK_MAX_K, H)}")
+        return ops.multik_points([top_k] if wide == top_k else [top_k, wide], wide, "default_multi_topk")
+
+    def _own_top_k(self) -> int:
+        return int(self.top_k if hasattr(self, "top_k") else self.topk)
+
+    def _multik_input(self, x, ks, who: str):
+        x = require_device_input(x, "x")
+        H, D = self.encoder.linear.weight.shape
+        if x.dim() != 2 or x.shape[1] != D:
+            raise ValueError(f"x is {tuple(x.shape)}, expected [batch, {D}]")
+        who = f"{type(self).__name__}.{who}"
+        try:
+            K = int(list(ks)[-1])
+        except (TypeError, IndexError, ValueError):
+            raise ValueError(f"{who}: ks must be a non-empty sequence of ints, got {ks!r}") from None
+        if K > H:
+            raise ValueError(f"{who}: ks = {list(ks)} ends above hidden_dim = {H}")
+        return x, ops.multik_points(ks, K, who), who
+
+    def forward_multi_topk(self, x, ks):
+        """``(latent fp32 [B,H], recons fp32 [P,B,D])`` without a ``grad_fn``: ONE selection at ``K = ks[-1]`` through the
+        model's own selection paths, and for every ``ks[p]`` (ascending) the reconstruction from the entries ranked below it,
+        decoded from what ``forward()`` decodes from -- bit for bit the model rebuilt with ``top_k = ks[p]``.  The latent is the
+        whole list's.  Every dictionary row is gathered once for up to four points (csrc/multi_topk.hip)."""
+        with torch.no_grad():
+            x, ks, who = self._multik_input(x, ks, "forward_multi_topk")
+            xf = as_f32c(x)
+            idx, val, latent = self._select(xf, ks[-1], self._select_path(xf.shape[0], ks[-1], who), True)
+            decoder, dec_bias = self._nested_decoder()
+            if decoder[0] == "packed":
+                D = self.encoder.linear.weight.shape[1]
+                return latent, ops.decode_multik_binary(idx, val, decoder[1], D, decoder[2], decoder[3], dec_bias, ks)
+            return latent, ops.decode_multik_table(idx, val, decoder[1], decoder[2], dec_bias, ks)
+
+    def forward_train_multi_topk(self, x, ks, *, dense_latent: bool = True):
+        """The tuple of the model's ``forward_train_nested`` with a ``grad_fn`` -- ``(latent [B,H] or None, (recon_0, ...,
+        recon_{P-1}))``, ``BinarySAE`` adds its polarize term -- where ``recon_p`` [B,D] decodes, through the model's training
+        table, the ``ks[p]`` best-ranked entries of ONE top-``ks[-1]`` list per row; the points are the rows of one [P,B,D]
+        tensor and the latent is the whole list's.  ``training.multi_topk_loss`` consumes it.  The backward is one sparse pass:
+        ``train_row_grad_multik`` -> ``train_csr`` -> the model's rank-keyed unit-gradient op -> ``train_col_sum(G[0])``.
+        ``model.activity`` is fed once, with the ranks below the model's own top-k only.  With ``ks = [top_k]`` outputs and
+        gradients are ``forward_train``'s bit for bit."""
+        x, ks, who = self._multik_input(x, ks, "forward_train_multi_topk")
+        lin = self.encoder.linear
+        D = lin.weight.shape[1]
+        if not ops.train_supported(D, ks[-1]):
+            raise ValueError(f"{who}: the gradient kernels take input_dim a multiple of 4 up to 4096 (got {D})")
+        if x.shape[0] * ks[-1] >= 2 ** 31:
+            raise ValueError(f"{who}: batch * K = {x.shape[0] * ks[-1]} is not below 2^31")
+        latent, points, extra = _MultiTopKTrainStep.apply(self, bool(dense_latent), tuple(ks), x, lin.weight, lin.bias,
+                                                          self.decoder.weight, self.decoder.bias)
+        out = ((latent if dense_latent else None), tuple(points[p] for p in range(len(ks))))
+        return out if extra is None else out + (extra,)
+
     # -- BatchTopK: the B k largest pre-activations of the batch, ragged rows ------------------------------------------------
     def _batch_topk_input(self, x, who: str):
         x = require_device_input(x, "x")
@@ -408,6 +471,54 @@ class _BatchTopKTrainStep(torch.autograd.Function):
             dx = dx.to(ctx.x_dtype)
         return (None, None, None, dx if need_x else None, dW if need_W else None, db if need_b else None,
                 ddec if need_dec else None, dbd)
+
+
+class _MultiTopKTrainStep(torch.autograd.Function):
+    """forward_train_multi_topk and its gradient.  The model supplies ``_nested_train_decoder() -> (table [H, D], step, extra
+    output or None)`` and ``_multik_unit_grad(offsets, entries, val, gv, x, G, ks, g_extra, want_encoder, want_decoder)``.  The
+    points are the rows of ONE output tensor, so a loss over them sends one gradient [P, B, D] back; its suffix sums
+    G[p] = g[p] + G[p + 1] are what reaches the dictionary row of an entry whose rank first appears in point p
+    (include/qsae_multik.h)."""
+
+    @staticmethod
+    def forward(ctx, model, dense_latent, ks, x, W_enc, b_enc, dec_param, b_dec):
+        table, step, extra = model._nested_train_decoder()
+        xf = as_f32c(x.detach())
+        who = f"{type(model).__name__}.forward_train_multi_topk"
+        idx, val, latent = model._select(xf, ks[-1], model._select_path(xf.shape[0], ks[-1], who), dense_latent)
+        points = ops.decode_multik_table(idx, val, table, step, b_dec.detach(), ks)
+        if model.activity is not None:
+            own = min(model._own_top_k(), ks[-1])             # a rank behind the model's own top-k is not a firing
+            if own == ks[-1]:
+                model.activity.add_compact(idx, val)
+            elif own > 0:
+                model.activity.add_compact(idx[:, :own].contiguous(), val[:, :own].contiguous())
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(xf, idx, val, table)
+        ctx.model, ctx.step, ctx.ks, ctx.x_dtype = model, step, ks, x.dtype
+        return latent, points, extra
+
+    @staticmethod
+    def backward(ctx, g_latent, g_points, g_extra):
+        xf, idx, val, table = ctx.saved_tensors
+        model, ks = ctx.model, ctx.ks
+        need_x, need_W, need_b, need_dec, need_bd = ctx.needs_input_grad[3:8]
+        want_units = need_W or need_b or need_dec
+        dx = dW = db = ddec = dbd = None
+        if (need_x or want_units or need_bd) and not (g_latent is None and g_points is None and g_extra is None):
+            g_list = [None] * len(ks) if g_points is None else [g_points[p] for p in range(len(ks))]
+            G, gv, dx = ops.train_row_grad_multik(idx, table, ctx.step, g_list, ks, g_latent,
+                                                  model.encoder.linear.weight.detach(), want_dx=need_x)
+            if want_units:
+                offsets, entries = ops.train_csr(idx, table.shape[0])
+                dW, db, ddec = model._multik_unit_grad(offsets, entries, val, gv, xf, G, ks, g_extra, need_W or need_b,
+                                                       need_dec)
+            if need_bd:
+                dbd = ops.train_col_sum(G[0])                  # every point adds the bias: its gradient is the whole sum
+            if dx is not None and dx.dtype != ctx.x_dtype:
+                dx = dx.to(ctx.x_dtype)
+        return (None, None, None, dx if need_x else None, dW if need_W else None, db if need_b else None,
+                ddec if need_dec else None, dbd if need_bd else None)
 
 
 class _NestedTrainStep(torch.autograd.Function):

@@ -1057,6 +1057,80 @@ def _(offsets, entries, val, gv, x, G, bounds, want_encoder, want_decoder):
             _f32((D, H if want_decoder else 0), x))
 
 
+# ---- Multi-TopK objective of the top-k SAEs (include/qsae_multik.h) ---------------------------------------------------------
+@_op("decode_multik_binary")
+def _decode_multik_binary(idx: Tensor, val: Tensor, packed: Tensor, D: int, n_bits: int, step: float, bias: Optional[Tensor],
+                          ks: List[int]) -> Tensor:
+    """-> fp32 [P, B, D]: one reconstruction per rank prefix from the packed n-bit dictionary"""
+    return _ops.decode_multik_binary(idx, val, packed, D, n_bits, step, bias, ks)
+
+
+@_decode_multik_binary.register_fake
+def _(idx, val, packed, D, n_bits, step, bias, ks):
+    return _f32((len(ks), idx.shape[0], D), idx)
+
+
+@_op("decode_multik_table")
+def _decode_multik_table(idx: Tensor, val: Tensor, table: Tensor, scale: float, bias: Optional[Tensor], ks: List[int]) -> Tensor:
+    """-> fp32 [P, B, D]: one reconstruction per rank prefix from an fp32 [H, D] table"""
+    return _ops.decode_multik_table(idx, val, table, scale, bias, ks)
+
+
+@_decode_multik_table.register_fake
+def _(idx, val, table, scale, bias, ks):
+    return _f32((len(ks), idx.shape[0], table.shape[1]), idx)
+
+
+@_op("train_row_grad_multik")
+def _train_row_grad_multik(idx: Tensor, table: Tensor, step: float, g_points: List[Optional[Tensor]], ks: List[int],
+                           g_latent: Optional[Tensor], W_enc: Optional[Tensor], want_dx: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    """-> (G [P, B, D], gv [B, K], dx [B, D] ([0, D] when not wanted))"""
+    G, gv, dx = _ops.train_row_grad_multik(idx, table, step, g_points, ks, g_latent, W_enc, want_dx)
+    return G, gv, (dx if dx is not None else _f32((0, table.shape[1]), idx))
+
+
+@_train_row_grad_multik.register_fake
+def _(idx, table, step, g_points, ks, g_latent, W_enc, want_dx):
+    B, D = idx.shape[0], table.shape[1]
+    return _f32((len(ks), B, D), idx), _f32(tuple(idx.shape), idx), _f32((B if want_dx else 0, D), idx)
+
+
+@_op("train_unit_grad_multik")
+def _train_unit_grad_multik(offsets: Tensor, entries: Tensor, val: Tensor, gv: Tensor, x: Tensor, G: Optional[Tensor],
+                            ks: List[int], logits: Tensor, n_bits: int, step: float, g_polarize: Optional[Tensor],
+                            want_encoder: bool, want_logits: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    """-> (dW_enc [H, D], db_enc [H], dlogits [H, D n_bits]); an output not wanted has 0 rows"""
+    dW, db, dl = _ops.train_unit_grad_multik(offsets, entries, val, gv, x, G, ks, logits, n_bits, step, g_polarize,
+                                             want_encoder, want_logits)
+    D = x.shape[1]
+    return (dW if dW is not None else _f32((0, D), x), db if db is not None else _f32((0,), x),
+            dl if dl is not None else _f32((0, logits.shape[1]), x))
+
+
+@_train_unit_grad_multik.register_fake
+def _(offsets, entries, val, gv, x, G, ks, logits, n_bits, step, g_polarize, want_encoder, want_logits):
+    H, D = offsets.shape[0] - 1, x.shape[1]
+    return (_f32((H if want_encoder else 0, D), x), _f32((H if want_encoder else 0,), x),
+            _f32((H if want_logits else 0, logits.shape[1]), x))
+
+
+@_op("train_table_unit_grad_multik")
+def _train_table_unit_grad_multik(offsets: Tensor, entries: Tensor, val: Tensor, gv: Tensor, x: Tensor, G: Optional[Tensor],
+                                  ks: List[int], want_encoder: bool, want_decoder: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    """-> (dW_enc [H, D], db_enc [H], dW_dec [D, H]); an output not wanted is empty ([0, D], [0], [D, 0])"""
+    dW, db, dWd = _ops.train_table_unit_grad_multik(offsets, entries, val, gv, x, G, ks, want_encoder, want_decoder)
+    D = x.shape[1]
+    return (dW if dW is not None else _f32((0, D), x), db if db is not None else _f32((0,), x),
+            dWd if dWd is not None else _f32((D, 0), x))
+
+
+@_train_table_unit_grad_multik.register_fake
+def _(offsets, entries, val, gv, x, G, ks, want_encoder, want_decoder):
+    H, D = offsets.shape[0] - 1, x.shape[1]
+    return (_f32((H if want_encoder else 0, D), x), _f32((H if want_encoder else 0,), x),
+            _f32((D, H if want_decoder else 0), x))
+
+
 # ---- BatchTopK of the top-k SAEs (include/qsae_batch.h) --------------------------------------------------------------------
 @_op("batch_select", mutates=("theta", "batches"))
 def _batch_select(val: Tensor, n_select: int, want_val: bool, theta: Optional[Tensor], batches: Optional[Tensor],
@@ -1813,6 +1887,41 @@ def train_unit_grad_nested(offsets, entries, val, gv, x, G, bounds, logits, n_bi
 
 def train_table_unit_grad_nested(offsets, entries, val, gv, x, G, bounds, want_encoder=True, want_decoder=True):
     dW, db, dWd = Q.train_table_unit_grad_nested(offsets, entries, val, gv, x, G, [int(b) for b in bounds], bool(want_encoder),
+                                                 bool(want_decoder))
+    return (dW if want_encoder else None), (db if want_encoder else None), (dWd if want_decoder else None)
+
+
+MULTIK_MAX_POINTS = _ops.MULTIK_MAX_POINTS
+MULTIK_MAX_K = _ops.TRAIN_MAX_K
+multik_points = _ops.multik_points
+
+
+def decode_multik_binary(idx, val, packed, D, n_bits, step, bias, ks):
+    """-> fp32 [P, B, D]"""
+    return Q.decode_multik_binary(idx, val, packed, int(D), int(n_bits), float(step), bias, [int(k) for k in ks])
+
+
+def decode_multik_table(idx, val, table, scale, bias, ks):
+    """-> fp32 [P, B, D]"""
+    return Q.decode_multik_table(idx, val, table, float(scale), bias, [int(k) for k in ks])
+
+
+def train_row_grad_multik(idx, table, step, g_points, ks, g_latent, W_enc=None, want_dx=False):
+    """-> (G fp32 [P, B, D], gv fp32 [B, K], dx fp32 [B, D] or None)"""
+    G, gv, dx = Q.train_row_grad_multik(idx, table, float(step), list(g_points), [int(k) for k in ks], g_latent,
+                                        W_enc if want_dx else None, bool(want_dx))
+    return G, gv, (dx if want_dx else None)
+
+
+def train_unit_grad_multik(offsets, entries, val, gv, x, G, ks, logits, n_bits, step, g_polarize, want_encoder=True,
+                           want_logits=True):
+    dW, db, dl = Q.train_unit_grad_multik(offsets, entries, val, gv, x, G, [int(k) for k in ks], logits, int(n_bits),
+                                          float(step), g_polarize, bool(want_encoder), bool(want_logits))
+    return (dW if want_encoder else None), (db if want_encoder else None), (dl if want_logits else None)
+
+
+def train_table_unit_grad_multik(offsets, entries, val, gv, x, G, ks, want_encoder=True, want_decoder=True):
+    dW, db, dWd = Q.train_table_unit_grad_multik(offsets, entries, val, gv, x, G, [int(k) for k in ks], bool(want_encoder),
                                                  bool(want_decoder))
     return (dW if want_encoder else None), (db if want_encoder else None), (dWd if want_decoder else None)
 

@@ -7,6 +7,7 @@ rows (csrc/resample.hip; section 4.28), and the AuxK loss that gives them a grad
 batch-wide selection they are trained with (csrc/batch_topk.hip; section 4.32)."""
 from .auxk import aux_k_loss  # noqa: F401
 from .nested import default_nested_bounds, nested_loss  # noqa: F401
+from .multi_topk import default_multi_topk, multi_topk_loss  # noqa: F401
 from .batch_topk import BatchTopK  # noqa: F401
 from .activity import ActivitySummary, FeatureActivity, activity_line  # noqa: F401
 from .batches import EpochPlan, ShuffledChunk, epoch_permutation, plan_epoch  # noqa: F401
@@ -18,4 +19,5 @@ from .watch import WATCH_MODES, ModelWatch, TensorStats, tensor_stats  # noqa: F
 __all__ = ["Trainer", "ShuffledChunk", "EpochPlan", "epoch_permutation", "plan_epoch", "trainer_loss", "recon_recipe",
            "model_path_for", "SAE_TYPES", "RQ_STAGE_WEIGHTS", "ModelWatch", "TensorStats", "tensor_stats", "WATCH_MODES",
            "FeatureActivity", "ActivitySummary", "activity_line", "resample_dead", "ResampleReport", "aux_k_loss",
-           "nested_loss", "default_nested_bounds", "BatchTopK"]
+           "nested_loss", "default_nested_bounds", "BatchTopK",
+           "multi_topk_loss", "default_multi_topk"]

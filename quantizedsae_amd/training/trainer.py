@@ -60,6 +60,14 @@ backward, ``trainer_loss`` the per-type loss, ``optim.Adam`` the step.  What dif
   reconstruction per dictionary prefix from the batch-wide selection (csrc/nested_ragged.hip), the loss is ``nested_loss``,
   and AuxK takes the last level.  Logging steps gain ``recon_loss_level_{l}`` and ``l0_level_{l}``, the mean number of selected
   units below ``b_l`` per row (one small host copy; none on other steps), next to the ``batch_topk/*`` metrics.
+* ``multi_topk="default" | [k_0, ..., k_{P-1}]`` (``baseline_sae`` and ``b_sae`` only; default ``None`` changes nothing) trains
+  with the Multi-TopK objective of Gao et al. (``multi_topk_loss``, csrc/multi_topk.hip): ``model.forward_train_multi_topk``
+  selects once at the widest point and gives one reconstruction per rank prefix; the objective is ``sum_p w_p * loss_p`` with
+  ``multi_topk_weights`` (default 1 for the point equal to the model's top-k and 1/8 for the others: ``L(k) + L(4k) / 8``).
+  ``"default"`` is ``default_multi_topk(top_k, hidden_dim)`` = ``[k, min(4 k, 256, H)]``.  The model's top-k must be one of
+  the points: that point is the model's reconstruction for ``aux_k``, ``resample_every`` and the logged ``recon_loss``.
+  Logging steps gain ``recon_loss_k{k_p}``.  Together with ``nested_bounds``, ``batch_topk`` or
+  ``batch_topk_nested_bounds`` it raises: the combinations are not built.
 * ``model=`` hands in the model instead of building the reference's.  The reference builds
   ``BinarySAE(input_dim, hidden_dim, n_bits)``, where ``n_bits`` lands in ``gamma`` and the decoder keeps its default of 8
   bits; that call is kept.
@@ -84,6 +92,7 @@ from .loss import SAE_TYPES, trainer_loss
 from .activity import FeatureActivity, activity_line
 from .auxk import AUX_MAX_K, aux_k_loss
 from .batch_topk import BatchTopK
+from .multi_topk import MULTI_TOPK_TYPES, default_multi_topk, default_multi_topk_weights, multi_topk_loss
 from .nested import NESTED_TYPES, default_nested_bounds, nested_loss
 from .resample import ResampleReport, resample_dead, resample_line
 from .watch import WATCH_MODES, ModelWatch, watch_line
@@ -123,7 +132,8 @@ class Trainer:
                  activity_window: Optional[int] = None, resample_every: Optional[int] = None, resample_seed: int = 0,
                  resample_scale: float = 0.2, aux_k: Optional[int] = None, aux_coef: float = 1 / 32,
                  aux_refresh: Optional[int] = None, nested_bounds=None, batch_topk: bool = False,
-                 batch_topk_cap: Optional[int] = None, batch_topk_nested_bounds=None):
+                 batch_topk_cap: Optional[int] = None, batch_topk_nested_bounds=None, multi_topk=None,
+                 multi_topk_weights=None):
         if sae_type not in SAE_TYPES:
             raise ValueError(f"unknown sae_type {sae_type!r}; expected one of {', '.join(SAE_TYPES)}")
         if sae_type == "t_sae" and not rigL:
@@ -169,6 +179,15 @@ class Trainer:
             raise ValueError("batch_topk_nested_bounds needs batch_topk=True (nested_bounds is the keyword of the per-row top-k)")
         if batch_topk_cap is not None and not batch_topk:
             raise ValueError("batch_topk_cap needs batch_topk=True")
+        if multi_topk is not None:
+            if sae_type not in MULTI_TOPK_TYPES:
+                raise ValueError(f"multi_topk: the Multi-TopK objective is built for baseline_sae and b_sae, the two top-k models; "
+                                 f"got {sae_type!r}")
+            if nested_bounds is not None or batch_topk or batch_topk_nested_bounds is not None:
+                raise ValueError("multi_topk together with nested_bounds, batch_topk or batch_topk_nested_bounds: the "
+                                 "combinations are not built; choose one objective")
+        elif multi_topk_weights is not None:
+            raise ValueError("multi_topk_weights needs multi_topk")
         self.config = config
         self.sae_type = sae_type
         self.device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
@@ -223,6 +242,36 @@ class Trainer:
                 self.nested_bounds = ops.nested_bounds(given, H, f"Trainer: {name}")
         #: the BatchTopK controller (k = the model's top-k), or None
         self.batch_topk = BatchTopK(self.model, cap=batch_topk_cap) if batch_topk else None
+        #: the points of the Multi-TopK objective, their weights and the index of the point equal to the model's top-k, or None
+        self.multi_topk = self.multi_topk_weights = self._multi_topk_own = None
+        if multi_topk is not None:
+            H = self.model.encoder.linear.weight.shape[0]
+            own = self.model._own_top_k()
+            if isinstance(multi_topk, str):
+                if multi_topk != "default":
+                    raise ValueError(f"multi_topk = {multi_topk!r}; expected None, 'default' or a list of points")
+                multi_topk = default_multi_topk(own, H)
+            try:
+                K = int(list(multi_topk)[-1])
+            except (TypeError, IndexError, ValueError):
+                raise ValueError(f"Trainer: multi_topk: ks must be a non-empty sequence of ints, got {multi_topk!r}") from None
+            if K > H:
+                raise ValueError(f"Trainer: multi_topk: ks = {list(multi_topk)} ends above hidden_dim = {H}")
+            self.multi_topk = ops.multik_points(multi_topk, K, "Trainer: multi_topk")
+            if own not in self.multi_topk:
+                raise ValueError(f"Trainer: multi_topk: ks = {self.multi_topk} must hold the model's top-k = {own}: that point is "
+                                 "the model's reconstruction")
+            self._multi_topk_own = self.multi_topk.index(own)
+            if multi_topk_weights is None:
+                multi_topk_weights = default_multi_topk_weights(self.multi_topk, own)
+            try:
+                self.multi_topk_weights = [float(w) for w in multi_topk_weights]
+            except (TypeError, ValueError):
+                raise ValueError(f"multi_topk_weights = {multi_topk_weights!r}; expected one number per point") from None
+            if len(self.multi_topk_weights) != len(self.multi_topk) or \
+                    not all(math.isfinite(w) and w >= 0 for w in self.multi_topk_weights):
+                raise ValueError(f"multi_topk_weights = {multi_topk_weights!r}; expected {len(self.multi_topk)} finite numbers "
+                                 ">= 0, one per point")
 
     # ---- one step ------------------------------------------------------------------------------------------------
     def _forward(self, batch, want_latent: bool):
@@ -231,6 +280,8 @@ class Trainer:
                                                               dense_latent=want_latent)
         if self.nested_bounds is not None:
             return self.model.forward_train_nested(batch, self.nested_bounds, dense_latent=want_latent)
+        if self.multi_topk is not None:
+            return self.model.forward_train_multi_topk(batch, self.multi_topk, dense_latent=want_latent)
         if self.batch_topk is not None:
             return self.model.forward_train_batch_topk(batch, self.batch_topk, dense_latent=want_latent)
         if self.sae_type in ("b_sae", "baseline_sae"):
@@ -247,10 +298,15 @@ class Trainer:
         optimizer.zero_grad(set_to_none=True)
         if self.nested_bounds is not None:
             losses = nested_loss(st, outputs, batch, self.config)
+        elif self.multi_topk is not None:
+            losses = multi_topk_loss(st, outputs, batch, self.config, self.multi_topk_weights)
         else:
             losses = trainer_loss(st, outputs, batch, self.config)
-        if self.aux_k is not None:                             # (nested: the last level is the model's reconstruction)
-            self._aux_backward(batch, outputs[1] if self.nested_bounds is None else outputs[1][-1])
+        if self.aux_k is not None:                             # (nested: the last level is the model's reconstruction;
+            if self.multi_topk is not None:                    #  Multi-TopK: the point at the model's own top-k)
+                self._aux_backward(batch, outputs[1][self._multi_topk_own])
+            else:
+                self._aux_backward(batch, outputs[1] if self.nested_bounds is None else outputs[1][-1])
         self._watched = self._watch.collect() if self._watch_due else None
         if st == "q_sae":
             model.decoder.apply_secant_grad()
@@ -299,6 +355,10 @@ class Trainer:
         if self.nested_bounds is not None:                     # the objective is the sum over the levels
             levels = {f"recon_loss_level_{i}": v for i, v in enumerate(lv)}
             lv = [sum(lv)]
+        if self.multi_topk is not None:                        # the objective is the weighted sum over the points
+            levels = {f"recon_loss_k{k}": v for k, v in zip(self.multi_topk, lv)}
+            levels["recon_loss"] = lv[self._multi_topk_own]
+            lv = [sum(w * v for w, v in zip(self.multi_topk_weights, lv))]
         if st == "b_sae":
             latent, _, pol = outputs
             pol = pol.item()
