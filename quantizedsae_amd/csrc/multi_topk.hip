@@ -15,13 +15,14 @@
 // point(j) on: G[p] = g[p] + G[p + 1].  multik_row_kernel is the row body of nested_rows.h with the lookup keyed by the rank of
 // an entry instead of by its unit; the unit sums are the kernels of train.hip with the same rank-keyed lookup
 // (unit_levels.h, train_*_unit_grad_ranks), which recover the rank of list entry e = r K + j as e % K.
-#include "nested_rows.h"
+#include "level_entry.h"
 #include "../../include/qsae_multik.h"
 
 namespace qsae {
 
 static_assert(kNestedMaxK == QSAEK_MAX_K, "nested_rows.h and qsae_multik.h name the same limit");
 static_assert(kMaxLevels == QSAEK_MAX_POINTS, "unit_levels.h and qsae_multik.h name the same limit");
+static_assert(kLevelMaxD == QSAEK_MAX_D, "level_entry.h and qsae_multik.h name the same limit");
 
 constexpr int kMultikWaves = 4;            // activation rows of a workgroup
 constexpr int kMultikMaxK = QSAEK_MAX_K;
@@ -226,30 +227,6 @@ multik_row_kernel(const int32_t* __restrict__ idx, int B, int K, int H, int D, c
     nested_row_body<true>(r < B, r, idx, K, K, B, H, D, table, step, gl, pts, gL, gl_ld, Wenc, G, gv, dx);
 }
 
-// ---- the checks every entry point shares, in the order the header states ---------------------------------------------------
-inline bool multik_misaligned(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
-// limits (from the sizes alone), then B and H, then the host array ks -> pts (the lookup of unit_levels.h over ranks)
-static int multik_limits(const char* who, int B, int K, int H, int D, bool packed, int n_bits, bool unit_call, const int* ks,
-                         int n_ks, UnitLevels* pts) {
-    if (n_ks < 1 || n_ks > kMaxLevels) return fail(QSAE_ERR_UNSUPPORTED, "%s: unsupported: 1 <= n_ks <= 8", who);
-    if (K < 1 || K > kMultikMaxK) return fail(QSAE_ERR_UNSUPPORTED, "%s: unsupported: 1 <= K <= 256", who);
-    if (D < 4 || D % 4 != 0 || D > QSAEK_MAX_D) return fail(QSAE_ERR_UNSUPPORTED, "%s: unsupported: D a positive multiple of 4 up to 4096", who);
-    if (packed && (n_bits < 1 || n_bits > 8)) return fail(QSAE_ERR_UNSUPPORTED, "%s: unsupported: 1 <= n_bits <= 8", who);
-    if (unit_call && static_cast<long long>(B) * K >= (1LL << 31)) return fail(QSAE_ERR_UNSUPPORTED, "%s: unsupported: B * K < 2^31", who);
-    if (B < 0 || H < 1) return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: B >= 0 and H >= 1 required", who);
-    if (!ks) return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: ks is null", who);
-    pts->stride = static_cast<long long>(B) * D;
-    pts->n = n_ks;
-    for (int i = 0; i < kMaxLevels; ++i) pts->bounds[i] = i < n_ks ? ks[i] : 0;
-    for (int i = 0; i < n_ks; ++i)
-        if (ks[i] <= (i > 0 ? ks[i - 1] : 0))
-            return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: 0 < ks[0] < ... < ks[n_ks - 1] == K required", who);
-    if (ks[n_ks - 1] != K)
-        return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: 0 < ks[0] < ... < ks[n_ks - 1] == K required", who);
-    return QSAE_OK;
-}
-
 template <int MODE>
 static void launch_multik_decode(dim3 grid, hipStream_t s, const int32_t* idx, const float* val, int B, int K, int H,
                                  const NestedDict& d, const float* bias, const UnitLevels& pts, float* recon) {
@@ -258,31 +235,27 @@ static void launch_multik_decode(dim3 grid, hipStream_t s, const int32_t* idx, c
         const int p0 = end > kMultikPass ? end - kMultikPass : 0, n_here = end - p0;
         MultikPoints part;
         for (int i = 0; i < kMultikPass; ++i) part.k[i] = i < n_here ? pts.bounds[p0 + i] : 0;
-        const int Kuse = part.k[n_here - 1];               // <= K: validated by multik_limits
+        const int Kuse = part.k[n_here - 1];               // <= K: validated by level_limits
         hipLaunchKernelGGL(multik_decode_kernel<MODE>, grid, block, 0, s, idx, val, B, K, H, d, bias, part, n_here, p0, Kuse, recon);
     }
 }
 
+// recon [n_ks][B][D] after the checks of level_entry.h
 static int decode_multik(const char* who, const int32_t* idx, const float* val, int B, int K, NestedDict d, int H,
                          const float* bias, const int* ks, int n_ks, float* recon, qsae_stream_t stream) {
-    const bool packed = d.table == nullptr && d.n != 0;
     UnitLevels pts;
-    if (const int rc = multik_limits(who, B, K, H, d.D, packed, d.n, false, ks, n_ks, &pts); rc != QSAE_OK) return rc;
+    if (const int rc = level_limits(who, kMultikRules, false, B, K, H, d.D, is_packed(d), d.n, ks, n_ks, &pts); rc != QSAE_OK)
+        return rc;
     if (B == 0) return QSAE_OK;
     if (!recon || !idx || !val || (!d.packed && !d.table))
         return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: null pointer", who);
-    if (multik_misaligned(idx, 4) || multik_misaligned(val, 4) || multik_misaligned(bias, 4) || multik_misaligned(recon, 16) ||
-        multik_misaligned(d.packed, 4) || multik_misaligned(d.table, 16))
+    if (misaligned(idx, 4) || misaligned(val, 4) || misaligned(bias, 4) || misaligned(recon, 16) || misaligned(d.packed, 4) ||
+        misaligned(d.table, 16))
         return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: a pointer is not aligned as the header asks", who);
-    hipStream_t s = as_stream(stream);
     const dim3 grid(static_cast<unsigned>((static_cast<long long>(B) + kMultikWaves - 1) / kMultikWaves));
-    switch (packed ? field_width(d.n) : 0) {
-        case 0: launch_multik_decode<0>(grid, s, idx, val, B, K, H, d, bias, pts, recon); break;
-        case 1: launch_multik_decode<1>(grid, s, idx, val, B, K, H, d, bias, pts, recon); break;
-        case 2: launch_multik_decode<2>(grid, s, idx, val, B, K, H, d, bias, pts, recon); break;
-        case 4: launch_multik_decode<4>(grid, s, idx, val, B, K, H, d, bias, pts, recon); break;
-        default: launch_multik_decode<8>(grid, s, idx, val, B, K, H, d, bias, pts, recon); break;
-    }
+    for_dict_mode(d, [&](auto mode) {
+        launch_multik_decode<decltype(mode)::value>(grid, as_stream(stream), idx, val, B, K, H, d, bias, pts, recon);
+    });
     QSAE_LAUNCH_CHECK();
     return QSAE_OK;
 }
@@ -294,55 +267,33 @@ using namespace qsae;
 extern "C" int qsaek_decode_multik_binary(const int32_t* idx, const float* val, int B, int K, const uint8_t* packed, int H, int D,
                                           int n_bits, float step, const float* dec_bias, const int* ks, int n_ks, float* recon,
                                           qsae_stream_t stream) {
-    const bool bits_ok = n_bits >= 1 && n_bits <= 8;
-    // n == 0 marks the table form, so a refused n_bits travels as -1
-    const NestedDict d{reinterpret_cast<const uint32_t*>(packed), nullptr,
-                       (bits_ok && D > 0 && D <= QSAEK_MAX_D) ? (D * field_width(n_bits) + 31) / 32 : 0,    // qsae_binary_row_bytes / 4
-                       bits_ok ? n_bits : -1, D, step};
-    return decode_multik(__func__, idx, val, B, K, d, H, dec_bias, ks, n_ks, recon, stream);
+    return decode_multik(__func__, idx, val, B, K, packed_dict(packed, D, n_bits, step), H, dec_bias, ks, n_ks, recon, stream);
 }
 
 extern "C" int qsaek_decode_multik_table(const int32_t* idx, const float* val, int B, int K, const float* table, int H, int D,
                                          float scale, const float* dec_bias, const int* ks, int n_ks, float* recon,
                                          qsae_stream_t stream) {
-    const NestedDict d{nullptr, table, 0, 0, D, scale};
-    return decode_multik(__func__, idx, val, B, K, d, H, dec_bias, ks, n_ks, recon, stream);
+    return decode_multik(__func__, idx, val, B, K, table_dict(table, D, scale), H, dec_bias, ks, n_ks, recon, stream);
 }
 
 extern "C" int qsaek_row_grad_multik(const int32_t* idx, int B, int K, const float* table, int H, int D, float step,
                                      const float* const* g_points, const int* ks, int n_ks, const float* g_latent,
                                      int64_t g_latent_ld, const float* W_enc, float* G, float* gv, float* dx,
                                      qsae_stream_t stream) {
-    UnitLevels pts;
-    if (const int rc = multik_limits(__func__, B, K, H, D, false, 0, false, ks, n_ks, &pts); rc != QSAE_OK) return rc;
-    QSAE_CHECK_ARG(g_points != nullptr, "g_points is null");
-    LevelGrads gl;
-    for (int p = 0; p < kMaxLevels; ++p) gl.p[p] = p < n_ks ? g_points[p] : nullptr;
-    if (B == 0) return QSAE_OK;
-    QSAE_CHECK_ARG(table && G && idx && gv, "null pointer");
-    QSAE_CHECK_ARG(!dx || W_enc, "dx needs W_enc");
-    bool g_ok = true;
-    for (int p = 0; p < kMaxLevels; ++p) g_ok = g_ok && aligned16(gl.p[p]);
-    QSAE_CHECK_ARG(g_ok && aligned16(table) && aligned16(G) && (!dx || (aligned16(dx) && aligned16(W_enc))),
-                   "table, g_points, G, W_enc and dx must be 16-byte aligned");
-    QSAE_CHECK_ARG(!multik_misaligned(idx, 4) && !multik_misaligned(gv, 4) && !multik_misaligned(g_latent, 4),
-                   "idx, gv and g_latent must be 4-byte aligned");
-    QSAE_CHECK_ARG(!g_latent || g_latent_ld >= 0, "g_latent_ld >= 0 required");
-    hipLaunchKernelGGL(multik_row_kernel, dim3((B + kNestedWaves - 1) / kNestedWaves), dim3(64 * kNestedWaves), 0,
-                       as_stream(stream), idx, B, K, H, D, table, step, gl, pts, g_latent, static_cast<long long>(g_latent_ld),
-                       W_enc, G, gv, dx);
-    QSAE_LAUNCH_CHECK();
-    return QSAE_OK;
+    return row_grad_levels(__func__, kMultikRules, false, false, "g_points", idx, nullptr, B, K, table, H, D, g_points, ks, n_ks,
+                           g_latent, g_latent_ld, W_enc, G, gv, dx, [&](const LevelGrads& gl, const UnitLevels& pts) {
+        hipLaunchKernelGGL(multik_row_kernel, dim3((B + kNestedWaves - 1) / kNestedWaves), dim3(64 * kNestedWaves), 0,
+                           as_stream(stream), idx, B, K, H, D, table, step, gl, pts, g_latent,
+                           static_cast<long long>(g_latent_ld), W_enc, G, gv, dx);
+    });
 }
 
 extern "C" size_t qsaek_train_unit_grad_multik_workspace_bytes(int B, int K, int H, int D) {
-    if (K < 1 || K > kMultikMaxK || static_cast<long long>(B) * K >= (1LL << 31)) return 0;
-    return qsae_train_unit_grad_workspace_bytes(B, K, H, D);
+    return unit_grad_levels_bytes(kMultikRules, B, K, H, D);
 }
 
 extern "C" size_t qsaek_train_table_unit_grad_multik_workspace_bytes(int B, int K, int H, int D) {
-    if (K < 1) return 0;
-    return qsae_train_table_unit_grad_workspace_bytes(B, K, H, D);
+    return table_unit_grad_levels_bytes(kMultikRules, B, K, H, D);
 }
 
 extern "C" int qsaek_train_unit_grad_multik(const int32_t* offsets, const int32_t* entries, const float* val, const float* gv,
@@ -351,16 +302,10 @@ extern "C" int qsaek_train_unit_grad_multik(const int32_t* offsets, const int32_
                                             float* dW_enc, float* db_enc, float* dlogits, void* workspace, size_t workspace_bytes,
                                             qsae_stream_t stream) {
     UnitLevels pts;
-    if (const int rc = multik_limits(__func__, B, K, H, D, true, n_bits, true, ks, n_ks, &pts); rc != QSAE_OK) return rc;
-    const long long Bk = static_cast<long long>(B) * K;
-    QSAE_CHECK_ARG(offsets != nullptr, "null pointer");
-    QSAE_CHECK_ARG(Bk == 0 || (entries && val && gv && x), "null pointer");
-    QSAE_CHECK_ARG(!dlogits || logits, "dlogits needs logits");
-    QSAE_CHECK_ARG((!x || aligned16(x)) && aligned16(G) && (!dW_enc || aligned16(dW_enc)) &&
-                   (!dlogits || (aligned16(dlogits) && aligned16(logits))),
-                   "x, G, logits, dW_enc and dlogits must be 16-byte aligned");
-    if (!workspace || workspace_bytes < qsaek_train_unit_grad_multik_workspace_bytes(B, K, H, D))
-        return fail(QSAE_ERR_WORKSPACE, "%s: workspace missing or smaller than the sizer's bytes", __func__);
+    if (const int rc = unit_grad_levels_checks(__func__, kMultikRules, offsets, entries, val, gv, B, K, x, G, ks, n_ks, logits, H,
+                                               D, n_bits, dW_enc, dlogits, workspace, workspace_bytes, &pts);
+        rc != QSAE_OK)
+        return rc;
     QSAE_HIP(train_unit_grad_ranks(offsets, entries, val, gv, B, K, x, G, pts, logits, H, D, n_bits, step, g_polarize, dW_enc,
                                    db_enc, dlogits, workspace, as_stream(stream)));
     return QSAE_OK;
@@ -372,15 +317,10 @@ extern "C" int qsaek_train_table_unit_grad_multik(const int32_t* offsets, const 
                                                   int64_t dW_dec_ld, void* workspace, size_t workspace_bytes,
                                                   qsae_stream_t stream) {
     UnitLevels pts;
-    if (const int rc = multik_limits(__func__, B, K, H, D, false, 0, true, ks, n_ks, &pts); rc != QSAE_OK) return rc;
-    const long long Bk = static_cast<long long>(B) * K;
-    QSAE_CHECK_ARG(offsets != nullptr, "null pointer");
-    QSAE_CHECK_ARG(Bk == 0 || (entries && val && gv && x), "null pointer");
-    QSAE_CHECK_ARG(!dW_dec || dW_dec_ld >= H, "dW_dec_ld >= H required");
-    QSAE_CHECK_ARG((!x || aligned16(x)) && aligned16(G) && (!dW_enc || aligned16(dW_enc)),
-                   "x, G and dW_enc must be 16-byte aligned");
-    if (!workspace || workspace_bytes < qsaek_train_table_unit_grad_multik_workspace_bytes(B, K, H, D))
-        return fail(QSAE_ERR_WORKSPACE, "%s: workspace missing or smaller than the sizer's bytes", __func__);
+    if (const int rc = table_unit_grad_levels_checks(__func__, kMultikRules, offsets, entries, val, gv, B, K, x, G, ks, n_ks, H,
+                                                     D, dW_enc, dW_dec, dW_dec_ld, workspace, workspace_bytes, &pts);
+        rc != QSAE_OK)
+        return rc;
     QSAE_HIP(train_table_unit_grad_ranks(offsets, entries, val, gv, B, K, x, G, pts, H, D, dW_enc, db_enc, dW_dec,
                                          static_cast<long long>(dW_dec_ld), workspace, as_stream(stream)));
     return QSAE_OK;

@@ -8,7 +8,7 @@ import collections
 import ctypes as C
 import functools
 import weakref
-from typing import Optional, Tuple
+from typing import Callable, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -2767,24 +2767,77 @@ def prefix_errors(x: torch.Tensor, idx: torch.Tensor, val: torch.Tensor, ks, dec
              ws.numel(), _stream()))
 
 
-# ---- nested-dictionary (Matryoshka) objective of the top-k SAEs (include/qsae_nested.h, csrc/nested.hip) --------------------
+# ---- the multi-level objectives of the top-k SAEs: what their wrappers share ------------------------------------------------
+# Four families (nested levels, Multi-TopK points, ragged BatchTopK rows, nested levels over ragged rows) with one decoder, one
+# row gradient and one pair of unit gradients between them.  The public names below say which family; the checks, their
+# order, their texts and every allocation live here once.
 NESTED_MAX_LEVELS = 8
+MULTIK_MAX_POINTS = 8
+
+
+def _ascending_ints(seq, end: int, who: str, name: str, noun: str, limit: int, end_name: str, end_max: Optional[int] = None):
+    """``seq`` as a list of ints: 1 .. ``limit`` whole numbers, 0 < seq[0] < ... < seq[-1] == end; ``end`` itself within
+    1 .. end_max where that is given."""
+    try:
+        out = [int(b) for b in seq]
+    except TypeError:
+        raise ValueError(f"{who}: {name} must be a sequence of ints, got {seq!r}") from None
+    if any(isinstance(b, bool) or int(b) != b for b in seq):
+        raise ValueError(f"{who}: {name} must be whole numbers, got {list(seq)!r}")
+    if not 1 <= len(out) <= limit:
+        raise ValueError(f"{who}: {len(out)} {noun}; 1 .. {limit} are supported")
+    if end_max is not None and not 1 <= int(end) <= end_max:
+        raise ValueError(f"{who}: {end_name} = {int(end)} is outside 1 .. {end_max}")
+    if out[0] < 1 or any(b <= a for a, b in zip(out, out[1:])) or out[-1] != int(end):
+        raise ValueError(f"{who}: {name} = {out} must be ascending and distinct, start above 0 and end at {end_name} = {int(end)}")
+    return out
 
 
 def nested_bounds(bounds, H: int, who: str = "nested_bounds"):
     """``bounds`` as a list of ints after the checks of qsae_nested.h: 1 .. 8 levels, 0 < bounds[0] < ... < bounds[-1] == H."""
-    try:
-        out = [int(b) for b in bounds]
-    except TypeError:
-        raise ValueError(f"{who}: bounds must be a sequence of ints, got {bounds!r}") from None
-    if any(isinstance(b, bool) or int(b) != b for b in bounds):
-        raise ValueError(f"{who}: bounds must be whole numbers, got {list(bounds)!r}")
-    if not 1 <= len(out) <= NESTED_MAX_LEVELS:
-        raise ValueError(f"{who}: {len(out)} levels; 1 .. {NESTED_MAX_LEVELS} are supported")
-    if out[0] < 1 or any(b <= a for a, b in zip(out, out[1:])) or out[-1] != int(H):
-        raise ValueError(f"{who}: bounds = {out} must be ascending and distinct, start above 0 and end at hidden_dim = {int(H)}")
-    return out
+    return _ascending_ints(bounds, H, who, "bounds", "levels", NESTED_MAX_LEVELS, "hidden_dim")
 
+
+def multik_points(ks, K: int, who: str = "multik_points"):
+    """``ks`` as a list of ints after the checks of qsae_multik.h: 1 .. 8 points, 0 < ks[0] < ... < ks[-1] == K <= 256."""
+    return _ascending_ints(ks, K, who, "ks", "points", MULTIK_MAX_POINTS, "the list width K", TRAIN_MAX_K)
+
+
+class _Levels(NamedTuple):
+    """How a family names and validates its host array of levels (unit bounds, ending at H) or points (rank prefixes,
+    ending at K)."""
+    validate: Callable
+    by_rank: bool
+    noun: str                    # "level" / "point"
+    grads: str                   # "g_levels" / "g_points"
+    k: str                       # what the messages call the list length
+    unit_prechecks: bool         # the packed unit gradient tests ranks, H >= 1 and B * k before the array
+    unit_symbol: str             # of the unit gradients, {} = "" (packed) or "_table"
+
+
+class _Decoder(NamedTuple):
+    symbol: str                  # of the C ABI, without _binary / _table
+    ragged: bool                 # takes counts: row r stops after counts[r] entries
+    levels: Optional[_Levels]    # None: one reconstruction [B, D]
+    below: bool                  # also returns counts_below [L, B]
+
+
+class _RowGrad(NamedTuple):
+    symbol: str
+    ragged: bool
+    need_2d: bool                # refuses an idx that is not 2-D in words of its own
+    levels: _Levels
+
+
+_NESTED = _Levels(nested_bounds, False, "level", "g_levels", "k", False, "qsaen_train{}_unit_grad_nested")
+_MULTIK = _Levels(multik_points, True, "point", "g_points", "K", True, "qsaek_train{}_unit_grad_multik")
+_DECODE_NESTED = _Decoder("qsaen_decode_nested", False, _NESTED, False)
+_DECODE_MULTIK = _Decoder("qsaek_decode_multik", False, _MULTIK, False)
+_DECODE_RAGGED = _Decoder("qsaeb_decode_ragged", True, None, False)
+_DECODE_NESTED_RAGGED = _Decoder("qsaem_decode_nested_ragged", True, _NESTED, True)
+_ROW_NESTED = _RowGrad("qsaen_row_grad_nested", False, False, _NESTED)
+_ROW_MULTIK = _RowGrad("qsaek_row_grad_multik", False, True, _MULTIK)
+_ROW_NESTED_RAGGED = _RowGrad("qsaem_row_grad_nested_ragged", True, False, _NESTED)
 
 def _bounds_arg(bounds):
     return C.cast((C.c_int * len(bounds))(*bounds), C.c_void_p)      # a host array: read before the call returns
@@ -2805,88 +2858,98 @@ def _nested_D(who: str, D: int) -> None:
         raise ValueError(f"{who}: D = {D} must be a positive multiple of 4 up to {TRAIN_MAX_D}")
 
 
-@_on_tensor_device
-def decode_nested_binary(idx, val, packed, D: int, n_bits: int, step: float, bias, bounds) -> torch.Tensor:
-    """-> fp32 [L, B, D]: level l is decode_binary_sparse on the lists without the entries of units >= bounds[l], bit for bit,
-    all levels from one walk over each row's list; see qsaen_decode_nested_binary."""
-    who = "decode_nested_binary"
-    idx, val = _nested_lists(who, idx, val)
-    _dev(packed, f"{who}: packed", torch.uint8)
+def _sparse_dictionary(who: str, dictionary, D, n_bits, device):
+    """The dictionary operand of a sparse decoder -> (kind, dictionary, H, D, n_bits): "binary" for packed uint8
+    [H, row_bytes] with D and n_bits given, "table" (n_bits None) for fp32 [H, D]."""
+    if n_bits is None:
+        table = _f32c(dictionary, "table")
+        if table.dim() != 2 or table.device != device:
+            raise ValueError(f"{who}: table is {tuple(table.shape)} on {table.device}, expected [H, D] on {device}")
+        H, D = table.shape
+        _nested_D(who, D)
+        return "table", table, H, D, None
+    packed = _dev(dictionary, f"{who}: packed", torch.uint8)
     D, n_bits = int(D), int(n_bits)
     _nested_D(who, D)
     if not 1 <= n_bits <= 8:
         raise ValueError(f"{who}: n_bits = {n_bits} is outside 1 .. 8")
-    if packed.dim() != 2 or packed.shape[1] != binary_row_bytes(D, n_bits) or not packed.is_contiguous() or packed.device != idx.device:
-        raise ValueError(f"{who}: packed is {tuple(packed.shape)}, expected contiguous [H, {binary_row_bytes(D, n_bits)}] on {idx.device}")
-    H = packed.shape[0]
-    bounds = nested_bounds(bounds, H, who)
+    if packed.dim() != 2 or packed.shape[1] != binary_row_bytes(D, n_bits) or not packed.is_contiguous() or packed.device != device:
+        raise ValueError(f"{who}: packed is {tuple(packed.shape)}, expected contiguous [H, {binary_row_bytes(D, n_bits)}] on {device}")
+    return "binary", packed, packed.shape[0], D, n_bits
+
+
+def _decode_sparse(fam: _Decoder, who: str, idx, val, counts, dictionary, D, n_bits, mult: float, bias, levels):
+    """Every sparse decoder of the four families: the lists, the dictionary, the levels or points, the bias -- in this order,
+    the bias after the levels -- and one call."""
+    if fam.ragged:
+        idx, val, counts = _batch_lists(who, idx, val, counts)
+    else:
+        idx, val = _nested_lists(who, idx, val)
+    kind, dictionary, H, D, n_bits = _sparse_dictionary(who, dictionary, D, n_bits, idx.device)
+    B, K = idx.shape
+    lv = fam.levels.validate(levels, K if fam.levels.by_rank else H, who) if fam.levels is not None else None
     b = _f32c(bias, "bias") if bias is not None else None
     if b is not None and tuple(b.shape) != (D,):
         raise ValueError(f"{who}: bias is {tuple(b.shape)}, expected [{D}]")
-    B, k = idx.shape
-    recon = torch.empty((len(bounds), B, D), dtype=torch.float32, device=idx.device)
-    check(_lib.load().qsaen_decode_nested_binary(_p(idx), _p(val), B, k, _p(packed), H, D, n_bits, float(step), _p(b),
-                                                 _bounds_arg(bounds), len(bounds), _p(recon), _stream()))
-    return recon
+    recon = torch.empty((B, D) if lv is None else (len(lv), B, D), dtype=torch.float32, device=idx.device)
+    below = torch.empty((len(lv), B), dtype=torch.int32, device=idx.device) if fam.below else None
+    args = [_p(idx), _p(val)] + ([_p(counts)] if fam.ragged else []) + [B, K, _p(dictionary), H, D]
+    args += ([n_bits] if kind == "binary" else []) + [float(mult), _p(b)]
+    args += ([_bounds_arg(lv), len(lv)] if lv is not None else []) + [_p(recon)] + ([_p(below)] if fam.below else [])
+    check(getattr(_lib.load(), f"{fam.symbol}_{kind}")(*args, _stream()))
+    return (recon, below) if fam.below else recon
 
 
-@_on_tensor_device
-def decode_nested_table(idx, val, table: torch.Tensor, scale: float, bias, bounds) -> torch.Tensor:
-    """-> fp32 [L, B, D]: level l is decode_table_sparse on the lists without the entries of units >= bounds[l], bit for bit;
-    see qsaen_decode_nested_table."""
-    who = "decode_nested_table"
-    idx, val = _nested_lists(who, idx, val)
+def _row_grad_lists(who: str, idx, counts, table, ragged: bool, need_2d: bool):
+    """The lists and the table of a row gradient -> (idx, counts, table, B, K, H, D)."""
+    if ragged:
+        idx, _, counts = _batch_lists(who, idx, None, counts)
+    else:
+        _dev(idx, f"{who}: idx", torch.int32)
+        if need_2d and idx.dim() != 2:
+            raise ValueError(f"{who}: idx is {tuple(idx.shape)}, expected [B, K]")
+        idx = idx.contiguous()
     table = _f32c(table, "table")
-    if table.dim() != 2 or table.device != idx.device:
-        raise ValueError(f"{who}: table is {tuple(table.shape)} on {table.device}, expected [H, D] on {idx.device}")
+    B, K = idx.shape
     H, D = table.shape
-    _nested_D(who, D)
-    bounds = nested_bounds(bounds, H, who)
-    b = _f32c(bias, "bias") if bias is not None else None
-    if b is not None and tuple(b.shape) != (D,):
-        raise ValueError(f"{who}: bias is {tuple(b.shape)}, expected [{D}]")
-    B, k = idx.shape
-    recon = torch.empty((len(bounds), B, D), dtype=torch.float32, device=idx.device)
-    check(_lib.load().qsaen_decode_nested_table(_p(idx), _p(val), B, k, _p(table), H, D, float(scale), _p(b),
-                                                _bounds_arg(bounds), len(bounds), _p(recon), _stream()))
-    return recon
+    if ragged:
+        _nested_D(who, D)
+    else:
+        _check_train_shape(D, K)
+    return idx, counts, table, B, K, H, D
 
 
-@_on_tensor_device
-def train_row_grad_nested(idx: torch.Tensor, table: torch.Tensor, step: float, g_levels, bounds,
-                          g_latent: Optional[torch.Tensor], W_enc: Optional[torch.Tensor], want_dx: bool = False):
-    """-> (G fp32 [L, B, D], gv fp32 [B, k], dx fp32 [B, D] or None).  ``g_levels``: L gradients [B, D], None for a level the
-    loss does not read.  G holds their suffix sums; gv and dx are train_row_grad's with g_recon = G[level(unit)] per entry.  See
-    qsaen_row_grad_nested."""
-    who = "train_row_grad_nested"
-    _dev(idx, f"{who}: idx", torch.int32)
-    idx = idx.contiguous()
-    table = _f32c(table, "table")
-    B, k = idx.shape
-    H, D = table.shape
-    _check_train_shape(D, k)
-    bounds = nested_bounds(bounds, H, who)
-    g_levels = list(g_levels)
-    if len(g_levels) != len(bounds):
-        raise ValueError(f"{who}: {len(g_levels)} level gradients for {len(bounds)} levels")
-    gs = []
-    for l, g in enumerate(g_levels):
-        if g is not None:
-            g = _f32c(g, f"g_levels[{l}]")
-            if tuple(g.shape) != (B, D) or g.device != idx.device:
-                raise ValueError(f"{who}: g_levels[{l}] is {tuple(g.shape)} on {g.device}, expected [{B}, {D}] on {idx.device}")
-        gs.append(g)
+def _row_grad_latent(g_latent, W_enc, want_dx: bool, B: int, H: int, D: int):
     gL, gl_ld = _latent_grad(g_latent, B, H)
     W = _f32c(W_enc, "W_enc") if want_dx else None
     if W is not None and tuple(W.shape) != (H, D):
         raise ValueError(f"W_enc is {tuple(W.shape)}, expected [{H}, {D}]")
-    G = torch.empty((len(bounds), B, D), dtype=torch.float32, device=idx.device)
-    gv = torch.empty((B, k), dtype=torch.float32, device=idx.device)
+    return gL, gl_ld, W
+
+
+def _row_grad_levels(fam: _RowGrad, who: str, idx, counts, table, step: float, grads, levels, g_latent, W_enc, want_dx: bool):
+    """-> (G [L, B, D], gv [B, K], dx [B, D] or None) of the three level/point forms."""
+    idx, counts, table, B, K, H, D = _row_grad_lists(who, idx, counts, table, fam.ragged, fam.need_2d)
+    words = fam.levels
+    lv = words.validate(levels, K if words.by_rank else H, who)
+    grads = list(grads)
+    if len(grads) != len(lv):
+        raise ValueError(f"{who}: {len(grads)} {words.noun} gradients for {len(lv)} {words.noun}s")
+    gs = []
+    for l, g in enumerate(grads):
+        if g is not None:
+            g = _f32c(g, f"{words.grads}[{l}]")
+            if tuple(g.shape) != (B, D) or g.device != idx.device:
+                raise ValueError(f"{who}: {words.grads}[{l}] is {tuple(g.shape)} on {g.device}, expected [{B}, {D}] on {idx.device}")
+        gs.append(g)
+    gL, gl_ld, W = _row_grad_latent(g_latent, W_enc, want_dx, B, H, D)
+    G = torch.empty((len(lv), B, D), dtype=torch.float32, device=idx.device)
+    gv = torch.empty((B, K), dtype=torch.float32, device=idx.device)
     dx = torch.empty((B, D), dtype=torch.float32, device=idx.device) if want_dx else None
     garr = (C.c_void_p * len(gs))(*[0 if g is None else g.data_ptr() for g in gs])     # host array of device pointers
-    check(_lib.load().qsaen_row_grad_nested(_p(idx), B, k, _p(table), H, D, float(step), C.cast(garr, C.c_void_p),
-                                            _bounds_arg(bounds), len(bounds), _p(gL), int(gl_ld), _p(W), _p(G), _p(gv), _p(dx),
-                                            _stream()))
+    args = [_p(idx)] + ([_p(counts)] if fam.ragged else [])
+    check(getattr(_lib.load(), fam.symbol)(*args, B, K, _p(table), H, D, float(step), C.cast(garr, C.c_void_p), _bounds_arg(lv),
+                                           len(lv), _p(gL), int(gl_ld), _p(W), _p(G), _p(gv), _p(dx), _stream()))
     return G, gv, dx
 
 
@@ -2899,44 +2962,42 @@ def _nested_G(who: str, G, L: int, B: int, D: int):
     return G
 
 
-@_on_tensor_device
-def train_unit_grad_nested(offsets: torch.Tensor, entries: torch.Tensor, val: torch.Tensor, gv: torch.Tensor, x: torch.Tensor,
-                           G: Optional[torch.Tensor], bounds, logits: torch.Tensor, n_bits: int, step: float,
-                           g_polarize: Optional[torch.Tensor], want_encoder: bool = True, want_logits: bool = True):
-    """train_unit_grad with g_recon = G[level(h)] for unit h (G fp32 [L, B, D] from train_row_grad_nested, or None);
-    see qsaen_train_unit_grad_nested."""
-    who = "train_unit_grad_nested"
+def _unit_grad_levels(words: _Levels, who: str, offsets, entries, val, gv, x, G, levels, logits, n_bits: int, step: float,
+                      g_polarize, want_encoder: bool, want_logits: bool):
+    """The packed unit gradient with g_recon = G[level or point] -> (dW_enc, db_enc, dlogits)."""
     _dev(offsets, "offsets", torch.int32)
     _dev(entries, "entries", torch.int32)
     val, gv, x, logits = _f32c(val, "val"), _f32c(gv, "gv"), _f32c(x, "x"), _f32c(logits, "logits")
+    if words.unit_prechecks and (val.dim() != 2 or x.dim() != 2 or offsets.dim() != 1):
+        raise ValueError(f"{who}: val and x must be 2-D, offsets 1-D")
     B, k = val.shape
     D = x.shape[1]
     H = offsets.shape[0] - 1
     _check_train_shape(D, k)
-    if tuple(logits.shape) != (H, D * n_bits) or tuple(x.shape) != (B, D) or tuple(gv.shape) != (B, k) \
-            or entries.numel() != B * k:
+    if (words.unit_prechecks and H < 1) or tuple(logits.shape) != (H, D * n_bits) or tuple(x.shape) != (B, D) \
+            or tuple(gv.shape) != (B, k) or entries.numel() != B * k:
         raise ValueError(f"{who}: inconsistent shapes")
-    bounds = nested_bounds(bounds, H, who)
-    G = _nested_G(who, G, len(bounds), B, D)
+    if words.unit_prechecks and B * k >= 2 ** 31:
+        raise ValueError(f"{who}: B * {words.k} = {B * k} is not below 2^31")
+    lv = words.validate(levels, k if words.by_rank else H, who)
+    G = _nested_G(who, G, len(lv), B, D)
     gP = _f32c(g_polarize.reshape(()), "g_polarize") if g_polarize is not None else None
     dev = x.device
     dW = torch.empty((H, D), dtype=torch.float32, device=dev) if want_encoder else None
     db = torch.empty((H,), dtype=torch.float32, device=dev) if want_encoder else None
     dl = torch.empty((H, D * n_bits), dtype=torch.float32, device=dev) if want_logits else None
     lib = _lib.load()
-    ws = _train_ws(lib.qsaen_train_unit_grad_nested_workspace_bytes(B, k, H, D), dev)
-    check(lib.qsaen_train_unit_grad_nested(_p(offsets.contiguous()), _p(entries.contiguous()), _p(val), _p(gv), B, k, _p(x),
-                                           _p(G), _bounds_arg(bounds), len(bounds), _p(logits), H, D, int(n_bits), float(step),
-                                           _p(gP), _p(dW), _p(db), _p(dl), _p(ws), ws.numel(), _stream()))
+    symbol = words.unit_symbol.format("")
+    ws = _train_ws(getattr(lib, symbol + "_workspace_bytes")(B, k, H, D), dev)
+    check(getattr(lib, symbol)(_p(offsets.contiguous()), _p(entries.contiguous()), _p(val), _p(gv), B, k, _p(x), _p(G),
+                               _bounds_arg(lv), len(lv), _p(logits), H, D, int(n_bits), float(step), _p(gP), _p(dW), _p(db),
+                               _p(dl), _p(ws), ws.numel(), _stream()))
     return dW, db, dl
 
 
-@_on_tensor_device
-def train_table_unit_grad_nested(offsets: torch.Tensor, entries: torch.Tensor, val: torch.Tensor, gv: torch.Tensor,
-                                 x: torch.Tensor, G: Optional[torch.Tensor], bounds, want_encoder: bool = True,
-                                 want_decoder: bool = True):
-    """train_table_unit_grad with g_recon = G[level(h)] for unit h; see qsaen_train_table_unit_grad_nested."""
-    who = "train_table_unit_grad_nested"
+def _table_unit_grad_levels(words: _Levels, who: str, offsets, entries, val, gv, x, G, levels, want_encoder: bool,
+                            want_decoder: bool):
+    """The table unit gradient with g_recon = G[level or point] -> (dW_enc, db_enc, dW_dec)."""
     _dev(offsets, "offsets", torch.int32)
     _dev(entries, "entries", torch.int32)
     val, gv, x = _f32c(val, "val"), _f32c(gv, "gv"), _f32c(x, "x")
@@ -2949,87 +3010,78 @@ def train_table_unit_grad_nested(offsets: torch.Tensor, entries: torch.Tensor, v
     if H < 1 or tuple(x.shape) != (B, D) or tuple(gv.shape) != (B, k) or entries.numel() != B * k:
         raise ValueError(f"{who}: inconsistent shapes")
     if B * k >= 2 ** 31:
-        raise ValueError(f"{who}: B * k = {B * k} is not below 2^31")
-    bounds = nested_bounds(bounds, H, who)
-    G = _nested_G(who, G, len(bounds), B, D)
+        raise ValueError(f"{who}: B * {words.k} = {B * k} is not below 2^31")
+    lv = words.validate(levels, k if words.by_rank else H, who)
+    G = _nested_G(who, G, len(lv), B, D)
     dev = x.device
     dW = torch.empty((H, D), dtype=torch.float32, device=dev) if want_encoder else None
     db = torch.empty((H,), dtype=torch.float32, device=dev) if want_encoder else None
     dWd = torch.empty((D, H), dtype=torch.float32, device=dev) if want_decoder else None
     lib = _lib.load()
-    ws = _train_ws(lib.qsaen_train_table_unit_grad_nested_workspace_bytes(B, k, H, D), dev)
-    check(lib.qsaen_train_table_unit_grad_nested(_p(offsets.contiguous()), _p(entries.contiguous()), _p(val), _p(gv), B, k,
-                                                 _p(x), _p(G), _bounds_arg(bounds), len(bounds), H, D, _p(dW), _p(db), _p(dWd),
-                                                 H, _p(ws), ws.numel(), _stream()))
+    symbol = words.unit_symbol.format("_table")
+    ws = _train_ws(getattr(lib, symbol + "_workspace_bytes")(B, k, H, D), dev)
+    check(getattr(lib, symbol)(_p(offsets.contiguous()), _p(entries.contiguous()), _p(val), _p(gv), B, k, _p(x), _p(G),
+                               _bounds_arg(lv), len(lv), H, D, _p(dW), _p(db), _p(dWd), H, _p(ws), ws.numel(), _stream()))
     return dW, db, dWd
 
 
+# ---- nested-dictionary (Matryoshka) objective of the top-k SAEs (include/qsae_nested.h, csrc/nested.hip) --------------------
+@_on_tensor_device
+def decode_nested_binary(idx, val, packed, D: int, n_bits: int, step: float, bias, bounds) -> torch.Tensor:
+    """-> fp32 [L, B, D]: level l is decode_binary_sparse on the lists without the entries of units >= bounds[l], bit for bit,
+    all levels from one walk over each row's list; see qsaen_decode_nested_binary."""
+    return _decode_sparse(_DECODE_NESTED, "decode_nested_binary", idx, val, None, packed, D, n_bits, step, bias, bounds)
+
+
+@_on_tensor_device
+def decode_nested_table(idx, val, table: torch.Tensor, scale: float, bias, bounds) -> torch.Tensor:
+    """-> fp32 [L, B, D]: level l is decode_table_sparse on the lists without the entries of units >= bounds[l], bit for bit;
+    see qsaen_decode_nested_table."""
+    return _decode_sparse(_DECODE_NESTED, "decode_nested_table", idx, val, None, table, None, None, scale, bias, bounds)
+
+
+@_on_tensor_device
+def train_row_grad_nested(idx: torch.Tensor, table: torch.Tensor, step: float, g_levels, bounds,
+                          g_latent: Optional[torch.Tensor], W_enc: Optional[torch.Tensor], want_dx: bool = False):
+    """-> (G fp32 [L, B, D], gv fp32 [B, k], dx fp32 [B, D] or None).  ``g_levels``: L gradients [B, D], None for a level the
+    loss does not read.  G holds their suffix sums; gv and dx are train_row_grad's with g_recon = G[level(unit)] per entry.  See
+    qsaen_row_grad_nested."""
+    return _row_grad_levels(_ROW_NESTED, "train_row_grad_nested", idx, None, table, step, g_levels, bounds, g_latent, W_enc,
+                            want_dx)
+
+
+@_on_tensor_device
+def train_unit_grad_nested(offsets: torch.Tensor, entries: torch.Tensor, val: torch.Tensor, gv: torch.Tensor, x: torch.Tensor,
+                           G: Optional[torch.Tensor], bounds, logits: torch.Tensor, n_bits: int, step: float,
+                           g_polarize: Optional[torch.Tensor], want_encoder: bool = True, want_logits: bool = True):
+    """train_unit_grad with g_recon = G[level(h)] for unit h (G fp32 [L, B, D] from train_row_grad_nested, or None);
+    see qsaen_train_unit_grad_nested."""
+    return _unit_grad_levels(_NESTED, "train_unit_grad_nested", offsets, entries, val, gv, x, G, bounds, logits, n_bits, step,
+                             g_polarize, want_encoder, want_logits)
+
+
+@_on_tensor_device
+def train_table_unit_grad_nested(offsets: torch.Tensor, entries: torch.Tensor, val: torch.Tensor, gv: torch.Tensor,
+                                 x: torch.Tensor, G: Optional[torch.Tensor], bounds, want_encoder: bool = True,
+                                 want_decoder: bool = True):
+    """train_table_unit_grad with g_recon = G[level(h)] for unit h; see qsaen_train_table_unit_grad_nested."""
+    return _table_unit_grad_levels(_NESTED, "train_table_unit_grad_nested", offsets, entries, val, gv, x, G, bounds, want_encoder,
+                                   want_decoder)
+
+
 # ---- Multi-TopK objective of the top-k SAEs (include/qsae_multik.h, csrc/multi_topk.hip) ------------------------------------
-MULTIK_MAX_POINTS = 8
-
-
-def multik_points(ks, K: int, who: str = "multik_points"):
-    """``ks`` as a list of ints after the checks of qsae_multik.h: 1 .. 8 points, 0 < ks[0] < ... < ks[-1] == K <= 256."""
-    try:
-        out = [int(k) for k in ks]
-    except TypeError:
-        raise ValueError(f"{who}: ks must be a sequence of ints, got {ks!r}") from None
-    if any(isinstance(k, bool) or int(k) != k for k in ks):
-        raise ValueError(f"{who}: ks must be whole numbers, got {list(ks)!r}")
-    if not 1 <= len(out) <= MULTIK_MAX_POINTS:
-        raise ValueError(f"{who}: {len(out)} points; 1 .. {MULTIK_MAX_POINTS} are supported")
-    if not 1 <= int(K) <= TRAIN_MAX_K:
-        raise ValueError(f"{who}: the list width K = {int(K)} is outside 1 .. {TRAIN_MAX_K}")
-    if out[0] < 1 or any(b <= a for a, b in zip(out, out[1:])) or out[-1] != int(K):
-        raise ValueError(f"{who}: ks = {out} must be ascending and distinct, start above 0 and end at the list width K = {int(K)}")
-    return out
-
-
 @_on_tensor_device
 def decode_multik_binary(idx, val, packed, D: int, n_bits: int, step: float, bias, ks) -> torch.Tensor:
     """-> fp32 [P, B, D]: point p is decode_binary_sparse on idx[:, :ks[p]], val[:, :ks[p]], bit for bit, every dictionary row
     gathered once for up to four points; see qsaek_decode_multik_binary."""
-    who = "decode_multik_binary"
-    idx, val = _nested_lists(who, idx, val)
-    _dev(packed, f"{who}: packed", torch.uint8)
-    D, n_bits = int(D), int(n_bits)
-    _nested_D(who, D)
-    if not 1 <= n_bits <= 8:
-        raise ValueError(f"{who}: n_bits = {n_bits} is outside 1 .. 8")
-    if packed.dim() != 2 or packed.shape[1] != binary_row_bytes(D, n_bits) or not packed.is_contiguous() or packed.device != idx.device:
-        raise ValueError(f"{who}: packed is {tuple(packed.shape)}, expected contiguous [H, {binary_row_bytes(D, n_bits)}] on {idx.device}")
-    H = packed.shape[0]
-    B, K = idx.shape
-    ks = multik_points(ks, K, who)
-    b = _f32c(bias, "bias") if bias is not None else None
-    if b is not None and tuple(b.shape) != (D,):
-        raise ValueError(f"{who}: bias is {tuple(b.shape)}, expected [{D}]")
-    recon = torch.empty((len(ks), B, D), dtype=torch.float32, device=idx.device)
-    check(_lib.load().qsaek_decode_multik_binary(_p(idx), _p(val), B, K, _p(packed), H, D, n_bits, float(step), _p(b),
-                                                 _bounds_arg(ks), len(ks), _p(recon), _stream()))
-    return recon
+    return _decode_sparse(_DECODE_MULTIK, "decode_multik_binary", idx, val, None, packed, D, n_bits, step, bias, ks)
 
 
 @_on_tensor_device
 def decode_multik_table(idx, val, table: torch.Tensor, scale: float, bias, ks) -> torch.Tensor:
     """-> fp32 [P, B, D]: point p is decode_table_sparse on idx[:, :ks[p]], val[:, :ks[p]], bit for bit; see
     qsaek_decode_multik_table."""
-    who = "decode_multik_table"
-    idx, val = _nested_lists(who, idx, val)
-    table = _f32c(table, "table")
-    if table.dim() != 2 or table.device != idx.device:
-        raise ValueError(f"{who}: table is {tuple(table.shape)} on {table.device}, expected [H, D] on {idx.device}")
-    H, D = table.shape
-    _nested_D(who, D)
-    B, K = idx.shape
-    ks = multik_points(ks, K, who)
-    b = _f32c(bias, "bias") if bias is not None else None
-    if b is not None and tuple(b.shape) != (D,):
-        raise ValueError(f"{who}: bias is {tuple(b.shape)}, expected [{D}]")
-    recon = torch.empty((len(ks), B, D), dtype=torch.float32, device=idx.device)
-    check(_lib.load().qsaek_decode_multik_table(_p(idx), _p(val), B, K, _p(table), H, D, float(scale), _p(b),
-                                                _bounds_arg(ks), len(ks), _p(recon), _stream()))
-    return recon
+    return _decode_sparse(_DECODE_MULTIK, "decode_multik_table", idx, val, None, table, None, None, scale, bias, ks)
 
 
 @_on_tensor_device
@@ -3038,38 +3090,7 @@ def train_row_grad_multik(idx: torch.Tensor, table: torch.Tensor, step: float, g
     """-> (G fp32 [P, B, D], gv fp32 [B, K], dx fp32 [B, D] or None).  ``g_points``: P gradients [B, D], None for a point the
     loss does not read.  G holds their suffix sums; gv and dx are train_row_grad's with g_recon = G[point(rank)] per entry.  See
     qsaek_row_grad_multik."""
-    who = "train_row_grad_multik"
-    _dev(idx, f"{who}: idx", torch.int32)
-    if idx.dim() != 2:
-        raise ValueError(f"{who}: idx is {tuple(idx.shape)}, expected [B, K]")
-    idx = idx.contiguous()
-    table = _f32c(table, "table")
-    B, K = idx.shape
-    H, D = table.shape
-    _check_train_shape(D, K)
-    ks = multik_points(ks, K, who)
-    g_points = list(g_points)
-    if len(g_points) != len(ks):
-        raise ValueError(f"{who}: {len(g_points)} point gradients for {len(ks)} points")
-    gs = []
-    for p, g in enumerate(g_points):
-        if g is not None:
-            g = _f32c(g, f"g_points[{p}]")
-            if tuple(g.shape) != (B, D) or g.device != idx.device:
-                raise ValueError(f"{who}: g_points[{p}] is {tuple(g.shape)} on {g.device}, expected [{B}, {D}] on {idx.device}")
-        gs.append(g)
-    gL, gl_ld = _latent_grad(g_latent, B, H)
-    W = _f32c(W_enc, "W_enc") if want_dx else None
-    if W is not None and tuple(W.shape) != (H, D):
-        raise ValueError(f"W_enc is {tuple(W.shape)}, expected [{H}, {D}]")
-    G = torch.empty((len(ks), B, D), dtype=torch.float32, device=idx.device)
-    gv = torch.empty((B, K), dtype=torch.float32, device=idx.device)
-    dx = torch.empty((B, D), dtype=torch.float32, device=idx.device) if want_dx else None
-    garr = (C.c_void_p * len(gs))(*[0 if g is None else g.data_ptr() for g in gs])     # host array of device pointers
-    check(_lib.load().qsaek_row_grad_multik(_p(idx), B, K, _p(table), H, D, float(step), C.cast(garr, C.c_void_p),
-                                            _bounds_arg(ks), len(ks), _p(gL), int(gl_ld), _p(W), _p(G), _p(gv), _p(dx),
-                                            _stream()))
-    return G, gv, dx
+    return _row_grad_levels(_ROW_MULTIK, "train_row_grad_multik", idx, None, table, step, g_points, ks, g_latent, W_enc, want_dx)
 
 
 @_on_tensor_device
@@ -3078,34 +3099,8 @@ def train_unit_grad_multik(offsets: torch.Tensor, entries: torch.Tensor, val: to
                            g_polarize: Optional[torch.Tensor], want_encoder: bool = True, want_logits: bool = True):
     """train_unit_grad with g_recon = G[point(e % K)] for list entry e (G fp32 [P, B, D] from train_row_grad_multik, or None);
     see qsaek_train_unit_grad_multik."""
-    who = "train_unit_grad_multik"
-    _dev(offsets, "offsets", torch.int32)
-    _dev(entries, "entries", torch.int32)
-    val, gv, x, logits = _f32c(val, "val"), _f32c(gv, "gv"), _f32c(x, "x"), _f32c(logits, "logits")
-    if val.dim() != 2 or x.dim() != 2 or offsets.dim() != 1:
-        raise ValueError(f"{who}: val and x must be 2-D, offsets 1-D")
-    B, K = val.shape
-    D = x.shape[1]
-    H = offsets.shape[0] - 1
-    _check_train_shape(D, K)
-    if H < 1 or tuple(logits.shape) != (H, D * n_bits) or tuple(x.shape) != (B, D) or tuple(gv.shape) != (B, K) \
-            or entries.numel() != B * K:
-        raise ValueError(f"{who}: inconsistent shapes")
-    if B * K >= 2 ** 31:
-        raise ValueError(f"{who}: B * K = {B * K} is not below 2^31")
-    ks = multik_points(ks, K, who)
-    G = _nested_G(who, G, len(ks), B, D)
-    gP = _f32c(g_polarize.reshape(()), "g_polarize") if g_polarize is not None else None
-    dev = x.device
-    dW = torch.empty((H, D), dtype=torch.float32, device=dev) if want_encoder else None
-    db = torch.empty((H,), dtype=torch.float32, device=dev) if want_encoder else None
-    dl = torch.empty((H, D * n_bits), dtype=torch.float32, device=dev) if want_logits else None
-    lib = _lib.load()
-    ws = _train_ws(lib.qsaek_train_unit_grad_multik_workspace_bytes(B, K, H, D), dev)
-    check(lib.qsaek_train_unit_grad_multik(_p(offsets.contiguous()), _p(entries.contiguous()), _p(val), _p(gv), B, K, _p(x),
-                                           _p(G), _bounds_arg(ks), len(ks), _p(logits), H, D, int(n_bits), float(step),
-                                           _p(gP), _p(dW), _p(db), _p(dl), _p(ws), ws.numel(), _stream()))
-    return dW, db, dl
+    return _unit_grad_levels(_MULTIK, "train_unit_grad_multik", offsets, entries, val, gv, x, G, ks, logits, n_bits, step,
+                             g_polarize, want_encoder, want_logits)
 
 
 @_on_tensor_device
@@ -3113,32 +3108,8 @@ def train_table_unit_grad_multik(offsets: torch.Tensor, entries: torch.Tensor, v
                                  x: torch.Tensor, G: Optional[torch.Tensor], ks, want_encoder: bool = True,
                                  want_decoder: bool = True):
     """train_table_unit_grad with g_recon = G[point(e % K)] for list entry e; see qsaek_train_table_unit_grad_multik."""
-    who = "train_table_unit_grad_multik"
-    _dev(offsets, "offsets", torch.int32)
-    _dev(entries, "entries", torch.int32)
-    val, gv, x = _f32c(val, "val"), _f32c(gv, "gv"), _f32c(x, "x")
-    if val.dim() != 2 or x.dim() != 2 or offsets.dim() != 1:
-        raise ValueError(f"{who}: val and x must be 2-D, offsets 1-D")
-    B, K = val.shape
-    D = x.shape[1]
-    H = offsets.shape[0] - 1
-    _check_train_shape(D, K)
-    if H < 1 or tuple(x.shape) != (B, D) or tuple(gv.shape) != (B, K) or entries.numel() != B * K:
-        raise ValueError(f"{who}: inconsistent shapes")
-    if B * K >= 2 ** 31:
-        raise ValueError(f"{who}: B * K = {B * K} is not below 2^31")
-    ks = multik_points(ks, K, who)
-    G = _nested_G(who, G, len(ks), B, D)
-    dev = x.device
-    dW = torch.empty((H, D), dtype=torch.float32, device=dev) if want_encoder else None
-    db = torch.empty((H,), dtype=torch.float32, device=dev) if want_encoder else None
-    dWd = torch.empty((D, H), dtype=torch.float32, device=dev) if want_decoder else None
-    lib = _lib.load()
-    ws = _train_ws(lib.qsaek_train_table_unit_grad_multik_workspace_bytes(B, K, H, D), dev)
-    check(lib.qsaek_train_table_unit_grad_multik(_p(offsets.contiguous()), _p(entries.contiguous()), _p(val), _p(gv), B, K,
-                                                 _p(x), _p(G), _bounds_arg(ks), len(ks), H, D, _p(dW), _p(db), _p(dWd),
-                                                 H, _p(ws), ws.numel(), _stream()))
-    return dW, db, dWd
+    return _table_unit_grad_levels(_MULTIK, "train_table_unit_grad_multik", offsets, entries, val, gv, x, G, ks, want_encoder,
+                                   want_decoder)
 
 
 # ---- BatchTopK of the top-k SAEs (include/qsae_batch.h, csrc/batch_topk.hip, csrc/batch_topk_decode.hip) -------------------
@@ -3234,45 +3205,14 @@ def threshold_select(val: torch.Tensor, theta, want_val: bool = True):
 def decode_ragged_binary(idx, val, counts, packed, D: int, n_bits: int, step: float, bias=None) -> torch.Tensor:
     """-> fp32 [B, D]: row r is decode_binary_sparse on the first counts[r] entries of its list, bit for bit; an entry behind
     the prefix is not read.  See qsaeb_decode_ragged_binary."""
-    who = "decode_ragged_binary"
-    idx, val, counts = _batch_lists(who, idx, val, counts)
-    _dev(packed, f"{who}: packed", torch.uint8)
-    D, n_bits = int(D), int(n_bits)
-    _nested_D(who, D)
-    if not 1 <= n_bits <= 8:
-        raise ValueError(f"{who}: n_bits = {n_bits} is outside 1 .. 8")
-    if packed.dim() != 2 or packed.shape[1] != binary_row_bytes(D, n_bits) or not packed.is_contiguous() or packed.device != idx.device:
-        raise ValueError(f"{who}: packed is {tuple(packed.shape)}, expected contiguous [H, {binary_row_bytes(D, n_bits)}] on {idx.device}")
-    H = packed.shape[0]
-    b = _f32c(bias, "bias") if bias is not None else None
-    if b is not None and tuple(b.shape) != (D,):
-        raise ValueError(f"{who}: bias is {tuple(b.shape)}, expected [{D}]")
-    B, K = idx.shape
-    recon = torch.empty((B, D), dtype=torch.float32, device=idx.device)
-    check(_lib.load().qsaeb_decode_ragged_binary(_p(idx), _p(val), _p(counts), B, K, _p(packed), H, D, n_bits, float(step), _p(b),
-                                                 _p(recon), _stream()))
-    return recon
+    return _decode_sparse(_DECODE_RAGGED, "decode_ragged_binary", idx, val, counts, packed, D, n_bits, step, bias, None)
 
 
 @_on_tensor_device
 def decode_ragged_table(idx, val, counts, table: torch.Tensor, scale: float = 1.0, bias=None) -> torch.Tensor:
     """-> fp32 [B, D]: row r is decode_table_sparse on the first counts[r] entries of its list, bit for bit.  See
     qsaeb_decode_ragged_table."""
-    who = "decode_ragged_table"
-    idx, val, counts = _batch_lists(who, idx, val, counts)
-    table = _f32c(table, "table")
-    if table.dim() != 2 or table.device != idx.device:
-        raise ValueError(f"{who}: table is {tuple(table.shape)} on {table.device}, expected [H, D] on {idx.device}")
-    H, D = table.shape
-    _nested_D(who, D)
-    b = _f32c(bias, "bias") if bias is not None else None
-    if b is not None and tuple(b.shape) != (D,):
-        raise ValueError(f"{who}: bias is {tuple(b.shape)}, expected [{D}]")
-    B, K = idx.shape
-    recon = torch.empty((B, D), dtype=torch.float32, device=idx.device)
-    check(_lib.load().qsaeb_decode_ragged_table(_p(idx), _p(val), _p(counts), B, K, _p(table), H, D, float(scale), _p(b),
-                                                _p(recon), _stream()))
-    return recon
+    return _decode_sparse(_DECODE_RAGGED, "decode_ragged_table", idx, val, counts, table, None, None, scale, bias, None)
 
 
 @_on_tensor_device
@@ -3282,18 +3222,11 @@ def train_row_grad_ragged(idx: torch.Tensor, counts: torch.Tensor, table: torch.
     """-> (gv fp32 [B, K], dx fp32 [B, D] or None): train_row_grad on the first counts[r] entries of every row, bit for bit;
     gv behind the prefix is +0.  See qsaeb_row_grad_ragged."""
     who = "train_row_grad_ragged"
-    idx, _, counts = _batch_lists(who, idx, None, counts)
-    table = _f32c(table, "table")
-    B, K = idx.shape
-    H, D = table.shape
-    _nested_D(who, D)
+    idx, counts, table, B, K, H, D = _row_grad_lists(who, idx, counts, table, True, False)
     gR = _f32c(g_recon, "g_recon") if g_recon is not None else None
     if gR is not None and tuple(gR.shape) != (B, D):
         raise ValueError(f"g_recon is {tuple(gR.shape)}, expected [{B}, {D}]")
-    gL, gl_ld = _latent_grad(g_latent, B, H)
-    W = _f32c(W_enc, "W_enc") if want_dx else None
-    if W is not None and tuple(W.shape) != (H, D):
-        raise ValueError(f"W_enc is {tuple(W.shape)}, expected [{H}, {D}]")
+    gL, gl_ld, W = _row_grad_latent(g_latent, W_enc, want_dx, B, H, D)
     gv = torch.empty((B, K), dtype=torch.float32, device=idx.device)
     dx = torch.empty((B, D), dtype=torch.float32, device=idx.device) if want_dx else None
     check(_lib.load().qsaeb_row_grad_ragged(_p(idx), _p(counts), B, K, _p(table), H, D, float(step), _p(gR), _p(gL), int(gl_ld),
@@ -3321,58 +3254,21 @@ def train_csr_ragged(idx: torch.Tensor, counts: torch.Tensor, H: int):
 
 
 # ---- nested levels over the ragged rows of BatchTopK (include/qsae_nested_batch.h, csrc/nested_ragged.hip) ------------------
-def _nested_ragged_out(bounds, B: int, D: int, device):
-    recon = torch.empty((len(bounds), B, D), dtype=torch.float32, device=device)
-    below = torch.empty((len(bounds), B), dtype=torch.int32, device=device)
-    return recon, below
-
-
 @_on_tensor_device
 def decode_nested_ragged_binary(idx, val, counts, packed, D: int, n_bits: int, step: float, bias, bounds):
     """-> (levels fp32 [L, B, D], counts_below int32 [L, B]): level l of row r is decode_nested_binary on the first counts[r]
     entries of its list, bit for bit; counts_below[l, r] = its kept entries below bounds[l].  An entry behind the prefix is not
     read.  See qsaem_decode_nested_ragged_binary."""
-    who = "decode_nested_ragged_binary"
-    idx, val, counts = _batch_lists(who, idx, val, counts)
-    _dev(packed, f"{who}: packed", torch.uint8)
-    D, n_bits = int(D), int(n_bits)
-    _nested_D(who, D)
-    if not 1 <= n_bits <= 8:
-        raise ValueError(f"{who}: n_bits = {n_bits} is outside 1 .. 8")
-    if packed.dim() != 2 or packed.shape[1] != binary_row_bytes(D, n_bits) or not packed.is_contiguous() or packed.device != idx.device:
-        raise ValueError(f"{who}: packed is {tuple(packed.shape)}, expected contiguous [H, {binary_row_bytes(D, n_bits)}] on {idx.device}")
-    H = packed.shape[0]
-    bounds = nested_bounds(bounds, H, who)
-    b = _f32c(bias, "bias") if bias is not None else None
-    if b is not None and tuple(b.shape) != (D,):
-        raise ValueError(f"{who}: bias is {tuple(b.shape)}, expected [{D}]")
-    B, K = idx.shape
-    recon, below = _nested_ragged_out(bounds, B, D, idx.device)
-    check(_lib.load().qsaem_decode_nested_ragged_binary(_p(idx), _p(val), _p(counts), B, K, _p(packed), H, D, n_bits, float(step),
-                                                        _p(b), _bounds_arg(bounds), len(bounds), _p(recon), _p(below), _stream()))
-    return recon, below
+    return _decode_sparse(_DECODE_NESTED_RAGGED, "decode_nested_ragged_binary", idx, val, counts, packed, D, n_bits, step, bias,
+                          bounds)
 
 
 @_on_tensor_device
 def decode_nested_ragged_table(idx, val, counts, table: torch.Tensor, scale: float, bias, bounds):
     """-> (levels fp32 [L, B, D], counts_below int32 [L, B]): level l of row r is decode_nested_table on the first counts[r]
     entries of its list, bit for bit.  See qsaem_decode_nested_ragged_table."""
-    who = "decode_nested_ragged_table"
-    idx, val, counts = _batch_lists(who, idx, val, counts)
-    table = _f32c(table, "table")
-    if table.dim() != 2 or table.device != idx.device:
-        raise ValueError(f"{who}: table is {tuple(table.shape)} on {table.device}, expected [H, D] on {idx.device}")
-    H, D = table.shape
-    _nested_D(who, D)
-    bounds = nested_bounds(bounds, H, who)
-    b = _f32c(bias, "bias") if bias is not None else None
-    if b is not None and tuple(b.shape) != (D,):
-        raise ValueError(f"{who}: bias is {tuple(b.shape)}, expected [{D}]")
-    B, K = idx.shape
-    recon, below = _nested_ragged_out(bounds, B, D, idx.device)
-    check(_lib.load().qsaem_decode_nested_ragged_table(_p(idx), _p(val), _p(counts), B, K, _p(table), H, D, float(scale), _p(b),
-                                                       _bounds_arg(bounds), len(bounds), _p(recon), _p(below), _stream()))
-    return recon, below
+    return _decode_sparse(_DECODE_NESTED_RAGGED, "decode_nested_ragged_table", idx, val, counts, table, None, None, scale, bias,
+                          bounds)
 
 
 @_on_tensor_device
@@ -3380,32 +3276,5 @@ def train_row_grad_nested_ragged(idx: torch.Tensor, counts: torch.Tensor, table:
                                  g_latent: Optional[torch.Tensor], W_enc: Optional[torch.Tensor] = None, want_dx: bool = False):
     """-> (G fp32 [L, B, D], gv fp32 [B, K], dx fp32 [B, D] or None): train_row_grad_nested on the first counts[r] entries of
     every row, bit for bit; G is written for every row, gv behind the prefix is +0.  See qsaem_row_grad_nested_ragged."""
-    who = "train_row_grad_nested_ragged"
-    idx, _, counts = _batch_lists(who, idx, None, counts)
-    table = _f32c(table, "table")
-    B, K = idx.shape
-    H, D = table.shape
-    _nested_D(who, D)
-    bounds = nested_bounds(bounds, H, who)
-    g_levels = list(g_levels)
-    if len(g_levels) != len(bounds):
-        raise ValueError(f"{who}: {len(g_levels)} level gradients for {len(bounds)} levels")
-    gs = []
-    for l, g in enumerate(g_levels):
-        if g is not None:
-            g = _f32c(g, f"g_levels[{l}]")
-            if tuple(g.shape) != (B, D) or g.device != idx.device:
-                raise ValueError(f"{who}: g_levels[{l}] is {tuple(g.shape)} on {g.device}, expected [{B}, {D}] on {idx.device}")
-        gs.append(g)
-    gL, gl_ld = _latent_grad(g_latent, B, H)
-    W = _f32c(W_enc, "W_enc") if want_dx else None
-    if W is not None and tuple(W.shape) != (H, D):
-        raise ValueError(f"W_enc is {tuple(W.shape)}, expected [{H}, {D}]")
-    G = torch.empty((len(bounds), B, D), dtype=torch.float32, device=idx.device)
-    gv = torch.empty((B, K), dtype=torch.float32, device=idx.device)
-    dx = torch.empty((B, D), dtype=torch.float32, device=idx.device) if want_dx else None
-    garr = (C.c_void_p * len(gs))(*[0 if g is None else g.data_ptr() for g in gs])     # host array of device pointers
-    check(_lib.load().qsaem_row_grad_nested_ragged(_p(idx), _p(counts), B, K, _p(table), H, D, float(step),
-                                                   C.cast(garr, C.c_void_p), _bounds_arg(bounds), len(bounds), _p(gL), int(gl_ld),
-                                                   _p(W), _p(G), _p(gv), _p(dx), _stream()))
-    return G, gv, dx
+    return _row_grad_levels(_ROW_NESTED_RAGGED, "train_row_grad_nested_ragged", idx, counts, table, step, g_levels, bounds,
+                            g_latent, W_enc, want_dx)

@@ -137,13 +137,13 @@ class BaselineSparseAutoencoder(ops.GraphForwardMixin, TopKCore, nn.Module):
     def _nested_train_decoder(self):
         return self._table(), 1.0, None
 
-    def _nested_unit_grad(self, offsets, entries, val, gv, x, G, bounds, g_extra, want_encoder: bool, want_decoder: bool):
-        return ops.train_table_unit_grad_nested(offsets, entries, val, gv, x, G, bounds, want_encoder=want_encoder,
-                                                want_decoder=want_decoder)
+    _LEVELS_UNIT_GRAD = {"nested": ops.train_table_unit_grad_nested, "multik": ops.train_table_unit_grad_multik}
 
-    def _multik_unit_grad(self, offsets, entries, val, gv, x, G, ks, g_extra, want_encoder: bool, want_decoder: bool):
-        return ops.train_table_unit_grad_multik(offsets, entries, val, gv, x, G, ks, want_encoder=want_encoder,
-                                                want_decoder=want_decoder)
+    def _levels_unit_grad(self, family: str, offsets, entries, val, gv, x, G, levels, g_extra, want_encoder: bool,
+                          want_decoder: bool):
+        """the unit sums with g_recon = G[level of the unit] ("nested") or G[point of the entry's rank] ("multik")"""
+        return self._LEVELS_UNIT_GRAD[family](offsets, entries, val, gv, x, G, levels, want_encoder=want_encoder,
+                                              want_decoder=want_decoder)
 
     def forward_compact(self, x):
         """(idx, val, reconstruction) without the dense latent; same path selection as forward()."""

@@ -334,15 +334,14 @@ class BinarySAE(ops.GraphForwardMixin, TopKCore, SparseAutoencoder):
         self._train_cache.put((dec.weight,), {"table": table})
         return table, dec.quantization_step, pol
 
-    def _nested_unit_grad(self, offsets, entries, val, gv, x, G, bounds, g_pol, want_encoder: bool, want_decoder: bool):
-        dec = self.decoder
-        return ops.train_unit_grad_nested(offsets, entries, val, gv, x, G, bounds, dec.weight.detach(), dec.n_bits,
-                                          dec.quantization_step, g_pol, want_encoder=want_encoder, want_logits=want_decoder)
+    _LEVELS_UNIT_GRAD = {"nested": ops.train_unit_grad_nested, "multik": ops.train_unit_grad_multik}
 
-    def _multik_unit_grad(self, offsets, entries, val, gv, x, G, ks, g_pol, want_encoder: bool, want_decoder: bool):
+    def _levels_unit_grad(self, family: str, offsets, entries, val, gv, x, G, levels, g_pol, want_encoder: bool,
+                          want_decoder: bool):
+        """the unit sums with g_recon = G[level of the unit] ("nested") or G[point of the entry's rank] ("multik")"""
         dec = self.decoder
-        return ops.train_unit_grad_multik(offsets, entries, val, gv, x, G, ks, dec.weight.detach(), dec.n_bits,
-                                          dec.quantization_step, g_pol, want_encoder=want_encoder, want_logits=want_decoder)
+        return self._LEVELS_UNIT_GRAD[family](offsets, entries, val, gv, x, G, levels, dec.weight.detach(), dec.n_bits,
+                                              dec.quantization_step, g_pol, want_encoder=want_encoder, want_logits=want_decoder)
 
     # -- two batches in flight --------------------------------------------------------------------------------
     def forward_submit(self, x, slot: int = 0, want_dense: bool = True):

@@ -409,24 +409,14 @@ class _NestedBatchTopKTrainStep(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_latent, g_levels, g_extra):
         xf, idx, val_sel, counts, table = ctx.saved_tensors
-        model, bounds = ctx.model, ctx.bounds
-        need_x, need_W, need_b, need_dec, need_bd = ctx.needs_input_grad[4:9]
-        want_units = need_W or need_b or need_dec
-        dx = dW = db = ddec = dbd = None
-        if (need_x or want_units or need_bd) and not (g_latent is None and g_levels is None and g_extra is None):
-            g_list = [None] * len(bounds) if g_levels is None else [g_levels[l] for l in range(len(bounds))]
-            G, gv, dx = ops.train_row_grad_nested_ragged(idx, counts, table, ctx.step, g_list, bounds, g_latent,
-                                                         model.encoder.linear.weight.detach(), want_dx=need_x)
-            if want_units:
-                offsets, entries = ops.train_csr_ragged(idx, counts, table.shape[0])
-                dW, db, ddec = model._nested_unit_grad(offsets, entries, val_sel, gv, xf, G, bounds, g_extra, need_W or need_b,
-                                                       need_dec)
-            if need_bd:
-                dbd = ops.train_col_sum(G[0])                  # every level adds the bias: its gradient is the whole sum
-            if dx is not None and dx.dtype != ctx.x_dtype:
-                dx = dx.to(ctx.x_dtype)
-        return (None, None, None, None, dx if need_x else None, dW if need_W else None, db if need_b else None,
-                ddec if need_dec else None, dbd if need_bd else None)
+        model, bounds, needs = ctx.model, ctx.bounds, ctx.needs_input_grad[4:9]
+
+        def unit_grad(offsets, entries, gv, G):
+            return model._levels_unit_grad("nested", offsets, entries, val_sel, gv, xf, G, bounds, g_extra, needs[1] or needs[2],
+                                           needs[3])
+        return (None,) * 4 + levels_backward((idx, counts), table, ctx.step, bounds, g_latent, g_levels, g_extra,
+                                             model.encoder.linear.weight, needs, ctx.x_dtype,
+                                             ops.train_row_grad_nested_ragged, ops.train_csr_ragged, unit_grad)
 
 
 class _BatchTopKTrainStep(torch.autograd.Function):
@@ -454,28 +444,17 @@ class _BatchTopKTrainStep(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_latent, g_recon, g_extra):
         xf, idx, val_sel, counts, table = ctx.saved_tensors
-        model = ctx.model
-        need_x, need_W, need_b, need_dec, need_bd = ctx.needs_input_grad[3:8]
-        want_units = need_W or need_b or need_dec
-        dx = dW = db = ddec = dbd = None
-        if need_x or want_units:
-            gv, dx = ops.train_row_grad_ragged(idx, counts, table, ctx.step, g_recon, g_latent,
-                                               model.encoder.linear.weight.detach(), want_dx=need_x)
-            if want_units:
-                offsets, entries = ops.train_csr_ragged(idx, counts, table.shape[0])
-                dW, db, ddec = model._batch_unit_grad(offsets, entries, val_sel, gv, xf, g_recon, g_extra, need_W or need_b,
-                                                      need_dec)
-        if need_bd:
-            dbd = ops.train_col_sum(g_recon) if g_recon is not None else torch.zeros_like(model.decoder.bias)
-        if dx is not None and dx.dtype != ctx.x_dtype:
-            dx = dx.to(ctx.x_dtype)
-        return (None, None, None, dx if need_x else None, dW if need_W else None, db if need_b else None,
-                ddec if need_dec else None, dbd)
+        model, needs = ctx.model, ctx.needs_input_grad[3:8]
+
+        def unit_grad(offsets, entries, gv):
+            return model._batch_unit_grad(offsets, entries, val_sel, gv, xf, g_recon, g_extra, needs[1] or needs[2], needs[3])
+        return (None,) * 3 + sparse_backward(idx, table, ctx.step, g_recon, g_latent, model.encoder.linear.weight,
+                                             model.decoder.bias, needs, ctx.x_dtype, unit_grad, counts=counts)
 
 
 class _MultiTopKTrainStep(torch.autograd.Function):
     """forward_train_multi_topk and its gradient.  The model supplies ``_nested_train_decoder() -> (table [H, D], step, extra
-    output or None)`` and ``_multik_unit_grad(offsets, entries, val, gv, x, G, ks, g_extra, want_encoder, want_decoder)``.  The
+    output or None)`` and ``_levels_unit_grad("multik", offsets, entries, val, gv, x, G, ks, g_extra, want_encoder, want_decoder)``.  The
     points are the rows of ONE output tensor, so a loss over them sends one gradient [P, B, D] back; its suffix sums
     G[p] = g[p] + G[p + 1] are what reaches the dictionary row of an entry whose rank first appears in point p
     (include/qsae_multik.h)."""
@@ -501,30 +480,18 @@ class _MultiTopKTrainStep(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_latent, g_points, g_extra):
         xf, idx, val, table = ctx.saved_tensors
-        model, ks = ctx.model, ctx.ks
-        need_x, need_W, need_b, need_dec, need_bd = ctx.needs_input_grad[3:8]
-        want_units = need_W or need_b or need_dec
-        dx = dW = db = ddec = dbd = None
-        if (need_x or want_units or need_bd) and not (g_latent is None and g_points is None and g_extra is None):
-            g_list = [None] * len(ks) if g_points is None else [g_points[p] for p in range(len(ks))]
-            G, gv, dx = ops.train_row_grad_multik(idx, table, ctx.step, g_list, ks, g_latent,
-                                                  model.encoder.linear.weight.detach(), want_dx=need_x)
-            if want_units:
-                offsets, entries = ops.train_csr(idx, table.shape[0])
-                dW, db, ddec = model._multik_unit_grad(offsets, entries, val, gv, xf, G, ks, g_extra, need_W or need_b,
-                                                       need_dec)
-            if need_bd:
-                dbd = ops.train_col_sum(G[0])                  # every point adds the bias: its gradient is the whole sum
-            if dx is not None and dx.dtype != ctx.x_dtype:
-                dx = dx.to(ctx.x_dtype)
-        return (None, None, None, dx if need_x else None, dW if need_W else None, db if need_b else None,
-                ddec if need_dec else None, dbd if need_bd else None)
+        model, ks, needs = ctx.model, ctx.ks, ctx.needs_input_grad[3:8]
+
+        def unit_grad(offsets, entries, gv, G):
+            return model._levels_unit_grad("multik", offsets, entries, val, gv, xf, G, ks, g_extra, needs[1] or needs[2], needs[3])
+        return (None,) * 3 + levels_backward((idx,), table, ctx.step, ks, g_latent, g_points, g_extra, model.encoder.linear.weight,
+                                             needs, ctx.x_dtype, ops.train_row_grad_multik, ops.train_csr, unit_grad)
 
 
 class _NestedTrainStep(torch.autograd.Function):
     """forward_train_nested and its gradient.  The model supplies ``_nested_train_decoder() -> (table [H, D], step, extra
-    output or None)``, ``_nested_select(x, want_dense) -> (idx, val, latent)`` and ``_nested_unit_grad(offsets, entries, val, gv,
-    x, G, bounds, g_extra, want_encoder, want_decoder)``.  The levels are the rows of ONE output tensor, so a loss over them
+    output or None)``, ``_nested_select(x, want_dense) -> (idx, val, latent)`` and ``_levels_unit_grad("nested", offsets, entries,
+    val, gv, x, G, bounds, g_extra, want_encoder, want_decoder)``.  The levels are the rows of ONE output tensor, so a loss over them
     sends one gradient [L, B, D] back; its suffix sums G[l] = g[l] + G[l + 1] are what reaches the dictionary rows of level l
     (include/qsae_nested.h)."""
 
@@ -544,24 +511,14 @@ class _NestedTrainStep(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_latent, g_levels, g_extra):
         xf, idx, val, table = ctx.saved_tensors
-        model, bounds = ctx.model, ctx.bounds
-        need_x, need_W, need_b, need_dec, need_bd = ctx.needs_input_grad[3:8]
-        want_units = need_W or need_b or need_dec
-        dx = dW = db = ddec = dbd = None
-        if (need_x or want_units or need_bd) and not (g_latent is None and g_levels is None and g_extra is None):
-            g_list = [None] * len(bounds) if g_levels is None else [g_levels[l] for l in range(len(bounds))]
-            G, gv, dx = ops.train_row_grad_nested(idx, table, ctx.step, g_list, bounds, g_latent,
-                                                  model.encoder.linear.weight.detach(), want_dx=need_x)
-            if want_units:
-                offsets, entries = ops.train_csr(idx, table.shape[0])
-                dW, db, ddec = model._nested_unit_grad(offsets, entries, val, gv, xf, G, bounds, g_extra, need_W or need_b,
-                                                       need_dec)
-            if need_bd:
-                dbd = ops.train_col_sum(G[0])                  # every level adds the bias: its gradient is the whole sum
-            if dx is not None and dx.dtype != ctx.x_dtype:
-                dx = dx.to(ctx.x_dtype)
-        return (None, None, None, dx if need_x else None, dW if need_W else None, db if need_b else None,
-                ddec if need_dec else None, dbd if need_bd else None)
+        model, bounds, needs = ctx.model, ctx.bounds, ctx.needs_input_grad[3:8]
+
+        def unit_grad(offsets, entries, gv, G):
+            return model._levels_unit_grad("nested", offsets, entries, val, gv, xf, G, bounds, g_extra, needs[1] or needs[2],
+                                           needs[3])
+        return (None,) * 3 + levels_backward((idx,), table, ctx.step, bounds, g_latent, g_levels, g_extra,
+                                             model.encoder.linear.weight, needs, ctx.x_dtype, ops.train_row_grad_nested,
+                                             ops.train_csr, unit_grad)
 
 
 class _AuxStep(torch.autograd.Function):
@@ -611,22 +568,50 @@ class SubmittedForward:
             return self._to_result(*self._outs)
 
 
-def sparse_backward(idx, table, step: float, g_recon, g_latent, W_enc, dec_bias, needs, x_dtype, unit_grad):
+def sparse_backward(idx, table, step: float, g_recon, g_latent, W_enc, dec_bias, needs, x_dtype, unit_grad, counts=None):
     """The gradient of encoder -> top-k -> ``step * table`` rows + bias, from the k selected entries of each row:
     gv = g_latent[r, h] + step <g_recon[r], table[h]> and dx per row, then ``unit_grad(offsets, entries, gv) ->
     (dW_enc, db_enc, d_decoder)`` per unit over the rows that selected it (the one step that differs between the models),
-    and the decoder bias' column sum.  ``needs`` = (need_x, need_W, need_b, need_decoder, need_dec_bias).
+    and the decoder bias' column sum.  ``needs`` = (need_x, need_W, need_b, need_decoder, need_dec_bias).  ``counts``: the
+    ragged rows of BatchTopK, row r using the first counts[r] entries of its list.
     -> (dx, dW_enc, db_enc, d_decoder, db_dec), None where not needed."""
     need_x, need_W, need_b, need_dec, need_bd = needs
+    lists = (idx,) if counts is None else (idx, counts)
+    row_grad, csr = (ops.train_row_grad, ops.train_csr) if counts is None else (ops.train_row_grad_ragged, ops.train_csr_ragged)
     want_units = need_W or need_b or need_dec
     dx = dW = db = ddec = dbd = None
     if need_x or want_units:
-        gv, dx = ops.train_row_grad(idx, table, step, g_recon, g_latent, W_enc.detach(), want_dx=need_x)
+        gv, dx = row_grad(*lists, table, step, g_recon, g_latent, W_enc.detach(), want_dx=need_x)
         if want_units:
-            offsets, entries = ops.train_csr(idx, table.shape[0])
+            offsets, entries = csr(*lists, table.shape[0])
             dW, db, ddec = unit_grad(offsets, entries, gv)
     if need_bd:
         dbd = ops.train_col_sum(g_recon) if g_recon is not None else torch.zeros_like(dec_bias)
     if dx is not None and dx.dtype != x_dtype:
         dx = dx.to(x_dtype)
     return (dx if need_x else None, dW if need_W else None, db if need_b else None, ddec if need_dec else None, dbd)
+
+
+def levels_backward(lists, table, step: float, levels, g_latent, g_levels, g_extra, W_enc, needs, x_dtype, row_grad, csr,
+                    unit_grad):
+    """``sparse_backward`` for an objective with one reconstruction per level or point (the rows of ONE output tensor, whose
+    gradient ``g_levels`` is [L, B, D] or None): ``row_grad`` (``ops.train_row_grad_nested`` / ``_multik`` /
+    ``_nested_ragged``) turns it into the suffix sums G, gv and dx over ``lists`` -- ``(idx,)`` or ``(idx, counts)`` --,
+    ``csr`` groups the lists by unit, ``unit_grad(offsets, entries, gv, G) -> (dW_enc, db_enc, d_decoder)`` is the model's,
+    and every level adds the bias, so its gradient is the whole sum G[0].  Nothing is computed when no gradient came in.
+    -> (dx, dW_enc, db_enc, d_decoder, db_dec), None where not needed."""
+    need_x, need_W, need_b, need_dec, need_bd = needs
+    want_units = need_W or need_b or need_dec
+    dx = dW = db = ddec = dbd = None
+    if (need_x or want_units or need_bd) and not (g_latent is None and g_levels is None and g_extra is None):
+        g_list = [None] * len(levels) if g_levels is None else [g_levels[l] for l in range(len(levels))]
+        G, gv, dx = row_grad(*lists, table, step, g_list, levels, g_latent, W_enc.detach(), want_dx=need_x)
+        if want_units:
+            offsets, entries = csr(*lists, table.shape[0])
+            dW, db, ddec = unit_grad(offsets, entries, gv, G)
+        if need_bd:
+            dbd = ops.train_col_sum(G[0])
+        if dx is not None and dx.dtype != x_dtype:
+            dx = dx.to(x_dtype)
+    return (dx if need_x else None, dW if need_W else None, db if need_b else None, ddec if need_dec else None,
+            dbd if need_bd else None)

@@ -19,6 +19,7 @@ CUDA (ROCm) tensors only: there is no CPU implementation to register, the ops ra
 """
 from __future__ import annotations
 
+import inspect
 import weakref
 from typing import List, Optional, Tuple
 
@@ -983,152 +984,96 @@ def _(x, idx, val, ks, dictionary, n_bits, mult, dec_bias, group_rows, sums, cou
     return None
 
 
-# ---- nested-dictionary objective of the top-k SAEs (include/qsae_nested.h) ------------------------------------------------
-@_op("decode_nested_binary")
-def _decode_nested_binary(idx: Tensor, val: Tensor, packed: Tensor, D: int, n_bits: int, step: float, bias: Optional[Tensor],
-                          bounds: List[int]) -> Tensor:
-    """-> fp32 [L, B, D]: one reconstruction per dictionary prefix from the packed n-bit dictionary"""
-    return _ops.decode_nested_binary(idx, val, packed, D, n_bits, step, bias, bounds)
+# ---- nested-dictionary and Multi-TopK objectives of the top-k SAEs (include/qsae_nested.h, include/qsae_multik.h) ---------
+# The two families have the same five operations; an op's schema carries its argument names, so each definition below is
+# written once over ``levels`` and ``grads`` and registered per family under that family's names.
+def _levels_op(name: str, make, fake, levels: str, grads: str):
+    fn = make(getattr(_ops, name))
+    sig = inspect.signature(fn)
+    renames = {"levels": levels, "grads": grads}
+    fn.__signature__ = sig.replace(parameters=[p.replace(name=renames.get(n, n)) for n, p in sig.parameters.items()])
+    _op(name)(fn).register_fake(fake)
 
 
-@_decode_nested_binary.register_fake
-def _(idx, val, packed, D, n_bits, step, bias, bounds):
-    return _f32((len(bounds), idx.shape[0], D), idx)
+def _make_decode_levels_binary(impl):
+    def op(idx: Tensor, val: Tensor, packed: Tensor, D: int, n_bits: int, step: float, bias: Optional[Tensor],
+           levels: List[int]) -> Tensor:
+        """-> fp32 [L, B, D]: one reconstruction per level or point from the packed n-bit dictionary"""
+        return impl(idx, val, packed, D, n_bits, step, bias, levels)
+    return op
 
 
-@_op("decode_nested_table")
-def _decode_nested_table(idx: Tensor, val: Tensor, table: Tensor, scale: float, bias: Optional[Tensor], bounds: List[int]) -> Tensor:
-    """-> fp32 [L, B, D]: one reconstruction per dictionary prefix from an fp32 [H, D] table"""
-    return _ops.decode_nested_table(idx, val, table, scale, bias, bounds)
+def _fake_decode_levels_binary(idx, val, packed, D, n_bits, step, bias, levels):
+    return _f32((len(levels), idx.shape[0], D), idx)
 
 
-@_decode_nested_table.register_fake
-def _(idx, val, table, scale, bias, bounds):
-    return _f32((len(bounds), idx.shape[0], table.shape[1]), idx)
+def _make_decode_levels_table(impl):
+    def op(idx: Tensor, val: Tensor, table: Tensor, scale: float, bias: Optional[Tensor], levels: List[int]) -> Tensor:
+        """-> fp32 [L, B, D]: one reconstruction per level or point from an fp32 [H, D] table"""
+        return impl(idx, val, table, scale, bias, levels)
+    return op
 
 
-@_op("train_row_grad_nested")
-def _train_row_grad_nested(idx: Tensor, table: Tensor, step: float, g_levels: List[Optional[Tensor]], bounds: List[int],
-                           g_latent: Optional[Tensor], W_enc: Optional[Tensor], want_dx: bool) -> Tuple[Tensor, Tensor, Tensor]:
-    """-> (G [L, B, D], gv [B, k], dx [B, D] ([0, D] when not wanted))"""
-    G, gv, dx = _ops.train_row_grad_nested(idx, table, step, g_levels, bounds, g_latent, W_enc, want_dx)
-    return G, gv, (dx if dx is not None else _f32((0, table.shape[1]), idx))
+def _fake_decode_levels_table(idx, val, table, scale, bias, levels):
+    return _f32((len(levels), idx.shape[0], table.shape[1]), idx)
 
 
-@_train_row_grad_nested.register_fake
-def _(idx, table, step, g_levels, bounds, g_latent, W_enc, want_dx):
+def _make_row_grad_levels(impl):
+    def op(idx: Tensor, table: Tensor, step: float, grads: List[Optional[Tensor]], levels: List[int],
+           g_latent: Optional[Tensor], W_enc: Optional[Tensor], want_dx: bool) -> Tuple[Tensor, Tensor, Tensor]:
+        """-> (G [L, B, D], gv [B, k], dx [B, D] ([0, D] when not wanted))"""
+        G, gv, dx = impl(idx, table, step, grads, levels, g_latent, W_enc, want_dx)
+        return G, gv, (dx if dx is not None else _f32((0, table.shape[1]), idx))
+    return op
+
+
+def _fake_row_grad_levels(idx, table, step, grads, levels, g_latent, W_enc, want_dx):
     B, D = idx.shape[0], table.shape[1]
-    return _f32((len(bounds), B, D), idx), _f32(tuple(idx.shape), idx), _f32((B if want_dx else 0, D), idx)
+    return _f32((len(levels), B, D), idx), _f32(tuple(idx.shape), idx), _f32((B if want_dx else 0, D), idx)
 
 
-@_op("train_unit_grad_nested")
-def _train_unit_grad_nested(offsets: Tensor, entries: Tensor, val: Tensor, gv: Tensor, x: Tensor, G: Optional[Tensor],
-                            bounds: List[int], logits: Tensor, n_bits: int, step: float, g_polarize: Optional[Tensor],
-                            want_encoder: bool, want_logits: bool) -> Tuple[Tensor, Tensor, Tensor]:
-    """-> (dW_enc [H, D], db_enc [H], dlogits [H, D n_bits]); an output not wanted has 0 rows"""
-    dW, db, dl = _ops.train_unit_grad_nested(offsets, entries, val, gv, x, G, bounds, logits, n_bits, step, g_polarize,
-                                             want_encoder, want_logits)
-    D = x.shape[1]
-    return (dW if dW is not None else _f32((0, D), x), db if db is not None else _f32((0,), x),
-            dl if dl is not None else _f32((0, logits.shape[1]), x))
+def _make_unit_grad_levels(impl):
+    def op(offsets: Tensor, entries: Tensor, val: Tensor, gv: Tensor, x: Tensor, G: Optional[Tensor], levels: List[int],
+           logits: Tensor, n_bits: int, step: float, g_polarize: Optional[Tensor], want_encoder: bool,
+           want_logits: bool) -> Tuple[Tensor, Tensor, Tensor]:
+        """-> (dW_enc [H, D], db_enc [H], dlogits [H, D n_bits]); an output not wanted has 0 rows"""
+        dW, db, dl = impl(offsets, entries, val, gv, x, G, levels, logits, n_bits, step, g_polarize, want_encoder, want_logits)
+        D = x.shape[1]
+        return (dW if dW is not None else _f32((0, D), x), db if db is not None else _f32((0,), x),
+                dl if dl is not None else _f32((0, logits.shape[1]), x))
+    return op
 
 
-@_train_unit_grad_nested.register_fake
-def _(offsets, entries, val, gv, x, G, bounds, logits, n_bits, step, g_polarize, want_encoder, want_logits):
+def _fake_unit_grad_levels(offsets, entries, val, gv, x, G, levels, logits, n_bits, step, g_polarize, want_encoder, want_logits):
     H, D = offsets.shape[0] - 1, x.shape[1]
     return (_f32((H if want_encoder else 0, D), x), _f32((H if want_encoder else 0,), x),
             _f32((H if want_logits else 0, logits.shape[1]), x))
 
 
-@_op("train_table_unit_grad_nested")
-def _train_table_unit_grad_nested(offsets: Tensor, entries: Tensor, val: Tensor, gv: Tensor, x: Tensor, G: Optional[Tensor],
-                                  bounds: List[int], want_encoder: bool, want_decoder: bool) -> Tuple[Tensor, Tensor, Tensor]:
-    """-> (dW_enc [H, D], db_enc [H], dW_dec [D, H]); an output not wanted is empty ([0, D], [0], [D, 0])"""
-    dW, db, dWd = _ops.train_table_unit_grad_nested(offsets, entries, val, gv, x, G, bounds, want_encoder, want_decoder)
-    D = x.shape[1]
-    return (dW if dW is not None else _f32((0, D), x), db if db is not None else _f32((0,), x),
-            dWd if dWd is not None else _f32((D, 0), x))
+def _make_table_unit_grad_levels(impl):
+    def op(offsets: Tensor, entries: Tensor, val: Tensor, gv: Tensor, x: Tensor, G: Optional[Tensor], levels: List[int],
+           want_encoder: bool, want_decoder: bool) -> Tuple[Tensor, Tensor, Tensor]:
+        """-> (dW_enc [H, D], db_enc [H], dW_dec [D, H]); an output not wanted is empty ([0, D], [0], [D, 0])"""
+        dW, db, dWd = impl(offsets, entries, val, gv, x, G, levels, want_encoder, want_decoder)
+        D = x.shape[1]
+        return (dW if dW is not None else _f32((0, D), x), db if db is not None else _f32((0,), x),
+                dWd if dWd is not None else _f32((D, 0), x))
+    return op
 
 
-@_train_table_unit_grad_nested.register_fake
-def _(offsets, entries, val, gv, x, G, bounds, want_encoder, want_decoder):
+def _fake_table_unit_grad_levels(offsets, entries, val, gv, x, G, levels, want_encoder, want_decoder):
     H, D = offsets.shape[0] - 1, x.shape[1]
     return (_f32((H if want_encoder else 0, D), x), _f32((H if want_encoder else 0,), x),
             _f32((D, H if want_decoder else 0), x))
 
 
-# ---- Multi-TopK objective of the top-k SAEs (include/qsae_multik.h) ---------------------------------------------------------
-@_op("decode_multik_binary")
-def _decode_multik_binary(idx: Tensor, val: Tensor, packed: Tensor, D: int, n_bits: int, step: float, bias: Optional[Tensor],
-                          ks: List[int]) -> Tensor:
-    """-> fp32 [P, B, D]: one reconstruction per rank prefix from the packed n-bit dictionary"""
-    return _ops.decode_multik_binary(idx, val, packed, D, n_bits, step, bias, ks)
-
-
-@_decode_multik_binary.register_fake
-def _(idx, val, packed, D, n_bits, step, bias, ks):
-    return _f32((len(ks), idx.shape[0], D), idx)
-
-
-@_op("decode_multik_table")
-def _decode_multik_table(idx: Tensor, val: Tensor, table: Tensor, scale: float, bias: Optional[Tensor], ks: List[int]) -> Tensor:
-    """-> fp32 [P, B, D]: one reconstruction per rank prefix from an fp32 [H, D] table"""
-    return _ops.decode_multik_table(idx, val, table, scale, bias, ks)
-
-
-@_decode_multik_table.register_fake
-def _(idx, val, table, scale, bias, ks):
-    return _f32((len(ks), idx.shape[0], table.shape[1]), idx)
-
-
-@_op("train_row_grad_multik")
-def _train_row_grad_multik(idx: Tensor, table: Tensor, step: float, g_points: List[Optional[Tensor]], ks: List[int],
-                           g_latent: Optional[Tensor], W_enc: Optional[Tensor], want_dx: bool) -> Tuple[Tensor, Tensor, Tensor]:
-    """-> (G [P, B, D], gv [B, K], dx [B, D] ([0, D] when not wanted))"""
-    G, gv, dx = _ops.train_row_grad_multik(idx, table, step, g_points, ks, g_latent, W_enc, want_dx)
-    return G, gv, (dx if dx is not None else _f32((0, table.shape[1]), idx))
-
-
-@_train_row_grad_multik.register_fake
-def _(idx, table, step, g_points, ks, g_latent, W_enc, want_dx):
-    B, D = idx.shape[0], table.shape[1]
-    return _f32((len(ks), B, D), idx), _f32(tuple(idx.shape), idx), _f32((B if want_dx else 0, D), idx)
-
-
-@_op("train_unit_grad_multik")
-def _train_unit_grad_multik(offsets: Tensor, entries: Tensor, val: Tensor, gv: Tensor, x: Tensor, G: Optional[Tensor],
-                            ks: List[int], logits: Tensor, n_bits: int, step: float, g_polarize: Optional[Tensor],
-                            want_encoder: bool, want_logits: bool) -> Tuple[Tensor, Tensor, Tensor]:
-    """-> (dW_enc [H, D], db_enc [H], dlogits [H, D n_bits]); an output not wanted has 0 rows"""
-    dW, db, dl = _ops.train_unit_grad_multik(offsets, entries, val, gv, x, G, ks, logits, n_bits, step, g_polarize,
-                                             want_encoder, want_logits)
-    D = x.shape[1]
-    return (dW if dW is not None else _f32((0, D), x), db if db is not None else _f32((0,), x),
-            dl if dl is not None else _f32((0, logits.shape[1]), x))
-
-
-@_train_unit_grad_multik.register_fake
-def _(offsets, entries, val, gv, x, G, ks, logits, n_bits, step, g_polarize, want_encoder, want_logits):
-    H, D = offsets.shape[0] - 1, x.shape[1]
-    return (_f32((H if want_encoder else 0, D), x), _f32((H if want_encoder else 0,), x),
-            _f32((H if want_logits else 0, logits.shape[1]), x))
-
-
-@_op("train_table_unit_grad_multik")
-def _train_table_unit_grad_multik(offsets: Tensor, entries: Tensor, val: Tensor, gv: Tensor, x: Tensor, G: Optional[Tensor],
-                                  ks: List[int], want_encoder: bool, want_decoder: bool) -> Tuple[Tensor, Tensor, Tensor]:
-    """-> (dW_enc [H, D], db_enc [H], dW_dec [D, H]); an output not wanted is empty ([0, D], [0], [D, 0])"""
-    dW, db, dWd = _ops.train_table_unit_grad_multik(offsets, entries, val, gv, x, G, ks, want_encoder, want_decoder)
-    D = x.shape[1]
-    return (dW if dW is not None else _f32((0, D), x), db if db is not None else _f32((0,), x),
-            dWd if dWd is not None else _f32((D, 0), x))
-
-
-@_train_table_unit_grad_multik.register_fake
-def _(offsets, entries, val, gv, x, G, ks, want_encoder, want_decoder):
-    H, D = offsets.shape[0] - 1, x.shape[1]
-    return (_f32((H if want_encoder else 0, D), x), _f32((H if want_encoder else 0,), x),
-            _f32((D, H if want_decoder else 0), x))
+for _family, _levels, _grads in (("nested", "bounds", "g_levels"), ("multik", "ks", "g_points")):
+    for _name, _make, _fake in (("decode_{}_binary", _make_decode_levels_binary, _fake_decode_levels_binary),
+                                ("decode_{}_table", _make_decode_levels_table, _fake_decode_levels_table),
+                                ("train_row_grad_{}", _make_row_grad_levels, _fake_row_grad_levels),
+                                ("train_unit_grad_{}", _make_unit_grad_levels, _fake_unit_grad_levels),
+                                ("train_table_unit_grad_{}", _make_table_unit_grad_levels, _fake_table_unit_grad_levels)):
+        _levels_op(_name.format(_family), _make, _fake, _levels, _grads)
 
 
 # ---- BatchTopK of the top-k SAEs (include/qsae_batch.h) --------------------------------------------------------------------
