@@ -265,6 +265,15 @@ MULTIK_SIGNATURES = {
                                                 _sz, _vp]),
 }
 
+# name -> (restype, argtypes) of the qsaej_* entry points of include/qsae_jump.h (csrc/jumprelu.hip): JumpReLU -- the per-unit
+# threshold selection and the thresholds' pseudo-gradient -- a table of its own for the same reason.  Must list every symbol
+# declared in qsae_jump.h.
+JUMP_SIGNATURES = {
+    "qsaej_jump_select_workspace_bytes": (_sz, [_i, _i, _i]),
+    "qsaej_jump_select": (_i, [_vp, _vp, _i, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "qsaej_threshold_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
+}
+
 
 class QsaeError(RuntimeError):
     """A libqsae_hip call returned a non-zero status."""
@@ -285,7 +294,8 @@ def _open(path: Path) -> C.CDLL:
             "(hipcc --offload-arch=gfx950).  quantizedsae_amd has no CPU / eager fallback.")
     lib = C.CDLL(str(path))
     for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(CURVE_SIGNATURES.items()) \
-            + list(NESTED_SIGNATURES.items()) + list(BATCH_SIGNATURES.items()) + list(NESTED_BATCH_SIGNATURES.items()) + list(MULTIK_SIGNATURES.items()):
+            + list(NESTED_SIGNATURES.items()) + list(BATCH_SIGNATURES.items()) + list(NESTED_BATCH_SIGNATURES.items()) + list(MULTIK_SIGNATURES.items()) \
+            + list(JUMP_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here means the library is stale
         fn.restype = res
         fn.argtypes = args

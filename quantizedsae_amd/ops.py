@@ -3278,3 +3278,90 @@ def train_row_grad_nested_ragged(idx: torch.Tensor, counts: torch.Tensor, table:
     every row, bit for bit; G is written for every row, gv behind the prefix is +0.  See qsaem_row_grad_nested_ragged."""
     return _row_grad_levels(_ROW_NESTED_RAGGED, "train_row_grad_nested_ragged", idx, counts, table, step, g_levels, bounds,
                             g_latent, W_enc, want_dx)
+
+
+# ---- JumpReLU of the top-k SAEs (include/qsae_jump.h, csrc/jumprelu.hip) ------------------------------------------------------
+JUMP_MAX_K = 256
+JUMP_REPORT_WORDS = 6             # selected, band entries, saturated rows, empty rows, uncertified rows, bits of theta_min
+
+
+def jump_half_eps(eps: float) -> float:
+    """fl32(0.5f * fl32(eps)), the half bandwidth the kernels compare against (one rounding: the product is exact in fp64)"""
+    return C.c_float(0.5 * C.c_float(float(eps)).value).value
+
+
+def _jump_eps(who: str, eps) -> float:
+    eps = C.c_float(float(eps)).value
+    if not (eps > 0.0 and eps != float("inf")):
+        raise ValueError(f"{who}: the bandwidth eps = {eps} must be positive and finite in fp32")
+    return eps
+
+
+def _jump_theta(who: str, theta, device) -> torch.Tensor:
+    _dev(theta, f"{who}: theta", torch.float32)
+    if theta.dim() != 1 or theta.shape[0] < 1 or theta.device != device:
+        raise ValueError(f"{who}: theta is {tuple(theta.shape)} on {theta.device}, expected [H] with H >= 1 on {device}")
+    return theta.contiguous()
+
+
+@_on_tensor_device
+def jump_select(idx: torch.Tensor, val: torch.Tensor, theta: torch.Tensor, eps: float, want_band: bool = True):
+    """JumpReLU on the top-K lists (idx int32, val fp32, both [B, K]) with the per-unit thresholds ``theta`` fp32 [H]: an entry
+    is selected iff val > theta[idx], in the band iff |val - theta[idx]| < eps / 2 -> (idx_sel, val_sel, counts, idx_band or
+    None, counts_band or None, l0 fp32 [1], report int64 [6]): the stable partition of every row by either predicate, the mean
+    number of selected entries per row, and {selected, band entries, saturated rows, empty rows, uncertified rows, bits of the
+    smallest threshold}.  No host read.  See qsaej_jump_select."""
+    who = "jump_select"
+    _dev(idx, f"{who}: idx", torch.int32)
+    val = _batch_vals(who, val)
+    if idx.shape != val.shape or idx.device != val.device:
+        raise ValueError(f"{who}: idx is {tuple(idx.shape)}, val {tuple(val.shape)}; expected two [B, K] tensors on one device")
+    idx = idx.contiguous()
+    theta = _jump_theta(who, theta, val.device)
+    eps = _jump_eps(who, eps)
+    B, K = val.shape
+    H = theta.shape[0]
+    dev = val.device
+    idx_sel, val_sel = torch.empty_like(idx), torch.empty_like(val)
+    counts = torch.empty((B,), dtype=torch.int32, device=dev)
+    idx_band = torch.empty_like(idx) if want_band else None
+    counts_band = torch.empty((B,), dtype=torch.int32, device=dev) if want_band else None
+    l0 = torch.zeros((1,), dtype=torch.float32, device=dev)
+    report = torch.zeros((JUMP_REPORT_WORDS,), dtype=torch.int64, device=dev)
+    lib = _lib.load()
+    ws = _train_ws(lib.qsaej_jump_select_workspace_bytes(B, K, H), dev)
+    check(lib.qsaej_jump_select(_p(idx), _p(val), B, K, _p(theta), H, eps, jump_half_eps(eps), _p(idx_sel), _p(val_sel), _p(counts),
+                                _p(idx_band), _p(counts_band), _p(l0), _p(report), _p(ws), ws.numel(), _stream()))
+    return idx_sel, val_sel, counts, idx_band, counts_band, l0, report
+
+
+@_on_tensor_device
+def jump_threshold_grad(offsets: torch.Tensor, entries: torch.Tensor, gv_band: Optional[torch.Tensor], theta: torch.Tensor,
+                        g_l0: Optional[torch.Tensor], B: int, K: int, eps: float) -> torch.Tensor:
+    """-> dtheta fp32 [H]: for every unit, -(theta[h] * sum of gv_band over its band entries + g_l0 * n / B) / eps in fp64 with
+    one rounding, from the lists train_csr_ragged writes over (idx_band, counts_band) and the gv train_row_grad_ragged writes
+    over them (None: no reconstruction term); g_l0: the gradient that reached l0 (one fp32 element on the device) or None.
+    See qsaej_threshold_grad."""
+    who = "jump_threshold_grad"
+    _dev(offsets, f"{who}: offsets", torch.int32)
+    _dev(entries, f"{who}: entries", torch.int32)
+    theta = _jump_theta(who, theta, offsets.device)
+    eps = _jump_eps(who, eps)
+    B, K, H = int(B), int(K), theta.shape[0]
+    if B < 0 or not 1 <= K <= JUMP_MAX_K or B * K >= 2 ** 31:
+        raise ValueError(f"{who}: B = {B}, K = {K}; expected B >= 0, 1 <= K <= {JUMP_MAX_K} and B * K below 2^31")
+    if tuple(offsets.shape) != (H + 1,) or entries.dim() != 1 or entries.shape[0] < B * K or entries.device != offsets.device:
+        raise ValueError(f"{who}: offsets is {tuple(offsets.shape)}, entries {tuple(entries.shape)}; expected [{H + 1}] and "
+                         f"[{B * K}] on one device")
+    if gv_band is not None:
+        gv_band = _f32c(gv_band, f"{who}: gv_band")
+        if gv_band.numel() != B * K or gv_band.device != offsets.device:
+            raise ValueError(f"{who}: gv_band is {tuple(gv_band.shape)} on {gv_band.device}, expected [{B}, {K}] on {offsets.device}")
+    if g_l0 is not None:
+        g_l0 = _f32c(g_l0, f"{who}: g_l0")
+        if g_l0.numel() != 1 or g_l0.device != offsets.device:
+            raise ValueError(f"{who}: g_l0 is one element on {offsets.device}")
+    dtheta = torch.empty((H,), dtype=torch.float32, device=offsets.device)
+    check(_lib.load().qsaej_threshold_grad(_p(offsets.contiguous()), _p(entries.contiguous()), _p(gv_band), _p(theta), _p(g_l0), B, K,
+                                           H, eps, _p(dtheta), _stream()))
+    return dtheta

@@ -384,6 +384,97 @@ class TopKCore:
         return out if extra is None else out + (extra,)
 
 
+    # -- JumpReLU: one learned threshold per unit, a subset of every row's list --------------------------------------------
+    def _jumprelu_input(self, x, jr, who: str):
+        x, who = self._batch_topk_input(x, who)
+        H = int(self.encoder.linear.weight.shape[0])
+        if not hasattr(jr, "log_threshold") or tuple(jr.log_threshold.shape) != (H,):
+            raise ValueError(f"{who}: expected a training.JumpReLU over hidden_dim = {H} units")
+        if not 1 <= jr.cap <= min(ops.JUMP_MAX_K, H):
+            raise ValueError(f"{who}: cap = {jr.cap}; expected 1 .. {min(ops.JUMP_MAX_K, H)}")
+        return x, who
+
+    def forward_jumprelu(self, x, jr):
+        """``(idx_sel int32 [B,K], val_sel fp32 [B,K], counts int32 [B], reconstruction [B,D])`` without a ``grad_fn``: of every
+        row's top-``K`` list (K = ``jr.cap``, ``training.JumpReLU``; no ReLU in front, as in ``forward()``) the entries above
+        their unit's threshold ``exp(jr.log_threshold)``, moved to the front of the row in list order; ``val_sel`` is +0 behind
+        the first ``counts[r]`` places, so ``(idx_sel, val_sel)`` reads like any compact selection.  Decoded from what
+        ``forward()`` decodes from, ``counts[r]`` entries per row.  ``jr.counts`` and ``jr.report`` are left on the device."""
+        with torch.no_grad():
+            x, who = self._jumprelu_input(x, jr, "forward_jumprelu")
+            xf = as_f32c(x)
+            idx, val = self._select_cap(xf, jr.cap, who)
+            idx_sel, val_sel, counts, _, _, _, report = ops.jump_select(idx, val, jr.thresholds(), jr.bandwidth, want_band=False)
+            jr.record(counts, report)
+            decoder, dec_bias = self._nested_decoder()
+            return idx_sel, val_sel, counts, self._decode_ragged(idx_sel, val_sel, counts, decoder, dec_bias)
+
+    def forward_train_jumprelu(self, x, jr, *, dense_latent: bool = True):
+        """The tuple of the model's ``forward_train`` with a ``grad_fn`` and ``l0`` -- the mean number of firing units per row, a
+        0-dim tensor -- appended as its last element, under the selection of ``forward_jumprelu``.  The reconstruction decodes
+        the selected entries through the model's training table.  Feeds ``model.activity`` with the selected entries only.  The
+        backward is ``sparse_backward`` over the compacted ragged rows, unchanged: a selected entry passes its gradient straight
+        through.  Only when ``jr.log_threshold`` needs a gradient it goes on over the entries within half a bandwidth of their
+        threshold, selected or not: ``train_row_grad_ragged`` (no dx) -> ``train_csr_ragged`` -> ``jump_threshold_grad``, the
+        rectangle-kernel pseudo-derivative of the JumpReLU and of the Heaviside step in ``l0``; torch's ``exp`` backward turns it
+        into the gradient of the log-parameter."""
+        x, who = self._jumprelu_input(x, jr, "forward_train_jumprelu")
+        lin = self.encoder.linear
+        D = lin.weight.shape[1]
+        if not ops.train_supported(D, jr.cap):
+            raise ValueError(f"{who}: the gradient kernels take input_dim a multiple of 4 up to 4096 (got {D})")
+        if x.shape[0] * jr.cap >= 2 ** 31:
+            raise ValueError(f"{who}: batch * cap = {x.shape[0] * jr.cap} is not below 2^31")
+        latent, recon, extra, l0 = _JumpReLUTrainStep.apply(self, jr, bool(dense_latent), x, lin.weight, lin.bias,
+                                                            self.decoder.weight, self.decoder.bias, jr.log_threshold.exp())
+        out = ((latent if dense_latent else None), recon)
+        return (out if extra is None else out + (extra,)) + (l0,)
+
+
+class _JumpReLUTrainStep(torch.autograd.Function):
+    """forward_train_jumprelu and its gradient: _BatchTopKTrainStep with ``jump_select`` in place of ``batch_select`` -- the
+    lists are the compacted [B, K] ones, of which row r uses the first counts[r] entries -- and ``theta`` as one more
+    differentiable input (include/qsae_jump.h)."""
+
+    @staticmethod
+    def forward(ctx, model, jr, dense_latent, x, W_enc, b_enc, dec_param, b_dec, theta):
+        table, step, extra = model._nested_train_decoder()
+        xf = as_f32c(x.detach())
+        idx, val = model._select_cap(xf, jr.cap, f"{type(model).__name__}.forward_train_jumprelu")
+        th = as_f32c(theta.detach())
+        idx_sel, val_sel, counts, idx_band, counts_band, l0, report = ops.jump_select(idx, val, th, jr.bandwidth,
+                                                                                      want_band=ctx.needs_input_grad[8])
+        jr.record(counts, report)
+        recon = ops.decode_ragged_table(idx_sel, val_sel, counts, table, step, b_dec.detach())
+        latent = ops.densify(idx_sel, val_sel, table.shape[0]) if dense_latent else None
+        if model.activity is not None:
+            model.activity.add_compact(idx_sel, val_sel)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(xf, idx_sel, val_sel, counts, table, th, idx_band, counts_band)
+        ctx.model, ctx.step, ctx.x_dtype, ctx.eps = model, step, x.dtype, jr.bandwidth
+        return latent, recon, extra, l0.reshape(())
+
+    @staticmethod
+    def backward(ctx, g_latent, g_recon, g_extra, g_l0):
+        xf, idx_sel, val_sel, counts, table, th, idx_band, counts_band = ctx.saved_tensors
+        model, needs = ctx.model, ctx.needs_input_grad[3:8]
+
+        def unit_grad(offsets, entries, gv):
+            return model._batch_unit_grad(offsets, entries, val_sel, gv, xf, g_recon, g_extra, needs[1] or needs[2], needs[3])
+        grads = sparse_backward(idx_sel, table, ctx.step, g_recon, g_latent, model.encoder.linear.weight, model.decoder.bias,
+                                needs, ctx.x_dtype, unit_grad, counts=counts)
+        dtheta = None
+        if ctx.needs_input_grad[8] and idx_band is not None:
+            B, K = idx_band.shape
+            gv_band = None
+            if g_recon is not None or g_latent is not None:
+                gv_band, _ = ops.train_row_grad_ragged(idx_band, counts_band, table, ctx.step, g_recon, g_latent, None, False)
+            offsets, entries = ops.train_csr_ragged(idx_band, counts_band, table.shape[0])
+            dtheta = ops.jump_threshold_grad(offsets, entries, gv_band, th, None if g_l0 is None else g_l0.reshape(1), B, K,
+                                             ctx.eps)
+        return (None,) * 3 + grads + (dtheta,)
+
+
 class _NestedBatchTopKTrainStep(torch.autograd.Function):
     """forward_train_nested_batch_topk and its gradient: _BatchTopKTrainStep's selection and ragged lists ([B, K] with stride K,
     row r uses the first counts[r] entries), _NestedTrainStep's levels (the rows of ONE output tensor, whose gradient's suffix

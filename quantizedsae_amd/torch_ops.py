@@ -1151,6 +1151,36 @@ def _(idx, counts, H):
     return _i32((H + 1,), idx), _i32((idx.shape[0] * idx.shape[1],), idx)
 
 
+# ---- JumpReLU of the top-k SAEs (include/qsae_jump.h) ----------------------------------------------------------------------
+@_op("jump_select")
+def _jump_select(idx: Tensor, val: Tensor, theta: Tensor, eps: float,
+                 want_band: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """-> (idx_sel, val_sel, counts, idx_band ([0, K] when not wanted), counts_band ([0]), l0 fp32 [1], report int64 [6])"""
+    idx_sel, val_sel, counts, idx_band, counts_band, l0, report = _ops.jump_select(idx, val, theta, eps, want_band)
+    if not want_band:
+        idx_band, counts_band = _i32((0, val.shape[1]), val), _i32((0,), val)
+    return idx_sel, val_sel, counts, idx_band, counts_band, l0, report
+
+
+@_jump_select.register_fake
+def _(idx, val, theta, eps, want_band):
+    B, K = val.shape
+    return (_i32((B, K), val), _f32((B, K), val), _i32((B,), val), _i32((B if want_band else 0, K), val),
+            _i32((B if want_band else 0,), val), _f32((1,), val), torch.empty((6,), dtype=torch.int64, device=val.device))
+
+
+@_op("jump_threshold_grad")
+def _jump_threshold_grad(offsets: Tensor, entries: Tensor, gv_band: Optional[Tensor], theta: Tensor, g_l0: Optional[Tensor],
+                         B: int, K: int, eps: float) -> Tensor:
+    """-> dtheta fp32 [H]"""
+    return _ops.jump_threshold_grad(offsets, entries, gv_band, theta, g_l0, B, K, eps)
+
+
+@_jump_threshold_grad.register_fake
+def _(offsets, entries, gv_band, theta, g_l0, B, K, eps):
+    return _f32((theta.shape[0],), theta)
+
+
 # ---- nested levels over the ragged rows of BatchTopK (include/qsae_nested_batch.h) ------------------------------------------
 @_op("decode_nested_ragged_binary")
 def _decode_nested_ragged_binary(idx: Tensor, val: Tensor, counts: Tensor, packed: Tensor, D: int, n_bits: int, step: float,
@@ -1920,3 +1950,17 @@ def train_row_grad_nested_ragged(idx, counts, table, step, g_levels, bounds, g_l
     G, gv, dx = Q.train_row_grad_nested_ragged(idx, counts, table, float(step), list(g_levels), [int(b) for b in bounds], g_latent,
                                                W_enc if want_dx else None, bool(want_dx))
     return G, gv, (dx if want_dx else None)
+
+
+JUMP_MAX_K = _ops.JUMP_MAX_K
+
+
+def jump_select(idx, val, theta, eps, want_band=True):
+    """-> (idx_sel, val_sel, counts, idx_band or None, counts_band or None, l0 fp32 [1], report int64 [6])"""
+    idx_sel, val_sel, counts, idx_band, counts_band, l0, report = Q.jump_select(idx, val, theta, float(eps), bool(want_band))
+    return idx_sel, val_sel, counts, (idx_band if want_band else None), (counts_band if want_band else None), l0, report
+
+
+def jump_threshold_grad(offsets, entries, gv_band, theta, g_l0, B, K, eps):
+    """-> dtheta fp32 [H]"""
+    return Q.jump_threshold_grad(offsets, entries, gv_band, theta, g_l0, int(B), int(K), float(eps))

@@ -60,12 +60,13 @@ def _levels_base(views):
     return base
 
 
-def trainer_loss(sae_type: str, outputs, batch: torch.Tensor, config: dict) -> torch.Tensor:
+def trainer_loss(sae_type: str, outputs, batch: torch.Tensor, config: dict, extra=None) -> torch.Tensor:
     """The loss of the type's recipe on ``outputs = model.forward_train(batch)``: returns the per-level reconstruction
     losses (fp32 [n] on the device; what the reference appends to ``recon_losses``, or its ``loss`` / ``recon_loss``) and
     runs ``torch.autograd.backward`` on the outputs the loss reads -- the kernel's gradients for the reconstructions, cached
     constants for the latent groups and the polarize loss.  Outputs the loss does not read get no gradient.  Nothing is
-    read back to the host."""
+    read back to the host.  ``extra``: further ``(output, gradient)`` pairs of terms that are linear in an output (the L0
+    term of JumpReLU), which join the same ``backward`` call."""
     mode, coef = recon_recipe(sae_type)
     if not batch.is_cuda:
         raise RuntimeError(f"trainer_loss: quantizedsae_amd runs on MI355X only; batch is on {batch.device} "
@@ -109,6 +110,8 @@ def trainer_loss(sae_type: str, outputs, batch: torch.Tensor, config: dict) -> t
         if sae_type == "b_sae":
             pol = outputs[2]
             roots.append(pol); grads.append(_const(batch.device, tuple(pol.shape), float(config["polarize_lambda"])))
+    for root, grad in (extra or ()):
+        roots.append(root); grads.append(grad)
     keep = [(r, g) for r, g in zip(roots, grads) if r.requires_grad]
     if keep:
         torch.autograd.backward([r for r, _ in keep], [g for _, g in keep])

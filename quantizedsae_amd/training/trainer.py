@@ -68,6 +68,17 @@ backward, ``trainer_loss`` the per-type loss, ``optim.Adam`` the step.  What dif
   the points: that point is the model's reconstruction for ``aux_k``, ``resample_every`` and the logged ``recon_loss``.
   Logging steps gain ``recon_loss_k{k_p}``.  Together with ``nested_bounds``, ``batch_topk`` or
   ``batch_topk_nested_bounds`` it raises: the combinations are not built.
+* ``jumprelu=True`` (``baseline_sae`` and ``b_sae`` only; default ``False`` changes nothing) trains with JumpReLU
+  (``JumpReLU``, csrc/jumprelu.hip): ``model.forward_train_jumprelu`` keeps, of every row's top-``jumprelu_cap`` list (default
+  ``min(256, hidden_dim)``), the entries above their unit's learned threshold; the objective is the recipe's loss plus
+  ``jumprelu_l0_coef`` (required: it has no sensible default) times the mean number of firing units per row, whose gradient
+  is that constant; ``log_threshold`` joins every epoch's optimizer as a parameter group of its own.  ``jumprelu_bandwidth``
+  is the width of the straight-through kernel; ``jumprelu_init`` is the initial threshold, or ``"calibrate"`` to set every
+  threshold, on the first batch, to the smallest value BatchTopK would select there at the model's k.  Logging steps gain
+  ``jumprelu/l0``, ``jumprelu/band_entries``, ``jumprelu/uncertified_rows``, ``jumprelu/saturated_rows`` and
+  ``jumprelu/theta_min``; nothing is read back between them.  ``aux_k``, ``resample_every`` and ``activity_window`` work as
+  with ``batch_topk``.  Together with ``batch_topk``, ``nested_bounds``, ``batch_topk_nested_bounds`` or ``multi_topk`` it
+  raises: the combinations are not built.
 * ``model=`` hands in the model instead of building the reference's.  The reference builds
   ``BinarySAE(input_dim, hidden_dim, n_bits)``, where ``n_bits`` lands in ``gamma`` and the decoder keeps its default of 8
   bits; that call is kept.
@@ -89,9 +100,11 @@ from ..sae import (BaselineSparseAutoencoder, BinarySAE, QuantizedMatryoshkaSAE,
 from ..sae.binary_latent import BinaryLatentSAE
 from .batches import ShuffledChunk
 from .loss import SAE_TYPES, trainer_loss
+from .loss import _const as _loss_const
 from .activity import FeatureActivity, activity_line
 from .auxk import AUX_MAX_K, aux_k_loss
 from .batch_topk import BatchTopK
+from .jumprelu import JumpReLU
 from .multi_topk import MULTI_TOPK_TYPES, default_multi_topk, default_multi_topk_weights, multi_topk_loss
 from .nested import NESTED_TYPES, default_nested_bounds, nested_loss
 from .resample import ResampleReport, resample_dead, resample_line
@@ -133,7 +146,8 @@ class Trainer:
                  resample_scale: float = 0.2, aux_k: Optional[int] = None, aux_coef: float = 1 / 32,
                  aux_refresh: Optional[int] = None, nested_bounds=None, batch_topk: bool = False,
                  batch_topk_cap: Optional[int] = None, batch_topk_nested_bounds=None, multi_topk=None,
-                 multi_topk_weights=None):
+                 multi_topk_weights=None, jumprelu: bool = False, jumprelu_l0_coef: Optional[float] = None,
+                 jumprelu_cap: Optional[int] = None, jumprelu_bandwidth: float = 1e-3, jumprelu_init=None):
         if sae_type not in SAE_TYPES:
             raise ValueError(f"unknown sae_type {sae_type!r}; expected one of {', '.join(SAE_TYPES)}")
         if sae_type == "t_sae" and not rigL:
@@ -188,6 +202,27 @@ class Trainer:
                                  "combinations are not built; choose one objective")
         elif multi_topk_weights is not None:
             raise ValueError("multi_topk_weights needs multi_topk")
+        if jumprelu:
+            if sae_type not in NESTED_TYPES:
+                raise ValueError(f"jumprelu: the per-unit thresholds are built for baseline_sae and b_sae, the two top-k models; "
+                                 f"got {sae_type!r}")
+            for name, given in (("batch_topk", batch_topk), ("nested_bounds", nested_bounds is not None),
+                                ("batch_topk_nested_bounds", batch_topk_nested_bounds is not None),
+                                ("multi_topk", multi_topk is not None)):
+                if given:
+                    raise ValueError(f"jumprelu together with {name}: the combination is not built; choose one objective")
+            if jumprelu_l0_coef is None:
+                raise ValueError("jumprelu needs jumprelu_l0_coef, the weight of the L0 penalty: it depends on the scale of the "
+                                 "data and has no default")
+            if not (math.isfinite(float(jumprelu_l0_coef)) and float(jumprelu_l0_coef) >= 0):
+                raise ValueError(f"jumprelu_l0_coef = {jumprelu_l0_coef}; expected a finite number >= 0")
+            if isinstance(jumprelu_init, str) and jumprelu_init != "calibrate":
+                raise ValueError(f"jumprelu_init = {jumprelu_init!r}; expected None, a threshold > 0 or 'calibrate'")
+        else:
+            for name, given in (("jumprelu_l0_coef", jumprelu_l0_coef), ("jumprelu_cap", jumprelu_cap),
+                                ("jumprelu_init", jumprelu_init)):
+                if given is not None:
+                    raise ValueError(f"{name} needs jumprelu=True")
         self.config = config
         self.sae_type = sae_type
         self.device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
@@ -273,6 +308,19 @@ class Trainer:
                 raise ValueError(f"multi_topk_weights = {multi_topk_weights!r}; expected {len(self.multi_topk)} finite numbers "
                                  ">= 0, one per point")
 
+        #: the JumpReLU controller (its log_threshold joins every epoch's optimizer as a group of its own), or None
+        self.jumprelu = None
+        self.jumprelu_l0_coef = float(jumprelu_l0_coef) if jumprelu else None
+        self._jumprelu_calibrate = False                       # calibrate on the next batch trained on
+        if jumprelu:
+            calibrate = isinstance(jumprelu_init, str)
+            self.jumprelu = JumpReLU(self.model, cap=jumprelu_cap, bandwidth=jumprelu_bandwidth,
+                                     init_threshold=None if calibrate else jumprelu_init)
+            self._jumprelu_calibrate = calibrate
+            if calibrate and self.model._own_top_k() > self.jumprelu.cap:
+                raise ValueError(f"jumprelu_init = 'calibrate': the model's top-k = {self.model._own_top_k()} exceeds "
+                                 f"jumprelu_cap = {self.jumprelu.cap}")
+
     # ---- one step ------------------------------------------------------------------------------------------------
     def _forward(self, batch, want_latent: bool):
         if self.nested_bounds is not None and self.batch_topk is not None:
@@ -284,6 +332,8 @@ class Trainer:
             return self.model.forward_train_multi_topk(batch, self.multi_topk, dense_latent=want_latent)
         if self.batch_topk is not None:
             return self.model.forward_train_batch_topk(batch, self.batch_topk, dense_latent=want_latent)
+        if self.jumprelu is not None:
+            return self.model.forward_train_jumprelu(batch, self.jumprelu, dense_latent=want_latent)
         if self.sae_type in ("b_sae", "baseline_sae"):
             return self.model.forward_train(batch, dense_latent=want_latent)
         return self.model.forward_train(batch)
@@ -294,12 +344,19 @@ class Trainer:
         after the backward, where wandb's hooks see the tensors: the parameters as the forward used them, the gradients as
         autograd left them (before apply_secant_grad / mask_grad and the optimizer step)."""
         st, model = self.sae_type, self.model
+        if self._jumprelu_calibrate:                           # the first batch: thresholds at the model's own k (on the device)
+            self.jumprelu.calibrate(batch, model._own_top_k())
+            self._jumprelu_calibrate = False
         outputs = self._forward(batch, log_step)
         optimizer.zero_grad(set_to_none=True)
         if self.nested_bounds is not None:
             losses = nested_loss(st, outputs, batch, self.config)
         elif self.multi_topk is not None:
             losses = multi_topk_loss(st, outputs, batch, self.config, self.multi_topk_weights)
+        elif self.jumprelu is not None:                        # l0 is linear in the objective: its gradient is the coefficient
+            l0, outputs = outputs[-1], outputs[:-1]
+            losses = trainer_loss(st, outputs, batch, self.config,
+                                  extra=[(l0, _loss_const(batch.device, tuple(l0.shape), self.jumprelu_l0_coef))])
         else:
             losses = trainer_loss(st, outputs, batch, self.config)
         if self.aux_k is not None:                             # (nested: the last level is the model's reconstruction;
@@ -398,6 +455,14 @@ class Trainer:
             d.update({f"l0_level_{l}": v for l, v in enumerate(l0)})
         return d
 
+    def _jumprelu_metrics(self) -> dict:
+        """What a logging step adds with ``jumprelu``: the last selection's report (one host copy of six words; no other step
+        reads it)"""
+        j = self.jumprelu.summary()
+        return {"jumprelu/l0": j["l0"], "jumprelu/band_entries": j["band_entries"],
+                "jumprelu/uncertified_rows": j["uncertified_rows"], "jumprelu/saturated_rows": j["saturated_rows"],
+                "jumprelu/theta_min": j["theta_min"]}
+
     def _activity_metrics(self, summary) -> dict:
         """What a logging step adds with ``activity_window``: the summary that ends the interval since the previous one"""
         d = {"dead_features": summary.dead, "dead_fraction": summary.dead_fraction, "never_fired": summary.never,
@@ -468,6 +533,8 @@ class Trainer:
             raise RuntimeError("Trainer.one_epoch: quantizedsae_amd runs on MI355X only (no CPU fallback exists)")
         chunk = dataset if isinstance(dataset, ShuffledChunk) else ShuffledChunk(dataset, self.config["batch_size"], self.device)
         optimizer = optim.Adam(self.model.parameters(), lr=self.config["lr"], model=self.model)
+        if self.jumprelu is not None:
+            optimizer.add_param_group({"params": [self.jumprelu.log_threshold]})
         self.trained_batches.append([])
         told = 0                                               # skipped batches announced so far, in batch order
 
@@ -494,6 +561,8 @@ class Trainer:
                     metrics.update(self._aux_metrics())
                 if log_step and self.batch_topk is not None:
                     metrics.update(self._batch_topk_metrics())
+                if log_step and self.jumprelu is not None:
+                    metrics.update(self._jumprelu_metrics())
                 self._log(batch_idx, metrics, self._watched, summary, resampled)
         announce(None)
         chunk.check()
