@@ -1,20 +1,13 @@
 """The activity kernels' own source, run on the CPU: csrc/activity.hip is compiled for the host against the stand-in runtime
-of tests/emu_watch (threads as lanes, real barriers; tests/emu_activity adds the leading-zero count) and compared with the
+of tests/emu (threads as lanes, real barriers, the leading-zero count and the integer atomics) and compared with the
 numpy restatement of tests/activity_util.py at the shapes the GPU tests use, bit for bit, with guard bytes around every
 buffer.  This checks what a GPU-less machine can: indexing, both load widths and the tails, the joins in LDS, the segment
 search, the prefix counts that place the dead list.  The source compiles for the host as it stands."""
-import subprocess
-from pathlib import Path
-
 import numpy as np
 import pytest
 
 import activity_util as U
-from test_dictionary_neighbors_emu_host import _clangxx
-
-ROOT = Path(__file__).resolve().parents[1]
-CSRC = ROOT / "quantizedsae_amd" / "csrc"
-EMU = ROOT / "tests" / "emu_activity"
+from emu_util import CSRC, compile_emu, run_emu
 
 
 @pytest.fixture(scope="module")
@@ -23,16 +16,12 @@ def emu(tmp_path_factory):
     src = (CSRC / "activity.hip").read_text()
     assert src.count('#include "common.h"') == 1
     (d / "activity_emu.hip").write_text(src.replace('#include "common.h"', f'#include "{CSRC / "common.h"}"'))
-    exe = d / "activity_emu"
-    r = subprocess.run([_clangxx(), "-O1", "-std=c++17", "-x", "c++", f"-I{EMU}", f"-I{d}", "-pthread",
-                        str(EMU / "activity_emu.cpp"), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = compile_emu(d, "activity_emu.cpp", "activity_emu", include=(d,))
 
     def run(head, arrays):
         head = list(head) + [0] * (8 - len(head))
         (d / "in.bin").write_bytes(np.array(head, np.int64).tobytes() + b"".join(np.ascontiguousarray(a).tobytes() for a in arrays))
-        r = subprocess.run([str(exe), "in.bin", "out.bin"], cwd=d, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stdout + r.stderr
+        run_emu(exe, ["in.bin", "out.bin"], d, 600)
         return (d / "out.bin").read_bytes()
     return run
 

@@ -1,6 +1,6 @@
 """The AuxK kernels' own source, run on the CPU: csrc/auxk.hip, csrc/gemm_mfma_f32.h and csrc/topk_lists.h are compiled for
-the host against the stand-in runtime of tests/emu (threads as lanes, real barriers; tests/emu_f32 adds the fp32 MFMA,
-tests/emu_kmeans the shuffle of doubles) and must reproduce the numpy restatements of tests/auxk_util.py bit for bit.  This
+the host against the stand-in runtime of tests/emu (threads as lanes, real barriers, the fp32 MFMA, the
+shuffle of doubles) and must reproduce the numpy restatements of tests/auxk_util.py bit for bit.  This
 checks what a GPU-less machine can: the loader's addressing through the unit list, the bias seed of the accumulators, the
 candidate split and the merge, the key decode, the loss kernels' indexing and summation order, and that nothing is written
 outside the outputs and the workspace (which arrives poisoned and is used twice).  The case whose list holds an entry below
@@ -8,47 +8,34 @@ outside the outputs and the workspace (which arrives poisoned and is used twice)
 is a heap block of exactly its size, so a read outside W, bias, x or the list would stop it.  The source lines that cannot
 compile for a host are rewritten as in tests/test_neighbors_f32_emu_host.py."""
 import re
-import subprocess
 from pathlib import Path
 
 import numpy as np
 import pytest
 
 import auxk_util as U
-from test_dictionary_neighbors_emu_host import _clangxx, _rewrite
-
-ROOT = Path(__file__).resolve().parents[1]
-CSRC = ROOT / "quantizedsae_amd" / "csrc"
-EMU = ROOT / "tests" / "emu_auxk"
+from emu_util import CSRC, ROOT, compile_emu, rewrite, run_emu
 
 
 @pytest.fixture(scope="module")
 def build_dir(tmp_path_factory):
     d = tmp_path_factory.mktemp("auxk_emu")
     gemm = (CSRC / "gemm_mfma_f32.h").read_text()
-    gemm = _rewrite(gemm, 'asm volatile("s_nop 4\\n\\tglobal_load_dwordx4 %0, %1, %2" : "=v"(r[P][i]) : "v"(voff[i]), "s"(base) : "memory");',
+    gemm = rewrite(gemm, 'asm volatile("s_nop 4\\n\\tglobal_load_dwordx4 %0, %1, %2" : "=v"(r[P][i]) : "v"(voff[i]), "s"(base) : "memory");',
                     "r[P][i] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(base) + voff[i]);")
-    gemm = _rewrite(gemm, "extern __shared__ __attribute__((aligned(16))) float smem[];", "float* smem = reinterpret_cast<float*>(g_lds);")
+    gemm = rewrite(gemm, "extern __shared__ __attribute__((aligned(16))) float smem[];", "float* smem = reinterpret_cast<float*>(g_lds);")
     gemm, n = re.subn(r'asm volatile\("s_waitcnt vmcnt\((?:%0|0)\)" ::[^;]*;', ";", gemm)
     assert n == 5
     assert gemm.count('"+v"') == 3
     gemm = gemm.replace('"+v"', '"+x"')
-    gemm = _rewrite(gemm, '#include "common.h"', f'#include "{CSRC / "common.h"}"')
-    hdr = _rewrite((CSRC / "topk_lists.h").read_text(), '#include "common.h"', f'#include "{CSRC / "common.h"}"')
-    src = _rewrite((CSRC / "auxk.hip").read_text(), '#include "../../include/qsae_ext.h"',
+    gemm = rewrite(gemm, '#include "common.h"', f'#include "{CSRC / "common.h"}"')
+    hdr = rewrite((CSRC / "topk_lists.h").read_text(), '#include "common.h"', f'#include "{CSRC / "common.h"}"')
+    src = rewrite((CSRC / "auxk.hip").read_text(), '#include "../../include/qsae_ext.h"',
                    f'#include "{ROOT / "include" / "qsae_ext.h"}"')
     (d / "gemm_mfma_f32.h").write_text(gemm)
     (d / "topk_lists.h").write_text(hdr)
     (d / "auxk_emu.hip").write_text(src)
     return d
-
-
-def _compile(d: Path, name: str, extra=()):
-    exe = d / name
-    r = subprocess.run([_clangxx(), "-O1", "-std=c++17", "-ffp-contract=off", *extra, "-x", "c++", f"-I{EMU}", f"-I{d}", "-pthread",
-                        str(EMU / "auxk_emu.cpp"), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
 
 
 def _run_topk(exe: Path, d: Path, x, W, bias, units, k, pad_x=0, pad_w=0):
@@ -64,21 +51,19 @@ def _run_topk(exe: Path, d: Path, x, W, bias, units, k, pad_x=0, pad_w=0):
     if bias is not None:
         np.ascontiguousarray(bias, dtype=np.float32).tofile(d / "bias.bin")
     np.ascontiguousarray(units, dtype=np.int32).tofile(d / "units.bin")
-    cmd = [str(exe), "topk", "x.bin", B, "w.bin", H, "-" if bias is None else "bias.bin", "units.bin", len(units), D, D + pad_x,
-           D + pad_w, k, "idx.bin", "val.bin"]
-    r = subprocess.run([str(c) for c in cmd], cwd=d, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout + r.stderr[-3000:]
+    run_emu(exe, ["topk", "x.bin", B, "w.bin", H, "-" if bias is None else "bias.bin", "units.bin", len(units), D, D + pad_x,
+                  D + pad_w, k, "idx.bin", "val.bin"], d, 900)
     return np.fromfile(d / "idx.bin", np.int32).reshape(B, k), np.fromfile(d / "val.bin", np.float32).reshape(B, k)
 
 
 @pytest.fixture(scope="module")
 def emu(build_dir):
-    return _compile(build_dir, "auxk_emu")
+    return compile_emu(build_dir, "auxk_emu.cpp", "auxk_emu", include=(build_dir,))
 
 
 @pytest.fixture(scope="module")
 def emu_asan(build_dir):
-    return _compile(build_dir, "auxk_emu_asan", ("-fsanitize=address", "-fno-omit-frame-pointer"))
+    return compile_emu(build_dir, "auxk_emu.cpp", "auxk_emu_asan", include=(build_dir,), asan=True)
 
 
 def _same(got, want):
@@ -130,9 +115,7 @@ def test_loss_source_on_the_host_equals_the_restatement(emu, build_dir, name):
     for a, f in ((x, "lx.bin"), (recon, "lr.bin"), (aux, "la.bin")):
         a.tofile(d / f)
     coef = 1 / 32
-    cmd = [str(emu), "loss", "lx.bin", "lr.bin", "la.bin", B, D, repr(coef), off, "loss.bin", "grad.bin", "sums.bin"]
-    r = subprocess.run([str(c) for c in cmd], cwd=d, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout + r.stderr[-3000:]
+    run_emu(emu, ["loss", "lx.bin", "lr.bin", "la.bin", B, D, repr(coef), off, "loss.bin", "grad.bin", "sums.bin"], d, 900)
     loss, grad, sums = U.auxk_loss(x, recon, aux, coef)
     assert np.array_equal(np.fromfile(d / "sums.bin", np.float64), sums)
     assert np.fromfile(d / "loss.bin", np.uint32)[0] == np.float32(loss).view(np.uint32)

@@ -2,12 +2,11 @@
 include/qsae_batch.h -- every function declared there is bound in _lib.BATCH_SIGNATURES with as many arguments as it declares,
 exported by the product and the debug library as qsaeb_*, and is either a *_bytes sizer or driven between guard words in
 tests/test_batch_topk_gpu.py; the calls of the C ABI that return before they look at a pointer, in the order the header states;
-the front ends' refusals; and the kernels' own source run on the CPU (tests/emu_batch_topk: threads as lanes, real barriers),
+the front ends' refusals; and the kernels' own source run on the CPU (tests/emu, tests/emu_util.py: threads as lanes, real barriers),
 which must equal the restatement bit for bit, twice on poisoned outputs and a poisoned workspace of exactly the sizer's bytes,
 also in a stand-alone build with AddressSanitizer where every operand is a heap block of exactly its size."""
 import ctypes as C
 import re
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -21,11 +20,7 @@ from quantizedsae_amd.sae import (BaselineSparseAutoencoder, BinaryLatentSAE, Bi
                                   ResidualQuantizedSAE, TernarySparseAutoencoder)
 from quantizedsae_amd.training import BatchTopK, Trainer
 from sparsity_curve_util import gaussian
-from test_dictionary_neighbors_emu_host import _clangxx
-
-ROOT = Path(__file__).resolve().parents[1]
-CSRC = ROOT / "quantizedsae_amd" / "csrc"
-EMU = ROOT / "tests" / "emu_batch_topk"
+from emu_util import CSRC, ROOT, compile_emu, run_emu
 
 
 def _f(*v):
@@ -250,14 +245,6 @@ def test_controller_and_trainer_validation(tmp_path):
 
 
 # ---- the kernels' own source on the CPU -------------------------------------------------------------------------------
-def _compile(d: Path, name: str, extra=()):
-    exe = d / name
-    r = subprocess.run([_clangxx(), "-O1", "-std=c++17", "-ffp-contract=off", *extra, "-x", "c++", f"-I{EMU}", f"-I{CSRC}", "-pthread",
-                        str(EMU / "batch_topk_emu.cpp"), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
-
-
 @pytest.fixture(scope="module")
 def build_dir(tmp_path_factory):
     return tmp_path_factory.mktemp("batch_topk_emu")
@@ -265,12 +252,12 @@ def build_dir(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def emu(build_dir):
-    return _compile(build_dir, "batch_topk_emu")
+    return compile_emu(build_dir, "batch_topk_emu.cpp", "batch_topk_emu", include=(CSRC,))
 
 
 @pytest.fixture(scope="module")
 def emu_asan(build_dir):
-    return _compile(build_dir, "batch_topk_emu_asan", ("-fsanitize=address", "-fno-omit-frame-pointer"))
+    return compile_emu(build_dir, "batch_topk_emu.cpp", "batch_topk_emu_asan", include=(CSRC,), asan=True)
 
 
 def _hex(v) -> str:
@@ -278,8 +265,7 @@ def _hex(v) -> str:
 
 
 def _call(exe, d, *args):
-    r = subprocess.run([str(exe)] + [str(a) for a in args], cwd=d, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout + r.stderr[-3000:]
+    run_emu(exe, args, d, 900)
 
 
 def _run_select(exe, d, val, n_select, state=None, lr=0.01):

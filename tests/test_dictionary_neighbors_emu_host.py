@@ -1,54 +1,30 @@
 """The nearest-atom kernels' own source, run on the CPU: csrc/dictionary_neighbors.hip and csrc/topk_lists.h are compiled
-for the host against the stand-in runtime of tests/emu (threads as lanes, real barriers, the MFMA computed from the lane
-maps the source states) and must reproduce the numpy restatement bit for bit.  This checks what a GPU-less machine can:
+for the host against the stand-in runtime of tests/emu (tests/emu_util.py: threads as lanes, real barriers, the MFMA
+computed from the lane maps the source states) and must reproduce the numpy restatement bit for bit.  This checks what a GPU-less machine can:
 indexing, the LDS layout, the append / merge rounds, the column split and the merge kernel, duplicate_of.  Two lines
 of the source cannot compile for a host and are rewritten here: the dynamic-LDS declaration becomes a pointer to the
 emulator's array, and the inline-asm register constraint "v" becomes "r"; the merge kernel's __shared__ array becomes
 static."""
-import shutil
-import subprocess
-from pathlib import Path
-
 import numpy as np
 import pytest
 
 import dictionary_neighbors_util as U
-from quantizedsae_amd import build
-
-ROOT = Path(__file__).resolve().parents[1]
-CSRC = ROOT / "quantizedsae_amd" / "csrc"
-EMU = ROOT / "tests" / "emu"
-
-
-def _clangxx() -> str:
-    near = Path(build._hipcc()).resolve().parent.parent / "lib" / "llvm" / "bin" / "clang++"
-    exe = str(near) if near.exists() else shutil.which("clang++")
-    if not exe:
-        raise RuntimeError("clang++ (the compiler hipcc drives) not found")
-    return exe
-
-
-def _rewrite(text: str, old: str, new: str) -> str:
-    assert text.count(old) == 1, old
-    return text.replace(old, new)
+from emu_util import CSRC, compile_emu, rewrite, run_emu
 
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
     d = tmp_path_factory.mktemp("nearest_atoms_emu")
     src = (CSRC / "dictionary_neighbors.hip").read_text()
-    src = _rewrite(src, "extern __shared__ __attribute__((aligned(16))) unsigned char lds[];", "unsigned char* lds = g_lds;")
-    src = _rewrite(src, '"+v"(rlh)', '"+r"(rlh)')
-    src = _rewrite(src, '#include "topk_lists.h"', '#include "topk_lists_emu.h"')
+    src = rewrite(src, "extern __shared__ __attribute__((aligned(16))) unsigned char lds[];", "unsigned char* lds = g_lds;")
+    src = rewrite(src, '"+v"(rlh)', '"+r"(rlh)')
+    src = rewrite(src, '#include "topk_lists.h"', '#include "topk_lists_emu.h"')
     hdr = (CSRC / "topk_lists.h").read_text()
-    hdr = _rewrite(hdr, "    __shared__ unsigned long long keys", "    static unsigned long long keys")
-    hdr = _rewrite(hdr, '#include "common.h"', f'#include "{CSRC / "common.h"}"')
+    hdr = rewrite(hdr, "    __shared__ unsigned long long keys", "    static unsigned long long keys")
+    hdr = rewrite(hdr, '#include "common.h"', f'#include "{CSRC / "common.h"}"')
     (d / "dictionary_neighbors_emu.hip").write_text(src)
     (d / "topk_lists_emu.h").write_text(hdr)
-    exe = d / "nearest_atoms_emu"
-    r = subprocess.run([_clangxx(), "-O1", "-std=c++17", "-x", "c++", f"-I{EMU}", f"-I{d}", "-pthread",
-                        str(EMU / "nearest_atoms_emu.cpp"), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = compile_emu(d, "nearest_atoms_emu.cpp", "nearest_atoms_emu", include=(d,))
 
     def run(a, b, k, exclude_self=False, pad=0):
         D = a.shape[1]
@@ -61,10 +37,8 @@ def emu(tmp_path_factory):
         dump(a, "a.bin")
         if b is not None:
             dump(b, "b.bin")
-        cmd = [str(exe), "a.bin", str(a.shape[0]), "-" if b is None else "b.bin", str(0 if b is None else b.shape[0]),
-               str(D), str(ld), str(k), str(int(exclude_self)), str(int(b is None)), "keys.bin", "dup.bin"]
-        r = subprocess.run(cmd, cwd=d, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stdout + r.stderr
+        run_emu(exe, ["a.bin", a.shape[0], "-" if b is None else "b.bin", 0 if b is None else b.shape[0],
+                      D, ld, k, int(exclude_self), int(b is None), "keys.bin", "dup.bin"], d, 600)
         keys = np.fromfile(d / "keys.bin", np.int64).reshape(a.shape[0], k)
         return keys, np.fromfile(d / "dup.bin", np.int32)
     return run

@@ -1,22 +1,15 @@
 """The evaluation kernels' own source, run on the CPU: csrc/evaluation.hip is compiled for the host against the stand-in
-runtime of tests/emu_kmeans (threads as lanes, real barriers; tests/emu_evaluation adds the float and 64-bit shuffles) and
+runtime of tests/emu (threads as lanes, real barriers, the wave shuffles of floats, doubles and 64-bit keys) and
 compared with the numpy restatement of tests/evaluation_util.py: the hard side, the counts and the moments for equality,
 the soft side (which goes through this machine's expf) within the derived eps.  Guard bytes around the result block,
 unit_err_sq, the running state and the workspace show that nothing is written outside them.  This checks what a GPU-less
 machine can: the indexing of both load widths, the lane chains and their join, the per-quantity rows of the workspace, the
 group cut, the NaN flags and the order of every sum.  The source compiles for the host as it stands."""
-import subprocess
-from pathlib import Path
-
 import numpy as np
 import pytest
 
 import evaluation_util as U
-from test_dictionary_neighbors_emu_host import _clangxx
-
-ROOT = Path(__file__).resolve().parents[1]
-CSRC = ROOT / "quantizedsae_amd" / "csrc"
-EMU = ROOT / "tests" / "emu_evaluation"
+from emu_util import CSRC, compile_emu, run_emu
 
 
 @pytest.fixture(scope="module")
@@ -25,14 +18,10 @@ def emu(tmp_path_factory):
     src = (CSRC / "evaluation.hip").read_text()
     assert src.count('#include "common.h"') == 1
     (d / "evaluation_emu.hip").write_text(src.replace('#include "common.h"', f'#include "{CSRC / "common.h"}"'))
-    exe = d / "evaluation_emu"
-    r = subprocess.run([_clangxx(), "-O1", "-std=c++17", "-ffp-contract=off", "-x", "c++", f"-I{EMU}", f"-I{d}", "-pthread",
-                        str(EMU / "evaluation_emu.cpp"), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = compile_emu(d, "evaluation_emu.cpp", "evaluation_emu", include=(d,))
 
     def run(cmd):
-        r = subprocess.run([str(exe)] + [str(c) for c in cmd], cwd=d, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stdout + r.stderr
+        run_emu(exe, cmd, d, 600)
 
     def quant(logits, D, n, step, shift=0):
         logits.tofile(d / "logits.bin")

@@ -2,12 +2,11 @@
 include/qsae_jump.h -- every function declared there is bound in _lib.JUMP_SIGNATURES with as many arguments as it declares,
 exported by the product and the debug library as qsaej_*, and is either a *_bytes sizer or driven between guard words in
 tests/test_jumprelu_gpu.py; the calls of the C ABI that return before they look at a pointer, in the order the header states;
-the refusals of the front ends, the controller and the Trainer; and the kernels' own source run on the CPU (tests/emu_jumprelu:
+the refusals of the front ends, the controller and the Trainer; and the kernels' own source run on the CPU (tests/emu, tests/emu_util.py:
 threads as lanes, real barriers), which must equal the restatement bit for bit, twice on poisoned outputs and a poisoned
 workspace of exactly the sizer's bytes, also in a stand-alone build with AddressSanitizer where every operand is a heap block of
 exactly its size."""
 import re
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -21,11 +20,8 @@ from quantizedsae_amd import _lib, build, ops, torch_ops, training
 from quantizedsae_amd.sae import (BaselineSparseAutoencoder, BinaryLatentSAE, BinarySAE, QuantizedMatryoshkaSAE,
                                   ResidualQuantizedSAE, TernarySparseAutoencoder)
 from quantizedsae_amd.training import BatchTopK, JumpReLU, Trainer
-from test_dictionary_neighbors_emu_host import _clangxx
+from emu_util import CSRC, ROOT, compile_emu, run_emu
 
-ROOT = Path(__file__).resolve().parents[1]
-CSRC = ROOT / "quantizedsae_amd" / "csrc"
-EMU = ROOT / "tests" / "emu_jumprelu"
 NAN, INF = np.float32(np.nan), np.float32(np.inf)
 
 
@@ -266,14 +262,6 @@ def test_controller_and_trainer_validation(tmp_path):
 
 
 # ---- the kernels' own source on the CPU -------------------------------------------------------------------------------
-def _compile(d: Path, name: str, extra=()):
-    exe = d / name
-    r = subprocess.run([_clangxx(), "-O1", "-std=c++17", "-ffp-contract=off", *extra, "-x", "c++", f"-I{EMU}", f"-I{CSRC}", "-pthread",
-                        str(EMU / "jumprelu_emu.cpp"), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
-
-
 @pytest.fixture(scope="module")
 def build_dir(tmp_path_factory):
     return tmp_path_factory.mktemp("jumprelu_emu")
@@ -281,12 +269,12 @@ def build_dir(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def emu(build_dir):
-    return _compile(build_dir, "jumprelu_emu")
+    return compile_emu(build_dir, "jumprelu_emu.cpp", "jumprelu_emu", include=(CSRC,))
 
 
 @pytest.fixture(scope="module")
 def emu_asan(build_dir):
-    return _compile(build_dir, "jumprelu_emu_asan", ("-fsanitize=address", "-fno-omit-frame-pointer"))
+    return compile_emu(build_dir, "jumprelu_emu.cpp", "jumprelu_emu_asan", include=(CSRC,), asan=True)
 
 
 def _hex(v) -> str:
@@ -294,8 +282,7 @@ def _hex(v) -> str:
 
 
 def _call(exe, d, *args):
-    r = subprocess.run([str(exe)] + [str(a) for a in args], cwd=d, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout + r.stderr[-3000:]
+    run_emu(exe, args, d, 900)
 
 
 def _run_select(exe, d, idx, val, theta, eps, with_band=True):

@@ -1,45 +1,36 @@
 """The k-means kernels' own source, run on the CPU: csrc/kmeans.hip with csrc/gemm_mfma_f32.h and csrc/csr_lists.h is
-compiled for the host against the stand-in runtime of tests/emu and tests/emu_f32 (threads as lanes, real barriers, the
-fp32 MFMA as an fmaf chain; tests/emu_kmeans adds the shuffles and integer atomics these kernels use) and must reproduce
+compiled for the host against the stand-in runtime of tests/emu (threads as lanes, real barriers, the fp32 MFMA as an
+fmaf chain, the wave shuffles and integer atomics these kernels use) and must reproduce
 the numpy restatement bit for bit.  This checks what a GPU-less machine can: indexing, both loaders' addressing, the
 per-lane running keys and their join, the center split with the atomicMax join, the member lists, the chunk plan and
 both summation orders, and that nothing is written outside the outputs and the workspace.  Lines of the source that
 cannot compile for a host are rewritten as in tests/test_neighbors_f32_emu_host.py."""
 import re
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 import kmeans_util as U
-from test_dictionary_neighbors_emu_host import _clangxx, _rewrite
-
-ROOT = Path(__file__).resolve().parents[1]
-CSRC = ROOT / "quantizedsae_amd" / "csrc"
-EMU = ROOT / "tests" / "emu_kmeans"
+from emu_util import CSRC, compile_emu, rewrite, run_emu
 
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
     d = tmp_path_factory.mktemp("kmeans_emu")
     gemm = (CSRC / "gemm_mfma_f32.h").read_text()
-    gemm = _rewrite(gemm, 'asm volatile("s_nop 4\\n\\tglobal_load_dwordx4 %0, %1, %2" : "=v"(r[P][i]) : "v"(voff[i]), "s"(base) : "memory");',
+    gemm = rewrite(gemm, 'asm volatile("s_nop 4\\n\\tglobal_load_dwordx4 %0, %1, %2" : "=v"(r[P][i]) : "v"(voff[i]), "s"(base) : "memory");',
                     "r[P][i] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(base) + voff[i]);")
-    gemm = _rewrite(gemm, "extern __shared__ __attribute__((aligned(16))) float smem[];", "float* smem = reinterpret_cast<float*>(g_lds);")
+    gemm = rewrite(gemm, "extern __shared__ __attribute__((aligned(16))) float smem[];", "float* smem = reinterpret_cast<float*>(g_lds);")
     gemm, n = re.subn(r'asm volatile\("s_waitcnt vmcnt\((?:%0|0)\)" ::[^;]*;', ";", gemm)
     assert n == 5
     assert gemm.count('"+v"') == 3
     gemm = gemm.replace('"+v"', '"+x"')
-    gemm = _rewrite(gemm, '#include "common.h"', f'#include "{CSRC / "common.h"}"')
-    csr = _rewrite((CSRC / "csr_lists.h").read_text(), '#include "common.h"', f'#include "{CSRC / "common.h"}"')
+    gemm = rewrite(gemm, '#include "common.h"', f'#include "{CSRC / "common.h"}"')
+    csr = rewrite((CSRC / "csr_lists.h").read_text(), '#include "common.h"', f'#include "{CSRC / "common.h"}"')
     (d / "gemm_mfma_f32.h").write_text(gemm)
     (d / "csr_lists.h").write_text(csr)
     (d / "kmeans_emu.hip").write_text((CSRC / "kmeans.hip").read_text())
-    exe = d / "kmeans_emu"
-    r = subprocess.run([_clangxx(), "-O1", "-std=c++17", "-ffp-contract=off", "-x", "c++", f"-I{EMU}", f"-I{d}", "-pthread",
-                        str(EMU / "kmeans_emu.cpp"), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = compile_emu(d, "kmeans_emu.cpp", "kmeans_emu", include=(d,))
 
     def dump(x, name, pad):
         w = np.full((x.shape[0], x.shape[1] + pad), np.nan, np.float32)     # NaN between D and ld
@@ -47,8 +38,7 @@ def emu(tmp_path_factory):
         w.tofile(d / name)
 
     def run(cmd):
-        r = subprocess.run([str(exe)] + [str(c) for c in cmd], cwd=d, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stdout + r.stderr
+        run_emu(exe, cmd, d, 600)
 
     def assign(a, c, metric, pad=0):
         dump(a, "a.bin", pad)

@@ -3,13 +3,12 @@ include/qsae_multik.h -- every function declared there is bound in _lib.MULTIK_S
 declares, exported by the product and the debug library as qsaek_* and nothing else, and is either a *_bytes sizer or driven
 between guard words in tests/test_multi_topk_gpu.py; the calls of the C ABI that return before they look at a pointer, in the
 order the header states; default_multi_topk; the front ends' refusal of host tensors, of bad points and of the four classes
-without a top-k; the Trainer's validation; the kernels' own source run on the CPU (tests/emu_multi_topk: threads as lanes, real
+without a top-k; the Trainer's validation; the kernels' own source run on the CPU (tests/emu, tests/emu_util.py: threads as lanes, real
 barriers), which must equal the restatement bit for bit, twice on poisoned outputs, also in a stand-alone build with
 AddressSanitizer where every operand is a heap block of exactly its size; and a derivative check of the restatement against
 fp64 autograd of the dense formulation."""
 import ctypes as C
 import re
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -25,11 +24,7 @@ from quantizedsae_amd.sae import (BaselineSparseAutoencoder, BinaryLatentSAE, Bi
 from quantizedsae_amd.sae.topk import TopKCore
 from quantizedsae_amd.training import Trainer, default_multi_topk, multi_topk_loss
 from sparsity_curve_util import gaussian
-from test_dictionary_neighbors_emu_host import _clangxx
-
-ROOT = Path(__file__).resolve().parents[1]
-CSRC = ROOT / "quantizedsae_amd" / "csrc"
-EMU = ROOT / "tests" / "emu_multi_topk"
+from emu_util import CSRC, ROOT, compile_emu, run_emu
 
 
 # ---- the restatement, by hand -----------------------------------------------------------------------------------------
@@ -259,14 +254,6 @@ def test_trainer_validation(tmp_path):
 
 
 # ---- the kernels' own source on the CPU -------------------------------------------------------------------------------
-def _compile(d: Path, name: str, extra=()):
-    exe = d / name
-    r = subprocess.run([_clangxx(), "-O1", "-std=c++17", "-ffp-contract=off", *extra, "-x", "c++", f"-I{EMU}", f"-I{CSRC}", "-pthread",
-                        str(EMU / "multi_topk_emu.cpp"), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
-
-
 @pytest.fixture(scope="module")
 def build_dir(tmp_path_factory):
     return tmp_path_factory.mktemp("multi_topk_emu")
@@ -274,12 +261,12 @@ def build_dir(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def emu(build_dir):
-    return _compile(build_dir, "multi_topk_emu")
+    return compile_emu(build_dir, "multi_topk_emu.cpp", "multi_topk_emu", include=(CSRC,))
 
 
 @pytest.fixture(scope="module")
 def emu_asan(build_dir):
-    return _compile(build_dir, "multi_topk_emu_asan", ("-fsanitize=address", "-fno-omit-frame-pointer"))
+    return compile_emu(build_dir, "multi_topk_emu.cpp", "multi_topk_emu_asan", include=(CSRC,), asan=True)
 
 
 def _run(exe: Path, d: Path, case):
@@ -292,10 +279,9 @@ def _run(exe: Path, d: Path, case):
         bias.tofile(d / "bias.bin")
     packed = decoder[0] == "packed"
     D = decoder[2] if packed else decoder[1].shape[1]
-    cmd = [exe, "p" if packed else "t", "idx.bin", "val.bin", B, K, "dict.bin", decoder[1].shape[0], D, decoder[3] if packed else 0,
+    cmd = ["p" if packed else "t", "idx.bin", "val.bin", B, K, "dict.bin", decoder[1].shape[0], D, decoder[3] if packed else 0,
            repr(float(decoder[-1])), "-" if bias is None else "bias.bin", ",".join(str(k) for k in ks), "recon.bin"]
-    r = subprocess.run([str(c) for c in cmd], cwd=d, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout + r.stderr[-3000:]
+    run_emu(exe, cmd, d, 900)
     return np.fromfile(d / "recon.bin", np.float32).reshape(len(ks), B, D)
 
 
@@ -345,10 +331,9 @@ def _run_row_grad(exe: Path, d: Path, idx, table, step, g, present, ks, g_latent
     np.ascontiguousarray(np.stack(g)).tofile(d / "g.bin")
     g_latent.tofile(d / "glat.bin")
     W.tofile(d / "wenc.bin")
-    cmd = [exe, "g", "idx.bin", B, K, "table.bin", H, D, repr(float(step)), ",".join(str(k) for k in ks), "g.bin",
+    cmd = ["g", "idx.bin", B, K, "table.bin", H, D, repr(float(step)), ",".join(str(k) for k in ks), "g.bin",
            ",".join(str(int(p)) for p in present), "glat.bin", "wenc.bin", "G.bin", "gv.bin", "dx.bin"]
-    r = subprocess.run([str(c) for c in cmd], cwd=d, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout + r.stderr[-3000:]
+    run_emu(exe, cmd, d, 900)
     return (np.fromfile(d / "G.bin", np.float32).reshape(len(ks), B, D), np.fromfile(d / "gv.bin", np.float32).reshape(B, K),
             np.fromfile(d / "dx.bin", np.float32).reshape(B, D))
 

@@ -1,6 +1,6 @@
 """The fp32 nearest-atom kernel's own source, run on the CPU: csrc/dictionary_neighbors_f32.hip, csrc/gemm_mfma_f32.h
 and csrc/topk_lists.h are compiled for the host against the stand-in runtime of tests/emu (threads as lanes, real
-barriers; tests/emu_f32 adds the fp32 MFMA, computed from the lane maps the source states) and must reproduce the numpy
+barriers, the fp32 MFMA computed from the lane maps the source states) and must reproduce the numpy
 restatement bit for bit.  This checks what a GPU-less machine can: indexing, both loaders' addressing, the LDS layout
 with the append buffer in the freed staging buffer, the four merge rounds, the candidate split and the merge kernel,
 and that nothing is written outside `keys` and the workspace.  Lines of the source that cannot compile for a host are
@@ -8,42 +8,33 @@ rewritten here: the dynamic-LDS declaration becomes a pointer to the emulator's 
 becomes the plain load of the same address (base + 32-bit byte offset), the counted waits disappear, the register
 constraint "v" becomes "x"; the merge kernel's __shared__ array becomes static."""
 import re
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 import neighbors_f32_util as U
-from test_dictionary_neighbors_emu_host import _clangxx, _rewrite
-
-ROOT = Path(__file__).resolve().parents[1]
-CSRC = ROOT / "quantizedsae_amd" / "csrc"
-EMU = ROOT / "tests" / "emu_f32"
+from emu_util import CSRC, compile_emu, rewrite, run_emu
 
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
     d = tmp_path_factory.mktemp("nearest_atoms_f32_emu")
     gemm = (CSRC / "gemm_mfma_f32.h").read_text()
-    gemm = _rewrite(gemm, 'asm volatile("s_nop 4\\n\\tglobal_load_dwordx4 %0, %1, %2" : "=v"(r[P][i]) : "v"(voff[i]), "s"(base) : "memory");',
+    gemm = rewrite(gemm, 'asm volatile("s_nop 4\\n\\tglobal_load_dwordx4 %0, %1, %2" : "=v"(r[P][i]) : "v"(voff[i]), "s"(base) : "memory");',
                     "r[P][i] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(base) + voff[i]);")
-    gemm = _rewrite(gemm, "extern __shared__ __attribute__((aligned(16))) float smem[];", "float* smem = reinterpret_cast<float*>(g_lds);")
+    gemm = rewrite(gemm, "extern __shared__ __attribute__((aligned(16))) float smem[];", "float* smem = reinterpret_cast<float*>(g_lds);")
     gemm, n = re.subn(r'asm volatile\("s_waitcnt vmcnt\((?:%0|0)\)" ::[^;]*;', ";", gemm)
     assert n == 5
     assert gemm.count('"+v"') == 3
     gemm = gemm.replace('"+v"', '"+x"')
-    gemm = _rewrite(gemm, '#include "common.h"', f'#include "{CSRC / "common.h"}"')
+    gemm = rewrite(gemm, '#include "common.h"', f'#include "{CSRC / "common.h"}"')
     hdr = (CSRC / "topk_lists.h").read_text()
-    hdr = _rewrite(hdr, "    __shared__ unsigned long long keys", "    static unsigned long long keys")
-    hdr = _rewrite(hdr, '#include "common.h"', f'#include "{CSRC / "common.h"}"')
+    hdr = rewrite(hdr, "    __shared__ unsigned long long keys", "    static unsigned long long keys")
+    hdr = rewrite(hdr, '#include "common.h"', f'#include "{CSRC / "common.h"}"')
     (d / "gemm_mfma_f32.h").write_text(gemm)
     (d / "topk_lists.h").write_text(hdr)
     (d / "dictionary_neighbors_f32_emu.hip").write_text((CSRC / "dictionary_neighbors_f32.hip").read_text())
-    exe = d / "nearest_atoms_f32_emu"
-    r = subprocess.run([_clangxx(), "-O1", "-std=c++17", "-ffp-contract=off", "-x", "c++", f"-I{EMU}", f"-I{d}", "-pthread",
-                        str(EMU / "nearest_atoms_f32_emu.cpp"), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = compile_emu(d, "nearest_atoms_f32_emu.cpp", "nearest_atoms_f32_emu", include=(d,))
 
     def run(a, b, k, exclude_self=False, pad=0):
         D = a.shape[1]
@@ -56,10 +47,8 @@ def emu(tmp_path_factory):
         dump(a, "a.bin")
         if b is not None:
             dump(b, "b.bin")
-        cmd = [str(exe), "a.bin", str(a.shape[0]), "-" if b is None else "b.bin", str(0 if b is None else b.shape[0]),
-               str(D), str(ld), str(k), str(int(exclude_self)), "keys.bin"]
-        r = subprocess.run(cmd, cwd=d, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stdout + r.stderr
+        run_emu(exe, ["a.bin", a.shape[0], "-" if b is None else "b.bin", 0 if b is None else b.shape[0],
+                      D, ld, k, int(exclude_self), "keys.bin"], d, 600)
         return np.fromfile(d / "keys.bin", np.int64).reshape(a.shape[0], k)
     return run
 

@@ -3,13 +3,12 @@ the coverage its planted inputs give; the ledger of include/qsae_nested_batch.h 
 _lib.NESTED_BATCH_SIGNATURES with as many arguments as it declares, exported by the product and the debug library as qsaem_* (and
 nothing else is), and driven between guard words in tests/test_nested_ragged_gpu.py; the calls of the C ABI that return before
 they look at a pointer; the front ends' refusal of host tensors, of bad bounds and of the four classes without a top-k; the
-Trainer's validation of ``batch_topk_nested_bounds``; and the kernels' own source run on the CPU (tests/emu_nested_ragged:
+Trainer's validation of ``batch_topk_nested_bounds``; and the kernels' own source run on the CPU (tests/emu, tests/emu_util.py:
 threads as lanes, real barriers), which must equal the restatement bit for bit, twice on poisoned outputs, also in a stand-alone
 build with AddressSanitizer where every operand -- the lists, read only up to counts[r], included -- is a heap block of exactly
 its size."""
 import ctypes as C
 import re
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -26,11 +25,8 @@ from quantizedsae_amd.sae import (BaselineSparseAutoencoder, BinaryLatentSAE, Bi
                                   ResidualQuantizedSAE, TernarySparseAutoencoder)
 from quantizedsae_amd.training import BatchTopK, Trainer
 from sparsity_curve_util import gaussian
-from test_dictionary_neighbors_emu_host import _clangxx
+from emu_util import CSRC, ROOT, compile_emu, run_emu
 
-ROOT = Path(__file__).resolve().parents[1]
-CSRC = ROOT / "quantizedsae_amd" / "csrc"
-EMU = ROOT / "tests" / "emu_nested_ragged"
 HEADER = ROOT / "include" / "qsae_nested_batch.h"
 
 
@@ -248,14 +244,6 @@ def test_trainer_validation(tmp_path):
 
 
 # ---- the kernels' own source on the CPU -------------------------------------------------------------------------------
-def _compile(d: Path, name: str, extra=()):
-    exe = d / name
-    r = subprocess.run([_clangxx(), "-O1", "-std=c++17", "-ffp-contract=off", *extra, "-x", "c++", f"-I{EMU}", f"-I{CSRC}", "-pthread",
-                        str(EMU / "nested_ragged_emu.cpp"), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
-
-
 @pytest.fixture(scope="module")
 def build_dir(tmp_path_factory):
     return tmp_path_factory.mktemp("nested_ragged_emu")
@@ -263,8 +251,8 @@ def build_dir(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def emus(build_dir):
-    return {False: _compile(build_dir, "nested_ragged_emu"),
-            True: _compile(build_dir, "nested_ragged_emu_asan", ("-fsanitize=address", "-fno-omit-frame-pointer"))}
+    return {False: compile_emu(build_dir, "nested_ragged_emu.cpp", "nested_ragged_emu", include=(CSRC,)),
+            True: compile_emu(build_dir, "nested_ragged_emu.cpp", "nested_ragged_emu_asan", include=(CSRC,), asan=True)}
 
 
 def _run(exe: Path, d: Path, idx, val, counts, bounds, decoder, bias, want_below=True):
@@ -277,11 +265,10 @@ def _run(exe: Path, d: Path, idx, val, counts, bounds, decoder, bias, want_below
         bias.tofile(d / "bias.bin")
     packed = decoder[0] == "packed"
     D = decoder[2] if packed else decoder[1].shape[1]
-    cmd = [exe, "p" if packed else "t", "idx.bin", "val.bin", "counts.bin", B, K, "dict.bin", decoder[1].shape[0], D,
+    cmd = ["p" if packed else "t", "idx.bin", "val.bin", "counts.bin", B, K, "dict.bin", decoder[1].shape[0], D,
            decoder[3] if packed else 0, repr(float(decoder[-1])), "-" if bias is None else "bias.bin",
            ",".join(str(b) for b in bounds), "recon.bin", "below.bin" if want_below else "-"]
-    r = subprocess.run([str(c) for c in cmd], cwd=d, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout + r.stderr[-3000:]
+    run_emu(exe, cmd, d, 900)
     recon = np.fromfile(d / "recon.bin", np.float32).reshape(len(bounds), B, D)
     return recon, (np.fromfile(d / "below.bin", np.int32).reshape(len(bounds), B) if want_below else None)
 
@@ -322,10 +309,9 @@ def _run_row_grad(exe: Path, d: Path, idx, counts, table, step, g, present, boun
     np.ascontiguousarray(np.stack(g)).tofile(d / "g.bin")
     g_latent.tofile(d / "glat.bin")
     W.tofile(d / "wenc.bin")
-    cmd = [exe, "g", "idx.bin", "counts.bin", B, K, "table.bin", H, D, repr(float(step)), ",".join(str(b) for b in bounds), "g.bin",
+    cmd = ["g", "idx.bin", "counts.bin", B, K, "table.bin", H, D, repr(float(step)), ",".join(str(b) for b in bounds), "g.bin",
            ",".join(str(int(p)) for p in present), "glat.bin", "wenc.bin", "G.bin", "gv.bin", "dx.bin"]
-    r = subprocess.run([str(c) for c in cmd], cwd=d, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout + r.stderr[-3000:]
+    run_emu(exe, cmd, d, 900)
     return (np.fromfile(d / "G.bin", np.float32).reshape(len(bounds), B, D), np.fromfile(d / "gv.bin", np.float32).reshape(B, K),
             np.fromfile(d / "dx.bin", np.float32).reshape(B, D))
 

@@ -1,22 +1,16 @@
 """The optimizer kernels' own source, run on the CPU: csrc/optim.hip (with csrc/prefilter_common.h, which it shares with
-qsae_prefilter_pack_w) is compiled for the host against the stand-in runtime of tests/emu_evaluation (threads as lanes, real
-barriers; tests/emu_optim adds the shuffle's width argument and the 32-bit atomicMax) and compared with the numpy restatement
+qsae_prefilter_pack_w) is compiled for the host against the stand-in runtime of tests/emu (threads as lanes, real
+barriers, the float shuffle with its width argument, the 32-bit atomicMax) and compared with the numpy restatement
 of tests/optim_util.py, bit for bit.  Guard bytes around every buffer the entry points write show that nothing is written
 outside them.  This checks what a GPU-less machine can: the indexing of both load widths and of the tail, the grid-stride
 trips (the emulated grid is capped at 8 workgroups), the lane chains and their join, the workgroup maxima with idle waves
 and idle lanes, and the hand-over of max |W'| through meta[0].  The source compiles for the host as it stands."""
-import subprocess
-from pathlib import Path
-
 import numpy as np
 import pytest
 
 import optim_util as U
-from test_dictionary_neighbors_emu_host import _clangxx
+from emu_util import CSRC, compile_emu, run_emu
 
-ROOT = Path(__file__).resolve().parents[1]
-CSRC = ROOT / "quantizedsae_amd" / "csrc"
-EMU = ROOT / "tests" / "emu_optim"
 SC = U.scalars()
 
 
@@ -31,15 +25,10 @@ def emu(tmp_path_factory):
     assert src.count('#include "prefilter_common.h"') == 1
     (d / "optim_emu.hip").write_text(src.replace('#include "prefilter_common.h"',
                                                  f'#include "{CSRC / "prefilter_common.h"}"'))
-    exe = d / "optim_emu"
-    r = subprocess.run([_clangxx(), "-O1", "-std=c++17", "-ffp-contract=off", "-DQSAE_ADAM_MAX_BLOCKS=8", "-x", "c++",
-                        f"-I{EMU}", f"-I{d}", "-pthread", str(EMU / "optim_emu.cpp"), "-o", str(exe)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = compile_emu(d, "optim_emu.cpp", "optim_emu", include=(d,), defines=("QSAE_ADAM_MAX_BLOCKS=8",))
 
     def run(cmd):
-        r = subprocess.run([str(exe)] + [str(c) for c in cmd], cwd=d, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stdout + r.stderr
+        run_emu(exe, cmd, d, 600)
 
     def adam(p, g, m, v, sc, shift_p=0, shift_g=0):
         n = p.size

@@ -1,22 +1,15 @@
 """The resampling kernels' own source, run on the CPU: csrc/resample.hip is compiled for the host against the stand-in
-runtime of tests/emu_activity (threads as lanes, real barriers; tests/emu_resample) and compared with the numpy restatement
+runtime of tests/emu (threads as lanes, real barriers, the integer atomics) and compared with the numpy restatement
 of tests/resample_util.py at the shapes the GPU tests use, bit for bit, with guard bytes around every buffer and the outputs
 and the workspace poisoned.  This checks what a GPU-less machine can: indexing and tails, the order of every sum, the
 three levels of the prefix sum, the binary search and the owner rule, the strided decoder column and the bit layout of the
 logit row, and that nothing but the stated positions is written.  The source compiles for the host as it stands (no
 multiply-add is contracted: -ffp-contract=off, as in the library's build)."""
-import subprocess
-from pathlib import Path
-
 import numpy as np
 import pytest
 
 import resample_util as U
-from test_dictionary_neighbors_emu_host import _clangxx
-
-ROOT = Path(__file__).resolve().parents[1]
-CSRC = ROOT / "quantizedsae_amd" / "csrc"
-EMU = ROOT / "tests" / "emu_resample"
+from emu_util import CSRC, compile_emu, run_emu
 
 
 @pytest.fixture(scope="module")
@@ -25,16 +18,12 @@ def emu(tmp_path_factory):
     src = (CSRC / "resample.hip").read_text()
     assert src.count('#include "common.h"') == 1
     (d / "resample_emu.hip").write_text(src.replace('#include "common.h"', f'#include "{CSRC / "common.h"}"'))
-    exe = d / "resample_emu"
-    r = subprocess.run([_clangxx(), "-O1", "-ffp-contract=off", "-std=c++17", "-x", "c++", f"-I{EMU}", f"-I{d}", "-pthread",
-                        str(EMU / "resample_emu.cpp"), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = compile_emu(d, "resample_emu.cpp", "resample_emu", include=(d,))
 
     def run(head, arrays):
         head = list(head) + [0] * (8 - len(head))
         (d / "in.bin").write_bytes(np.array(head, np.int64).tobytes() + b"".join(np.ascontiguousarray(a).tobytes() for a in arrays))
-        r = subprocess.run([str(exe), "in.bin", "out.bin"], cwd=d, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stdout + r.stderr
+        run_emu(exe, ["in.bin", "out.bin"], d, 600)
         return (d / "out.bin").read_bytes()
     return run
 

@@ -3,12 +3,11 @@ ledger of include/qsae_curve.h -- every function declared there is bound in _lib
 declares, exported by the product and the debug library as qsaec_*, and is either a *_bytes sizer or driven between guard
 words in tests/test_sparsity_curve_gpu.py; the calls of the C ABI that return before they look at a pointer; default_ks; the
 front ends' refusal of host tensors and of the four classes whose sparsity is not a k; and the kernel's own source run on
-the CPU (tests/emu_sparsity_curve: threads as lanes, real barriers), which must equal the restatement bit for bit, twice on
+the CPU (tests/emu, tests/emu_util.py: threads as lanes, real barriers), which must equal the restatement bit for bit, twice on
 one poisoned workspace, also in a stand-alone build with AddressSanitizer where every operand is a heap block of exactly
 its size."""
 import ctypes as C
 import re
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -21,11 +20,7 @@ from quantizedsae_amd import _lib, build, inference, ops, torch_ops
 from quantizedsae_amd.inference import SparsityCurve, default_ks
 from quantizedsae_amd.sae import (BaselineSparseAutoencoder, BinaryLatentSAE, BinarySAE, QuantizedMatryoshkaSAE,
                                   ResidualQuantizedSAE, TernarySparseAutoencoder)
-from test_dictionary_neighbors_emu_host import _clangxx
-
-ROOT = Path(__file__).resolve().parents[1]
-CSRC = ROOT / "quantizedsae_amd" / "csrc"
-EMU = ROOT / "tests" / "emu_sparsity_curve"
+from emu_util import CSRC, ROOT, compile_emu, run_emu
 
 
 # ---- the restatement, by hand -----------------------------------------------------------------------------------------
@@ -219,14 +214,6 @@ def test_front_end_validates_ks():
 
 
 # ---- the kernel's own source on the CPU -------------------------------------------------------------------------------
-def _compile(d: Path, name: str, extra=()):
-    exe = d / name
-    r = subprocess.run([_clangxx(), "-O1", "-std=c++17", "-ffp-contract=off", *extra, "-x", "c++", f"-I{EMU}", f"-I{CSRC}", "-pthread",
-                        str(EMU / "sparsity_curve_emu.cpp"), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
-
-
 @pytest.fixture(scope="module")
 def build_dir(tmp_path_factory):
     return tmp_path_factory.mktemp("sparsity_curve_emu")
@@ -234,12 +221,12 @@ def build_dir(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def emu(build_dir):
-    return _compile(build_dir, "curve_emu")
+    return compile_emu(build_dir, "sparsity_curve_emu.cpp", "curve_emu", include=(CSRC,))
 
 
 @pytest.fixture(scope="module")
 def emu_asan(build_dir):
-    return _compile(build_dir, "curve_emu_asan", ("-fsanitize=address", "-fno-omit-frame-pointer"))
+    return compile_emu(build_dir, "sparsity_curve_emu.cpp", "curve_emu_asan", include=(CSRC,), asan=True)
 
 
 def _run(exe: Path, d: Path, case, xoff=0, split=0, want_recon=True):
@@ -253,11 +240,10 @@ def _run(exe: Path, d: Path, case, xoff=0, split=0, want_recon=True):
     if bias is not None:
         bias.tofile(d / "bias.bin")
     packed = decoder[0] == "packed"
-    cmd = [exe, "p" if packed else "t", "x.bin", B, D, "idx.bin", "val.bin", K, "dict.bin", decoder[1].shape[0],
+    cmd = ["p" if packed else "t", "x.bin", B, D, "idx.bin", "val.bin", K, "dict.bin", decoder[1].shape[0],
            decoder[3] if packed else 0, repr(float(decoder[-1])), "-" if bias is None else "bias.bin", ",".join(str(k) for k in ks),
            group_rows, xoff, split, "sums.bin", "counts.bin", "recon.bin" if want_recon else "-"]
-    r = subprocess.run([str(c) for c in cmd], cwd=d, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout + r.stderr[-3000:]
+    run_emu(exe, cmd, d, 900)
     recon = np.fromfile(d / "recon.bin", np.float32).reshape(len(ks), B, D) if want_recon and not split else None
     return np.fromfile(d / "sums.bin", np.float64), np.fromfile(d / "counts.bin", np.int64), recon
 

@@ -1,43 +1,31 @@
 """The top-examples kernels' own source, run on the CPU: csrc/top_examples.hip with csrc/topk_lists.h and
-csrc/csr_lists.h is compiled for the host against the stand-in runtime of tests/emu_kmeans (threads as lanes, real
-barriers; tests/emu_top_examples) and must reproduce the numpy restatement bit for bit, fed in uneven batches through
+csrc/csr_lists.h is compiled for the host against the stand-in runtime of tests/emu (threads as lanes, real
+barriers, __syncthreads_or) and must reproduce the numpy restatement bit for bit, fed in uneven batches through
 one workspace, with guard words around keys, the workspace and the decoded outputs.  This checks what a GPU-less machine
 can: the mark / count / scan / fill indexing, the per-wave rounds with their ballot compaction, rank merge and running
 threshold, the dense form's LDS lists, row split and partial-list join, and the bounds of every write.  One line of the
 source cannot compile for a host and is rewritten here: the dynamic-LDS declaration becomes a pointer to the emulator's
 array."""
-import subprocess
-from pathlib import Path
-
 import numpy as np
 import pytest
 
 import top_examples_util as U
-from test_dictionary_neighbors_emu_host import _clangxx, _rewrite
-
-ROOT = Path(__file__).resolve().parents[1]
-CSRC = ROOT / "quantizedsae_amd" / "csrc"
-EMU = ROOT / "tests" / "emu_top_examples"
+from emu_util import CSRC, compile_emu, rewrite, run_emu
 
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
     d = tmp_path_factory.mktemp("top_examples_emu")
     src = (CSRC / "top_examples.hip").read_text()
-    src = _rewrite(src, "extern __shared__ __attribute__((aligned(16))) unsigned char lds[];", "unsigned char* lds = g_lds;")
+    src = rewrite(src, "extern __shared__ __attribute__((aligned(16))) unsigned char lds[];", "unsigned char* lds = g_lds;")
     for h in ("csr_lists.h", "topk_lists.h"):
-        (d / h).write_text(_rewrite((CSRC / h).read_text(), '#include "common.h"', f'#include "{CSRC / "common.h"}"'))
+        (d / h).write_text(rewrite((CSRC / h).read_text(), '#include "common.h"', f'#include "{CSRC / "common.h"}"'))
     (d / "top_examples_emu.hip").write_text(src)
-    exe = d / "top_examples_emu"
-    r = subprocess.run([_clangxx(), "-O1", "-std=c++17", "-ffp-contract=off", "-x", "c++", f"-I{EMU}", f"-I{d}", "-pthread",
-                        str(EMU / "top_examples_emu.cpp"), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = compile_emu(d, "top_examples_emu.cpp", "top_examples_emu", include=(d,))
 
     def run(kind, head, H, n, floor, base, state, cuts):
         (np.zeros((H, n), np.uint64) if state is None else state).tofile(d / "state.bin")
-        cmd = [str(exe), kind] + [str(c) for c in head] + [H, n, repr(float(floor)), base, "state.bin", "out"] + cuts
-        r = subprocess.run([str(c) for c in cmd], cwd=d, capture_output=True, text=True, timeout=900)
-        assert r.returncode == 0, r.stdout + r.stderr
+        run_emu(exe, [kind] + list(head) + [H, n, repr(float(floor)), base, "state.bin", "out"] + cuts, d, 900)
         keys = np.fromfile(d / "out_keys.bin", np.uint64).reshape(H, n)
         got = (np.fromfile(d / "out_values.bin", np.float32).reshape(H, n), np.fromfile(d / "out_positions.bin", np.int64).reshape(H, n),
                np.fromfile(d / "out_counts.bin", np.int32))

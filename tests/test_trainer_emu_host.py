@@ -1,23 +1,16 @@
 """The trainer kernels' own source, run on the CPU: csrc/trainer.hip is compiled for the host against the stand-in runtime
-of tests/emu_evaluation (threads as lanes, real barriers) and compared with the restatements of tests/trainer_util.py, bit
+of tests/emu (threads as lanes, real barriers) and compared with the restatements of tests/trainer_util.py, bit
 for bit, at the kernel shapes of the GPU tests.  Guard bytes around every buffer show that nothing is written outside them.
 This checks what a GPU-less machine can: the indexing of both load widths (a base pointer moved off its 16-byte boundary
 takes the element-wise path), rows past the end of the last bitmap word, indices outside the chunk, the tail of the last
 slab, the lane / wave / workgroup joins of the loss sum and the chain of the rq_sae targets.  The source compiles for the
 host as it stands."""
-import subprocess
-from pathlib import Path
-
 import numpy as np
 import pytest
 import torch
 
 import trainer_util as U
-from test_dictionary_neighbors_emu_host import _clangxx
-
-ROOT = Path(__file__).resolve().parents[1]
-CSRC = ROOT / "quantizedsae_amd" / "csrc"
-EMU = ROOT / "tests" / "emu_trainer"
+from emu_util import CSRC, compile_emu, run_emu
 
 
 def _raw(t: torch.Tensor) -> bytes:
@@ -31,16 +24,11 @@ def emu(tmp_path_factory):
     src = (CSRC / "trainer.hip").read_text()
     assert src.count('#include "common.h"') == 1
     (d / "trainer_emu.hip").write_text(src.replace('#include "common.h"', f'#include "{CSRC / "common.h"}"'))
-    exe = d / "trainer_emu"
-    r = subprocess.run([_clangxx(), "-O1", "-std=c++17", "-ffp-contract=off", "-x", "c++", f"-I{EMU}", f"-I{d}", "-pthread",
-                        str(EMU / "trainer_emu.cpp"), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = compile_emu(d, "trainer_emu.cpp", "trainer_emu", include=(d,))
 
     def run(cmd, payload: bytes) -> bytes:
         (d / "in.bin").write_bytes(payload)
-        r = subprocess.run([str(exe)] + [str(c) for c in cmd] + ["in.bin", "out.bin"], cwd=d, capture_output=True, text=True,
-                           timeout=600)
-        assert r.returncode == 0, r.stdout + r.stderr
+        run_emu(exe, list(cmd) + ["in.bin", "out.bin"], d, 600)
         return (d / "out.bin").read_bytes()
     return run
 

@@ -1,22 +1,15 @@
 """The watch kernels' own source, run on the CPU: csrc/watch.hip is compiled for the host against the stand-in runtime of
-tests/emu_trainer (threads as lanes, real barriers; tests/emu_watch adds the 64-bit integer add) and compared with the
+tests/emu (threads as lanes, real barriers, the 64-bit integer add on global memory) and compared with the
 numpy restatement of tests/watch_util.py: every count, lo, hi and every fp64 word bit for bit.  Guard bytes around the
 result block, the workspace and every tensor show that nothing is written outside them.  This checks what a GPU-less
 machine can: the (tensor, chunk) table and its search, lists longer than one table, both load widths and the tail, the
 ballot that joins the lanes of a bin, the LDS histogram and its flush, the order of every sum and the widened range.  The
 source compiles for the host as it stands."""
-import subprocess
-from pathlib import Path
-
 import numpy as np
 import pytest
 
 import watch_util as U
-from test_dictionary_neighbors_emu_host import _clangxx
-
-ROOT = Path(__file__).resolve().parents[1]
-CSRC = ROOT / "quantizedsae_amd" / "csrc"
-EMU = ROOT / "tests" / "emu_watch"
+from emu_util import CSRC, compile_emu, run_emu
 
 
 @pytest.fixture(scope="module")
@@ -25,18 +18,14 @@ def emu(tmp_path_factory):
     src = (CSRC / "watch.hip").read_text()
     assert src.count('#include "common.h"') == 1
     (d / "watch_emu.hip").write_text(src.replace('#include "common.h"', f'#include "{CSRC / "common.h"}"'))
-    exe = d / "watch_emu"
-    r = subprocess.run([_clangxx(), "-O1", "-std=c++17", "-ffp-contract=off", "-x", "c++", f"-I{EMU}", f"-I{d}", "-pthread",
-                        str(EMU / "watch_emu.cpp"), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = compile_emu(d, "watch_emu.cpp", "watch_emu", include=(d,))
 
     def run(tensors, bins, shift=0):
         T = len(tensors)
         meta = np.array([[t.size, shift] for t in tensors], np.int64).reshape(-1)
         payload = np.array([T, bins], np.int64).tobytes() + meta.tobytes() + b"".join(np.ascontiguousarray(t, np.float32).tobytes() for t in tensors)
         (d / "in.bin").write_bytes(payload)
-        r = subprocess.run([str(exe), "in.bin", "out.bin"], cwd=d, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stdout + r.stderr
+        run_emu(exe, ["in.bin", "out.bin"], d, 600)
         return np.fromfile(d / "out.bin", np.uint64).reshape(T, U.HEAD + bins)
     return run
 
