@@ -274,6 +274,15 @@ JUMP_SIGNATURES = {
     "qsaej_threshold_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
 }
 
+# name -> (restype, argtypes) of the qsaed_* entry points of include/qsae_jump_dense.h (csrc/jump_dense.hip): the dense (uncapped)
+# JumpReLU encoder -- the thresholds in the epilogue of the encoder's contraction -- a table of its own for the same reason.  Must
+# list every symbol declared in qsae_jump_dense.h.
+JUMP_DENSE_SIGNATURES = {
+    "qsaed_encode_jump_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "qsaed_encode_jump": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                               _vp]),
+}
+
 
 class QsaeError(RuntimeError):
     """A libqsae_hip call returned a non-zero status."""
@@ -295,7 +304,7 @@ def _open(path: Path) -> C.CDLL:
     lib = C.CDLL(str(path))
     for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(CURVE_SIGNATURES.items()) \
             + list(NESTED_SIGNATURES.items()) + list(BATCH_SIGNATURES.items()) + list(NESTED_BATCH_SIGNATURES.items()) + list(MULTIK_SIGNATURES.items()) \
-            + list(JUMP_SIGNATURES.items()):
+            + list(JUMP_SIGNATURES.items()) + list(JUMP_DENSE_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here means the library is stale
         fn.restype = res
         fn.argtypes = args

@@ -3365,3 +3365,56 @@ def jump_threshold_grad(offsets: torch.Tensor, entries: torch.Tensor, gv_band: O
     check(_lib.load().qsaej_threshold_grad(_p(offsets.contiguous()), _p(entries.contiguous()), _p(gv_band), _p(theta), _p(g_l0), B, K,
                                            H, eps, _p(dtheta), _stream()))
     return dtheta
+
+
+# ---- the dense (uncapped) JumpReLU encoder (include/qsae_jump_dense.h, csrc/jump_dense.hip) -----------------------------------
+JUMP_DENSE_MAX_K = 256
+JUMP_DENSE_REPORT_WORDS = 6       # selected, band entries, truncated rows, empty rows, band-truncated rows, firing units (uncapped)
+
+
+@_on_tensor_device
+def encode_jump(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], theta: torch.Tensor, K: int, bandwidth: float,
+                want_band: bool = True):
+    """JumpReLU over ALL pre-activations z = x W^T + bias (the encoder's fp32 fmaf chain; x fp32 [B, D], W fp32 [H, D], bias fp32
+    [H] or None) with the per-unit thresholds ``theta`` fp32 [H]: unit h fires in row r iff z > theta[h], is in the band iff
+    |z - theta[h]| < bandwidth / 2 -> (idx_sel, val_sel, counts, idx_band or None, counts_band or None, l0 fp32 [1], report
+    int64 [6]), in the order ``jump_select`` returns: the firing units of every row by value descending, then unit ascending,
+    the first ``K`` of them (-1 / +0 behind the first counts[r]), the same for the band, the mean number of firing units per
+    row from the uncapped counts, and {selected, band entries, truncated rows, empty rows, band-truncated rows, firing units}.
+    No top-K list, no certificate, no host read.  See qsaed_encode_jump."""
+    who = "encode_jump"
+    x, W = _f32c(x, f"{who}: x"), _f32c(W, f"{who}: W")
+    if x.dim() != 2 or W.dim() != 2 or x.shape[1] != W.shape[1] or W.shape[0] < 1 or W.device != x.device:
+        raise ValueError(f"{who}: x is {tuple(x.shape)} on {x.device}, W {tuple(W.shape)} on {W.device}; expected [B, D] and [H, D] "
+                         f"on one device")
+    B, D = x.shape
+    H = W.shape[0]
+    b = _f32c(bias, f"{who}: bias") if bias is not None else None
+    if b is not None and (tuple(b.shape) != (H,) or b.device != x.device):
+        raise ValueError(f"{who}: bias is {tuple(b.shape)} on {b.device}, expected [{H}] on {x.device}")
+    theta = _jump_theta(who, theta, x.device)
+    if theta.shape[0] != H:
+        raise ValueError(f"{who}: theta is {tuple(theta.shape)}, expected [{H}]")
+    eps = _jump_eps(who, bandwidth)
+    K = int(K)
+    if not 1 <= K <= min(JUMP_DENSE_MAX_K, H):
+        raise ValueError(f"{who}: K = {K} is outside 1 .. {min(JUMP_DENSE_MAX_K, H)} (the width of the kernel's lists and H = {H})")
+    if D < 4 or D % 4 != 0:
+        raise ValueError(f"{who}: D = {D} must be a positive multiple of 4")
+    if B * K >= 2 ** 31:
+        raise ValueError(f"{who}: B * K = {B * K} is not below 2^31")
+    dev = x.device
+    idx_sel = torch.empty((B, K), dtype=torch.int32, device=dev)
+    val_sel = torch.empty((B, K), dtype=torch.float32, device=dev)
+    counts = torch.empty((B,), dtype=torch.int32, device=dev)
+    idx_band = torch.empty((B, K), dtype=torch.int32, device=dev) if want_band else None
+    counts_band = torch.empty((B,), dtype=torch.int32, device=dev) if want_band else None
+    l0 = torch.zeros((1,), dtype=torch.float32, device=dev)
+    report = torch.zeros((JUMP_DENSE_REPORT_WORDS,), dtype=torch.int64, device=dev)
+    if B == 0:
+        return idx_sel, val_sel, counts, idx_band, counts_band, l0, report
+    lib = _lib.load()
+    ws = _train_ws(lib.qsaed_encode_jump_workspace_bytes(B, D, H, K), dev)
+    check(lib.qsaed_encode_jump(_p(x), D, _p(W), D, _p(b), _p(theta), B, D, H, K, eps, jump_half_eps(eps), _p(idx_sel), _p(val_sel),
+                                _p(counts), _p(idx_band), _p(counts_band), _p(l0), _p(report), _p(ws), ws.numel(), _stream()))
+    return idx_sel, val_sel, counts, idx_band, counts_band, l0, report

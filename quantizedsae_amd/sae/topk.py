@@ -430,6 +430,37 @@ class TopKCore:
         out = ((latent if dense_latent else None), recon)
         return (out if extra is None else out + (extra,)) + (l0,)
 
+    # -- dense JumpReLU: the thresholds in the encoder's epilogue, no top-K list in between ----------------------------------
+    def forward_jumprelu_dense(self, x, jr):
+        """The tuple of ``forward_jumprelu`` from the dense encoder (``ops.encode_jump``, csrc/jump_dense.hip): every unit of a
+        row whose pre-activation exceeds its threshold, found among all ``hidden_dim`` pre-activations -- no top-``cap`` list,
+        no certificate.  ``idx_sel`` holds the firing units by value descending, then unit ascending, the first K = ``jr.cap``
+        of them when more fire, and -1 (``val_sel``: +0) behind the first ``counts[r]`` places.  ``jr.report`` holds the dense
+        encoder's six words (``jr.report_names``): a truncated row is one with more than K firing units."""
+        with torch.no_grad():
+            x, who = self._jumprelu_input(x, jr, "forward_jumprelu_dense")
+            lin = self.encoder.linear
+            idx_sel, val_sel, counts, _, _, _, report = ops.encode_jump(as_f32c(x), as_f32c(lin.weight.detach()), lin.bias,
+                                                                        jr.thresholds(), jr.cap, jr.bandwidth, want_band=False)
+            jr.record(counts, report, dense=True)
+            decoder, dec_bias = self._nested_decoder()
+            return idx_sel, val_sel, counts, self._decode_ragged(idx_sel, val_sel, counts, decoder, dec_bias)
+
+    def forward_train_jumprelu_dense(self, x, jr, *, dense_latent: bool = True):
+        """``forward_train_jumprelu`` with the selection of ``forward_jumprelu_dense``: the same tuple, the same backward over
+        the ragged rows.  ``l0`` counts every firing unit, also those of a truncated row beyond its K-th."""
+        x, who = self._jumprelu_input(x, jr, "forward_train_jumprelu_dense")
+        lin = self.encoder.linear
+        D = lin.weight.shape[1]
+        if not ops.train_supported(D, jr.cap):
+            raise ValueError(f"{who}: the gradient kernels take input_dim a multiple of 4 up to 4096 (got {D})")
+        if x.shape[0] * jr.cap >= 2 ** 31:
+            raise ValueError(f"{who}: batch * cap = {x.shape[0] * jr.cap} is not below 2^31")
+        latent, recon, extra, l0 = _JumpReLUDenseTrainStep.apply(self, jr, bool(dense_latent), x, lin.weight, lin.bias,
+                                                                 self.decoder.weight, self.decoder.bias, jr.log_threshold.exp())
+        out = ((latent if dense_latent else None), recon)
+        return (out if extra is None else out + (extra,)) + (l0,)
+
 
 class _JumpReLUTrainStep(torch.autograd.Function):
     """forward_train_jumprelu and its gradient: _BatchTopKTrainStep with ``jump_select`` in place of ``batch_select`` -- the
@@ -437,14 +468,23 @@ class _JumpReLUTrainStep(torch.autograd.Function):
     differentiable input (include/qsae_jump.h)."""
 
     @staticmethod
+    def _select(model, jr, xf, W_enc, b_enc, th, want_band):
+        """-> (idx_sel, val_sel, counts, idx_band, counts_band, l0); records the report on ``jr``"""
+        idx, val = model._select_cap(xf, jr.cap, f"{type(model).__name__}.forward_train_jumprelu")
+        idx_sel, val_sel, counts, idx_band, counts_band, l0, report = ops.jump_select(idx, val, th, jr.bandwidth, want_band=want_band)
+        jr.record(counts, report)
+        return idx_sel, val_sel, counts, idx_band, counts_band, l0
+
+    @staticmethod
     def forward(ctx, model, jr, dense_latent, x, W_enc, b_enc, dec_param, b_dec, theta):
+        return _JumpReLUTrainStep._run(ctx, _JumpReLUTrainStep._select, model, jr, dense_latent, x, W_enc, b_enc, b_dec, theta)
+
+    @staticmethod
+    def _run(ctx, select, model, jr, dense_latent, x, W_enc, b_enc, b_dec, theta):
         table, step, extra = model._nested_train_decoder()
         xf = as_f32c(x.detach())
-        idx, val = model._select_cap(xf, jr.cap, f"{type(model).__name__}.forward_train_jumprelu")
         th = as_f32c(theta.detach())
-        idx_sel, val_sel, counts, idx_band, counts_band, l0, report = ops.jump_select(idx, val, th, jr.bandwidth,
-                                                                                      want_band=ctx.needs_input_grad[8])
-        jr.record(counts, report)
+        idx_sel, val_sel, counts, idx_band, counts_band, l0 = select(model, jr, xf, W_enc, b_enc, th, ctx.needs_input_grad[8])
         recon = ops.decode_ragged_table(idx_sel, val_sel, counts, table, step, b_dec.detach())
         latent = ops.densify(idx_sel, val_sel, table.shape[0]) if dense_latent else None
         if model.activity is not None:
@@ -473,6 +513,23 @@ class _JumpReLUTrainStep(torch.autograd.Function):
             dtheta = ops.jump_threshold_grad(offsets, entries, gv_band, th, None if g_l0 is None else g_l0.reshape(1), B, K,
                                              ctx.eps)
         return (None,) * 3 + grads + (dtheta,)
+
+
+class _JumpReLUDenseTrainStep(_JumpReLUTrainStep):
+    """forward_train_jumprelu_dense and its gradient: _JumpReLUTrainStep with ``encode_jump`` in place of ``_select_cap`` +
+    ``jump_select`` (include/qsae_jump_dense.h).  Everything behind the selection takes the lists unchanged: every reader goes by
+    ``counts``, or drops the -1 behind a row's prefix (``densify``, ``activity.add_compact``)."""
+
+    @staticmethod
+    def _select(model, jr, xf, W_enc, b_enc, th, want_band):
+        idx_sel, val_sel, counts, idx_band, counts_band, l0, report = ops.encode_jump(
+            xf, as_f32c(W_enc.detach()), None if b_enc is None else b_enc.detach(), th, jr.cap, jr.bandwidth, want_band=want_band)
+        jr.record(counts, report, dense=True)
+        return idx_sel, val_sel, counts, idx_band, counts_band, l0
+
+    @staticmethod
+    def forward(ctx, model, jr, dense_latent, x, W_enc, b_enc, dec_param, b_dec, theta):
+        return _JumpReLUTrainStep._run(ctx, _JumpReLUDenseTrainStep._select, model, jr, dense_latent, x, W_enc, b_enc, b_dec, theta)
 
 
 class _NestedBatchTopKTrainStep(torch.autograd.Function):

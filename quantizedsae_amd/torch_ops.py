@@ -1181,6 +1181,24 @@ def _(offsets, entries, gv_band, theta, g_l0, B, K, eps):
     return _f32((theta.shape[0],), theta)
 
 
+# ---- the dense (uncapped) JumpReLU encoder (include/qsae_jump_dense.h) ------------------------------------------------------
+@_op("encode_jump")
+def _encode_jump(x: Tensor, W: Tensor, bias: Optional[Tensor], theta: Tensor, K: int, bandwidth: float,
+                 want_band: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """-> (idx_sel, val_sel, counts, idx_band ([0, K] when not wanted), counts_band ([0]), l0 fp32 [1], report int64 [6])"""
+    idx_sel, val_sel, counts, idx_band, counts_band, l0, report = _ops.encode_jump(x, W, bias, theta, K, bandwidth, want_band)
+    if not want_band:
+        idx_band, counts_band = _i32((0, K), x), _i32((0,), x)
+    return idx_sel, val_sel, counts, idx_band, counts_band, l0, report
+
+
+@_encode_jump.register_fake
+def _(x, W, bias, theta, K, bandwidth, want_band):
+    B = x.shape[0]
+    return (_i32((B, K), x), _f32((B, K), x), _i32((B,), x), _i32((B if want_band else 0, K), x),
+            _i32((B if want_band else 0,), x), _f32((1,), x), torch.empty((6,), dtype=torch.int64, device=x.device))
+
+
 # ---- nested levels over the ragged rows of BatchTopK (include/qsae_nested_batch.h) ------------------------------------------
 @_op("decode_nested_ragged_binary")
 def _decode_nested_ragged_binary(idx: Tensor, val: Tensor, counts: Tensor, packed: Tensor, D: int, n_bits: int, step: float,
@@ -1964,3 +1982,13 @@ def jump_select(idx, val, theta, eps, want_band=True):
 def jump_threshold_grad(offsets, entries, gv_band, theta, g_l0, B, K, eps):
     """-> dtheta fp32 [H]"""
     return Q.jump_threshold_grad(offsets, entries, gv_band, theta, g_l0, int(B), int(K), float(eps))
+
+
+JUMP_DENSE_MAX_K = _ops.JUMP_DENSE_MAX_K
+
+
+def encode_jump(x, W, bias, theta, K, bandwidth, want_band=True):
+    """-> (idx_sel, val_sel, counts, idx_band or None, counts_band or None, l0 fp32 [1], report int64 [6])"""
+    idx_sel, val_sel, counts, idx_band, counts_band, l0, report = Q.encode_jump(x, W, bias, theta, int(K), float(bandwidth),
+                                                                                bool(want_band))
+    return idx_sel, val_sel, counts, (idx_band if want_band else None), (counts_band if want_band else None), l0, report

@@ -7,6 +7,8 @@ gradient passes straight through with a rectangle kernel of width ``bandwidth``,
     jr.calibrate(batch, k)                                    thresholds from what BatchTopK would select at k
     outputs = model.forward_train_jumprelu(batch, jr)         the tuple of forward_train with l0 appended
     idx, val, counts, recon = model.forward_jumprelu(x, jr)   evaluation
+    ... = model.forward_train_jumprelu_dense(batch, jr)       the same two from the dense encoder: the thresholds applied to
+    ... = model.forward_jumprelu_dense(x, jr)                 all pre-activations, no list and no certificate (section 4.37)
 
 The selection runs over every row's top-``cap`` list (csrc/jumprelu.hip): the entries above their unit's threshold are moved to
 the front of the row in list order, so every ragged row operation of BatchTopK takes the result unchanged.  It is JumpReLU
@@ -60,9 +62,16 @@ class JumpReLU(torch.nn.Module):
         #: smallest threshold) of the last selection, on the device
         self.counts: Optional[torch.Tensor] = None
         self.report: Optional[torch.Tensor] = None
+        #: the names of the report's words: REPORT_NAMES after a capped selection, REPORT_NAMES_DENSE after a dense one
+        self.report_names = self.REPORT_NAMES
 
-    def record(self, counts: torch.Tensor, report: torch.Tensor) -> None:
+    #: what the six words of ``report`` count, on the capped path (csrc/jumprelu.hip) and on the dense one (csrc/jump_dense.hip)
+    REPORT_NAMES = ("selected", "band_entries", "saturated_rows", "empty_rows", "uncertified_rows", "theta_min")
+    REPORT_NAMES_DENSE = ("selected", "band_entries", "truncated_rows", "empty_rows", "band_truncated_rows", "firing")
+
+    def record(self, counts: torch.Tensor, report: torch.Tensor, dense: bool = False) -> None:
         self.counts, self.report = counts, report
+        self.report_names = self.REPORT_NAMES_DENSE if dense else self.REPORT_NAMES
 
     def thresholds(self) -> torch.Tensor:
         """theta = exp(log_threshold), fp32 [H] on the device, without a ``grad_fn``"""
@@ -74,6 +83,10 @@ class JumpReLU(torch.nn.Module):
             raise ValueError("JumpReLU: no selection has run yet")
         rep = self.report.tolist()
         rows = int(self.counts.shape[0])
+        if self.report_names is self.REPORT_NAMES_DENSE:       # the dense encoder: l0 from the uncapped count of firing units
+            out = dict(zip(self.report_names, rep))
+            out["l0"] = rep[5] / rows if rows else 0.0
+            return out
         return {"selected": rep[0], "band_entries": rep[1], "saturated_rows": rep[2], "empty_rows": rep[3],
                 "uncertified_rows": rep[4], "theta_min": struct.unpack("<f", struct.pack("<I", rep[5] & 0xFFFFFFFF))[0],
                 "l0": rep[0] / rows if rows else 0.0}

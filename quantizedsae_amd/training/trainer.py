@@ -77,7 +77,11 @@ backward, ``trainer_loss`` the per-type loss, ``optim.Adam`` the step.  What dif
   threshold, on the first batch, to the smallest value BatchTopK would select there at the model's k.  Logging steps gain
   ``jumprelu/l0``, ``jumprelu/band_entries``, ``jumprelu/uncertified_rows``, ``jumprelu/saturated_rows`` and
   ``jumprelu/theta_min``; nothing is read back between them.  ``aux_k``, ``resample_every`` and ``activity_window`` work as
-  with ``batch_topk``.  Together with ``batch_topk``, ``nested_bounds``, ``batch_topk_nested_bounds`` or ``multi_topk`` it
+  with ``batch_topk``.  ``jumprelu_dense=True`` (default ``False``; it needs ``jumprelu=True``) routes the step through
+  ``model.forward_train_jumprelu_dense`` (csrc/jump_dense.hip): the thresholds are applied to all pre-activations, no list
+  and no certificate stand in between, ``jumprelu_cap`` is the widest row the step keeps; logging steps then report
+  ``jumprelu/truncated_rows`` (rows with more firing units than the cap) in place of ``jumprelu/uncertified_rows`` and
+  ``jumprelu/saturated_rows``, and no ``jumprelu/theta_min``.  Together with ``batch_topk``, ``nested_bounds``, ``batch_topk_nested_bounds`` or ``multi_topk`` it
   raises: the combinations are not built.
 * ``model=`` hands in the model instead of building the reference's.  The reference builds
   ``BinarySAE(input_dim, hidden_dim, n_bits)``, where ``n_bits`` lands in ``gamma`` and the decoder keeps its default of 8
@@ -147,7 +151,8 @@ class Trainer:
                  aux_refresh: Optional[int] = None, nested_bounds=None, batch_topk: bool = False,
                  batch_topk_cap: Optional[int] = None, batch_topk_nested_bounds=None, multi_topk=None,
                  multi_topk_weights=None, jumprelu: bool = False, jumprelu_l0_coef: Optional[float] = None,
-                 jumprelu_cap: Optional[int] = None, jumprelu_bandwidth: float = 1e-3, jumprelu_init=None):
+                 jumprelu_cap: Optional[int] = None, jumprelu_bandwidth: float = 1e-3, jumprelu_init=None,
+                 jumprelu_dense: bool = False):
         if sae_type not in SAE_TYPES:
             raise ValueError(f"unknown sae_type {sae_type!r}; expected one of {', '.join(SAE_TYPES)}")
         if sae_type == "t_sae" and not rigL:
@@ -223,6 +228,8 @@ class Trainer:
                                 ("jumprelu_init", jumprelu_init)):
                 if given is not None:
                     raise ValueError(f"{name} needs jumprelu=True")
+            if jumprelu_dense:
+                raise ValueError("jumprelu_dense needs jumprelu=True")
         self.config = config
         self.sae_type = sae_type
         self.device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
@@ -312,6 +319,7 @@ class Trainer:
         self.jumprelu = None
         self.jumprelu_l0_coef = float(jumprelu_l0_coef) if jumprelu else None
         self._jumprelu_calibrate = False                       # calibrate on the next batch trained on
+        self.jumprelu_dense = bool(jumprelu_dense)
         if jumprelu:
             calibrate = isinstance(jumprelu_init, str)
             self.jumprelu = JumpReLU(self.model, cap=jumprelu_cap, bandwidth=jumprelu_bandwidth,
@@ -333,7 +341,8 @@ class Trainer:
         if self.batch_topk is not None:
             return self.model.forward_train_batch_topk(batch, self.batch_topk, dense_latent=want_latent)
         if self.jumprelu is not None:
-            return self.model.forward_train_jumprelu(batch, self.jumprelu, dense_latent=want_latent)
+            step = self.model.forward_train_jumprelu_dense if self.jumprelu_dense else self.model.forward_train_jumprelu
+            return step(batch, self.jumprelu, dense_latent=want_latent)
         if self.sae_type in ("b_sae", "baseline_sae"):
             return self.model.forward_train(batch, dense_latent=want_latent)
         return self.model.forward_train(batch)
@@ -459,6 +468,9 @@ class Trainer:
         """What a logging step adds with ``jumprelu``: the last selection's report (one host copy of six words; no other step
         reads it)"""
         j = self.jumprelu.summary()
+        if self.jumprelu_dense:
+            return {"jumprelu/l0": j["l0"], "jumprelu/band_entries": j["band_entries"],
+                    "jumprelu/truncated_rows": j["truncated_rows"], "jumprelu/empty_rows": j["empty_rows"]}
         return {"jumprelu/l0": j["l0"], "jumprelu/band_entries": j["band_entries"],
                 "jumprelu/uncertified_rows": j["uncertified_rows"], "jumprelu/saturated_rows": j["saturated_rows"],
                 "jumprelu/theta_min": j["theta_min"]}
