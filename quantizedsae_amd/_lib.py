@@ -283,6 +283,15 @@ JUMP_DENSE_SIGNATURES = {
                                _vp]),
 }
 
+# name -> (restype, argtypes) of the qsaebd_* entry points of include/qsae_batch_dense.h (csrc/batch_dense.hip): the dense
+# BatchTopK encoder -- a scalar floor in the epilogue of the encoder's contraction, the batch-wide selection over the candidates
+# and its certificate -- a table of its own for the same reason.  Must list every symbol declared in qsae_batch_dense.h.
+BATCH_DENSE_SIGNATURES = {
+    "qsaebd_encode_batch_topk_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "qsaebd_encode_batch_topk": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i, _i, _i, _i64, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _f, _vp, _sz, _vp]),
+}
+
 
 class QsaeError(RuntimeError):
     """A libqsae_hip call returned a non-zero status."""
@@ -304,7 +313,8 @@ def _open(path: Path) -> C.CDLL:
     lib = C.CDLL(str(path))
     for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(CURVE_SIGNATURES.items()) \
             + list(NESTED_SIGNATURES.items()) + list(BATCH_SIGNATURES.items()) + list(NESTED_BATCH_SIGNATURES.items()) + list(MULTIK_SIGNATURES.items()) \
-            + list(JUMP_SIGNATURES.items()) + list(JUMP_DENSE_SIGNATURES.items()):
+            + list(JUMP_SIGNATURES.items()) + list(JUMP_DENSE_SIGNATURES.items()) \
+            + list(BATCH_DENSE_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here means the library is stale
         fn.restype = res
         fn.argtypes = args

@@ -3418,3 +3418,68 @@ def encode_jump(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], 
     check(lib.qsaed_encode_jump(_p(x), D, _p(W), D, _p(b), _p(theta), B, D, H, K, eps, jump_half_eps(eps), _p(idx_sel), _p(val_sel),
                                 _p(counts), _p(idx_band), _p(counts_band), _p(l0), _p(report), _p(ws), ws.numel(), _stream()))
     return idx_sel, val_sel, counts, idx_band, counts_band, l0, report
+
+
+# ---- the dense BatchTopK encoder (include/qsae_batch_dense.h, csrc/batch_dense.hip) ------------------------------------------
+BATCH_DENSE_MAX_K = 256
+BATCH_DENSE_REPORT_WORDS = 8      # selected, saturated rows, empty rows, bits of the smallest selected value, candidates of attempt
+#                                   one, second attempt ran, rows with more than K candidates, bits of the floor used
+
+
+@_on_tensor_device
+def encode_batch_topk(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], n_select: int, K: int, floor,
+                      floor_ratio: float = 1.0, state=None):
+    """BatchTopK capped at ``K`` per row straight from the encoder: the ``n_select`` largest entries of the whole batch of top-K
+    lists of z = x W^T + bias (the encoder's fp32 fmaf chain; x fp32 [B, D], W fp32 [H, D], bias fp32 [H] or None), ties to the
+    lowest row, then list position -> (idx_sel int32 [B, K], val_sel fp32 [B, K], counts int32 [B], report int64 [8]): what
+    ``batch_select`` gives on the lists of ``encode_topk`` at width K, with -1 / +0 behind the first counts[r] entries of a row.
+    ``floor``: only pre-activations above it are candidates; a one-element fp32 device tensor (read on the device, and
+    overwritten with fl32(floor_ratio * m), m the batch's smallest selected value, when something was selected and m > 0) or a
+    number.  The result does not depend on it: when fewer than n_select candidates lie above it a second attempt without a floor
+    runs on the device (report[5]).  ``state``: None or (theta fp32 [1], batches int64 [1], lr), the threshold state of
+    ``batch_select``, updated in place.  No host read.  See qsaebd_encode_batch_topk."""
+    who = "encode_batch_topk"
+    x, W = _f32c(x, f"{who}: x"), _f32c(W, f"{who}: W")
+    if x.dim() != 2 or W.dim() != 2 or x.shape[1] != W.shape[1] or W.shape[0] < 1 or W.device != x.device:
+        raise ValueError(f"{who}: x is {tuple(x.shape)} on {x.device}, W {tuple(W.shape)} on {W.device}; expected [B, D] and [H, D] "
+                         f"on one device")
+    B, D = x.shape
+    H = W.shape[0]
+    b = _f32c(bias, f"{who}: bias") if bias is not None else None
+    if b is not None and (tuple(b.shape) != (H,) or b.device != x.device):
+        raise ValueError(f"{who}: bias is {tuple(b.shape)} on {b.device}, expected [{H}] on {x.device}")
+    K = int(K)
+    if not 1 <= K <= min(BATCH_DENSE_MAX_K, H):
+        raise ValueError(f"{who}: K = {K} is outside 1 .. {min(BATCH_DENSE_MAX_K, H)} (the width of the kernel's lists and H = {H})")
+    if D < 4 or D % 4 != 0:
+        raise ValueError(f"{who}: D = {D} must be a positive multiple of 4")
+    if B * K >= 2 ** 31:
+        raise ValueError(f"{who}: B * K = {B * K} is not below 2^31")
+    n_select = int(n_select)
+    if not 0 <= n_select <= B * K:
+        raise ValueError(f"{who}: n_select = {n_select} is outside 0 .. B * K = {B * K}")
+    floor_ratio = float(floor_ratio)
+    if not 0.0 < floor_ratio <= 1.0:
+        raise ValueError(f"{who}: floor_ratio = {floor_ratio} is outside (0, 1]")
+    if isinstance(floor, torch.Tensor):
+        _dev(floor, f"{who}: floor", torch.float32)
+        if floor.numel() != 1 or floor.device != x.device or not floor.is_contiguous():
+            raise ValueError(f"{who}: floor is one element on {x.device}")
+        f_dev, f_host = floor, 0.0
+    else:
+        f_dev, f_host = None, float(floor)
+    theta, batches, lr = state if state is not None else (None, None, 0.0)
+    _batch_state(who, theta, batches, x.device)
+    dev = x.device
+    idx_sel = torch.empty((B, K), dtype=torch.int32, device=dev)
+    val_sel = torch.empty((B, K), dtype=torch.float32, device=dev)
+    counts = torch.empty((B,), dtype=torch.int32, device=dev)
+    report = torch.zeros((BATCH_DENSE_REPORT_WORDS,), dtype=torch.int64, device=dev)
+    if B == 0:
+        return idx_sel, val_sel, counts, report
+    lib = _lib.load()
+    ws = _train_ws(lib.qsaebd_encode_batch_topk_workspace_bytes(B, D, H, K), dev)
+    check(lib.qsaebd_encode_batch_topk(_p(x), D, _p(W), D, _p(b), B, D, H, K, n_select, _p(f_dev), f_host, floor_ratio, _p(idx_sel),
+                                       _p(val_sel), _p(counts), _p(report), _p(theta), _p(batches), float(lr), _p(ws), ws.numel(),
+                                       _stream()))
+    return idx_sel, val_sel, counts, report

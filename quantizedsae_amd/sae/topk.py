@@ -384,6 +384,90 @@ class TopKCore:
         return out if extra is None else out + (extra,)
 
 
+    # -- dense BatchTopK: the batch-wide selection over the pre-activations above a floor, no top-K sweep in between -----------
+    def _batch_topk_dense_input(self, x, ctl, who: str):
+        x, who = self._batch_topk_input(x, who)
+        if not getattr(ctl, "dense", False):
+            raise ValueError(f"{who}: the controller was not made with dense=True (training.BatchTopK(model, dense=True))")
+        return x, who
+
+    def _select_batch_dense(self, xf, ctl, W_enc, b_enc, who: str, train: bool):
+        """-> (idx, val_sel, counts) of the batch-wide selection through ``ops.encode_batch_topk`` (csrc/batch_dense.hip): the
+        bits of ``_select_cap`` + ``ops.batch_select`` within every row's prefix, for any floor.  ``train``: moves the threshold
+        state and the floor word; a controller whose floor was never seeded runs the capped selection once and seeds the floor
+        from its report, on the device.  Without ``train`` neither is moved, and an unseeded controller selects capped."""
+        n_select = xf.shape[0] * ctl.k
+        state = ctl.state(xf.device) + (ctl.threshold_lr,) if train else None
+        if not ctl.floor_seeded:
+            idx, val = self._select_cap(xf, ctl.cap, who)
+            theta, batches, lr = state if train else (None, None, 0.01)
+            counts, val_sel, report = ops.batch_select(val, n_select, True, theta, batches, lr)
+            if train:
+                ctl.seed_floor(report)
+            ctl.record(counts, report)
+            return idx, val_sel, counts
+        floor = ctl.floor_state(xf.device)
+        idx, val_sel, counts, report = ops.encode_batch_topk(xf, as_f32c(W_enc.detach()), None if b_enc is None else b_enc.detach(),
+                                                             n_select, ctl.cap, floor if train else floor.clone(), ctl.floor_ratio,
+                                                             state)
+        ctl.record(counts, report)
+        return idx, val_sel, counts
+
+    def forward_batch_topk_dense(self, x, ctl):
+        """The tuple of ``forward_batch_topk`` from the dense encoder (``ops.encode_batch_topk``, csrc/batch_dense.hip): the same
+        counts, the same values and the same units within every row's prefix, bit for bit, whatever the floor of ``ctl`` (a
+        ``training.BatchTopK(model, dense=True)``); ``idx`` holds -1 behind the first ``counts[r]`` places.  Neither the
+        threshold state nor the floor is moved.  ``ctl.report_dense`` holds the dense encoder's eight words."""
+        with torch.no_grad():
+            x, who = self._batch_topk_dense_input(x, ctl, "forward_batch_topk_dense")
+            lin = self.encoder.linear
+            idx, val_sel, counts = self._select_batch_dense(as_f32c(x), ctl, lin.weight, lin.bias, who, False)
+            decoder, dec_bias = self._nested_decoder()
+            return idx, val_sel, counts, self._decode_ragged(idx, val_sel, counts, decoder, dec_bias)
+
+    def forward_train_batch_topk_dense(self, x, ctl, *, dense_latent: bool = True):
+        """``forward_train_batch_topk`` with the selection of ``forward_batch_topk_dense``: the same tuple, the same backward
+        over the ragged rows, the same bits.  Moves ``ctl``'s threshold state and its floor on the device."""
+        x, who = self._batch_topk_dense_input(x, ctl, "forward_train_batch_topk_dense")
+        lin = self.encoder.linear
+        D = lin.weight.shape[1]
+        if not ops.train_supported(D, ctl.cap):
+            raise ValueError(f"{who}: the gradient kernels take input_dim a multiple of 4 up to 4096 (got {D})")
+        if x.shape[0] * ctl.cap >= 2 ** 31:
+            raise ValueError(f"{who}: batch * cap = {x.shape[0] * ctl.cap} is not below 2^31")
+        latent, recon, extra = _BatchTopKDenseTrainStep.apply(self, ctl, bool(dense_latent), x, lin.weight, lin.bias,
+                                                              self.decoder.weight, self.decoder.bias)
+        out = ((latent if dense_latent else None), recon)
+        return out if extra is None else out + (extra,)
+
+    def forward_nested_batch_topk_dense(self, x, ctl, bounds):
+        """The tuple of ``forward_nested_batch_topk`` with the selection of ``forward_batch_topk_dense``."""
+        with torch.no_grad():
+            x, who = self._batch_topk_dense_input(x, ctl, "forward_nested_batch_topk_dense")
+            bounds = ops.nested_bounds(bounds, self.encoder.linear.weight.shape[0], who)
+            lin = self.encoder.linear
+            idx, val_sel, counts = self._select_batch_dense(as_f32c(x), ctl, lin.weight, lin.bias, who, False)
+            decoder, dec_bias = self._nested_decoder()
+            levels, ctl.level_counts = self._decode_nested_ragged(idx, val_sel, counts, decoder, dec_bias, bounds)
+            return idx, val_sel, counts, levels
+
+    def forward_train_nested_batch_topk_dense(self, x, ctl, bounds, *, dense_latent: bool = True):
+        """``forward_train_nested_batch_topk`` with the selection of ``forward_batch_topk_dense``: the same tuple, the same
+        backward, the same bits."""
+        x, who = self._batch_topk_dense_input(x, ctl, "forward_train_nested_batch_topk_dense")
+        lin = self.encoder.linear
+        H, D = lin.weight.shape
+        bounds = ops.nested_bounds(bounds, H, who)
+        if not ops.train_supported(D, ctl.cap):
+            raise ValueError(f"{who}: the gradient kernels take input_dim a multiple of 4 up to 4096 (got {D})")
+        if x.shape[0] * ctl.cap >= 2 ** 31:
+            raise ValueError(f"{who}: batch * cap = {x.shape[0] * ctl.cap} is not below 2^31")
+        latent, levels, extra = _NestedBatchTopKDenseTrainStep.apply(self, ctl, bool(dense_latent), tuple(bounds), x, lin.weight,
+                                                                     lin.bias, self.decoder.weight, self.decoder.bias)
+        out = ((latent if dense_latent else None), tuple(levels[l] for l in range(len(bounds))))
+        return out if extra is None else out + (extra,)
+
+
     # -- JumpReLU: one learned threshold per unit, a subset of every row's list --------------------------------------------
     def _jumprelu_input(self, x, jr, who: str):
         x, who = self._batch_topk_input(x, who)
@@ -598,6 +682,47 @@ class _BatchTopKTrainStep(torch.autograd.Function):
             return model._batch_unit_grad(offsets, entries, val_sel, gv, xf, g_recon, g_extra, needs[1] or needs[2], needs[3])
         return (None,) * 3 + sparse_backward(idx, table, ctx.step, g_recon, g_latent, model.encoder.linear.weight,
                                              model.decoder.bias, needs, ctx.x_dtype, unit_grad, counts=counts)
+
+
+class _BatchTopKDenseTrainStep(_BatchTopKTrainStep):
+    """forward_train_batch_topk_dense and its gradient: _BatchTopKTrainStep with ``encode_batch_topk`` in place of ``_select_cap``
+    + ``batch_select`` (include/qsae_batch_dense.h).  Everything behind the selection takes the lists unchanged: every reader goes
+    by ``counts``, or drops the -1 behind a row's prefix (``densify``, ``activity.add_compact``)."""
+
+    @staticmethod
+    def forward(ctx, model, ctl, dense_latent, x, W_enc, b_enc, dec_param, b_dec):
+        table, step, extra = model._nested_train_decoder()
+        xf = as_f32c(x.detach())
+        idx, val_sel, counts = model._select_batch_dense(xf, ctl, W_enc, b_enc,
+                                                         f"{type(model).__name__}.forward_train_batch_topk_dense", True)
+        recon = ops.decode_ragged_table(idx, val_sel, counts, table, step, b_dec.detach())
+        latent = ops.densify(idx, val_sel, table.shape[0]) if dense_latent else None
+        if model.activity is not None:
+            model.activity.add_compact(idx, val_sel)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(xf, idx, val_sel, counts, table)
+        ctx.model, ctx.step, ctx.x_dtype = model, step, x.dtype
+        return latent, recon, extra
+
+
+class _NestedBatchTopKDenseTrainStep(_NestedBatchTopKTrainStep):
+    """forward_train_nested_batch_topk_dense and its gradient: _NestedBatchTopKTrainStep with the selection of
+    _BatchTopKDenseTrainStep."""
+
+    @staticmethod
+    def forward(ctx, model, ctl, dense_latent, bounds, x, W_enc, b_enc, dec_param, b_dec):
+        table, step, extra = model._nested_train_decoder()
+        xf = as_f32c(x.detach())
+        idx, val_sel, counts = model._select_batch_dense(xf, ctl, W_enc, b_enc,
+                                                         f"{type(model).__name__}.forward_train_nested_batch_topk_dense", True)
+        levels, ctl.level_counts = ops.decode_nested_ragged_table(idx, val_sel, counts, table, step, b_dec.detach(), bounds)
+        latent = ops.densify(idx, val_sel, table.shape[0]) if dense_latent else None
+        if model.activity is not None:
+            model.activity.add_compact(idx, val_sel)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(xf, idx, val_sel, counts, table)
+        ctx.model, ctx.step, ctx.bounds, ctx.x_dtype = model, step, bounds, x.dtype
+        return latent, levels, extra
 
 
 class _MultiTopKTrainStep(torch.autograd.Function):

@@ -1199,6 +1199,23 @@ def _(x, W, bias, theta, K, bandwidth, want_band):
             _i32((B if want_band else 0,), x), _f32((1,), x), torch.empty((6,), dtype=torch.int64, device=x.device))
 
 
+# ---- the dense BatchTopK encoder (include/qsae_batch_dense.h) ----------------------------------------------------------------
+@_op("encode_batch_topk", mutates=("floor_dev", "theta", "batches"))
+def _encode_batch_topk(x: Tensor, W: Tensor, bias: Optional[Tensor], n_select: int, K: int, floor_dev: Optional[Tensor],
+                       floor_host: float, floor_ratio: float, theta: Optional[Tensor], batches: Optional[Tensor],
+                       lr: float) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """-> (idx_sel int32 [B, K], val_sel fp32 [B, K], counts int32 [B], report int64 [8]); the floor is floor_dev (read and
+    written on the device) or, without one, floor_host; theta / batches in place"""
+    return _ops.encode_batch_topk(x, W, bias, n_select, K, floor_dev if floor_dev is not None else floor_host, floor_ratio,
+                                  None if theta is None and batches is None else (theta, batches, lr))
+
+
+@_encode_batch_topk.register_fake
+def _(x, W, bias, n_select, K, floor_dev, floor_host, floor_ratio, theta, batches, lr):
+    B = x.shape[0]
+    return _i32((B, K), x), _f32((B, K), x), _i32((B,), x), torch.empty((8,), dtype=torch.int64, device=x.device)
+
+
 # ---- nested levels over the ragged rows of BatchTopK (include/qsae_nested_batch.h) ------------------------------------------
 @_op("decode_nested_ragged_binary")
 def _decode_nested_ragged_binary(idx: Tensor, val: Tensor, counts: Tensor, packed: Tensor, D: int, n_bits: int, step: float,
@@ -1992,3 +2009,15 @@ def encode_jump(x, W, bias, theta, K, bandwidth, want_band=True):
     idx_sel, val_sel, counts, idx_band, counts_band, l0, report = Q.encode_jump(x, W, bias, theta, int(K), float(bandwidth),
                                                                                 bool(want_band))
     return idx_sel, val_sel, counts, (idx_band if want_band else None), (counts_band if want_band else None), l0, report
+
+
+BATCH_DENSE_MAX_K = _ops.BATCH_DENSE_MAX_K
+
+
+def encode_batch_topk(x, W, bias, n_select, K, floor, floor_ratio=1.0, state=None):
+    """-> (idx_sel, val_sel, counts, report int64 [8]); floor: a one-element fp32 device tensor (read and written on the device)
+    or a number; state: None or (theta, batches, lr)"""
+    on_dev = isinstance(floor, Tensor)
+    theta, batches, lr = state if state is not None else (None, None, 0.0)
+    return Q.encode_batch_topk(x, W, bias, int(n_select), int(K), floor if on_dev else None, 0.0 if on_dev else float(floor),
+                               float(floor_ratio), theta, batches, float(lr))

@@ -18,6 +18,13 @@ The threshold state -- ``theta`` (fp32) and ``batches`` (int64) -- lives on the 
 kernel chain: with m the smallest selected value of a batch, ``theta <- m`` on the first update and
 ``theta <- theta + lr * (m - theta)`` afterwards, when m > 0.  Nothing is read back unless ``threshold()`` or ``summary()`` is
 called.  The models' state-dict keys stay the reference's; the controller has a ``state_dict()`` of its own.
+
+``BatchTopK(model, dense=True)`` selects through the dense encoder (csrc/batch_dense.hip): the
+``forward*_batch_topk_dense`` methods of the models collect the pre-activations above a *floor* in the encoder's contraction and
+select among those.  The floor -- one fp32 word on the device, ``floor_ratio`` times the last batch's smallest selected value,
+written by the kernel chain -- changes the time, never the result: a batch with too few candidates above it is selected again
+without a floor, on the device.  A controller whose floor was never seeded runs one capped step and seeds it from that step's
+report.  The default (``dense=False``) is the capped path and nothing above changes.
 """
 from __future__ import annotations
 
@@ -32,7 +39,16 @@ __all__ = ["BatchTopK"]
 
 
 class BatchTopK:
-    def __init__(self, model, k: Optional[int] = None, cap: Optional[int] = None, threshold_lr: float = 0.01) -> None:
+    #: the floor of a dense controller as a fraction of the last batch's smallest selected value, unless the caller says otherwise:
+    #: the largest of the ratios tried at which no batch of the measured run needed the second attempt (DESIGN.md section 4.38,
+    #: profiles/batch_dense.txt)
+    DEFAULT_FLOOR_RATIO = 0.97
+    #: what the eight words of the dense encoder's report count (``report_dense``); the first four are ``report``
+    REPORT_NAMES_DENSE = ("selected", "saturated_rows", "empty_rows", "min_selected_bits", "candidates", "second_attempt",
+                          "rows_over_cap", "floor_bits")
+
+    def __init__(self, model, k: Optional[int] = None, cap: Optional[int] = None, threshold_lr: float = 0.01, dense: bool = False,
+                 floor_ratio: Optional[float] = None) -> None:
         if not isinstance(model, TopKCore):
             raise TypeError(f"BatchTopK: expected one of the two top-k models (BinarySAE, BaselineSparseAutoencoder), got "
                             f"{type(model).__name__}: the sparsity of the other classes is not a k")
@@ -49,8 +65,22 @@ class BatchTopK:
         threshold_lr = float(threshold_lr)
         if not 0.0 <= threshold_lr <= 1.0:
             raise ValueError(f"BatchTopK: threshold_lr = {threshold_lr}; expected a rate in [0, 1]")
+        if floor_ratio is not None and not dense:
+            raise ValueError("BatchTopK: floor_ratio needs dense=True")
+        floor_ratio = self.DEFAULT_FLOOR_RATIO if floor_ratio is None else float(floor_ratio)
+        if not 0.0 < floor_ratio <= 1.0:
+            raise ValueError(f"BatchTopK: floor_ratio = {floor_ratio}; expected a ratio in (0, 1]")
         self.model, self.k, self.cap, self.threshold_lr = model, k, cap, threshold_lr
+        self.dense, self.floor_ratio = bool(dense), floor_ratio
         device = model.encoder.linear.weight.device
+        #: the floor of the dense selection, on the device; NaN until a step has seeded it (a NaN floor admits no candidate)
+        self.floor = torch.full((), float("nan"), dtype=torch.float32, device=device)
+        self.floor_seeded = False
+        #: the dense encoder's report int64 [8] of the last dense selection, the number of dense selections and how many of
+        #: them needed the second attempt (int64, counted on the device)
+        self.report_dense: Optional[torch.Tensor] = None
+        self.dense_selections = 0
+        self.second_attempts = torch.zeros((), dtype=torch.int64, device=device)
         #: the inference threshold and the number of batches that have moved it, on the device
         self.theta = torch.zeros((), dtype=torch.float32, device=device)
         self.batches = torch.zeros((), dtype=torch.int64, device=device)
@@ -69,7 +99,38 @@ class BatchTopK:
         return self.theta, self.batches
 
     def record(self, counts: torch.Tensor, report: torch.Tensor) -> None:
+        """``report``: the four words of ``batch_select``, or the eight of ``encode_batch_topk`` (whose first four they are)"""
+        if report.numel() == len(self.REPORT_NAMES_DENSE):
+            self.report_dense, report = report, report[:4]
+            self.dense_selections += 1
+            if self.second_attempts.device != report.device:
+                self.second_attempts = self.second_attempts.to(report.device)
+            self.second_attempts += self.report_dense[5]
         self.counts, self.report = counts, report
+
+    def floor_state(self, device) -> torch.Tensor:
+        """-> the floor word on ``device`` (moved there once, when the model has moved since)"""
+        if self.floor.device != device:
+            self.floor = self.floor.to(device)
+        return self.floor
+
+    def seed_floor(self, report: torch.Tensor) -> None:
+        """The floor from the report of a capped selection, on the device: fl32(floor_ratio * m) when something was selected
+        and the smallest selected value m is > 0 -- what the dense chain writes at its own end.  No host read."""
+        floor = self.floor_state(report.device)
+        m = report[3:4].to(torch.int32).view(torch.float32).reshape(())
+        ratio = torch.tensor(self.floor_ratio, dtype=torch.float32, device=report.device)
+        floor.copy_(torch.where((report[0] > 0) & (m > 0), ratio * m, floor))
+        self.floor_seeded = True
+
+    def dense_summary(self) -> dict:
+        """The last dense selection's extra report words as numbers (one host copy)."""
+        if self.report_dense is None:
+            raise ValueError("BatchTopK: no dense selection has run yet")
+        words = torch.cat([self.report_dense, self.second_attempts.reshape(1)]).tolist()
+        rows = int(self.counts.shape[0])
+        return {"candidates": int(words[4]), "candidates_per_row": int(words[4]) / max(rows, 1), "second_attempt": int(words[5]),
+                "rows_over_cap": int(words[6]), "second_attempts": int(words[8]), "dense_selections": self.dense_selections}
 
     def threshold(self) -> float:
         """The learned threshold (one host read)."""
@@ -83,8 +144,12 @@ class BatchTopK:
         return {"selected": int(both[0]), "saturated_rows": int(both[1]), "empty_rows": int(both[2]), "threshold": both[4]}
 
     def state_dict(self) -> dict:
-        return {"theta": self.theta.detach().cpu().clone(), "batches": self.batches.detach().cpu().clone(), "k": self.k,
-                "cap": self.cap, "threshold_lr": self.threshold_lr}
+        state = {"theta": self.theta.detach().cpu().clone(), "batches": self.batches.detach().cpu().clone(), "k": self.k,
+                 "cap": self.cap, "threshold_lr": self.threshold_lr}
+        if self.dense:
+            state["dense_floor"] = {"floor": self.floor.detach().cpu().clone(), "seeded": self.floor_seeded,
+                                    "floor_ratio": self.floor_ratio}
+        return state
 
     def load_state_dict(self, state: dict) -> None:
         if int(state["k"]) != self.k or int(state["cap"]) != self.cap:
@@ -94,3 +159,7 @@ class BatchTopK:
         self.theta = torch.as_tensor(state["theta"], dtype=torch.float32).reshape(()).to(device).clone()
         self.batches = torch.as_tensor(state["batches"], dtype=torch.int64).reshape(()).to(device).clone()
         self.threshold_lr = float(state["threshold_lr"])
+        saved = state.get("dense_floor")                      # absent in states saved by a capped controller: the floor is
+        if saved is not None and self.dense:                   # then seeded again by the first step
+            self.floor = torch.as_tensor(saved["floor"], dtype=torch.float32).reshape(()).to(device).clone()
+            self.floor_seeded = bool(saved["seeded"])

@@ -54,7 +54,13 @@ backward, ``trainer_loss`` the per-type loss, ``optim.Adam`` the step.  What dif
   threshold on the device.  Logging steps gain ``batch_topk/threshold``, ``batch_topk/saturated_rows`` and
   ``batch_topk/empty_rows``; nothing is read back between them.  ``aux_k``, ``resample_every`` and ``activity_window`` work
   as before.  Together with ``nested_bounds`` it raises: that keyword means the per-row top-k of ``forward_train_nested``, and
-  the combination is asked for by name, with ``batch_topk_nested_bounds``.
+  the combination is asked for by name, with ``batch_topk_nested_bounds``.  ``batch_topk_dense=True`` (default ``False``; it
+  needs ``batch_topk=True``) routes the step through ``model.forward_train_batch_topk_dense`` (csrc/batch_dense.hip), with
+  ``batch_topk_nested_bounds`` through ``model.forward_train_nested_batch_topk_dense``: the same selection, bit for bit, taken
+  from the pre-activations above a floor of ``batch_topk_floor_ratio`` (default ``BatchTopK.DEFAULT_FLOOR_RATIO``) times the
+  last batch's smallest selected value instead of from every row's top-``cap`` list; the first step runs capped and seeds the
+  floor.  Logging steps gain ``batch_topk/second_attempts`` (the batches so far whose floor was too high and that were
+  selected again without one, on the device) and ``batch_topk/candidates_per_row``.
 * ``batch_topk_nested_bounds="default" | [b_0, ..., b_{L-1}]`` (needs ``batch_topk=True``; default ``None`` changes nothing)
   trains the Matryoshka SAE as Bussmann et al. do, with BatchTopK: ``model.forward_train_nested_batch_topk`` gives one
   reconstruction per dictionary prefix from the batch-wide selection (csrc/nested_ragged.hip), the loss is ``nested_loss``,
@@ -152,7 +158,8 @@ class Trainer:
                  batch_topk_cap: Optional[int] = None, batch_topk_nested_bounds=None, multi_topk=None,
                  multi_topk_weights=None, jumprelu: bool = False, jumprelu_l0_coef: Optional[float] = None,
                  jumprelu_cap: Optional[int] = None, jumprelu_bandwidth: float = 1e-3, jumprelu_init=None,
-                 jumprelu_dense: bool = False):
+                 jumprelu_dense: bool = False, batch_topk_dense: bool = False,
+                 batch_topk_floor_ratio: Optional[float] = None):
         if sae_type not in SAE_TYPES:
             raise ValueError(f"unknown sae_type {sae_type!r}; expected one of {', '.join(SAE_TYPES)}")
         if sae_type == "t_sae" and not rigL:
@@ -198,6 +205,10 @@ class Trainer:
             raise ValueError("batch_topk_nested_bounds needs batch_topk=True (nested_bounds is the keyword of the per-row top-k)")
         if batch_topk_cap is not None and not batch_topk:
             raise ValueError("batch_topk_cap needs batch_topk=True")
+        if batch_topk_dense and not batch_topk:
+            raise ValueError("batch_topk_dense needs batch_topk=True")
+        if batch_topk_floor_ratio is not None and not batch_topk_dense:
+            raise ValueError("batch_topk_floor_ratio needs batch_topk_dense=True")
         if multi_topk is not None:
             if sae_type not in MULTI_TOPK_TYPES:
                 raise ValueError(f"multi_topk: the Multi-TopK objective is built for baseline_sae and b_sae, the two top-k models; "
@@ -283,7 +294,12 @@ class Trainer:
                     given = default_nested_bounds(H)
                 self.nested_bounds = ops.nested_bounds(given, H, f"Trainer: {name}")
         #: the BatchTopK controller (k = the model's top-k), or None
-        self.batch_topk = BatchTopK(self.model, cap=batch_topk_cap) if batch_topk else None
+        self.batch_topk = None
+        if batch_topk:
+            self.batch_topk = BatchTopK(self.model, cap=batch_topk_cap, dense=bool(batch_topk_dense),
+                                        floor_ratio=batch_topk_floor_ratio)
+        #: whether BatchTopK selects through the dense encoder (csrc/batch_dense.hip)
+        self.batch_topk_dense = bool(batch_topk_dense)
         #: the points of the Multi-TopK objective, their weights and the index of the point equal to the model's top-k, or None
         self.multi_topk = self.multi_topk_weights = self._multi_topk_own = None
         if multi_topk is not None:
@@ -332,14 +348,16 @@ class Trainer:
     # ---- one step ------------------------------------------------------------------------------------------------
     def _forward(self, batch, want_latent: bool):
         if self.nested_bounds is not None and self.batch_topk is not None:
-            return self.model.forward_train_nested_batch_topk(batch, self.batch_topk, self.nested_bounds,
-                                                              dense_latent=want_latent)
+            step = self.model.forward_train_nested_batch_topk_dense if self.batch_topk_dense else \
+                self.model.forward_train_nested_batch_topk
+            return step(batch, self.batch_topk, self.nested_bounds, dense_latent=want_latent)
         if self.nested_bounds is not None:
             return self.model.forward_train_nested(batch, self.nested_bounds, dense_latent=want_latent)
         if self.multi_topk is not None:
             return self.model.forward_train_multi_topk(batch, self.multi_topk, dense_latent=want_latent)
         if self.batch_topk is not None:
-            return self.model.forward_train_batch_topk(batch, self.batch_topk, dense_latent=want_latent)
+            step = self.model.forward_train_batch_topk_dense if self.batch_topk_dense else self.model.forward_train_batch_topk
+            return step(batch, self.batch_topk, dense_latent=want_latent)
         if self.jumprelu is not None:
             step = self.model.forward_train_jumprelu_dense if self.jumprelu_dense else self.model.forward_train_jumprelu
             return step(batch, self.jumprelu, dense_latent=want_latent)
@@ -459,6 +477,11 @@ class Trainer:
         b = self.batch_topk.summary()
         d = {"batch_topk/threshold": b["threshold"], "batch_topk/saturated_rows": b["saturated_rows"],
              "batch_topk/empty_rows": b["empty_rows"]}
+        if self.batch_topk_dense:
+            # (no dense report yet: only the capped step that seeds the floor has run, over every row's whole list)
+            e = self.batch_topk.dense_summary() if self.batch_topk.report_dense is not None else \
+                {"second_attempts": 0, "candidates_per_row": float(self.batch_topk.cap)}
+            d.update({"batch_topk/second_attempts": e["second_attempts"], "batch_topk/candidates_per_row": e["candidates_per_row"]})
         if self.nested_bounds is not None:                     # the mean selected units per row below every bound (one copy)
             l0 = self.batch_topk.level_counts.to(torch.float64).mean(dim=1).tolist()
             d.update({f"l0_level_{l}": v for l, v in enumerate(l0)})
