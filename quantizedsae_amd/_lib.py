@@ -292,6 +292,15 @@ BATCH_DENSE_SIGNATURES = {
                                       _f, _vp, _sz, _vp]),
 }
 
+# name -> (restype, argtypes) of the qsaer_* entry points of include/qsae_recycle.h (csrc/prefilter_topk.hip): the
+# forward-in-one-call prefilter entry points on a recycled dense latent -- their namesakes of SIGNATURES plus (stale_idx,
+# stale_k) -- a table of its own for the same reason.  Must list every symbol declared in qsae_recycle.h.
+RECYCLE_SIGNATURES = {
+    "qsaer_" + name[len("qsae_"):]: (SIGNATURES[name][0], SIGNATURES[name][1] + [_vp, _i])
+    for name in ("qsae_binary_forward_prefilter", "qsae_table_forward_prefilter", "qsae_prefilter_submit",
+                 "qsae_prefilter_submit_table")
+}
+
 
 class QsaeError(RuntimeError):
     """A libqsae_hip call returned a non-zero status."""
@@ -314,7 +323,7 @@ def _open(path: Path) -> C.CDLL:
     for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(CURVE_SIGNATURES.items()) \
             + list(NESTED_SIGNATURES.items()) + list(BATCH_SIGNATURES.items()) + list(NESTED_BATCH_SIGNATURES.items()) + list(MULTIK_SIGNATURES.items()) \
             + list(JUMP_SIGNATURES.items()) + list(JUMP_DENSE_SIGNATURES.items()) \
-            + list(BATCH_DENSE_SIGNATURES.items()):
+            + list(BATCH_DENSE_SIGNATURES.items()) + list(RECYCLE_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here means the library is stale
         fn.restype = res
         fn.argtypes = args

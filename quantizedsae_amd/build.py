@@ -55,7 +55,8 @@ def build_native(force: bool = False, verbose: bool = False, debug: bool = False
                                         PKG.parent / "include" / "qsae_batch.h", PKG.parent / "include" / "qsae_nested_batch.h",
                                         PKG.parent / "include" / "qsae_multik.h", PKG.parent / "include" / "qsae_jump.h",
                                         PKG.parent / "include" / "qsae_jump_dense.h",
-                                        PKG.parent / "include" / "qsae_batch_dense.h"]
+                                        PKG.parent / "include" / "qsae_batch_dense.h",
+                                        PKG.parent / "include" / "qsae_recycle.h"]
     objdir = OBJDIR / "debug" if debug else OBJDIR
     lib = DEBUG_LIB if debug else LIB
     flags = FLAGS + (["-DQSAE_DEBUG_BUILD=1"] if debug else [])

@@ -12,6 +12,7 @@ int topk_rows_dispatch(float* latent, int64_t ld, int B, int H, int k, int32_t* 
                        float* tau, uint2* cand, int* cnt, int cap, float* dense, int64_t dense_ld, hipStream_t s,
                        const float* margin = nullptr, int stride = 0);
 int scatter_rows(const int32_t* idx, const float* val, int B, int k, int H, float* dense, int64_t ld, hipStream_t s);
+int erase_rows(const int32_t* idx, int B, int k, int H, float* dense, int64_t ld, hipStream_t s);    // +0 at the listed positions
 int decode_binary_sparse_rows(const int* rows, int nrows, const int32_t* idx, const float* val, int k, int H,
                               const RowDecode& d, hipStream_t s);
 int densify_rows(const int32_t* idx, const float* val, int B, int k, int H, float* dense, int64_t ld, hipStream_t s);

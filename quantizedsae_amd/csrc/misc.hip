@@ -66,6 +66,18 @@ scatter_rows_kernel(const int32_t* __restrict__ idx, const float* __restrict__ v
     if (h >= 0 && h < H) dense[b * ld + h] = val[gid];
 }
 
+// dense[b][idx[b][j]] = +0 for every list entry inside [0, H): the scatter above with no values.  It turns a latent that
+// is +0 everywhere except (possibly) at the listed positions back into all zeros (qsae_recycle.h); an entry of -1 or at or
+// past H causes no access.
+__global__ void __launch_bounds__(256)
+erase_rows_kernel(const int32_t* __restrict__ idx, long long total, int k, int H, float* __restrict__ dense, int64_t ld) {
+    const long long gid = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (gid >= total) return;
+    const long long b = gid / k;
+    const uint32_t h = static_cast<uint32_t>(idx[gid]);
+    if (h < static_cast<uint32_t>(H)) dense[b * ld + h] = 0.0f;
+}
+
 // sum of (float)((r - x)^2) in double: per-thread fp32 square, double accumulation, one atomic per
 // wave (scripts/analysis/dynamic_analysis.py:86-100 accumulates a fp32 per-batch sum into a
 // Python float; double accumulation is at least as accurate).
@@ -207,6 +219,15 @@ int scatter_rows(const int32_t* idx, const float* val, int B, int k, int H, floa
     if (total == 0) return QSAE_OK;
     hipLaunchKernelGGL(scatter_rows_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, idx,
                        val, total, k, H, dense, ld);
+    QSAE_LAUNCH_CHECK();
+    return QSAE_OK;
+}
+
+int erase_rows(const int32_t* idx, int B, int k, int H, float* dense, int64_t ld, hipStream_t s) {
+    const long long total = static_cast<long long>(B) * k;
+    if (total == 0) return QSAE_OK;
+    hipLaunchKernelGGL(erase_rows_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, idx, total, k, H,
+                       dense, ld);
     QSAE_LAUNCH_CHECK();
     return QSAE_OK;
 }

@@ -8,6 +8,7 @@
 #include "sweep_xstat_f16.h"
 #include "refine_row.h"
 #include "refine_sliced.h"
+#include "../../include/qsae_recycle.h"
 
 namespace qsae {
 
@@ -318,6 +319,20 @@ static int launch_fill_co(ThreadDeviceCtx* ctx, float* dense, int64_t dense_ld, 
     return QSAE_OK;
 }
 
+// The erase of a recycled latent in the fill kernel's place: same fork and join, same head start for the sweep.  Its waves
+// (12 VGPRs, one store each) fit the registers the sweep leaves free, and the sweep leaves the memory system nearly idle.
+static int launch_erase_co(ThreadDeviceCtx* ctx, const int32_t* stale_idx, int stale_k, float* dense, int64_t dense_ld, int B, int H,
+                           hipStream_t s) {
+    QSAE_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
+    hipLaunchKernelGGL(co_delay_kernel, dim3(1), dim3(64), 0, ctx->side, 2000);     // 20 us
+    QSAE_LAUNCH_CHECK();
+    const int rc = erase_rows(stale_idx, B, stale_k, H, dense, dense_ld, ctx->side);
+    if (rc != QSAE_OK) return rc;
+    QSAE_HIP(hipEventRecord(ctx->ev_join, ctx->side));
+    QSAE_HIP(hipStreamWaitEvent(s, ctx->ev_join, 0));        // refine writes the survivors into the zeros
+    return QSAE_OK;
+}
+
 static bool prefilter_shape_ok(int B, int D, int H, int k) {
     return use_fused(B, D, H, k) && D % 64 == 0 && D <= kRefMaxD && (H - pilot_width(H)) > 0;
 }
@@ -338,6 +353,9 @@ struct PrefCall {
     char* ws; qsae_stream_t stream;
     float* dense; int64_t dense_ld;
     const RowDecode* dec;                 // BinarySAE: rows are decoded as they are ranked; nullptr = no reconstruction
+    // recycled latent (qsae_recycle.h): `dense` is +0 in all B x H positions except possibly at dense[r][stale_idx[r][j]];
+    // device [B][stale_k], nullptr = `dense` holds anything
+    const int32_t* stale_idx; int stale_k;
 };
 struct PrefPlan {
     FusedLayout L; PrefLayout PL;
@@ -345,6 +363,7 @@ struct PrefPlan {
     bool xstat, inkernel, fill_co, fill_in_sweep;
     int Hs, hoff, parts, cap_part;
     float* filled;                        // the dense latent if its zeros are written during the sweep launch, else nullptr
+    bool recycled;                        // `filled` needs no zeros written, only the stale list erased (submit; finish is the same either way)
 };
 static PrefPlan pref_plan(const PrefCall& c) {
     PrefPlan p;
@@ -369,6 +388,8 @@ static PrefPlan pref_plan(const PrefCall& c) {
                 co_fill_fits();
     p.fill_in_sweep = !p.fill_co && p.xstat && c.dense && g_fill_in_sweep && c.H % 256 == 0 && c.dense_ld % 4 == 0;
     p.filled = (p.fill_in_sweep || p.fill_co) ? c.dense : nullptr;
+    // only plans that write the zeros during the sweep launch recycle: everywhere else the list is ignored
+    p.recycled = c.stale_idx != nullptr && p.filled != nullptr;
     return p;
 }
 
@@ -391,7 +412,11 @@ static int prefilter_submit(const PrefCall& c) {
     float* inv = reinterpret_cast<float*>(ws + PL.inv);
     float* margin = reinterpret_cast<float*>(ws + PL.margin);
     int* cnt_parts = reinterpret_cast<int*>(ws + PL.cnt_parts);
-    const bool xstat = pl.xstat, inkernel = pl.inkernel, fill_co = pl.fill_co, fill_in_sweep = pl.fill_in_sweep;
+    // a recycled latent has its zeros: no fill kernel, the sweep build without fill code.  Where the fill kernel would have
+    // run beside the sweep, the erase does (measured in front of the x prep on `s`: 0.12 ms of scattered 4-byte stores, and the
+    // x prep behind it 0.07 ms instead of 0.04); elsewhere it goes first on `s`.
+    const bool xstat = pl.xstat, inkernel = pl.inkernel, fill_co = pl.fill_co && !pl.recycled,
+               fill_in_sweep = pl.fill_in_sweep && !pl.recycled, erase_co = pl.recycled && pl.fill_co && (g_x_phase & 1);
     float* fused_fill = xstat ? nullptr : c.dense;
     const int Hs = pl.Hs, hoff = pl.hoff, parts = pl.parts, cap_part = pl.cap_part;
     // activation-stationary sweep with its own fill: all H columns, spread over the iterations of every part (its
@@ -399,8 +424,15 @@ static int prefilter_submit(const PrefCall& c) {
     const int xs_iters = xstat ? (Hs / kXsHT) / parts + (inkernel ? P / kXsHT : 0) : 0;
     const int fill_cw = xs_iters > 0 ? (32 * (H / 256) / parts + xs_iters - 1) / xs_iters : 0;   // 1-KiB pieces per wave and iteration
     ThreadDeviceCtx* ctx = nullptr;
-    if (fill_co) {
+    if (fill_co || erase_co) {
         const int rc0 = thread_device_ctx(&ctx);
+        if (rc0 != QSAE_OK) return rc0;
+    }
+    // 0. recycled latent: +0 at the at most B * stale_k positions that can hold anything else, ahead of the refinement and
+    //    the fallback, which write the survivors straight into `dense` -- by stream order here, by the join of the side
+    //    stream in step 4.
+    if (pl.recycled && !erase_co) {
+        const int rc0 = erase_rows(c.stale_idx, B, c.stale_k, H, c.dense, c.dense_ld, s);
         if (rc0 != QSAE_OK) return rc0;
     }
     // 1. fp16 copy of the batch + per-row scale and error margin (the stationary sweep with the in-kernel pilot can do
@@ -447,10 +479,11 @@ static int prefilter_submit(const PrefCall& c) {
             xa.dense = fill_in_sweep ? c.dense : nullptr;  xa.dense_ld = c.dense_ld;  xa.pilot_stages = inkernel ? P / kXsHT : 0;
             xa.pilot_rank = g_inkernel_rank > 0 ? g_inkernel_rank : inkernel_rank(k);  xa.tau_out = tau;  xa.meta = c.meta;
             xa.x32 = fuse_prep ? c.x : nullptr;  xa.inv_out = inv;  xa.margin_out = margin;  xa.parts = parts;  xa.cnt_parts = cnt_parts;
-            if (fill_co) QSAE_HIP(hipEventRecord(ctx->ev_fork, s));     // everything before the sweep (x prep, earlier users of `dense`)
+            if (fill_co || erase_co) QSAE_HIP(hipEventRecord(ctx->ev_fork, s));     // everything before the sweep (x prep, earlier users of `dense`)
             // (the build without fill code whenever this launch has no zeros to write itself)
             rc = launch_xstat(D, xa, s, (g_xstat_ablate == 0 && D == 512 && !fill_in_sweep) ? 9 : g_xstat_ablate);
             if (fill_co && rc == QSAE_OK) rc = launch_fill_co(ctx, c.dense, c.dense_ld, B, H, s);
+            if (erase_co && rc == QSAE_OK) rc = launch_erase_co(ctx, c.stale_idx, c.stale_k, c.dense, c.dense_ld, B, H, s);
         } else if (g_pref_tile != 1) {
             // 256 hidden x 256 activation rows per workgroup: 128 FLOP per staged byte (256 x 128: 85)
             using EpiW = EpiFilter<256, 256, 4, 2, true>;
@@ -721,7 +754,8 @@ enum class PrefMode { blocking, submit, finish };
 static int prefilter_entry(const char* who, PrefMode mode, bool need_dict, const float* x, const float* W, const float* bias,
                            const void* Wq, const float* meta, int B, int D, int H, int k, const uint8_t* packed, int n_bits, float step,
                            const float* table, const float* dec_bias, int32_t* idx, float* val, float* dense, int64_t dense_ld,
-                           float* recon, void* workspace, size_t workspace_bytes, int n, int* out, qsae_stream_t stream) {
+                           float* recon, void* workspace, size_t workspace_bytes, int n, int* out, qsae_stream_t stream,
+                           const int32_t* stale_idx = nullptr, int stale_k = 0) {
     if (!(B >= 0 && D > 0 && H > 0)) return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: B >= 0, D > 0, H > 0 required", who);
     if (mode == PrefMode::submit && !out)
         return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: flagged_host must point to a host int", who);
@@ -733,6 +767,13 @@ static int prefilter_entry(const char* who, PrefMode mode, bool need_dict, const
     int rc = prefilter_call(who, x, W, bias, Wq, meta, B, D, H, k, packed, n_bits, step, dec_bias, idx, val, dense, dense_ld, recon,
                             workspace, workspace_bytes, stream, call, dec, table);
     if (rc != QSAE_OK) return rc;
+    if (stale_idx) {
+        if (!(stale_k >= 1 && stale_k <= QSAER_MAX_STALE_K && (reinterpret_cast<uintptr_t>(stale_idx) & 3u) == 0))
+            return fail(QSAE_ERR_INVALID_ARG, "%s: invalid argument: 1 <= stale_k <= %d and a 4-byte aligned stale_idx required", who,
+                        QSAER_MAX_STALE_K);
+        call.stale_idx = stale_idx;
+        call.stale_k = stale_k;
+    }
     if (mode == PrefMode::blocking) return run_prefilter(call, n, out);
     if (mode == PrefMode::finish) return prefilter_finish(call, /*first=*/0, n);
     rc = prefilter_submit(call);
@@ -800,4 +841,44 @@ extern "C" int qsae_prefilter_finish_table(const float* x, const float* W, const
                                            void* workspace, size_t workspace_bytes, int flagged, qsae_stream_t stream) {
     return prefilter_entry(__func__, PrefMode::finish, true, x, W, bias, Wq, meta, B, D, H, k, nullptr, 0, scale, table, dec_bias, idx,
                            val, dense, dense_ld, recon, workspace, workspace_bytes, flagged, nullptr, stream);
+}
+
+// ---- the same four calls on a recycled dense latent (include/qsae_recycle.h) ------------------------------------------
+extern "C" int qsaer_binary_forward_prefilter(const float* x, const float* W, const float* bias, const void* Wq,
+                                              const float* meta, int B, int D, int H, int k, const uint8_t* packed,
+                                              int n_bits, float step, const float* dec_bias, int32_t* idx, float* val,
+                                              float* dense, int64_t dense_ld, float* recon, void* workspace,
+                                              size_t workspace_bytes, int spec_rows, int* flagged_rows,
+                                              qsae_stream_t stream, const int32_t* stale_idx, int stale_k) {
+    return prefilter_entry(__func__, PrefMode::blocking, true, x, W, bias, Wq, meta, B, D, H, k, packed, n_bits, step, nullptr, dec_bias,
+                           idx, val, dense, dense_ld, recon, workspace, workspace_bytes, spec_rows, flagged_rows, stream, stale_idx,
+                           stale_k);
+}
+
+extern "C" int qsaer_table_forward_prefilter(const float* x, const float* W, const float* bias, const void* Wq,
+                                             const float* meta, int B, int D, int H, int k, const float* table, float scale,
+                                             const float* dec_bias, int32_t* idx, float* val, float* dense, int64_t dense_ld,
+                                             float* recon, void* workspace, size_t workspace_bytes, int spec_rows,
+                                             int* flagged_rows, qsae_stream_t stream, const int32_t* stale_idx, int stale_k) {
+    return prefilter_entry(__func__, PrefMode::blocking, true, x, W, bias, Wq, meta, B, D, H, k, nullptr, 0, scale, table, dec_bias, idx,
+                           val, dense, dense_ld, recon, workspace, workspace_bytes, spec_rows, flagged_rows, stream, stale_idx,
+                           stale_k);
+}
+
+extern "C" int qsaer_prefilter_submit(const float* x, const float* W, const float* bias, const void* Wq, const float* meta,
+                                      int B, int D, int H, int k, const uint8_t* packed, int n_bits, float step,
+                                      const float* dec_bias, int32_t* idx, float* val, float* dense, int64_t dense_ld,
+                                      float* recon, void* workspace, size_t workspace_bytes, int* flagged_host,
+                                      qsae_stream_t stream, const int32_t* stale_idx, int stale_k) {
+    return prefilter_entry(__func__, PrefMode::submit, false, x, W, bias, Wq, meta, B, D, H, k, packed, n_bits, step, nullptr, dec_bias,
+                           idx, val, dense, dense_ld, recon, workspace, workspace_bytes, 0, flagged_host, stream, stale_idx, stale_k);
+}
+
+extern "C" int qsaer_prefilter_submit_table(const float* x, const float* W, const float* bias, const void* Wq, const float* meta,
+                                            int B, int D, int H, int k, const float* table, float scale, const float* dec_bias,
+                                            int32_t* idx, float* val, float* dense, int64_t dense_ld, float* recon,
+                                            void* workspace, size_t workspace_bytes, int* flagged_host, qsae_stream_t stream,
+                                            const int32_t* stale_idx, int stale_k) {
+    return prefilter_entry(__func__, PrefMode::submit, true, x, W, bias, Wq, meta, B, D, H, k, nullptr, 0, scale, table, dec_bias, idx,
+                           val, dense, dense_ld, recon, workspace, workspace_bytes, 0, flagged_host, stream, stale_idx, stale_k);
 }

@@ -7,6 +7,8 @@ from __future__ import annotations
 import collections
 import ctypes as C
 import functools
+import sys
+import threading
 import weakref
 from typing import Callable, NamedTuple, Optional, Tuple
 
@@ -303,6 +305,8 @@ def topk_rows(latent: torch.Tensor, k: int, zero_rest: bool) -> Tuple[torch.Tens
     B, H = latent.shape
     idx = torch.empty((B, k), dtype=torch.int32, device=latent.device)
     val = torch.empty((B, k), dtype=torch.float32, device=latent.device)
+    if zero_rest:
+        _latent_pool_forget(latent)
     check(_lib.load().qsae_topk_rows(_p(latent), latent.stride(0) if B else H, B, H, k, _p(idx), _p(val),
                                      1 if zero_rest else 0, _stream()))
     return idx, val
@@ -342,8 +346,90 @@ def _workspace(device: torch.device, nbytes: int, slot: int = 0, kind: str = "ca
 
 def release_workspaces() -> None:
     """Drop every cached scratch buffer (they are re-created on demand).  Buffers of batches still in flight stay alive
-    through their PendingForward handles."""
+    through their PendingForward handles.  The pool of dropped dense latents (below) is emptied too."""
     _workspaces.clear()
+    with _latent_pool_lock:
+        del _latent_pool[:]
+
+
+# ---- dropped dense latents, reused (INTEGRATION.md, section C; DESIGN.md 7.7) -------------------------------------------
+# A [B, H] latent that a forward-in-one-call prefilter entry point allocated and wrote is +0 everywhere except at the k
+# positions per row listed in that call's idx.  Once its caller has dropped it, the next call of the same shape on the same
+# stream takes it back and has the library erase those B k entries (qsae_recycle.h) in place of writing B H zeros.
+#: False: every call allocates its latent with torch.empty and has all its zeros written (no record is kept either)
+LATENT_RECYCLE = True
+#: records kept per device, the oldest dropped first; each holds a [B, H] latent (8.6 GB at the headline shape) and its idx
+LATENT_POOL_PER_DEVICE = 4
+_LatentRecord = collections.namedtuple("_LatentRecord", "key dense idx dense_version idx_version")
+_latent_pool = []                               # _LatentRecord, oldest first; key = (device, stream handle, B, H, k)
+_latent_pool_lock = threading.Lock()
+#: lookups of the pool since import: a hit took a dropped latent back, a miss fell through to torch.empty
+latent_pool_stats = {"hits": 0, "misses": 0}
+_latent_holder_baseline = None
+
+
+def _latent_holders(rec):
+    """The counters that together see every other holder of rec.dense: a second Python reference, a view or slice, a
+    detached alias, .numpy(), a DLPack capsule -- and, by the last one, the storage object itself (torch hands out one
+    Python object per storage, so holding it moves none of the first three)."""
+    dense = rec.dense
+    storage = dense.untyped_storage()
+    return (sys.getrefcount(dense), dense._use_count(), torch._C._storage_Use_Count(storage._cdata), sys.getrefcount(storage))
+
+
+def _latent_unheld(rec) -> bool:
+    """Whether the record is the only holder of its latent: the counters stand where they stand for a fresh tensor held
+    the same way (measured once, not assumed)."""
+    global _latent_holder_baseline
+    if _latent_holder_baseline is None:
+        _latent_holder_baseline = _latent_holders(_LatentRecord(None, torch.empty((1, 1)), None, 0, 0))
+    return _latent_holders(rec) == _latent_holder_baseline
+
+
+def _latent_pool_take(key):
+    """-> (dense, idx) of the first record of ``key`` whose latent nobody else holds and whose tensors torch has not seen
+    written since, removed from the pool; None when there is none.  A record torch has seen written is dropped."""
+    with _latent_pool_lock:
+        edited = [r for r in _latent_pool if r.dense._version != r.dense_version or r.idx._version != r.idx_version]
+        if edited:
+            _latent_pool[:] = [r for r in _latent_pool if not any(r is e for e in edited)]
+        for i, rec in enumerate(_latent_pool):
+            if rec.key == key and _latent_unheld(rec):
+                del _latent_pool[i]
+                latent_pool_stats["hits"] += 1
+                return rec.dense, rec.idx
+        latent_pool_stats["misses"] += 1
+    return None
+
+
+def _latent_pool_register(key, dense, idx) -> None:
+    """``dense`` [B, H] is finished: zeros and the entries listed in ``idx``.  Called when the last kernel that writes it has
+    been enqueued."""
+    try:
+        rec = _LatentRecord(key, dense, idx, dense._version, idx._version)
+    except RuntimeError:                        # inference tensors carry no version counter: an edit would go unseen
+        return
+    with _latent_pool_lock:
+        _latent_pool.append(rec)
+        mine = [r for r in _latent_pool if r.key[0] == key[0]]
+        drop = mine[:max(0, len(mine) - LATENT_POOL_PER_DEVICE)]
+        if drop:
+            _latent_pool[:] = [r for r in _latent_pool if not any(r is d for d in drop)]
+
+
+def _latent_pool_forget(t: torch.Tensor) -> None:
+    """``t`` is about to be written through its raw pointer, which torch's version counter does not see: whatever record
+    shares its storage no longer describes it."""
+    if not _latent_pool:
+        return
+    ptr = t.untyped_storage().data_ptr()
+    with _latent_pool_lock:
+        _latent_pool[:] = [r for r in _latent_pool if r.dense.untyped_storage().data_ptr() != ptr]
+
+
+def _recycled(name: str, tail) -> str:
+    """The library symbol for a call with a stale list: the qsaer_* form of qsae_recycle.h."""
+    return "qsaer_" + name[len("qsae_"):] if tail else name
 
 
 def encode_topk_supported(B: int, D: int, H: int, k: int) -> bool:
@@ -436,6 +522,7 @@ def encode_topk_prefilter(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch
         if dense_out.dim() != 2 or dense_out.shape[0] != B or dense_out.shape[1] < H or dense_out.stride(1) != 1:
             raise ValueError("dense_out must be a [B, >=H] fp32 tensor with unit column stride")
         dense, ld = dense_out, dense_out.stride(0)
+        _latent_pool_forget(dense_out)
     else:
         dense = torch.empty((B, H), dtype=torch.float32, device=x.device) if want_dense else None
         ld = H
@@ -450,7 +537,10 @@ def encode_topk_prefilter(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch
 
 def _decode_prefilter_args(x, W, bias, Wq, meta, k, decoder, dec_bias, want_dense, slot, kind):
     """Argument tuple shared by the forward-in-one-call entry points.  ``decoder`` = ("packed", packed uint8 [H, row_bytes],
-    n_bits, step) or ("table", fp32 [H, D], scale)."""
+    n_bits, step) or ("table", fp32 [H, D], scale).
+    -> (cargs, keep, outs, pool key or None, tail): with a dense latent and LATENT_RECYCLE the latent is a dropped one of the
+    pool where there is one -- ``tail`` = (stale_idx, stale_k), the arguments the qsaer_* form of the call takes behind the
+    stream, else () -- and the caller registers (pool key, dense, idx) once the call has fully finished."""
     x, W = _f32c(x, "x"), _f32c(W, "W")
     B, D = x.shape
     H = W.shape[0]
@@ -470,12 +560,18 @@ def _decode_prefilter_args(x, W, bias, Wq, meta, k, decoder, dec_bias, want_dens
     ws = _workspace(x.device, need, slot, kind)
     idx = torch.empty((B, k), dtype=torch.int32, device=x.device)
     val = torch.empty((B, k), dtype=torch.float32, device=x.device)
-    dense = torch.empty((B, H), dtype=torch.float32, device=x.device) if want_dense else None
+    dense = stale = pool_key = None
+    if want_dense and LATENT_RECYCLE:
+        dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+        pool_key = (dev, torch.cuda.current_stream(x.device).cuda_stream, B, H, k)
+        dense, stale = _latent_pool_take(pool_key) or (None, None)
+    if want_dense and dense is None:
+        dense = torch.empty((B, H), dtype=torch.float32, device=x.device)
     recon = torch.empty((B, D), dtype=torch.float32, device=x.device)
     cargs = (_p(x), _p(W), _p(b), _p(Wq), _p(meta), B, D, H, k) + dargs + (_p(db), _p(idx), _p(val), _p(dense), H, _p(recon),
                                                                           _p(ws), ws.numel())
-    keep = (x, W, b, Wq, meta, dict_t, db, ws)          # referenced by the pointers above
-    return cargs, keep, (idx, val, dense, recon)
+    keep = (x, W, b, Wq, meta, dict_t, db, ws, stale)   # referenced by the pointers above
+    return cargs, keep, (idx, val, dense, recon), pool_key, ((_p(stale), k) if stale is not None else ())
 
 
 # library symbols of the forward-in-one-call entry points, by the kind of decoder description
@@ -486,10 +582,13 @@ _PREFILTER_SUBMIT = {"packed": ("qsae_prefilter_submit", "qsae_prefilter_finish"
 
 @_on_tensor_device
 def _forward_prefilter(x, W, bias, Wq, meta, k, decoder, dec_bias, want_dense, spec_rows, info):
-    cargs, keep, outs = _decode_prefilter_args(x, W, bias, Wq, meta, k, decoder, dec_bias, want_dense, 0, "call")
+    cargs, keep, outs, pool_key, tail = _decode_prefilter_args(x, W, bias, Wq, meta, k, decoder, dec_bias, want_dense, 0, "call")
     flagged = C.c_int(0)
     kernel_timer.arm_sweep()
-    check(getattr(_lib.load(), _PREFILTER_FORWARD[decoder[0]])(*cargs, int(spec_rows), C.byref(flagged), _stream()))
+    fn = getattr(_lib.load(), _recycled(_PREFILTER_FORWARD[decoder[0]], tail))
+    check(fn(*cargs, int(spec_rows), C.byref(flagged), _stream(), *tail))
+    if pool_key is not None:
+        _latent_pool_register(pool_key, outs[2], outs[0])
     if info is not None:
         info["flagged_rows"] = int(flagged.value)
     return outs
@@ -522,9 +621,10 @@ class PendingForward:
     blocking entry points use buffers of their own, so nothing between the two calls can disturb the lists the fallback
     reads.  Not safe to share between threads."""
 
-    def __init__(self, finish_fn, cargs, keep, outs, word, event, device, stream, slot_key):
+    def __init__(self, finish_fn, cargs, keep, outs, word, event, device, stream, slot_key, latent_record=None):
         self._finish_fn, self._cargs, self._keep, self._outs = finish_fn, cargs, keep, outs
         self._word, self._event, self._device, self._stream, self._slot_key = word, event, device, stream, slot_key
+        self._latent_record = latent_record             # (pool key, dense, idx): registered once finish() has enqueued the rest
         self.flagged_rows = None
         _busy_slots[slot_key] = weakref.ref(self)       # (weak: a dropped handle must still be collected)
 
@@ -532,7 +632,7 @@ class PendingForward:
         ref = _busy_slots.get(self._slot_key)
         if ref is not None and ref() in (self, None):
             del _busy_slots[self._slot_key]
-        self._cargs = self._keep = None
+        self._cargs = self._keep = self._latent_record = None
 
     def finish(self):
         if self._cargs is None:
@@ -542,6 +642,8 @@ class PendingForward:
         try:
             with torch.cuda.device(self._device), torch.cuda.stream(self._stream):
                 check(self._finish_fn(*self._cargs, self.flagged_rows, _stream()))
+            if self._latent_record is not None:
+                _latent_pool_register(*self._latent_record)
         finally:
             self._release()
         return self._outs
@@ -556,15 +658,17 @@ class PendingForward:
             pass
 
 
-def _submit(submit_fn, finish_fn, cargs, keep, outs, device, slot):
+def _submit(submit_fn, finish_fn, cargs, keep, outs, device, slot, tail=(), latent_record=None):
+    """``tail``: arguments of submit_fn behind the stream (the finish function takes none); ``latent_record``: what
+    finish() registers with the pool of dropped latents."""
     stream = torch.cuda.current_stream(device)
     slot_key = (device.index if device.index is not None else torch.cuda.current_device(), stream.cuda_stream, slot)
     word = torch.zeros((1,), dtype=torch.int32).pin_memory()
     kernel_timer.arm_sweep()
-    check(submit_fn(*cargs, C.c_void_p(word.data_ptr()), _stream()))
+    check(submit_fn(*cargs, C.c_void_p(word.data_ptr()), _stream(), *tail))
     ev = torch.cuda.Event()
     ev.record(stream)
-    return PendingForward(finish_fn, cargs, keep, outs, word, ev, device, stream, slot_key)
+    return PendingForward(finish_fn, cargs, keep, outs, word, ev, device, stream, slot_key, latent_record)
 
 
 def _claim_slot(device, slot):
@@ -583,10 +687,12 @@ def _claim_slot(device, slot):
 def _forward_prefilter_submit(x, W, bias, Wq, meta, k, decoder, dec_bias, want_dense, slot, owner) -> PendingForward:
     slot = (owner, slot)            # slots are per owner (module): two models on one stream do not share workspaces
     _claim_slot(x.device, slot)
-    cargs, keep, outs = _decode_prefilter_args(x, W, bias, Wq, meta, k, decoder, dec_bias, want_dense, slot, "pending")
+    cargs, keep, outs, pool_key, tail = _decode_prefilter_args(x, W, bias, Wq, meta, k, decoder, dec_bias, want_dense, slot,
+                                                               "pending")
     lib = _lib.load()
-    submit_fn, finish_fn = (getattr(lib, name) for name in _PREFILTER_SUBMIT[decoder[0]])
-    return _submit(submit_fn, finish_fn, cargs, keep, outs, x.device, slot)
+    submit_name, finish_name = _PREFILTER_SUBMIT[decoder[0]]
+    return _submit(getattr(lib, _recycled(submit_name, tail)), getattr(lib, finish_name), cargs, keep, outs, x.device, slot,
+                   tail=tail, latent_record=(pool_key, outs[2], outs[0]) if pool_key is not None else None)
 
 
 def binary_forward_prefilter_submit(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], Wq: torch.Tensor,
@@ -615,6 +721,8 @@ def densify(idx: torch.Tensor, val: torch.Tensor, H: int, out: Optional[torch.Te
     B, k = idx.shape
     if out is None:
         out = torch.empty((B, H), dtype=torch.float32, device=idx.device)
+    else:
+        _latent_pool_forget(out)
     check(_lib.load().qsae_densify(_p(idx.contiguous()), _p(val.contiguous()), B, k, H, _p(out),
                                    out.stride(0) if B else H, _stream()))
     return out
@@ -1850,6 +1958,7 @@ def train_matryoshka_dpre(pre: torch.Tensor, g_levels: Optional[torch.Tensor], g
     _dev(pre, "pre", torch.float32)
     if pre.dim() != 2 or not pre.is_contiguous():
         raise ValueError("train_matryoshka_dpre: pre must be a contiguous [B, H] tensor (it is updated in place)")
+    _latent_pool_forget(pre)
     B, H = pre.shape
     sign_rows, scale = _f32c(sign_rows, "sign_rows"), _f32c(scale, "scale")
     D = sign_rows.shape[1]
@@ -2064,6 +2173,7 @@ def train_blatent_dpre(pre: torch.Tensor, g_recon: torch.Tensor, w_dec: torch.Te
     _dev(pre, "pre", torch.float32)
     if pre.dim() != 2 or not pre.is_contiguous():
         raise ValueError("train_blatent_dpre: pre must be a contiguous [B, H] tensor (it is updated in place)")
+    _latent_pool_forget(pre)
     B, H = pre.shape
     G, w_dec = _f32c(g_recon, "g_recon"), _f32c(w_dec, "w_dec")
     D = w_dec.shape[0]
