@@ -301,6 +301,18 @@ RECYCLE_SIGNATURES = {
                  "qsae_prefilter_submit_table")
 }
 
+# name -> (restype, argtypes) of the qsaeo_* entry points of include/qsae_optim.h (csrc/optim_recipe.hip): the recipe around the
+# Adam step -- the joint gradient norm and its clip coefficient, the steps that read it and carry the weights' moving average,
+# the projection of the decoder gradient -- a table of its own for the same reason.  Must list every symbol declared in
+# qsae_optim.h.
+OPTIM_SIGNATURES = {
+    "qsaeo_project_columns": (_i, [_vp, _vp, _i, _i, _i64, _vp]),
+    "qsaeo_grad_norm_workspace_bytes": (_sz, [_vp, _i]),
+    "qsaeo_grad_norm": (_i, [_vp, _vp, _i, C.c_double, _vp, _vp, _vp, _sz, _vp]),
+    "qsaeo_adam_step": (_i, SIGNATURES["qsae_adam_step"][1][:-1] + [_vp, _vp, _f, _vp]),
+    "qsaeo_adam_step_prefilter": (_i, SIGNATURES["qsae_adam_step_prefilter"][1][:-3] + [_vp, _vp, _vp, _f, _vp, _vp, _vp]),
+}
+
 
 class QsaeError(RuntimeError):
     """A libqsae_hip call returned a non-zero status."""
@@ -323,7 +335,7 @@ def _open(path: Path) -> C.CDLL:
     for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(CURVE_SIGNATURES.items()) \
             + list(NESTED_SIGNATURES.items()) + list(BATCH_SIGNATURES.items()) + list(NESTED_BATCH_SIGNATURES.items()) + list(MULTIK_SIGNATURES.items()) \
             + list(JUMP_SIGNATURES.items()) + list(JUMP_DENSE_SIGNATURES.items()) \
-            + list(BATCH_DENSE_SIGNATURES.items()) + list(RECYCLE_SIGNATURES.items()):
+            + list(BATCH_DENSE_SIGNATURES.items()) + list(RECYCLE_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here means the library is stale
         fn.restype = res
         fn.argtypes = args

@@ -2304,6 +2304,160 @@ def adam_step_prefilter(W: torch.Tensor, gW: torch.Tensor, mW: torch.Tensor, vW:
     return Wq, meta
 
 
+# ---- the recipe around the step (csrc/optim_recipe.hip, include/qsae_optim.h; quantizedsae_amd.optim.Adam is the user) ----------
+GRAD_NORM_HEAD = 4
+GRAD_NORM_MAX_TENSORS = 65536
+
+
+def project_columns_supported(H: int) -> bool:
+    """qsaeo_project_columns takes H a multiple of 4 (the limit of normalize_columns_table)"""
+    return H > 0 and H % 4 == 0
+
+
+@_on_tensor_device
+def project_columns(W: torch.Tensor, G: torch.Tensor) -> None:
+    """G [D, H] (the gradient of W, updated IN PLACE) loses, column by column, its component along the column of W [D, H]:
+    G[:, h] -= (G[:, h] . W[:, h]) * W[:, h].  Both fp32, 16-byte aligned, rows contiguous with the same row stride (a
+    multiple of 4 elements).  See qsaeo_project_columns for the order of the sums."""
+    who = "project_columns"
+    _dev(W, f"{who}: W", torch.float32)
+    _dev(G, f"{who}: G", torch.float32)
+    if W.dim() != 2 or G.shape != W.shape or G.device != W.device:
+        raise ValueError(f"{who}: W is {tuple(W.shape)} on {W.device}, G is {tuple(G.shape)} on {G.device}; expected two [D, H]")
+    D, H = W.shape
+    if D == 0 or H == 0:
+        return
+    if not project_columns_supported(H):
+        raise ValueError(f"{who}: W is {tuple(W.shape)}, expected [D >= 1, H a multiple of 4]")
+    ld = W.stride(0) if D > 1 else max(H, W.stride(0))
+    if W.stride(1) != 1 or G.stride(1) != 1 or (D > 1 and G.stride(0) != ld) or ld < H or ld % 4 != 0:
+        raise ValueError(f"{who}: W and G must have unit inner stride and the same row stride, a multiple of 4 (strides "
+                         f"{W.stride()} and {G.stride()})")
+    if W.data_ptr() % 16 != 0 or G.data_ptr() % 16 != 0:
+        raise ValueError(f"{who}: W and G must be 16-byte aligned")
+    if W.data_ptr() == G.data_ptr():
+        raise ValueError(f"{who}: W and G are the same memory")
+    check(_lib.load().qsaeo_project_columns(_p(W), _p(G), D, H, ld, _stream()))
+
+
+def _recipe_words(who: str, device, coef: Optional[torch.Tensor], report: Optional[torch.Tensor], T: int):
+    if coef is None:
+        coef = torch.empty((1,), dtype=torch.float32, device=device)
+    if report is None:
+        report = torch.empty((GRAD_NORM_HEAD + T,), dtype=torch.int64, device=device)
+    _dev(coef, f"{who}: coef", torch.float32)
+    _dev(report, f"{who}: report", torch.int64)
+    if coef.numel() != 1 or coef.device != device or tuple(report.shape) != (GRAD_NORM_HEAD + T,) or report.device != device \
+            or not report.is_contiguous():
+        raise ValueError(f"{who}: coef must be one fp32 word and report a contiguous int64 [{GRAD_NORM_HEAD + T}] on {device}")
+    return coef, report
+
+
+def grad_norm(tensors, max_norm: float, coef: Optional[torch.Tensor] = None,
+              report: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (coef fp32 [1], report int64 [4 + T]), both on the device: the joint L2 norm of ``tensors`` (fp32, contiguous, any
+    shapes and sizes, at least one) in fp64 and the clip coefficient of ``torch.nn.utils.clip_grad_norm_(max_norm)`` as one fp32
+    word.  report: the fp64 bits of the total sum of squares, the norm and the coefficient, 1 where the coefficient is not 1,
+    then every tensor's sum of squares.  ``coef`` / ``report``: buffers to write into.  One call, nothing read back.  See
+    qsaeo_grad_norm."""
+    who = "grad_norm"
+    tensors = list(tensors)
+    T = len(tensors)
+    if not 1 <= T <= GRAD_NORM_MAX_TENSORS:
+        raise ValueError(f"{who}: takes 1 to {GRAD_NORM_MAX_TENSORS} tensors, got {T}")
+    max_norm = float(max_norm)
+    if not max_norm >= 0:
+        raise ValueError(f"{who}: max_norm must be a number >= 0, got {max_norm}")
+    for i, t in enumerate(tensors):
+        _dev(t, f"{who}: tensors[{i}]")
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{who}: tensors[{i}] must be a contiguous fp32 tensor, got {t.dtype} {tuple(t.shape)} with strides "
+                             f"{t.stride()} (no silent copy is made)")
+        if t.device != tensors[0].device:
+            raise ValueError(f"{who}: tensors[{i}] is on {t.device}, tensors[0] on {tensors[0].device}")
+    device = tensors[0].device
+    with torch.cuda.device(device):
+        coef, report = _recipe_words(who, device, coef, report, T)
+        lib = _lib.load()
+        counts = (C.c_int64 * T)(*[t.numel() for t in tensors])
+        ptrs = (C.c_void_p * T)(*[t.data_ptr() if t.numel() else 0 for t in tensors])
+        ws = _workspace(device, max(int(lib.qsaeo_grad_norm_workspace_bytes(counts, T)), 16))
+        check(lib.qsaeo_grad_norm(ptrs, counts, T, max_norm, _p(coef), _p(report), _p(ws), ws.numel(), _stream()))
+    return coef, report
+
+
+def _recipe_streams(who: str, like: torch.Tensor, coef: Optional[torch.Tensor], emas) -> None:
+    if coef is not None:
+        _dev(coef, f"{who}: coef", torch.float32)
+        if coef.numel() != 1 or coef.device != like.device:
+            raise ValueError(f"{who}: coef must be one fp32 word on {like.device}")
+    for name, e, ref in emas:
+        if e is not None:
+            _dev(e, f"{who}: {name}", torch.float32)
+            if e.shape != ref.shape or e.device != ref.device or not e.is_contiguous():
+                raise ValueError(f"{who}: {name} must be a contiguous fp32 {tuple(ref.shape)} on {ref.device} (it is updated in "
+                                 "place)")
+
+
+@_on_tensor_device
+def adam_step_clipped(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, one_minus_b1: float, b2: float,
+                      one_minus_b2: float, bc2_sqrt: float, eps: float, step_size: float,
+                      coef: Optional[torch.Tensor] = None, ema: Optional[torch.Tensor] = None,
+                      one_minus_decay: float = 0.0) -> None:
+    """adam_step with the recipe's two optional streams: ``coef`` (one fp32 word on the device, e.g. grad_norm's) multiplies the
+    gradient on its way into the step (g is not written); ``ema`` (like p, updated IN PLACE) moves towards the new p by
+    ``one_minus_decay``.  With neither it is adam_step bit for bit.  See qsaeo_adam_step."""
+    who = "adam_step_clipped"
+    _adam_operands(who, ("p", "g", "m", "v"), (p, g, m, v))
+    _recipe_streams(who, p, coef, (("ema", ema, p),))
+    check(_lib.load().qsaeo_adam_step(_p(p), _p(g), _p(m), _p(v), p.numel(), one_minus_b1, b2, one_minus_b2, bc2_sqrt, eps,
+                                      step_size, _p(coef), _p(ema), one_minus_decay, _stream()))
+
+
+@_on_tensor_device
+def adam_step_prefilter_clipped(W: torch.Tensor, gW: torch.Tensor, mW: torch.Tensor, vW: torch.Tensor,
+                                bias: Optional[torch.Tensor], gb: Optional[torch.Tensor], mb: Optional[torch.Tensor],
+                                vb: Optional[torch.Tensor], one_minus_b1: float, b2: float, one_minus_b2: float,
+                                bc2_sqrt: float, eps: float, step_size: float, coef: Optional[torch.Tensor] = None,
+                                emaW: Optional[torch.Tensor] = None, emab: Optional[torch.Tensor] = None,
+                                one_minus_decay: float = 0.0, Wq: Optional[torch.Tensor] = None,
+                                meta: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """adam_step_prefilter with the recipe's two optional streams (see adam_step_clipped); ``emaW`` and ``emab`` are given
+    together where there is a bias.  -> (Wq, meta), bit-identical to prefilter_pack_w of the updated W / bias.  See
+    qsaeo_adam_step_prefilter."""
+    who = "adam_step_prefilter_clipped"
+    _adam_operands(who, ("W", "gW", "mW", "vW"), (W, gW, mW, vW))
+    if W.dim() != 2 or W.numel() == 0:
+        raise ValueError(f"{who}: W is {tuple(W.shape)}, expected [H >= 1, D >= 1]")
+    H, D = W.shape
+    quad = (bias, gb, mb, vb)
+    if any(t is None for t in quad) and not all(t is None for t in quad):
+        raise ValueError(f"{who}: bias, gb, mb and vb are given together or not at all")
+    if bias is not None:
+        _adam_operands(who, ("bias", "gb", "mb", "vb"), quad)
+        if tuple(bias.shape) != (H,) or bias.device != W.device:
+            raise ValueError(f"{who}: bias is {tuple(bias.shape)} on {bias.device}, W is {tuple(W.shape)} on {W.device}")
+    if W.data_ptr() % 16 != 0:
+        raise ValueError(f"{who}: W must be 16-byte aligned (the prefilter entry points ask for that too)")
+    if (emab is not None) != (emaW is not None and bias is not None):
+        raise ValueError(f"{who}: emab is given exactly where emaW and bias both are")
+    _recipe_streams(who, W, coef, (("emaW", emaW, W), ("emab", emab, bias)))
+    if Wq is None:
+        Wq = torch.empty((H, D), dtype=torch.float16, device=W.device)
+    if meta is None:
+        meta = torch.empty((4,), dtype=torch.float32, device=W.device)
+    _dev(Wq, f"{who}: Wq", torch.float16)
+    _dev(meta, f"{who}: meta", torch.float32)
+    if tuple(Wq.shape) != (H, D) or tuple(meta.shape) != (4,) or not Wq.is_contiguous() or not meta.is_contiguous() \
+            or Wq.device != W.device or meta.device != W.device or Wq.data_ptr() % 16 != 0:
+        raise ValueError(f"{who}: Wq must be a contiguous 16-byte aligned fp16 [{H}, {D}] and meta a contiguous fp32 [4] on "
+                         f"{W.device}")
+    check(_lib.load().qsaeo_adam_step_prefilter(_p(W), _p(gW), _p(mW), _p(vW), _p(bias), _p(gb), _p(mb), _p(vb), H, D,
+                                                one_minus_b1, b2, one_minus_b2, bc2_sqrt, eps, step_size, _p(coef), _p(emaW),
+                                                _p(emab), one_minus_decay, _p(Wq), _p(meta), _stream()))
+    return Wq, meta
+
+
 # ---- trainer: batch supply and loss (csrc/trainer.hip; quantizedsae_amd.training is the user) ------------------------------------
 TRAINER_LOSS_MAX_LEVELS = 8
 

@@ -6,10 +6,17 @@ the encoder's weight and bias are stepped together by ``torch.ops.qsae.adam_step
 candidate-pass copy of the new weights; the optimizer installs it in the model's cache, so the next forward does not
 rebuild it.  The state (``step``, ``exp_avg``, ``exp_avg_sq``) has the names, dtypes and placement of torch's non-capturable
 Adam: state dicts go back and forth between the two.
+
+Around the step, the recipe of the top-k SAE papers (csrc/optim_recipe.hip), each piece in the pass
+that already touches the data: ``max_grad_norm`` clips the joint gradient norm -- one ``grad_norm`` call leaves the coefficient
+as a device word that every step kernel multiplies the gradient by -- and ``ema_decay`` keeps an exponential moving average
+of the weights as one more stream of the step kernel.  Without them ``step()`` calls exactly the ops it called before.
 """
 from __future__ import annotations
 
+import contextlib
 import math
+from collections import namedtuple
 from typing import Optional
 
 import torch
@@ -17,7 +24,11 @@ import torch
 from . import torch_ops as ops
 from .sae.topk import TopKCore
 
-__all__ = ["Adam"]
+__all__ = ["Adam", "ClipReport"]
+
+#: ``Adam.clip_report()``: the joint gradient norm of the last step (fp64), the coefficient its kernels multiplied the gradients
+#: by, whether that was a clip, and every tensor's sum of squares in the order of the param groups
+ClipReport = namedtuple("ClipReport", ["norm", "coef", "clipped", "per_tensor"])
 
 # options of torch.optim.Adam that have no kernel here; kept in the param groups (off) so that state dicts stay
 # interchangeable
@@ -37,6 +48,11 @@ def _check_group(group: dict) -> None:
         raise ValueError(f"Invalid epsilon value: {eps}")
     if not 0.0 <= b1 < 1.0 or not 0.0 <= b2 < 1.0:
         raise ValueError(f"Invalid betas: {(b1, b2)}")
+    clip, decay = group.get("max_grad_norm"), group.get("ema_decay")
+    if clip is not None and (isinstance(clip, bool) or not isinstance(clip, (int, float)) or not 0.0 < clip < math.inf):
+        raise ValueError(f"Invalid max_grad_norm: {clip!r} (expected None or a finite number > 0)")
+    if decay is not None and (isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 <= decay < 1.0):
+        raise ValueError(f"Invalid ema_decay: {decay!r} (expected None or a float in [0, 1))")
 
 
 class Adam(torch.optim.Optimizer):
@@ -50,17 +66,54 @@ class Adam(torch.optim.Optimizer):
     The keyword-only options after ``model`` are torch.optim.Adam's and exist so that the param groups carry torch's keys
     (state dicts load both ways): a truthy ``weight_decay``, ``amsgrad``, ``maximize``, ``capturable``, ``differentiable``
     or ``fused`` is a ``ValueError`` that names it (``fused`` also because torch reads it from a loaded state dict to place
-    ``step`` on the device); ``foreach`` has no meaning here -- there is one implementation -- and is kept as given."""
+    ``step`` on the device); ``foreach`` has no meaning here -- there is one implementation -- and is kept as given.
+
+    ``max_grad_norm``: clip the joint L2 norm of all gradients of a step to this value (a finite number > 0), as
+    ``torch.nn.utils.clip_grad_norm_`` would.  One number for the whole optimizer: a differing value in any param group is a
+    ``ValueError``.  ``step()`` makes one ``grad_norm`` call over every parameter that has a gradient, in param-group order,
+    and every step kernel of that step reads the same coefficient word.  ``.grad`` IS LEFT UNSCALED -- what reads it after
+    the step (``ModelWatch``, a logger) sees the raw gradients.  ``last_clip`` is the device report of the last step,
+    ``clip_report()`` its host copy.
+    ``ema_decay``: a float in [0, 1); ``state[p]["ema"]`` starts as a copy of ``p`` at the parameter's first step and moves
+    towards the new ``p`` by ``1 - ema_decay`` in the step kernel.  ``ema_state`` (a dict parameter -> tensor): where the
+    averages live instead, so that a caller that builds a fresh optimizer per epoch keeps them (``state[p]["ema"]`` is then
+    the same tensor; the dict wins over a loaded state dict).  ``ema_weights()`` exchanges weights and averages for the
+    duration of a block.
+    Both options are param-group keys next to torch's, present only when set; a state dict that carries them (and the
+    per-parameter ``"ema"``) loads into ``torch.optim.Adam``, which then steps without them.
+    The fused encoder route additionally needs weight and bias to agree on ``ema_decay``."""
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, *, model: Optional[torch.nn.Module] = None,
                  weight_decay: float = 0, amsgrad: bool = False, maximize: bool = False, foreach: Optional[bool] = None,
-                 capturable: bool = False, differentiable: bool = False, fused: Optional[bool] = None):
+                 capturable: bool = False, differentiable: bool = False, fused: Optional[bool] = None,
+                 max_grad_norm: Optional[float] = None, ema_decay: Optional[float] = None, ema_state: Optional[dict] = None):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize,
                         foreach=foreach, capturable=capturable, differentiable=differentiable, fused=fused,
                         decoupled_weight_decay=False)
+        self._recipe = {}                                  # the recipe's keys that are set: group keys only then
+        if max_grad_norm is not None:
+            self._recipe["max_grad_norm"] = max_grad_norm
+        if ema_decay is not None:
+            self._recipe["ema_decay"] = ema_decay
+        defaults.update(self._recipe)
         _check_group(defaults)
+        if ema_state is not None and not isinstance(ema_state, dict):
+            raise ValueError(f"ema_state must be a dict parameter -> tensor, got {type(ema_state).__name__}")
+        if ema_state is not None and ema_decay is None:
+            raise ValueError("ema_state needs ema_decay")
         self._model = model if isinstance(model, TopKCore) else None
+        self._owner = model                                # whose caches ema_weights() invalidates
+        self._ema_state = ema_state
+        self._coef = None                                  # the coefficient word of the last clipped step
+        #: the device report of the last clipped step (``ops.grad_norm``), or None
+        self.last_clip = None
         super().__init__(params, defaults)
+
+    def load_state_dict(self, state_dict) -> None:
+        super().load_state_dict(state_dict)
+        for group in self.param_groups:                    # a dict saved without the recipe's keys leaves this optimizer's
+            for key, value in self._recipe.items():
+                group.setdefault(key, value)
 
     def add_param_group(self, param_group: dict) -> None:
         super().add_param_group(param_group)
@@ -103,7 +156,8 @@ class Adam(torch.optim.Optimizer):
         if b is None or W not in todo or b not in todo:
             return None
         gW, gb = todo[W], todo[b]
-        if (gW["lr"], tuple(gW["betas"]), gW["eps"]) != (gb["lr"], tuple(gb["betas"]), gb["eps"]):
+        if (gW["lr"], tuple(gW["betas"]), gW["eps"], gW.get("ema_decay")) != \
+                (gb["lr"], tuple(gb["betas"]), gb["eps"], gb.get("ema_decay")):
             return None
         sW, sb = self.state.get(W), self.state.get(b)
         tW = float(sW["step"]) if sW else 0.0
@@ -130,6 +184,20 @@ class Adam(torch.optim.Optimizer):
                     raise RuntimeError(f"quantizedsae_amd.optim.Adam runs on MI355X only; a parameter is on {p.device} "
                                        "(no CPU fallback exists)")
                 todo[p] = group
+        clips = {group.get("max_grad_norm") for group in self.param_groups}
+        if len(clips) > 1:
+            raise ValueError(f"quantizedsae_amd.optim.Adam: max_grad_norm is one number for the whole optimizer, the param "
+                             f"groups hold {sorted(clips, key=repr)}")
+        clip = clips.pop() if clips else None
+        grads = {p: (p.grad if p.grad.is_contiguous() else p.grad.contiguous()) for p in todo}
+        coef = None
+        if clip is not None and todo:
+            T = len(todo)
+            keep = self.last_clip is not None and self.last_clip.shape[0] == ops.GRAD_NORM_HEAD + T \
+                and self.last_clip.device == next(iter(todo)).device
+            coef, self.last_clip = ops.grad_norm(list(grads.values()), clip, self._coef if keep else None,
+                                                 self.last_clip if keep else None)
+            self._coef = coef
         pair = self._encoder_pair(todo)
         for p, group in todo.items():
             if pair is not None and p is pair[1]:
@@ -137,20 +205,66 @@ class Adam(torch.optim.Optimizer):
             state = self._state_of(p)
             state["step"] += 1
             scalars = self._scalars(group, float(state["step"]))
-            g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+            decay = group.get("ema_decay")
+            ema = self._ema_of(p, state) if decay is not None else None
             if pair is not None and p is pair[0]:
-                self._step_pair(pair[1], g, state, scalars)
+                self._step_pair(pair[1], grads[p], grads[pair[1]], state, scalars, coef, ema, decay)
+            elif coef is None and ema is None:
+                ops.adam_step(p.detach(), grads[p], state["exp_avg"], state["exp_avg_sq"], *scalars)
             else:
-                ops.adam_step(p.detach(), g, state["exp_avg"], state["exp_avg_sq"], *scalars)
+                ops.adam_step_clipped(p.detach(), grads[p], state["exp_avg"], state["exp_avg_sq"], *scalars, coef=coef, ema=ema,
+                                      one_minus_decay=0.0 if decay is None else 1 - decay)
         return loss
 
-    def _step_pair(self, b, gW, stateW, scalars) -> None:
+    def _ema_of(self, p, state):
+        """The average of p: a copy of p at the parameter's first step; kept in ``ema_state`` where one was given."""
+        if self._ema_state is not None:
+            ema = self._ema_state.get(p)
+            if ema is None:
+                ema = self._ema_state[p] = p.detach().clone(memory_format=torch.contiguous_format)
+            state["ema"] = ema
+        elif "ema" not in state:
+            state["ema"] = p.detach().clone(memory_format=torch.contiguous_format)
+        return state["ema"]
+
+    def clip_report(self) -> Optional[ClipReport]:
+        """The report of the last clipped step on the host (one copy of 32 + 8 T bytes), or None before the first."""
+        if self.last_clip is None:
+            return None
+        words = self.last_clip.cpu()
+        f = words.view(torch.float64)
+        return ClipReport(norm=f[1].item(), coef=f[2].item(), clipped=bool(words[3].item()),
+                          per_tensor=tuple(f[ops.GRAD_NORM_HEAD:].tolist()))
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block every parameter that has an average holds it, and the average holds the weights; on exit they
+        are exchanged back.  Plain torch copies under ``no_grad`` (version counters move, every cache keyed on a parameter
+        rebuilds by itself; a model with ``invalidate_packed`` is told as well).  Not for the hot path."""
+        def exchange():
+            with torch.no_grad():
+                for group in self.param_groups:
+                    for p in group["params"]:
+                        ema = self._ema_state.get(p) if self._ema_state is not None else self.state.get(p, {}).get("ema")
+                        if ema is not None:
+                            kept = p.detach().clone()
+                            p.copy_(ema)
+                            ema.copy_(kept)
+            if hasattr(self._owner, "invalidate_packed"):
+                self._owner.invalidate_packed()
+        exchange()
+        try:
+            yield self
+        finally:
+            exchange()
+
+    def _step_pair(self, b, gW, gb, stateW, scalars, coef, emaW, decay) -> None:
         model = self._model
         lin = model.encoder.linear
         W = lin.weight
         stateb = self._state_of(b)
         stateb["step"] += 1
-        gb = b.grad if b.grad.is_contiguous() else b.grad.contiguous()
+        emab = self._ema_of(b, stateb) if decay is not None else None
         # the buffers of the copy that is about to go stale take the new one (work on one stream is ordered)
         Wq = meta = None
         old = model._pref_cache.peek()
@@ -160,7 +274,13 @@ class Adam(torch.optim.Optimizer):
                     and oq.data_ptr() % 16 == 0 and tuple(om.shape) == (4,) and om.dtype == torch.float32 \
                     and om.device == W.device:
                 Wq, meta = oq, om
-        Wq, meta = ops.adam_step_prefilter(W.detach(), gW, stateW["exp_avg"], stateW["exp_avg_sq"], b.detach(), gb,
-                                           stateb["exp_avg"], stateb["exp_avg_sq"], *scalars, Wq=Wq, meta=meta)
+        if coef is None and emaW is None:
+            Wq, meta = ops.adam_step_prefilter(W.detach(), gW, stateW["exp_avg"], stateW["exp_avg_sq"], b.detach(), gb,
+                                               stateb["exp_avg"], stateb["exp_avg_sq"], *scalars, Wq=Wq, meta=meta)
+        else:
+            Wq, meta = ops.adam_step_prefilter_clipped(W.detach(), gW, stateW["exp_avg"], stateW["exp_avg_sq"], b.detach(), gb,
+                                                       stateb["exp_avg"], stateb["exp_avg_sq"], *scalars, coef=coef, emaW=emaW,
+                                                       emab=emab, one_minus_decay=0.0 if decay is None else 1 - decay,
+                                                       Wq=Wq, meta=meta)
         # after the op: its writes have moved the version counters that the cache key reads
         model._pref_cache.put((lin.weight, lin.bias), {"Wq": Wq, "meta": meta})

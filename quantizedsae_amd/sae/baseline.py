@@ -198,6 +198,23 @@ class BaselineSparseAutoencoder(ops.GraphForwardMixin, TopKCore, nn.Module):
             self.decoder.weight.data = w / torch.clamp(torch.norm(w, dim=0, keepdim=True), min=1e-8)
             self.invalidate_packed()
 
+    def project_decoder_grad(self):
+        """Remove from ``decoder.weight.grad`` its component parallel to each atom (Bricken et al., Gao et al.): column h
+        loses ``(g_h . w_h) w_h``, so that Adam's moments do not collect a radial part that the next
+        normalize_decoder_weights() throws away.  One HIP pass over the gradient, in place; call it between the backward and
+        the optimizer step.  Does nothing without a gradient.  Shapes the kernel does not take go through the torch
+        composition (elementwise product, column sum, ``addcmul_``), as in normalize_decoder_weights."""
+        w, g = self.decoder.weight, self.decoder.weight.grad
+        if g is None:
+            return
+        with torch.no_grad():
+            if w.is_cuda and w.dtype == torch.float32 and g.dtype == torch.float32 and w.is_contiguous() and g.is_contiguous() \
+                    and w.data_ptr() % 16 == 0 and g.data_ptr() % 16 == 0 and ops.project_columns_supported(w.shape[1]):
+                ops.project_columns(w.detach(), g)
+                return
+            dot = (g * w).sum(dim=0, keepdim=True)
+            g.addcmul_(dot, w, value=-1)
+
 
 class _BaselineTrainStep(torch.autograd.Function):
     """The baseline forward and its gradient (the table in DESIGN.md section 4.11): the BinarySAE gradient without the

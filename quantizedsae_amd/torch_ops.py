@@ -789,6 +789,58 @@ def _(W, gW, mW, vW, bias, gb, mb, vb, one_minus_b1, b2, one_minus_b2, bc2_sqrt,
     return None
 
 
+# ---- the recipe around the step (csrc/optim_recipe.hip): the written tensors are mutated arguments, as above ----------------
+@_op("project_columns", mutates=("G",))
+def _project_columns(W: Tensor, G: Tensor) -> None:
+    """G [D, H] loses its component along every column of W [D, H], in place"""
+    _ops.project_columns(W, G)
+
+
+@_project_columns.register_fake
+def _(W, G):
+    return None
+
+
+@_op("grad_norm", mutates=("coef", "report"))
+def _grad_norm(tensors: List[Tensor], max_norm: float, coef: Tensor, report: Tensor) -> None:
+    """coef fp32 [1] receives the clip coefficient of the joint norm, report int64 [4 + T] the sums behind it"""
+    _ops.grad_norm(tensors, max_norm, coef, report)
+
+
+@_grad_norm.register_fake
+def _(tensors, max_norm, coef, report):
+    return None
+
+
+@_op("adam_step_clipped", mutates=("p", "m", "v", "ema"))
+def _adam_step_clipped(p: Tensor, g: Tensor, m: Tensor, v: Tensor, one_minus_b1: float, b2: float, one_minus_b2: float,
+                       bc2_sqrt: float, eps: float, step_size: float, coef: Optional[Tensor], ema: Optional[Tensor],
+                       one_minus_decay: float) -> None:
+    _ops.adam_step_clipped(p, g, m, v, one_minus_b1, b2, one_minus_b2, bc2_sqrt, eps, step_size, coef, ema, one_minus_decay)
+
+
+@_adam_step_clipped.register_fake
+def _(p, g, m, v, one_minus_b1, b2, one_minus_b2, bc2_sqrt, eps, step_size, coef, ema, one_minus_decay):
+    return None
+
+
+@_op("adam_step_prefilter_clipped", mutates=("W", "mW", "vW", "bias", "mb", "vb", "emaW", "emab", "Wq", "meta"))
+def _adam_step_prefilter_clipped(W: Tensor, gW: Tensor, mW: Tensor, vW: Tensor, bias: Optional[Tensor], gb: Optional[Tensor],
+                                 mb: Optional[Tensor], vb: Optional[Tensor], one_minus_b1: float, b2: float,
+                                 one_minus_b2: float, bc2_sqrt: float, eps: float, step_size: float, coef: Optional[Tensor],
+                                 emaW: Optional[Tensor], emab: Optional[Tensor], one_minus_decay: float, Wq: Tensor,
+                                 meta: Tensor) -> None:
+    """Wq fp16 [H, D] and meta fp32 [4] receive the prefilter state of the updated W / bias"""
+    _ops.adam_step_prefilter_clipped(W, gW, mW, vW, bias, gb, mb, vb, one_minus_b1, b2, one_minus_b2, bc2_sqrt, eps, step_size,
+                                     coef, emaW, emab, one_minus_decay, Wq, meta)
+
+
+@_adam_step_prefilter_clipped.register_fake
+def _(W, gW, mW, vW, bias, gb, mb, vb, one_minus_b1, b2, one_minus_b2, bc2_sqrt, eps, step_size, coef, emaW, emab,
+      one_minus_decay, Wq, meta):
+    return None
+
+
 # ---- trainer: batch supply and loss (csrc/trainer.hip) -------------------------------------------------------------------
 @_op("rows_nan_bitmap")
 def _rows_nan_bitmap(src: Tensor) -> Tensor:
@@ -1763,6 +1815,46 @@ def adam_step_prefilter(W, gW, mW, vW, bias, gb, mb, vb, one_minus_b1, b2, one_m
         meta = torch.empty((4,), dtype=torch.float32, device=W.device)
     Q.adam_step_prefilter(W, gW, mW, vW, bias, gb, mb, vb, float(one_minus_b1), float(b2), float(one_minus_b2),
                           float(bc2_sqrt), float(eps), float(step_size), Wq, meta)
+    return Wq, meta
+
+
+project_columns_supported = _ops.project_columns_supported
+GRAD_NORM_HEAD = _ops.GRAD_NORM_HEAD
+
+
+def project_columns(W, G):
+    Q.project_columns(W, G)
+
+
+def grad_norm(tensors, max_norm, coef=None, report=None):
+    """-> (coef fp32 [1], report int64 [4 + T]); given: written in place and returned"""
+    tensors = list(tensors)
+    if not tensors:
+        raise ValueError("grad_norm: takes at least one tensor")
+    if coef is None:
+        coef = torch.empty((1,), dtype=torch.float32, device=tensors[0].device)
+    if report is None:
+        report = torch.empty((GRAD_NORM_HEAD + len(tensors),), dtype=torch.int64, device=tensors[0].device)
+    Q.grad_norm(tensors, float(max_norm), coef, report)
+    return coef, report
+
+
+def adam_step_clipped(p, g, m, v, one_minus_b1, b2, one_minus_b2, bc2_sqrt, eps, step_size, coef=None, ema=None,
+                      one_minus_decay=0.0):
+    Q.adam_step_clipped(p, g, m, v, float(one_minus_b1), float(b2), float(one_minus_b2), float(bc2_sqrt), float(eps),
+                        float(step_size), coef, ema, float(one_minus_decay))
+
+
+def adam_step_prefilter_clipped(W, gW, mW, vW, bias, gb, mb, vb, one_minus_b1, b2, one_minus_b2, bc2_sqrt, eps, step_size,
+                                coef=None, emaW=None, emab=None, one_minus_decay=0.0, Wq=None, meta=None):
+    """-> (Wq, meta); ``Wq`` / ``meta`` given: written in place and returned"""
+    if Wq is None:
+        Wq = torch.empty(W.shape, dtype=torch.float16, device=W.device)
+    if meta is None:
+        meta = torch.empty((4,), dtype=torch.float32, device=W.device)
+    Q.adam_step_prefilter_clipped(W, gW, mW, vW, bias, gb, mb, vb, float(one_minus_b1), float(b2), float(one_minus_b2),
+                                  float(bc2_sqrt), float(eps), float(step_size), coef, emaW, emab, float(one_minus_decay),
+                                  Wq, meta)
     return Wq, meta
 
 

@@ -89,6 +89,17 @@ backward, ``trainer_loss`` the per-type loss, ``optim.Adam`` the step.  What dif
   ``jumprelu/truncated_rows`` (rows with more firing units than the cap) in place of ``jumprelu/uncertified_rows`` and
   ``jumprelu/saturated_rows``, and no ``jumprelu/theta_min``.  Together with ``batch_topk``, ``nested_bounds``, ``batch_topk_nested_bounds`` or ``multi_topk`` it
   raises: the combinations are not built.
+* ``grad_clip=c`` (a finite number > 0; every ``sae_type``; default ``None`` changes nothing) clips the joint gradient norm of
+  every step to ``c`` (``optim.Adam(max_grad_norm=c)``, csrc/optim_recipe.hip): one norm call inside ``optimizer.step()``, over
+  every parameter with a gradient -- the JumpReLU thresholds included -- and a coefficient word that the step kernels
+  multiply the gradients by; ``.grad`` itself stays unscaled, so ``watch`` shows raw gradients.  Logging steps gain
+  ``grad_norm``, ``grad_clip_coef`` and ``grad_clipped`` (one small host copy; no other step reads anything back).
+  ``decoder_grad_projection=True`` (``baseline_sae`` only, the one model with unit-norm atoms; default ``False``) calls
+  ``model.project_decoder_grad()`` between the backward (after ``apply_secant_grad`` / ``mask_grad`` and the watch
+  collection) and ``optimizer.step()``: the decoder gradient loses its component along each atom.  ``ema_decay=d`` (a float
+  in [0, 1); default ``None``) keeps an exponential moving average of every parameter in the step kernels
+  (``optim.Adam(ema_decay=d, ema_state=trainer.ema_state)``); the Trainer owns the averages across the per-epoch optimizers,
+  and ``train()`` saves them as a state dict next to the checkpoint, ``<model_path without .pth>_ema.pth``.
 * ``model=`` hands in the model instead of building the reference's.  The reference builds
   ``BinarySAE(input_dim, hidden_dim, n_bits)``, where ``n_bits`` lands in ``gamma`` and the decoder keeps its default of 8
   bits; that call is kept.
@@ -159,7 +170,8 @@ class Trainer:
                  multi_topk_weights=None, jumprelu: bool = False, jumprelu_l0_coef: Optional[float] = None,
                  jumprelu_cap: Optional[int] = None, jumprelu_bandwidth: float = 1e-3, jumprelu_init=None,
                  jumprelu_dense: bool = False, batch_topk_dense: bool = False,
-                 batch_topk_floor_ratio: Optional[float] = None):
+                 batch_topk_floor_ratio: Optional[float] = None, grad_clip: Optional[float] = None,
+                 decoder_grad_projection: bool = False, ema_decay: Optional[float] = None):
         if sae_type not in SAE_TYPES:
             raise ValueError(f"unknown sae_type {sae_type!r}; expected one of {', '.join(SAE_TYPES)}")
         if sae_type == "t_sae" and not rigL:
@@ -241,8 +253,24 @@ class Trainer:
                     raise ValueError(f"{name} needs jumprelu=True")
             if jumprelu_dense:
                 raise ValueError("jumprelu_dense needs jumprelu=True")
+        if grad_clip is not None:
+            if isinstance(grad_clip, bool) or not isinstance(grad_clip, (int, float)) or \
+                    not (math.isfinite(grad_clip) and grad_clip > 0):
+                raise ValueError(f"grad_clip = {grad_clip!r}; expected None or a finite number > 0")
+        if decoder_grad_projection and sae_type != "baseline_sae":
+            raise ValueError(f"decoder_grad_projection: the projection is for baseline_sae, the one model with unit-norm atoms; "
+                             f"got {sae_type!r}")
+        if ema_decay is not None:
+            if isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float)) or not 0.0 <= ema_decay < 1.0:
+                raise ValueError(f"ema_decay = {ema_decay!r}; expected None or a float in [0, 1)")
         self.config = config
         self.sae_type = sae_type
+        #: the recipe around the optimizer step: the clip value, whether the decoder gradient is projected, the decay
+        self.grad_clip = grad_clip
+        self.decoder_grad_projection = bool(decoder_grad_projection)
+        self.ema_decay = ema_decay
+        #: parameter -> its exponential moving average, shared by every epoch's optimizer (None without ``ema_decay``)
+        self.ema_state = {} if ema_decay is not None else None
         self.device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
         self.model = (model if model is not None else _build_model(sae_type, config)).to(self.device)
         if sae_type == "b_sae":
@@ -398,6 +426,8 @@ class Trainer:
             model.apply_secant_grad()
         elif st == "t_sae":
             model.decoder.mask_grad()
+        if self.decoder_grad_projection:
+            model.project_decoder_grad()
         optimizer.step()
         if st == "t_sae":
             model.decoder.update_mask(self.f_decay, 0.7)
@@ -559,6 +589,14 @@ class Trainer:
                 for key, s in watched.items():
                     print(watch_line(key, s))
 
+    def _make_optimizer(self):
+        """An epoch's optimizer: a fresh Adam, as in the reference, with the recipe's options and the Trainer's averages"""
+        optimizer = optim.Adam(self.model.parameters(), lr=self.config["lr"], model=self.model, max_grad_norm=self.grad_clip,
+                               ema_decay=self.ema_decay, ema_state=self.ema_state)
+        if self.jumprelu is not None:
+            optimizer.add_param_group({"params": [self.jumprelu.log_threshold]})
+        return optimizer
+
     # ---- the reference's interface -----------------------------------------------------------------------------------------
     def one_epoch(self, dataset, dead_neuron_threshold=0.2, no_log=False, rigL=False, f_decay=None):
         """One pass over a chunk: ``dataset`` is a ``ShuffledChunk``, a ``HiddenStatesTorchDataset``, a chunk file or the
@@ -567,9 +605,7 @@ class Trainer:
         if self.device.type != "cuda":
             raise RuntimeError("Trainer.one_epoch: quantizedsae_amd runs on MI355X only (no CPU fallback exists)")
         chunk = dataset if isinstance(dataset, ShuffledChunk) else ShuffledChunk(dataset, self.config["batch_size"], self.device)
-        optimizer = optim.Adam(self.model.parameters(), lr=self.config["lr"], model=self.model)
-        if self.jumprelu is not None:
-            optimizer.add_param_group({"params": [self.jumprelu.log_threshold]})
+        optimizer = self._make_optimizer()
         self.trained_batches.append([])
         told = 0                                               # skipped batches announced so far, in batch order
 
@@ -598,10 +634,28 @@ class Trainer:
                     metrics.update(self._batch_topk_metrics())
                 if log_step and self.jumprelu is not None:
                     metrics.update(self._jumprelu_metrics())
+                if log_step and self.grad_clip is not None:
+                    clip = optimizer.clip_report()
+                    metrics.update({"grad_norm": clip.norm, "grad_clip_coef": clip.coef, "grad_clipped": int(clip.clipped)})
                 self._log(batch_idx, metrics, self._watched, summary, resampled)
         announce(None)
         chunk.check()
         return self.model
+
+    @property
+    def ema_path(self) -> str:
+        """Where ``train()`` saves the averaged weights: beside the checkpoint"""
+        root = self.model_path[:-len(".pth")] if self.model_path.endswith(".pth") else self.model_path
+        return root + "_ema.pth"
+
+    def ema_state_dict(self) -> dict:
+        """The model's state dict with every averaged parameter replaced by its average (``ema_decay`` set; a parameter that has
+        not been stepped yet keeps its value)"""
+        if self.ema_state is None:
+            raise ValueError("ema_state_dict needs ema_decay")
+        averaged = {name: self.ema_state[p] for name, p in self.model.named_parameters() if p in self.ema_state}
+        return {name: averaged[name].detach().clone() if name in averaged else value.detach().clone()
+                for name, value in self.model.state_dict().items()}
 
     def train(self):
         total_start = time.perf_counter()
@@ -619,6 +673,8 @@ class Trainer:
             self._wandb.finish()
         os.makedirs(os.path.dirname(self.model_path) or ".", exist_ok=True)
         torch.save(self.model.state_dict(), self.model_path)
+        if self.ema_state is not None:
+            torch.save(self.ema_state_dict(), self.ema_path)
         print(f"Training completed. Model been saved to {self.model_path}.")
         total_time = time.perf_counter() - total_start
         print(f"Total training time: {total_time:.2f} seconds")
