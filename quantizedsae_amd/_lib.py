@@ -313,6 +313,19 @@ OPTIM_SIGNATURES = {
     "qsaeo_adam_step_prefilter": (_i, SIGNATURES["qsae_adam_step_prefilter"][1][:-3] + [_vp, _vp, _vp, _f, _vp, _vp, _vp]),
 }
 
+# name -> (restype, argtypes) of the qsaew_* entry points of include/qsae_wide.h (csrc/wide.hip): per-row top-k over hidden
+# slabs -- the plan, the S-way merge of the slabs' lists, and the two whole selections -- a table of its own for the same reason.
+# Must list every symbol declared in qsae_wide.h.
+WIDE_SIGNATURES = {
+    "qsaew_slab_plan": (_i, [_i, _i, _i, C.POINTER(_i)]),
+    "qsaew_merge_topk": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(_i), _vp, _vp, _vp, _i64, _vp]),
+    "qsaew_encode_topk_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "qsaew_encode_topk": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _sz, _vp]),
+    "qsaew_encode_topk_prefilter_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "qsaew_encode_topk_prefilter": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _sz, _i,
+                                          C.POINTER(_i), _vp]),
+}
+
 
 class QsaeError(RuntimeError):
     """A libqsae_hip call returned a non-zero status."""
@@ -335,7 +348,8 @@ def _open(path: Path) -> C.CDLL:
     for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(CURVE_SIGNATURES.items()) \
             + list(NESTED_SIGNATURES.items()) + list(BATCH_SIGNATURES.items()) + list(NESTED_BATCH_SIGNATURES.items()) + list(MULTIK_SIGNATURES.items()) \
             + list(JUMP_SIGNATURES.items()) + list(JUMP_DENSE_SIGNATURES.items()) \
-            + list(BATCH_DENSE_SIGNATURES.items()) + list(RECYCLE_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()):
+            + list(BATCH_DENSE_SIGNATURES.items()) + list(RECYCLE_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) \
+            + list(WIDE_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError here means the library is stale
         fn.restype = res
         fn.argtypes = args

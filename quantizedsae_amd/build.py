@@ -23,7 +23,7 @@ SOURCES = ["encode.hip", "topk.hip", "binary.hip", "dense_dec.hip", "encode_topk
            "encode_emu.hip", "misc.hip", "analysis.hip", "coactivation_bits.hip", "coactivation_partners.hip", "token_overlap.hip", "token_lists.hip", "dictionary.hip", "dictionary_neighbors.hip", "dictionary_neighbors_f32.hip", "kmeans.hip", "top_examples.hip", "evaluation.hip", "train.hip", "train_gemm.hip",
            "train_mask.hip", "optim.hip", "trainer.hip", "watch.hip", "activity.hip", "resample.hip", "auxk.hip",
            "sparsity_curve.hip", "nested.hip", "batch_topk.hip", "batch_topk_decode.hip", "nested_ragged.hip", "multi_topk.hip", "jumprelu.hip",
-           "jump_dense.hip", "batch_dense.hip", "optim_recipe.hip"]
+           "jump_dense.hip", "batch_dense.hip", "optim_recipe.hip", "wide.hip"]
 HEADERS = sorted(p.name for p in (Path(__file__).resolve().parent / "csrc").glob("*.h"))   # every header: all sources rebuild
 ARCH = "gfx950"
 FLAGS = ["-O3", f"--offload-arch={ARCH}", "-ffp-contract=off", "-fPIC", "-std=c++17", "-Wall",
@@ -57,7 +57,8 @@ def build_native(force: bool = False, verbose: bool = False, debug: bool = False
                                         PKG.parent / "include" / "qsae_jump_dense.h",
                                         PKG.parent / "include" / "qsae_batch_dense.h",
                                         PKG.parent / "include" / "qsae_recycle.h",
-                                        PKG.parent / "include" / "qsae_optim.h"]
+                                        PKG.parent / "include" / "qsae_optim.h",
+                                        PKG.parent / "include" / "qsae_wide.h"]
     objdir = OBJDIR / "debug" if debug else OBJDIR
     lib = DEBUG_LIB if debug else LIB
     flags = FLAGS + (["-DQSAE_DEBUG_BUILD=1"] if debug else [])

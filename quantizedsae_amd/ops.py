@@ -3747,3 +3747,115 @@ def encode_batch_topk(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Ten
                                        _p(val_sel), _p(counts), _p(report), _p(theta), _p(batches), float(lr), _p(ws), ws.numel(),
                                        _stream()))
     return idx_sel, val_sel, counts, report
+
+
+# ---- dictionaries wider than one selection kernel: top-k over hidden slabs (include/qsae_wide.h, csrc/wide.hip) ------------------
+WIDE_MAX_SLABS = 32
+WIDE_MAX_H = 1 << 20
+WIDE_DEFAULT_SLAB = 32768
+
+
+def wide_plan(H: int, k: int, slab: int = WIDE_DEFAULT_SLAB):
+    """-> the S + 1 slab starts of qsaew_slab_plan (ascending multiples of 256, the last entry H); ValueError where it refuses."""
+    starts = (C.c_int * (WIDE_MAX_SLABS + 1))()
+    lib = _lib.load()
+    S = int(lib.qsaew_slab_plan(int(H), int(k), int(slab), starts))
+    if S < 1:
+        msg = lib.qsae_last_error()
+        raise ValueError(f"wide_plan: H = {H}, k = {k}, slab = {slab}: {msg.decode(errors='replace') if msg else S}")
+    return [int(starts[s]) for s in range(S + 1)]
+
+
+def encode_topk_wide_supported(B: int, D: int, H: int, k: int, slab: int = WIDE_DEFAULT_SLAB) -> bool:
+    """Whether encode_topk_wide runs this shape: H <= 2^20 in at most 32 slabs of at least k units, each a shape that some
+    existing selection form takes."""
+    return int(_lib.load().qsaew_encode_topk_prefilter_workspace_bytes(int(B), int(D), int(H), int(k), int(slab))) > 0
+
+
+@_on_tensor_device
+def merge_topk_parts(pidx: torch.Tensor, pval: torch.Tensor, starts, dense: Optional[torch.Tensor] = None):
+    """The rows' top-k from the top-k lists of S hidden slabs: ``pidx`` int32 / ``pval`` fp32 [S, B, k], each list by value
+    descending, then unit ascending, unit ids relative to ``starts[s]`` (``starts``: S + 1 ascending ints, ``wide_plan``)
+    -> (idx int32 [B, k] with global unit ids, val fp32 [B, k]) in the same order, the order of the one-piece kernels.  ``dense``
+    (fp32 [B, >= starts[S]], unit column stride): +0 is stored at the element of every entry that lost.  See qsaew_merge_topk."""
+    who = "merge_topk_parts"
+    _dev(pidx, f"{who}: pidx", torch.int32)
+    _dev(pval, f"{who}: pval", torch.float32)
+    if pidx.dim() != 3 or pidx.shape != pval.shape or pidx.device != pval.device:
+        raise ValueError(f"{who}: pidx is {tuple(pidx.shape)}, pval {tuple(pval.shape)}; expected [S, B, k] twice on one device")
+    S, B, k = (int(n) for n in pidx.shape)
+    starts = [int(h) for h in starts]
+    if not 1 <= S <= WIDE_MAX_SLABS or len(starts) != S + 1 or k < 1:
+        raise ValueError(f"{who}: S = {S}, k = {k}, {len(starts)} starts; expected 1 <= S <= {WIDE_MAX_SLABS}, k >= 1 and S + 1 starts")
+    if starts[0] < 0 or any(starts[s + 1] - starts[s] < k for s in range(S)):
+        raise ValueError(f"{who}: starts = {starts}: every slab must be at least k = {k} wide")
+    if B * k >= 2 ** 31:
+        raise ValueError(f"{who}: B * k = {B * k} is not below 2^31")
+    pidx, pval = pidx.contiguous(), pval.contiguous()
+    ld = 0
+    if dense is not None:
+        _dev(dense, f"{who}: dense", torch.float32)
+        if dense.dim() != 2 or dense.shape[0] != B or dense.shape[1] < starts[S] or (B and dense.stride(1) != 1) \
+                or dense.device != pidx.device:
+            raise ValueError(f"{who}: dense is {tuple(dense.shape)}; expected [{B}, >= {starts[S]}] with unit column stride")
+        ld = dense.stride(0) if B else starts[S]
+        _latent_pool_forget(dense)
+    idx = torch.empty((B, k), dtype=torch.int32, device=pidx.device)
+    val = torch.empty((B, k), dtype=torch.float32, device=pidx.device)
+    check(_lib.load().qsaew_merge_topk(_p(pidx), _p(pval), S, B, k, (C.c_int * (S + 1))(*starts), _p(idx), _p(val), _p(dense), ld,
+                                       _stream()))
+    return idx, val
+
+
+@_on_tensor_device
+def encode_topk_wide(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], k: int, *, Wq: Optional[torch.Tensor] = None,
+                     meta: Optional[torch.Tensor] = None, want_dense: bool = True, slab: int = WIDE_DEFAULT_SLAB,
+                     spec_rows: int = 0, info: Optional[dict] = None):
+    """Encoder + exact per-row top-k (+ dense latent) over a dictionary of up to 2^20 units: the hidden range in slabs of
+    ``wide_plan(H, k, slab)``, every slab through the existing selection forms on its row range of ``W`` (nothing is copied), the
+    slabs' lists merged on the device -> (idx int32 [B, k], val fp32 [B, k], dense [B, H] or None), bit for bit what
+    ``encode_topk_latent`` gives wherever that runs.  With ``Wq`` and ``meta`` (``prefilter_pack_w`` of the WHOLE matrix) a slab
+    the fp16 prefilter takes goes through it; without, every slab takes the exact fused or chunked form.  ``info`` receives
+    ``flagged_rows`` (summed over the slabs) and ``slabs``.  See qsaew_encode_topk / qsaew_encode_topk_prefilter."""
+    who = "encode_topk_wide"
+    x, W = _f32c(x, f"{who}: x"), _f32c(W, f"{who}: W")
+    if x.dim() != 2 or W.dim() != 2 or x.shape[1] != W.shape[1] or W.device != x.device:
+        raise ValueError(f"{who}: x is {tuple(x.shape)} on {x.device}, W {tuple(W.shape)} on {W.device}; expected [B, D] and [H, D] "
+                         f"on one device")
+    B, D = x.shape
+    H = W.shape[0]
+    k, slab = int(k), int(slab)
+    b = _f32c(bias, f"{who}: bias") if bias is not None else None
+    if b is not None and (tuple(b.shape) != (H,) or b.device != x.device):
+        raise ValueError(f"{who}: bias is {tuple(b.shape)} on {b.device}, expected [{H}] on {x.device}")
+    if (Wq is None) != (meta is None):
+        raise ValueError(f"{who}: Wq and meta come together (prefilter_pack_w of the whole matrix)")
+    starts = wide_plan(H, k, slab)
+    pref = Wq is not None
+    if pref:
+        _dev(Wq, f"{who}: Wq", torch.float16)
+        _dev(meta, f"{who}: meta", torch.float32)
+        if tuple(Wq.shape) != (H, D) or not Wq.is_contiguous() or meta.numel() != 4 or Wq.device != x.device or meta.device != x.device:
+            raise ValueError(f"{who}: Wq is {tuple(Wq.shape)}, meta {tuple(meta.shape)}; expected contiguous [{H}, {D}] and [4] on {x.device}")
+    lib = _lib.load()
+    sizer = lib.qsaew_encode_topk_prefilter_workspace_bytes if pref else lib.qsaew_encode_topk_workspace_bytes
+    need = int(sizer(max(B, 1), D, H, k, slab))
+    if need == 0:
+        raise ValueError(f"{who}: shape B={B}, D={D}, H={H}, k={k}, slab={slab} is outside what the slab selection runs (D % 4 == 0, "
+                         f"H % 4 == 0, H <= 2^20, k <= 256, at most {WIDE_MAX_SLABS} slabs of at least k units)")
+    idx = torch.empty((B, k), dtype=torch.int32, device=x.device)
+    val = torch.empty((B, k), dtype=torch.float32, device=x.device)
+    dense = torch.empty((B, H), dtype=torch.float32, device=x.device) if want_dense else None
+    flagged = C.c_int(0)
+    if B > 0:
+        ws = _workspace(x.device, need)
+        if pref:
+            check(lib.qsaew_encode_topk_prefilter(_p(x), _p(W), _p(b), _p(Wq), _p(meta), B, D, H, k, slab, _p(idx), _p(val), _p(dense), H,
+                                                  _p(ws), ws.numel(), int(spec_rows), C.byref(flagged), _stream()))
+        else:
+            check(lib.qsaew_encode_topk(_p(x), _p(W), _p(b), B, D, H, k, slab, _p(idx), _p(val), _p(dense), H, _p(ws), ws.numel(),
+                                        _stream()))
+    if info is not None:
+        info["flagged_rows"] = int(flagged.value)
+        info["slabs"] = len(starts) - 1
+    return idx, val, dense

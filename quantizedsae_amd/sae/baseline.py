@@ -19,7 +19,7 @@ class BaselineSparseAutoencoder(ops.GraphForwardMixin, TopKCore, nn.Module):
         self.encoder = HipEncoder(nn.Linear(input_dim, hidden_dim))   # no ReLU in the reference either
         self.decoder = nn.Linear(hidden_dim, input_dim)
         self.topk = 32
-        self.latent_path = "auto"      # "auto" | "prefilter" | "fused" | "inplace" (see BinarySAE.latent_path)
+        self.latent_path = "auto"      # "auto" | "prefilter" | "fused" | "inplace" | "slabs" (see BinarySAE.latent_path)
         self._cache = PackedCache()
         self._init_topk()
         ops.module_handle(self)
@@ -34,6 +34,8 @@ class BaselineSparseAutoencoder(ops.GraphForwardMixin, TopKCore, nn.Module):
         it: ``latent_path`` is not validated here, and an explicit "prefilter" or "fused" on a small batch falls to the
         in-place path (BinarySAE honours it)."""
         H, D = self.encoder.linear.weight.shape
+        if self.latent_path == "slabs":         # opt-in only: no other value resolves to it
+            return "slabs"
         big = rows >= 2048 and H >= 8192
         if big and self.latent_path in ("auto", "prefilter") and ops.prefilter_supported(rows, D, H, self.topk):
             return "prefilter"
@@ -41,10 +43,17 @@ class BaselineSparseAutoencoder(ops.GraphForwardMixin, TopKCore, nn.Module):
 
     def _check_limits(self, rows: int) -> None:
         H, D = self.encoder.linear.weight.shape
+        if self.latent_path == "slabs":
+            if not self._slabs_supported(rows, self.topk):
+                raise ValueError(f"BaselineSparseAutoencoder: the slab selection does not take input_dim = {D}, hidden_dim = {H}, "
+                                 f"topk = {self.topk} at slab_width = {self.slab_width} (input_dim and hidden_dim multiples of 4, "
+                                 "hidden_dim <= 2^20, topk <= 256, slab_width a multiple of 256 up to 32768, at most 32 slabs of "
+                                 "at least topk units)")
+            return
         if (H > 32768 and self.latent_path == "inplace") or not ops.encode_topk_supported(max(rows, 1), D, H, self.topk):
             raise ValueError(f"BaselineSparseAutoencoder: no top-k path takes input_dim = {D}, hidden_dim = {H} at a batch of "
                              f"{rows} rows (input_dim and hidden_dim multiples of 4; hidden_dim <= 32768, or up to 65536 for "
-                             "batches of >= 2048 rows off the in-place path)")
+                             "batches of >= 2048 rows off the in-place path; latent_path = 'slabs' takes wider dictionaries)")
 
     def _run(self, x, want_dense: bool):
         """-> (idx, val, dense latent or None, reconstruction): the one implementation behind forward() and
@@ -156,6 +165,9 @@ class BaselineSparseAutoencoder(ops.GraphForwardMixin, TopKCore, nn.Module):
         returned handle gives ``(h_sparse, reconstruction)`` (``(idx, val, reconstruction)`` with want_dense=False)."""
         def to_result(idx, val, h, recon):
             return (h, recon) if want_dense else (idx, val, recon)
+        if self.latent_path == "slabs":
+            raise ValueError("BaselineSparseAutoencoder.forward_submit: the two-call form is not built for latent_path = 'slabs' "
+                             "(every slab reads its flagged-row count back); call forward() or forward_compact()")
         with torch.no_grad():
             xd = require_device_input(x, "x")
             self._check_limits(xd.shape[0])

@@ -134,7 +134,8 @@ class BinarySAE(ops.GraphForwardMixin, TopKCore, SparseAutoencoder):
     (sae/binary.py:71-103).  k = int(hidden_dim * self.k) with self.k = 0.002.
 
     Shape limits of the kernels (checked before every forward's first launch, ValueError): k <= 256, input_dim and
-    hidden_dim multiples of 4, hidden_dim <= 32768 for batches under 2048 rows and the in-place path, <= 65536 otherwise.  k == 0 (hidden_dim < 500) is served like the reference: an
+    hidden_dim multiples of 4, hidden_dim <= 32768 for batches under 2048 rows and the in-place path, <= 65536 otherwise; ``latent_path = "slabs"`` goes up to 2^20 at any batch
+    (k <= 256 stays: past 128499 units lower ``self.k``).  k == 0 (hidden_dim < 500) is served like the reference: an
     all-zero latent and a bias-only reconstruction."""
 
     def __init__(self, input_dim, hidden_dim, gamma=4.0, n_bits=8):
@@ -165,7 +166,9 @@ class BinarySAE(ops.GraphForwardMixin, TopKCore, SparseAutoencoder):
     #: contraction, top-k masks it in place; prefilter: an fp16 MFMA pass with a rigorous error bound
     #: picks ~90 candidates per row, which are re-evaluated and ranked in exact fp32.  All paths return
     #: bit-identical outputs; auto takes prefilter for large batches (fused where its shape limits do not
-    #: hold) and inplace for small ones.
+    #: hold) and inplace for small ones.  "slabs" (never chosen by auto): the selection over ``slab_width`` hidden units at
+    #: a time, merged on the device -- the same bits again, and the one path for hidden_dim above 65536 (above 32768 for
+    #: batches under 2048 rows), up to 2^20; it decodes with the separate sparse decoders.
     latent_path = "auto"
     #: prefilter path: the refinement kernel also decodes each row it has ranked (one launch less, the decode's work in
     #: the refinement's idle issue slots); False = separate decode kernel.  Bit-identical either way.
@@ -174,8 +177,10 @@ class BinarySAE(ops.GraphForwardMixin, TopKCore, SparseAutoencoder):
     def resolved_latent_path(self, batch_rows: int) -> str:
         """Which path forward() takes for a batch of this many rows (after the auto / shape fallbacks)."""
         path = self.latent_path
-        if path not in ("auto", "fused", "inplace", "prefilter"):
-            raise ValueError(f"latent_path must be 'auto', 'fused', 'inplace' or 'prefilter', got {path!r}")
+        if path not in ("auto", "fused", "inplace", "prefilter", "slabs"):
+            raise ValueError(f"latent_path must be 'auto', 'fused', 'inplace', 'prefilter' or 'slabs', got {path!r}")
+        if path == "slabs":                     # opt-in only: "auto" never resolves to it
+            return path
         big = batch_rows >= 2048 and self.hidden_dim >= 8192
         if path == "auto":
             path = "prefilter" if big else "inplace"
@@ -193,14 +198,23 @@ class BinarySAE(ops.GraphForwardMixin, TopKCore, SparseAutoencoder):
     def _check_limits(self, path: str, rows: int) -> None:
         k = self.top_k
         if k > 256:
-            raise ValueError(f"BinarySAE: top-k = int({self.hidden_dim} * {self.k}) = {k} exceeds the kernels' limit of 256")
+            raise ValueError(f"BinarySAE: top-k = int({self.hidden_dim} * {self.k}) = {k} exceeds the kernels' limit of 256 "
+                             "(on every path, latent_path = 'slabs' included: lower model.k)")
+        if path == "slabs":
+            if not self._slabs_supported(rows, k):
+                raise ValueError(f"BinarySAE: the slab selection does not take input_dim = {self.input_dim}, hidden_dim = "
+                                 f"{self.hidden_dim}, top-k = {k} at slab_width = {self.slab_width} (input_dim and hidden_dim "
+                                 "multiples of 4, hidden_dim <= 2^20, slab_width a multiple of 256 up to 32768, at most 32 "
+                                 "slabs of at least top-k units)")
+            return
         if self.hidden_dim > 32768 and path == "inplace":
             raise ValueError(f"BinarySAE: hidden_dim = {self.hidden_dim} exceeds the in-place top-k kernel's limit of 32768 "
-                             "(batches of >= 2048 rows take the fused path up to 65536)")
+                             "(batches of >= 2048 rows take the fused path up to 65536; latent_path = 'slabs' takes wider "
+                             "dictionaries at any batch)")
         if not ops.encode_topk_supported(max(rows, 1), self.input_dim, self.hidden_dim, k):
             raise ValueError(f"BinarySAE: no top-k path takes input_dim = {self.input_dim}, hidden_dim = {self.hidden_dim} at "
                              f"a batch of {rows} rows (input_dim and hidden_dim multiples of 4; hidden_dim <= 32768, or up "
-                             "to 65536 for batches of >= 2048 rows)")
+                             "to 65536 for batches of >= 2048 rows; latent_path = 'slabs' takes wider dictionaries)")
 
     def _zero_k(self, x, want_dense: bool):
         """k == 0: the reference's topk(0) keeps nothing -- zero latent, reconstruction = decoder bias (sae/binary.py:94-99)."""
@@ -353,6 +367,9 @@ class BinarySAE(ops.GraphForwardMixin, TopKCore, SparseAutoencoder):
         together need different ``slot`` numbers; other paths compute eagerly and return a finished handle."""
         def to_result(idx, val, latent, recon):
             return (latent, recon, self.decoder.packed()["polarize"]) if want_dense else (idx, val, recon)
+        if self.latent_path == "slabs":
+            raise ValueError("BinarySAE.forward_submit: the two-call form is not built for latent_path = 'slabs' (every slab "
+                             "reads its flagged-row count back); call forward() or forward_compact()")
         with torch.no_grad():
             xd = require_device_input(x, "x")
             if self.top_k > 0 and self.resolved_latent_path(xd.shape[0]) == "prefilter" and self.fuse_decode:

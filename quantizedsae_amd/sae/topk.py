@@ -51,9 +51,36 @@ class TopKCore:
         if hasattr(self.encoder, "_kperm_cache"):
             self.encoder._kperm_cache.clear()
 
-    def _select(self, x, k: int, path: str, want_dense: bool):
-        """-> (idx, val, dense latent or None) on the resolved path; bit-identical on all three."""
+    #: hidden units per slab of ``latent_path = "slabs"`` (a multiple of 256 up to 32768): the per-row top-k of every slab's row
+    #: range of the encoder, through the same kernels as the other paths, merged on the device (include/qsae_wide.h).  The
+    #: bits do not depend on it.
+    slab_width = ops.WIDE_DEFAULT_SLAB
+
+    def _slabs_supported(self, rows: int, K: int) -> bool:
+        H, D = (int(n) for n in self.encoder.linear.weight.shape)
+        return 1 <= K <= H and ops.encode_topk_wide_supported(max(rows, 1), D, H, K, int(self.slab_width))
+
+    def _select_slabs(self, x, k: int, want_dense: bool):
+        """The selection over hidden slabs: the fp16 prefilter copy (of the whole matrix: its ``meta`` bounds every row range) is
+        only taken -- and, after a weight update, only rebuilt -- when some slab's shape goes through the prefilter."""
         lin = self.encoder.linear
+        H, D = (int(n) for n in lin.weight.shape)
+        starts = ops.wide_plan(H, k, int(self.slab_width))
+        if any(ops.prefilter_supported(x.shape[0], D, h1 - h0, k) for h0, h1 in zip(starts, starts[1:])):
+            xf, W, b, Wq, meta = self._prefilter_operands(x)
+        else:
+            xf, W, b, Wq, meta = as_f32c(x), lin.weight.detach(), lin.bias.detach(), None, None
+        info = {}
+        idx, val, latent = ops.encode_topk_wide(xf, W, b, k, Wq=Wq, meta=meta, want_dense=want_dense, slab=int(self.slab_width),
+                                                spec_rows=self._spec_rows(), info=info)
+        self.last_flagged_rows = info["flagged_rows"]
+        return idx, val, latent
+
+    def _select(self, x, k: int, path: str, want_dense: bool):
+        """-> (idx, val, dense latent or None) on the resolved path; bit-identical on all four."""
+        lin = self.encoder.linear
+        if path == "slabs":
+            return self._select_slabs(x, k, want_dense)
         if path == "prefilter":
             info = {}
             idx, val, latent = ops.encode_topk_prefilter(*self._prefilter_operands(x), k, want_dense=want_dense,
@@ -75,6 +102,11 @@ class TopKCore:
         BatchTopK): what ``resolved_latent_path`` gives for the batch, the fused path where the prefilter does not take K."""
         H, D = (int(n) for n in self.encoder.linear.weight.shape)
         path = self.resolved_latent_path(rows)
+        if path == "slabs":
+            if not self._slabs_supported(rows, K):
+                raise ValueError(f"{who}: the slab selection does not take input_dim = {D}, hidden_dim = {H}, k = {K} at "
+                                 f"slab_width = {self.slab_width}")
+            return path
         if path == "prefilter" and not ops.prefilter_supported(rows, D, H, K):
             path = "fused"
         if not ops.encode_topk_supported(max(rows, 1), D, H, K) or (path == "inplace" and H > 32768):

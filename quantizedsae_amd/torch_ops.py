@@ -2113,3 +2113,47 @@ def encode_batch_topk(x, W, bias, n_select, K, floor, floor_ratio=1.0, state=Non
     theta, batches, lr = state if state is not None else (None, None, 0.0)
     return Q.encode_batch_topk(x, W, bias, int(n_select), int(K), floor if on_dev else None, 0.0 if on_dev else float(floor),
                                float(floor_ratio), theta, batches, float(lr))
+
+
+# ---- dictionaries wider than one selection kernel: top-k over hidden slabs (include/qsae_wide.h) ----------------------------
+WIDE_DEFAULT_SLAB = _ops.WIDE_DEFAULT_SLAB
+wide_plan = _ops.wide_plan
+encode_topk_wide_supported = _ops.encode_topk_wide_supported
+
+
+@_op("merge_topk_parts", mutates=("dense",))
+def _merge_topk_parts(pidx: Tensor, pval: Tensor, starts: List[int], dense: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+    return _ops.merge_topk_parts(pidx, pval, starts, dense)
+
+
+@_merge_topk_parts.register_fake
+def _(pidx, pval, starts, dense):
+    return _i32((pidx.shape[1], pidx.shape[2]), pidx), _f32((pidx.shape[1], pidx.shape[2]), pidx)
+
+
+@_op("encode_topk_wide")
+def _encode_topk_wide(x: Tensor, W: Tensor, bias: Optional[Tensor], k: int, Wq: Optional[Tensor], meta: Optional[Tensor],
+                      want_dense: bool, slab: int, spec_rows: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    info = {}
+    idx, val, dense = _ops.encode_topk_wide(x, W, bias, k, Wq=Wq, meta=meta, want_dense=want_dense, slab=slab, spec_rows=spec_rows,
+                                            info=info)
+    return idx, val, _dense_or_empty(dense, x, W.shape[0]), torch.tensor([info["flagged_rows"], info["slabs"]], dtype=torch.int64)
+
+
+@_encode_topk_wide.register_fake
+def _(x, W, bias, k, Wq, meta, want_dense, slab, spec_rows):
+    B, H = x.shape[0], W.shape[0]
+    return _i32((B, k), x), _f32((B, k), x), _f32((B if want_dense else 0, H), x), torch.empty((2,), dtype=torch.int64)
+
+
+def merge_topk_parts(pidx, pval, starts, dense=None):
+    """-> (idx int32 [B, k], val fp32 [B, k]); dense: +0 stored at the element of every entry that lost"""
+    return Q.merge_topk_parts(pidx, pval, [int(h) for h in starts], dense)
+
+
+def encode_topk_wide(x, W, bias, k, *, Wq=None, meta=None, want_dense=True, slab=WIDE_DEFAULT_SLAB, spec_rows=0, info=None):
+    """-> (idx, val, dense latent or None); info receives flagged_rows and slabs"""
+    idx, val, dense, words = Q.encode_topk_wide(x, W, bias, int(k), Wq, meta, bool(want_dense), int(slab), int(spec_rows))
+    if info is not None:
+        info["flagged_rows"], info["slabs"] = int(words[0]), int(words[1])
+    return idx, val, _none_if_empty(dense, want_dense)
